@@ -12,6 +12,19 @@ configs[1] = C1: seq_len 256 = 8+8 blocks, B = 256 windows / GPU, 15 negatives, 
 0.1): forward of all 34 816 blocks, InfoNCE + quantisation loss, backward, RCCL all-reduce, global-norm clip, Adam.
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, `--warmup` steps (plus the graph capture), the `--steps` timed steps,
+the outputs of the last timed step when `--dump-outputs DIR` is given, and the JSON line.  Everything else the benchmark
+measures -- the roofline from per-launch GEMM events, the bare train_step figure, the sysfs clock, c1_long, the extra
+arithmetic legs, the live PMC passes, the CPU baseline, the secondary configurations and, on several ranks, the all-reduce
+alone and the single-rank leg -- runs only with `--full` (the --no-* switches below then deselect parts of it):
+
+    python bench.py --full --gpus 1 --steps 20 --warmup 5
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64): the step's outputs
+(step_*), the epoch means (epoch_*) and the updated flat parameters (params; a fixed seeded sample when larger than the
+64 MB budget).  Inputs, initial weights and dropout seeds are fixed, so two builds run with the same arguments can be
+compared output for output.
+
 roofline  : the dominant kernel is the NT GEMM `gemm_nt` (forward + dgrad = 2/3 of the GEMM FLOPs); achieved =
             algorithmic FLOPs (2 M N K per launch) / launch durations measured with HIP events on the launch stream inside
             the timed region (every launch of every 4th timed step); peak = 416.7 TFLOP/s algorithmic for the default
@@ -81,6 +94,11 @@ def parse():
                     help='skip the short runs of the other configurations (C3 student step, DEC decoder step, C4 in bf16) that '
                          'the default N = 1 / C1 run reports under "secondary" after -- and outside -- the headline measurement')
     ap.add_argument('--gemm-breakdown', action='store_true', help='per-shape GEMM times of the sampled steps, to stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beyond the headline (roofline, train_step_only, clock, c1_long, extras, live PMC, '
+                         'CPU baseline, secondary configurations, all-reduce and single-rank legs); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step, the epoch means and the updated parameters to DIR/<name>.npy')
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -319,7 +337,7 @@ def live_pmc(args, B, timeout_s=100):
     n_steps = warm + 2 * steps                   # warm-up epoch + the bare-step loop + the timed epoch of the inner run
     inner = [sys.executable, os.path.abspath(__file__), '--config', args.config, '--steps', str(steps), '--warmup', str(warm),
              '--batch', str(B), '--dropout', str(args.dropout), '--gemm-mode', str(args.gemm_mode), '--grad-arith',
-             str(args.grad_arith), '--fwd-arith', str(args.fwd_arith), '--no-graph',
+             str(args.grad_arith), '--fwd-arith', str(args.fwd_arith), '--no-graph', '--full',
              '--no-cpu-baseline', '--no-kernel-timing', '--no-live-pmc', '--no-extras', '--no-secondary']
     out = {'steps': n_steps}
     tmp = tempfile.mkdtemp(prefix='vqcpc_pmc_', dir='/tmp')
@@ -549,7 +567,7 @@ def secondary_runs(timeout_s=240):
     import subprocess
     out = {}
     for name, extra in SECONDARY:
-        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ['--no-cpu-baseline', '--no-live-pmc', '--no-extras',
+        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ['--full', '--no-cpu-baseline', '--no-live-pmc', '--no-extras',
                                                                      '--no-secondary']
         t0 = time.perf_counter()
         try:
@@ -580,7 +598,8 @@ def n1_same_node_leg(args, B, device_index, timeout_s=300):
     env['HIP_VISIBLE_DEVICES'] = ids[device_index] if ids and device_index < len(ids) else str(device_index)
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--config', args.config, '--steps', str(args.steps), '--warmup',
            str(args.warmup), '--batch', str(B), '--dropout', str(args.dropout), '--gemm-mode', str(args.gemm_mode), '--grad-arith',
-           str(args.grad_arith), '--fwd-arith', str(args.fwd_arith), '--no-cpu-baseline', '--no-live-pmc', '--no-extras', '--no-secondary', '--no-kernel-timing']
+           str(args.grad_arith), '--fwd-arith', str(args.fwd_arith), '--full', '--no-cpu-baseline', '--no-live-pmc', '--no-extras', '--no-secondary',
+           '--no-kernel-timing']
     if not args.graph:
         cmd.append('--no-graph')
     t0 = time.perf_counter()
@@ -593,6 +612,57 @@ def n1_same_node_leg(args, B, device_index, timeout_s=300):
                         'the other ranks idle at a barrier'}
     except Exception as e:
         return {'error': f'{type(e).__name__}: {str(e)[:200]}', 'wall_s': round(time.perf_counter() - t0, 1)}
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def _host_arrays(name, obj, out):
+    """Flattens a step's / an epoch's result into {name: numpy array}: floating tensors as float32, integer tensors and
+    Python numbers as float64 (exact for codebook indices and counts)."""
+    import numpy as np
+    if obj is None:
+        return
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        out[name] = (t.float() if t.is_floating_point() else t.double()).cpu().contiguous().numpy()
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _host_arrays(f'{name}_{k}', v, out)
+    elif isinstance(obj, (list, tuple)) and all(isinstance(v, (bool, int, float)) for v in obj):
+        out[name] = np.asarray(obj, dtype=np.float64)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _host_arrays(f'{name}_{i}', v, out)
+    elif isinstance(obj, (bool, int, float)):
+        out[name] = np.asarray(obj, dtype=np.float64)
+
+
+def dump_outputs(directory, step_out, means, params):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the step's outputs (step_*), the epoch
+    means (epoch_*) and the updated flat parameters (params) -- as DIR/<name>.npy.  Arrays above 1 MB are cut to a fixed
+    seeded sample of their elements when the whole set would exceed DUMP_BUDGET_BYTES."""
+    import re
+    import numpy as np
+    arrays = {}
+    _host_arrays('step', step_out, arrays)
+    _host_arrays('epoch', means, arrays)
+    _host_arrays('params', params, arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        big = {k for k, a in arrays.items() if a.nbytes > 2 ** 20}
+        room = 0.95 * DUMP_BUDGET_BYTES - sum(a.nbytes for k, a in arrays.items() if k not in big)
+        frac = max(room, 0.0) / sum(arrays[k].nbytes for k in big)
+        for k in big:
+            a = arrays[k].reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(1, int(a.size * frac)), replace=False))
+            arrays[k] = a[idx]
+            print(f'bench.py: --dump-outputs: {k} is a seeded sample of {idx.size} of its {a.size} elements', file=sys.stderr)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, re.sub(r'[^A-Za-z0-9_.-]', '_', k) + '.npy'), a)
+    print(f'bench.py: --dump-outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 2 ** 20:.1f} MiB in '
+          f'{directory}', file=sys.stderr)
 
 
 def flush_c_stdio():
@@ -696,8 +766,10 @@ def main():
     from vqcpc_bach_amd.graphs import dp_graph_mode
     use_graph = bool(args.graph) and (not dp.distributed or dp_graph_mode() != 'off')
 
+    # per-launch GEMM events feed the roofline: a --full measurement (or --gemm-breakdown), never part of a plain run
+    kernel_timing = not args.no_kernel_timing and (args.full or args.gemm_breakdown)
     timer = GemmTimer()
-    if not args.no_kernel_timing:
+    if kernel_timing:
         timer.install(ops)
 
     # synthetic batches resident in HBM before the timed region (4 distinct batches, cycled)
@@ -713,7 +785,7 @@ def main():
         """n batches from the resident pool; HIP events bracket the GEMM launches of every 4th step when `sample`
         (bracketing all of them costs ~2 % of the step)"""
         for i in range(n):
-            timer.enabled = sample and (not args.no_kernel_timing) and (i % every == 0)
+            timer.enabled = sample and kernel_timing and (i % every == 0)
             yield pool[i % len(pool)]
         timer.enabled = False
 
@@ -731,7 +803,7 @@ def main():
         # individual launches of a replayed graph cannot be bracketed with events from the host: the per-kernel samples
         # of the roofline object come from eager steps run right BEFORE the graph is captured (same kernels, same shapes,
         # same launch order; the rocprofv3 kernel trace of this command under profiles/ covers the replayed launches)
-        sampled_eager_steps = 0 if args.no_kernel_timing else min(args.steps, 12)
+        sampled_eager_steps = min(args.steps, 12) if kernel_timing else 0
         for b in batches(sampled_eager_steps, True, every=1):
             trainer.train_step(b, train=True)
         torch.cuda.synchronize()
@@ -742,22 +814,33 @@ def main():
             trainer.precapture_step_graphs(pool[0])     # student step: one graph per masked event index (96 at C3)
         torch.cuda.synchronize()
     torch.cuda.synchronize()
-    # (a) bare training steps, no metric bookkeeping: reported next to the metric when the two differ
-    dp.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    n_host = min(args.steps, 8)                    # host cost per step from the first few calls: with a long queue of
-    t_enqueued = 0.0                               # graph launches in flight the runtime blocks the caller (back-pressure),
-    for i, b in enumerate(batches(args.steps, False)):   # which is GPU time, not host work
-        trainer.train_step(b, train=True)
-        if i + 1 == n_host:
-            t_enqueued = time.perf_counter() - t0  # no sync inside a step
-    torch.cuda.synchronize()
-    dp.barrier()
-    torch.cuda.synchronize()
-    dt_steps = dp.max_over_ranks(time.perf_counter() - t0)
+    # (a) --full: bare training steps, no metric bookkeeping: reported next to the metric when the two differ
+    dt_steps = None
+    if args.full:
+        dp.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_host = min(args.steps, 8)                    # host cost per step from the first few calls: with a long queue of
+        t_enqueued = 0.0                               # graph launches in flight the runtime blocks the caller (back-pressure),
+        for i, b in enumerate(batches(args.steps, False)):   # which is GPU time, not host work
+            trainer.train_step(b, train=True)
+            if i + 1 == n_host:
+                t_enqueued = time.perf_counter() - t0  # no sync inside a step
+        torch.cuda.synchronize()
+        dp.barrier()
+        torch.cuda.synchronize()
+        dt_steps = dp.max_over_ranks(time.perf_counter() - t0)
+    # --dump-outputs: keep a reference to what each step returns (the last one survives the epoch); off otherwise
+    last_step = {}
+    if args.dump_outputs:
+        raw_train_step = trainer.train_step
+
+        def train_step(*a, **kw):
+            last_step['out'] = raw_train_step(*a, **kw)
+            return last_step['out']
+        trainer.train_step = train_step
     # (b) the timed region of `value`: EXACTLY args.steps iterations of epoch(train=True)
-    clock = ClockSampler() if dp.rank == 0 else None
+    clock = ClockSampler() if (dp.rank == 0 and args.full) else None
     dp.barrier()
     torch.cuda.synchronize()
     if clock is not None:
@@ -771,6 +854,10 @@ def main():
     dt = time.perf_counter() - t0
     clock_info = clock.finish() if clock is not None else None
     timer.enabled = False
+    if args.dump_outputs:
+        del trainer.train_step
+        if dp.rank == 0:
+            dump_outputs(args.dump_outputs, last_step.get('out'), means, trainer.flat.flat)
     dt = dp.max_over_ranks(dt)
     per_rank_ms = dp.gather_floats(1e3 * dt_local / args.steps) if dp.distributed else None
     timed_steps = max(1, len(range(0, args.steps, 4)))
@@ -778,7 +865,7 @@ def main():
     # outside `value`: the driver's --steps 20 times 0.44 s, where box-to-box and run-to-run spread (+- 2 %) is the size of the
     # gains a round claims; 300 steps (SURVEY.md section 8(d) asks >= 50) put the figure's own noise below that
     c1_long = None
-    if (args.config == 'C1' and dp.world_size == 1 and not args.no_extras and not args.host_inputs and args.batch is None
+    if (args.full and args.config == 'C1' and dp.world_size == 1 and not args.no_extras and not args.host_inputs and args.batch is None
             and not args.no_long):
         n_long = 300
         torch.cuda.synchronize()
@@ -799,7 +886,7 @@ def main():
         timed_steps = max(1, sampled_eager_steps)
     # the collective of the data-parallel step alone: the flat gradient bucket (what every step all-reduces), back to back
     allreduce = None
-    if dp.distributed:
+    if dp.distributed and args.full:
         import torch.distributed as dist
         bucket = torch.zeros_like(trainer.flat.flat_grad)
         for _ in range(3):
@@ -822,7 +909,7 @@ def main():
                              'ranks); inside the step the same call sits between the two graph replays'}
         del bucket
     n1_leg = None
-    if dp.distributed and not args.no_n1_leg:
+    if dp.distributed and args.full and not args.no_n1_leg:
         torch.cuda.synchronize()
         if dp.rank == 0:
             n1_leg = n1_same_node_leg(args, B, dev.index if dev.index is not None else 0)
@@ -857,7 +944,7 @@ def main():
             if use_graph:
                 trainer.enable_step_graph(False)
 
-    if (gemm_mode == 1 and args.grad_arith == 'f16x3' and not args.no_extras and args.config == 'C1' and dp.world_size == 1
+    if (args.full and gemm_mode == 1 and args.grad_arith == 'f16x3' and not args.no_extras and args.config == 'C1' and dp.world_size == 1
             and not args.host_inputs):
         if args.fwd_arith == 'f16x3':
             extra_fwd_six = extra_leg('f16x3', 'six',
@@ -867,7 +954,8 @@ def main():
                               'NOT the headline: the same steps with six-product (bf16x6) GEMMs everywhere, forward and backward '
                               '(bench.py --grad-arith six --fwd-arith six), i.e. the configuration rounds 1-4 reported')
     pmc = None
-    want_pmc = args.live_pmc if args.live_pmc is not None else (dp.world_size == 1 and args.config == 'C1' and not args.host_inputs)
+    want_pmc = args.live_pmc if args.live_pmc is not None else (args.full and dp.world_size == 1 and args.config == 'C1'
+                                                                and not args.host_inputs)
     if want_pmc and dp.rank == 0 and dp.world_size == 1:
         pmc = live_pmc(args, B)
     flush_c_stdio()
@@ -1060,10 +1148,11 @@ def main():
                                      f'each training step is {graphs_per_step} HIP-graph replays around the eagerly issued '
                                      'all-reduce(s) of the gradient bucket') + ' (vqcpc_bach_amd/graphs.py); --no-graph runs the same launches eagerly'}
                            if use_graph else None),
-            'train_step_only': {'value': round(B * dp.world_size * args.steps / dt_steps, 2),
-                                'ms_per_step': round(1e3 * dt_steps / args.steps, 3),
-                                'host_enqueue_ms_per_step': round(1e3 * t_enqueued / n_host, 3),
-                                'note': 'same steps without epoch()\'s metric bookkeeping; not the metric'},
+            'train_step_only': ({'value': round(B * dp.world_size * args.steps / dt_steps, 2),
+                                 'ms_per_step': round(1e3 * dt_steps / args.steps, 3),
+                                 'host_enqueue_ms_per_step': round(1e3 * t_enqueued / n_host, 3),
+                                 'note': 'same steps without epoch()\'s metric bookkeeping; not the metric'}
+                                if dt_steps is not None else None),
         }
         if gemm_mode == 1 and 'f16x3' in (args.grad_arith, args.fwd_arith) and hasattr(trainer, 'flat'):
             # operands that outgrew the head-room of their previous-step scale (clamped for one step), over the whole run
@@ -1104,13 +1193,13 @@ def main():
                                           f'anticausal cross / causal target, batch={B}/GPU, dropout={args.dropout}',
                               'global_batch': B * dp.world_size, 'seq_len': 384, 'parallelism': f'dp{dp.world_size}',
                               'params': n_params, 'gemm': line['config']['gemm']}
-        if dp.world_size == 1 and not args.no_cpu_baseline:
+        if dp.world_size == 1 and args.full and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.config, args.dropout, args.cpu_batch, args.cpu_steps)
             if line['cpu_baseline'].get('value'):
                 line['speedup_vs_cpu'] = round(value / line['cpu_baseline']['value'], 1)
         else:
             line['cpu_baseline'] = None
-        if (dp.world_size == 1 and args.config == 'C1' and not args.no_secondary and not args.host_inputs
+        if (args.full and dp.world_size == 1 and args.config == 'C1' and not args.no_secondary and not args.host_inputs
                 and args.batch is None and gemm_mode == 1):
             line['secondary'] = secondary_runs()
         print(json.dumps(line), flush=True)

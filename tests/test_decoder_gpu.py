@@ -465,7 +465,7 @@ def test_bench_contract_through_single_rank_rccl(config, batch, gemm_mode):
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
-    line = _run_bench(['--config', config, '--batch', str(batch), '--steps', '3', '--warmup', '1', '--no-cpu-baseline'],
+    line = _run_bench(['--config', config, '--batch', str(batch), '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline'],
                       dict(VQCPC_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK='0', WORLD_SIZE='1',
                            LOCAL_RANK='0'))
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',

@@ -3,7 +3,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/r06e
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-kernel-timing --no-live-pmc --no-extras --no-secondary --no-long"
+COMMON="--full --no-cpu-baseline --no-kernel-timing --no-live-pmc --no-extras --no-secondary --no-long"
 for p in 1 0; do
   rm -rf /tmp/prof_p$p
   VQCPC_WEIGHT_PLANES=$p timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_p$p -- python $REPO/bench.py --steps 20 --warmup 4 $COMMON > $OUT/p${p}_bench.log 2>&1

@@ -3,7 +3,7 @@
 import os
 import sys, time, collections
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-sys.argv = ['bench.py', '--config', sys.argv[1], '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-kernel-timing']
+sys.argv = ['bench.py', '--config', sys.argv[1], '--steps', '10', '--warmup', '3', '--full', '--no-cpu-baseline', '--no-kernel-timing']
 import torch
 from vqcpc_bach_amd import hip, ops
 stats = collections.defaultdict(lambda: [0, 0.0])

@@ -1,6 +1,6 @@
 """HBM bytes per GEMM launch from two rocprofv3 PMC passes of bench.py (MI355X_MICROARCH.md, HBM / rocprofv3 section):
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d <dir>/fetch -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d <dir>/fetch -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing
     rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d <dir>/write -- python bench.py ... (same command)
     python tools/pmc_hbm_traffic.py <dir> [steps incl. warm-up = 3] > profiles/rNN_gemm_hbm_traffic.json
 

@@ -32,7 +32,7 @@ def main():
         d = '/tmp/pmc_k'
         shutil.rmtree(d, ignore_errors=True)
         cmd = ['rocprofv3', '--kernel-trace', '--pmc'] + g + ['-f', 'csv', '-d', d, '--', sys.executable, os.path.join(REPO, 'bench.py'),
-               '--config', cfg, '--steps', '2', '--warmup', '1', '--no-graph', '--no-cpu-baseline', '--no-kernel-timing', '--no-live-pmc',
+               '--config', cfg, '--steps', '2', '--warmup', '1', '--no-graph', '--full', '--no-cpu-baseline', '--no-kernel-timing', '--no-live-pmc',
                '--no-extras'] + (['--gemm-mode', 'bf16'] if cfg == 'C4' else [])
         subprocess.run(cmd, cwd='/tmp', env=dict(os.environ, TMPDIR='/tmp'), capture_output=True, text=True, timeout=900)
         for f in glob.glob(d + '/**/*counter_collection.csv', recursive=True):

@@ -10,7 +10,7 @@ import traceback
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 cfg = sys.argv[1] if len(sys.argv) > 1 else 'C1'
 STEPS = 4
-sys.argv = ['bench.py', '--config', cfg, '--steps', str(STEPS), '--warmup', '1', '--no-cpu-baseline', '--no-kernel-timing', '--no-graph']
+sys.argv = ['bench.py', '--config', cfg, '--steps', str(STEPS), '--warmup', '1', '--full', '--no-cpu-baseline', '--no-kernel-timing', '--no-graph']
 import torch  # noqa: E402
 
 count = collections.Counter()
