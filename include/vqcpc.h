@@ -654,6 +654,37 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
                         float eps, const uint64_t* step_dev, float grad_scale, float max_norm, const double* sumsq,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Autoregressive generation (VQCPCB/decoders/decoder.py:552-723, utils.py:101-128): the kernels of one KV-cached
+ * decoder step for M <= 64 sequences (vqcpc_bach_amd/decoders/generation.py).  Adding them left the ABI version alone.
+ *
+ * vqcpc_decode_linear: y[M][N] = relu?(x W^T + bias) + res  (bias, res optional; relu != 0 applies the ReLU before the
+ *   residual).  x row m = x + (gather ? gather[m] : m) * ldx; W [N][K] row-major.  M <= 64, N, K <= 4096, K % 4 == 0.
+ *   Plain fp32 FMA in a fixed reduction order per element that does not depend on M (batch-invariant rows).  y != x.
+ * vqcpc_decode_attn: one query row per (sequence b, head h); the position is read from pos[0] (device int32).
+ *   Self mode (k_new, v_new != NULL; mask 1, ratio 1): rows b of k_new / v_new (stride ldn, head h = columns [h*hd,
+ *   (h+1)*hd)) are stored into k_cache / v_cache at row b * Lk + pos (stride ldc), then keys 0..pos are attended with the
+ *   bias q.e1[h, Lk-1-(pos-j)].  Cross mode (k_new == NULL): the Lk cached memory rows, p = pos / ratio, mask 0 none /
+ *   1 causal (j <= p) / 2 anticausal (j >= p), bias of vqcpc_relattn_x_fwd.  q unscaled; ctx [M][ldo].  hd in
+ *   {16, 32, 64, 128}, Lk <= 1024, no dropout.
+ * vqcpc_decode_sample: one step's tail, ONE workgroup.  voice c = pos % nc; voice_offsets (HOST int32 [nc + 1]) give its
+ *   logits columns.  Per row b: logits / temperature, tokens whose bit is set in exclude[c][8] (device uint32, NULL =
+ *   none) to -inf, top-k (drop logits < the k-th largest; 0 = off), top-p (utils.py:116-126; top_p <= 0 or >= 1 = off),
+ *   softmax, one draw from the counter-based hash keyed by (seeds[b], pos) -- or, teacher != NULL, the token
+ *   teacher[b * ldteach + pos].  Writes tokens[b * ldtok + pos], next_in row b = table row token * U + pos % U (the
+ *   input of position pos + 1, decoders/decoder.py:_target_rows), optionally the filtered probabilities probs[b][0..V_c),
+ *   and finally pos[0] = pos + 1.  Nothing happens once pos >= T.  M <= 64, nc <= 16, V_c <= 256, d <= 4096.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_decode_linear(const float* x, int64_t ldx, const int64_t* gather, const float* w, const float* bias, const float* res,
+                        int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int relu, void* stream);
+int vqcpc_decode_attn(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
+                      const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
+                      const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, void* stream);
+int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
+                        int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
+                        int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,
+                        int U, float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

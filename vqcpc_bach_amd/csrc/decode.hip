@@ -1,0 +1,487 @@
+// Autoregressive generation of the decoder (reference: VQCPCB/decoders/decoder.py:552-723, utils.py:101-128): the
+// kernels of ONE incremental step, for a few rows (M <= 64 sequences) at a time.
+//
+// Nothing in the decoder looks ahead (causal target self-attention, a memory that does not depend on the target,
+// row-wise embedding / LayerNorm / FFN), so position t's logits depend on tokens < t only and a KV-cached step computes
+// the same function at one row per layer and token (vqcpc_bach_amd/decoders/generation.py):
+//   * vqcpc_decode_linear: y = x W^T + b (ReLU) (+ residual) for M <= 64 rows.  Weight-streaming: a wavefront owns two
+//     output columns, reads their rows of W once per 32 input rows and applies them to every row.  Plain fp32 FMA in a fixed
+//     order per output element -- lane l sums k = 4l + 256i (i ascending, the four components in order), then a xor
+//     butterfly over the 64 lanes -- which does not depend on M: row b of a batch is bit-identical to the row alone.
+//   * vqcpc_decode_attn: one query row per (sequence, head) against the layer's K/V cache (self: the step's k / v row is
+//     stored at row `pos` first; causal) or the memory's K/V (cross: the rectangular rule of vqcpc_relattn_x_fwd).
+//     `pos` is read from device memory, so a captured step is position-independent.
+//   * vqcpc_decode_sample: temperature, exclusion mask, top-k, top-p, softmax and one counter-based draw per row; writes the
+//     token, the next step's input row (a row of the target table) and advances `pos`.  ONE workgroup: the position
+//     counter is read by every kernel of the step and written here once, after a barrier.
+#include <algorithm>
+
+#include "common.h"
+
+namespace vq {
+
+constexpr int kDecMaxRows = 64;
+constexpr int kDecMaxDim = 4096;
+constexpr int kDecMaxLk = 1024;
+constexpr int kDecMaxVoices = 16;
+constexpr int kDecMaxVocab = 256;
+constexpr int kLinCols = 2;                  // output columns per wavefront
+constexpr int kLinWaves = 4;
+constexpr float kDecNegBig = -1.0e30f;       // the masked score of relattn_x.hip: exp(kDecNegBig - max) == 0
+
+// =====================================================================================================================
+// decode_linear
+template <int RB>
+__global__ __launch_bounds__(64 * kLinWaves) void decode_linear_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                       const int64_t* __restrict__ gather,
+                                                                       const float* __restrict__ w,
+                                                                       const float* __restrict__ bias,
+                                                                       const float* __restrict__ res, int64_t ldr,
+                                                                       float* __restrict__ y, int64_t ldy, int M, int N,
+                                                                       int K, int relu) {
+    static_assert(RB * kLinCols <= 64, "one output element per lane in the epilogue");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n0 = (blockIdx.x * kLinWaves + wave) * kLinCols;
+    if (n0 >= N) return;                                     // wave-uniform; the kernel has no barrier
+    const float* wr[kLinCols];
+#pragma unroll
+    for (int c = 0; c < kLinCols; ++c) wr[c] = w + (int64_t)min(n0 + c, N - 1) * K;
+    for (int m0 = 0; m0 < M; m0 += RB) {
+        const int rows = min(RB, M - m0);
+        const float* xr[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const int m = m0 + min(r, rows - 1);
+            xr[r] = x + (gather ? gather[m] : (int64_t)m) * ldx;
+        }
+        float acc[kLinCols][RB];
+#pragma unroll
+        for (int c = 0; c < kLinCols; ++c)
+#pragma unroll
+            for (int r = 0; r < RB; ++r) acc[c][r] = 0.0f;
+        for (int k = 4 * lane; k < K; k += 256) {
+            float4 wv[kLinCols];
+#pragma unroll
+            for (int c = 0; c < kLinCols; ++c) wv[c] = *reinterpret_cast<const float4*>(wr[c] + k);
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                if (r < rows) {
+                    const float4 xv = *reinterpret_cast<const float4*>(xr[r] + k);
+#pragma unroll
+                    for (int c = 0; c < kLinCols; ++c) {
+                        float a = acc[c][r];
+                        a = fmaf(wv[c].x, xv.x, a);
+                        a = fmaf(wv[c].y, xv.y, a);
+                        a = fmaf(wv[c].z, xv.z, a);
+                        a = fmaf(wv[c].w, xv.w, a);
+                        acc[c][r] = a;
+                    }
+                }
+            }
+        }
+        // butterfly: every lane ends with the same sums (a + b == b + a at each level), lane c * RB + r stores (r, c)
+        float mine = 0.0f;
+#pragma unroll
+        for (int c = 0; c < kLinCols; ++c)
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                if (r < rows) {
+                    const float s = wave_sum(acc[c][r]);
+                    if (lane == c * RB + r) mine = s;
+                }
+            }
+        const int c = lane / RB, r = lane % RB;
+        if (c < kLinCols && r < rows && n0 + c < N) {
+            const int m = m0 + r, n = n0 + c;
+            float v = mine + (bias ? bias[n] : 0.0f);
+            if (relu) v = fmaxf(v, 0.0f);
+            if (res) v += res[(int64_t)m * ldr + n];
+            y[(int64_t)m * ldy + n] = v;
+        }
+    }
+}
+
+// =====================================================================================================================
+// decode_attn: one workgroup per (sequence, head); thread j walks keys j, j + 256, ...
+__device__ __forceinline__ float block_max256(float v, float* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// s_k = qs.k and s_e = qs.e in one pass (the loads of both rows in flight together); sequential fp32 FMA over c
+template <int HD>
+__device__ __forceinline__ void dot_rows(const float* __restrict__ qs, const float* __restrict__ kr, const float* __restrict__ er,
+                                         float& s_k, float& s_e) {
+    float a = 0.0f, e = 0.0f;
+#pragma unroll 4
+    for (int c = 0; c < HD; c += 4) {
+        const float4 t = *reinterpret_cast<const float4*>(kr + c);
+        const float4 u = *reinterpret_cast<const float4*>(er + c);
+        a = fmaf(qs[c], t.x, a);
+        a = fmaf(qs[c + 1], t.y, a);
+        a = fmaf(qs[c + 2], t.z, a);
+        a = fmaf(qs[c + 3], t.w, a);
+        e = fmaf(qs[c], u.x, e);
+        e = fmaf(qs[c + 1], u.y, e);
+        e = fmaf(qs[c + 2], u.z, e);
+        e = fmaf(qs[c + 3], u.w, e);
+    }
+    s_k = a;
+    s_e = e;
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void decode_attn_kernel(const float* __restrict__ q, int64_t ldq, float* __restrict__ kc,
+                                                          float* __restrict__ vc, int64_t ldc,
+                                                          const float* __restrict__ knew, const float* __restrict__ vnew,
+                                                          int64_t ldn, const float* __restrict__ e1,
+                                                          const float* __restrict__ e2, float* __restrict__ ctx, int64_t ldo,
+                                                          const int32_t* __restrict__ posp, int Lk, int ratio, int H,
+                                                          int mask, float scale) {
+    constexpr int G = 1024 / HD;                             // key groups of the P.V product
+    __shared__ __attribute__((aligned(16))) float qs[HD];
+    __shared__ float sc[kDecMaxLk];
+    __shared__ __attribute__((aligned(16))) float part[1024];
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x / H;
+    const int h = (int)(blockIdx.x % H);
+    const int pos = *posp;
+    const bool self = knew != nullptr;
+    const int p = self ? pos : pos / ratio;
+    if (pos < 0 || p >= Lk) return;                          // past the end: nothing to attend (uniform)
+    const int64_t hoff = (int64_t)h * HD;
+    if (self) {                                              // the step's k / v row joins the cache at row pos
+        for (int c = tid; c < HD; c += 256) {
+            kc[(b * Lk + pos) * ldc + hoff + c] = knew[b * ldn + hoff + c];
+            vc[(b * Lk + pos) * ldc + hoff + c] = vnew[b * ldn + hoff + c];
+        }
+    }
+    for (int c = tid; c < HD; c += 256) qs[c] = q[b * ldq + hoff + c] * scale;
+    __syncthreads();
+    // scores: qs.k_j + qs.Erel[j - p + Lk - 1] (the two sums of relattn_x_fwd_kernel, added in the same order)
+    float mx = kDecNegBig;
+    for (int j = tid; j < Lk; j += 256) {
+        const bool keep = ((mask == 0) | ((mask == 1) & (j <= p)) | ((mask == 2) & (j >= p))) && (!self || j <= pos);
+        float s = kDecNegBig;
+        if (keep) {
+            const float* kr = (self && j == pos) ? knew + b * ldn + hoff : kc + (b * Lk + j) * ldc + hoff;
+            const int xr = j - p + Lk - 1;
+            const float* er = xr < Lk ? e1 + ((int64_t)h * Lk + xr) * HD : e2 + ((int64_t)h * Lk + (xr - Lk + 1)) * HD;
+            float sk, se;
+            dot_rows<HD>(qs, kr, er, sk, se);
+            s = sk + se;
+        }
+        sc[j] = s;
+        mx = fmaxf(mx, s);
+    }
+    const float m = block_max256(mx, red);
+    float sum = 0.0f;
+    for (int j = tid; j < Lk; j += 256) {
+        const float s = sc[j];
+        const float e = s > 0.5f * kDecNegBig ? __expf(s - m) : 0.0f;
+        sc[j] = e;
+        sum += e;
+    }
+    const float inv = 1.0f / block_sum256(sum, red);
+    // ctx[c] = sum_j p_j v_j[c]: thread (g, c4) owns columns 4c4 .. 4c4 + 3 and keys j = g, g + G, ...  (eight in flight);
+    // the G partial sums are added in group order
+    const int c4 = tid % (HD / 4), g = tid / (HD / 4);
+    const int jend = self ? pos + 1 : Lk;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j0 = g; j0 < jend; j0 += 8 * G) {
+        float4 vv[8];
+        float pj[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = min(j0 + u * G, jend - 1);
+            const float* vr = (self && j == pos) ? vnew + b * ldn + hoff : vc + (b * Lk + j) * ldc + hoff;
+            vv[u] = *reinterpret_cast<const float4*>(vr + 4 * c4);
+            pj[u] = j0 + u * G < jend ? sc[j] * inv : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {                    // masked keys: p == 0 and the (unwritten) row is never used
+            if (pj[u] != 0.0f) {
+                o.x = fmaf(pj[u], vv[u].x, o.x);
+                o.y = fmaf(pj[u], vv[u].y, o.y);
+                o.z = fmaf(pj[u], vv[u].z, o.z);
+                o.w = fmaf(pj[u], vv[u].w, o.w);
+            }
+        }
+    }
+    reinterpret_cast<float4*>(part)[tid] = o;
+    __syncthreads();
+    if (tid < HD) {
+        const int cc = tid;
+        float t = part[cc];
+        for (int gg = 1; gg < G; ++gg) t += part[gg * HD + cc];
+        ctx[b * ldo + hoff + cc] = t;
+    }
+}
+
+// =====================================================================================================================
+// decode_sample: one workgroup of 16 wavefronts; wavefront w takes rows w, w + 16, ...  Lane l owns tokens 4l .. 4l + 3
+// of the row (V_c <= 256), so the cumulative sums are a lane-serial scan of four plus a wave scan of the lane totals.
+constexpr int kSampWaves = 16;
+
+struct VoiceOffsets {
+    int off[kDecMaxVoices + 1];
+};
+
+__device__ __forceinline__ float wave_incl_scan(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
+    const float* __restrict__ logits, int64_t ldl, VoiceOffsets vo, int nc, int M, float temperature, int top_k, float top_p,
+    const uint32_t* __restrict__ exclude, const int64_t* __restrict__ seeds, const int64_t* __restrict__ teacher,
+    int64_t ldteach, int64_t* __restrict__ tokens, int64_t ldtok, int T, const float* __restrict__ table, int64_t table_rows,
+    int d, int U, float* __restrict__ next_in, int64_t ldn, float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp) {
+    __shared__ float sl[kSampWaves][kDecMaxVocab];            // a wave's (filtered) logits
+    __shared__ float srt[kSampWaves][kDecMaxVocab];           // top-p: probabilities in descending order, then their cumsum
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pos = *posp;
+    const bool live_pos = pos >= 0 && pos < T;
+    const int c = live_pos ? pos % nc : 0;
+    const int V = vo.off[c + 1] - vo.off[c];
+    const float ninf = -INFINITY;
+    for (int r0 = 0; r0 < M; r0 += kSampWaves) {             // uniform trip count: every wave reaches every barrier
+        const int b = r0 + wave;
+        const bool act = live_pos && b < M;
+        float l[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int i = 4 * lane + t;
+            float v = ninf;
+            if (act && i < V) {
+                v = logits[(int64_t)b * ldl + vo.off[c] + i] / temperature;
+                if (exclude && ((exclude[c * 8 + (i >> 5)] >> (i & 31)) & 1u)) v = ninf;
+            }
+            l[t] = v;
+            sl[wave][i] = v;
+        }
+        __syncthreads();
+        // top-k (utils.py:111-114): drop logits < the k-th largest, i.e. those with at least k strictly larger ones
+        if (act && top_k > 0 && top_k < V) {
+            int gt[4] = {0, 0, 0, 0};
+            for (int j = 0; j < V; ++j) {
+                const float o = sl[wave][j];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) gt[t] += o > l[t];
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (gt[t] >= top_k) l[t] = ninf;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sl[wave][4 * lane + t] = l[t];
+        __syncthreads();
+        // top-p (utils.py:116-126): softmax over the sorted survivors, drop entries whose cumulative probability BEFORE
+        // them exceeds top_p (the shift by one), the first is always kept
+        const bool nucleus = top_p > 0.0f && top_p < 1.0f;
+        int rank[4];
+        if (act && nucleus) {
+            float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
+            mx = wave_max(mx);
+            float e[4], s = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                e[t] = l[t] > ninf ? expf(l[t] - mx) : 0.0f;
+                s += e[t];
+            }
+            const float inv = 1.0f / wave_sum(s);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) rank[t] = 4 * lane + t;          // tokens >= V keep their own slot
+            int gt[4] = {0, 0, 0, 0};
+            for (int j = 0; j < V; ++j) {
+                const float o = sl[wave][j];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) gt[t] += (o > l[t]) | ((o == l[t]) & (j < 4 * lane + t));
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (4 * lane + t < V) rank[t] = gt[t];
+                srt[wave][rank[t]] = 4 * lane + t < V ? e[t] * inv : 0.0f;
+            }
+        }
+        __syncthreads();
+        if (act && nucleus) {
+            float v[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v[t] = srt[wave][4 * lane + t];
+            v[1] += v[0];
+            v[2] += v[1];
+            v[3] += v[2];
+            const float base = wave_incl_scan(v[3], lane) - v[3];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v[t] += base;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) srt[wave][4 * lane + t] = v[t];
+        }
+        __syncthreads();
+        if (act && nucleus) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (rank[t] >= 1 && rank[t] < V && srt[wave][rank[t] - 1] > top_p) l[t] = ninf;
+        }
+        // softmax of the filtered row and one draw: the first token whose inclusive cumulative weight exceeds u * total
+        if (act) {
+            float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
+            mx = wave_max(mx);
+            float e[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) e[t] = l[t] > ninf ? expf(l[t] - mx) : 0.0f;
+            float cum[4];
+            cum[0] = e[0];
+            cum[1] = cum[0] + e[1];
+            cum[2] = cum[1] + e[2];
+            cum[3] = cum[2] + e[3];
+            const float base = wave_incl_scan(cum[3], lane) - cum[3];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) cum[t] += base;
+            const float total = __shfl(cum[3], 63, 64);
+            if (probs) {
+                const float inv = 1.0f / total;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (4 * lane + t < V) probs[(int64_t)b * ldp + 4 * lane + t] = e[t] * inv;
+            }
+            int tok;
+            if (teacher) {
+                tok = (int)teacher[(int64_t)b * ldteach + pos];
+            } else {
+                const uint64_t sd = (uint64_t)seeds[b];
+                const uint32_t r = rng_u24_from_x0(rng_x0(sd, (uint32_t)pos), (uint32_t)(sd >> 32));
+                const float target = ((float)r + 0.5f) * (1.0f / 16777216.0f) * total;
+                // the first token of non-zero weight whose cumulative weight exceeds the target (the cumulative sums
+                // need not be monotone to the last bit across lanes: the scan rounds in tree order); none (u * total
+                // rounded up to total): the last token of non-zero weight
+                int first = 1 << 30, last = -1;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    if (e[t] > 0.0f) {
+                        if (cum[t] > target) first = min(first, 4 * lane + t);
+                        last = 4 * lane + t;
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    first = min(first, __shfl_xor(first, o, 64));
+                    last = max(last, __shfl_xor(last, o, 64));
+                }
+                tok = first < (1 << 30) ? first : last;
+            }
+            tok = min(max(tok, 0), V - 1);
+            if (lane == 0) tokens[(int64_t)b * ldtok + pos] = tok;
+            const int64_t row = min((int64_t)tok * U + pos % U, table_rows - 1);     // _target_rows: input of position pos + 1
+            for (int k = lane; k < d; k += 64) next_in[(int64_t)b * ldn + k] = table[row * d + k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && live_pos) *posp = pos + 1;      // after the barrier: every thread has read pos
+}
+
+}  // namespace vq
+
+using namespace vq;
+
+extern "C" {
+
+int vqcpc_decode_linear(const float* x, int64_t ldx, const int64_t* gather, const float* w, const float* bias, const float* res,
+                        int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int relu, void* stream) {
+    VQ_REQUIRE(x && w && y && M >= 1 && M <= kDecMaxRows && N >= 1 && N <= kDecMaxDim && K >= 4 && K <= kDecMaxDim && K % 4 == 0,
+               "decode_linear: bad arguments (1 <= M <= 64, 1 <= N <= 4096, 4 <= K <= 4096, K %% 4 == 0)");
+    VQ_REQUIRE(ldx >= K && ldx % 4 == 0 && ldy >= N && (!res || ldr >= N) && aligned16(x) && aligned16(w),
+               "decode_linear: bad leading dimensions or alignment");
+    VQ_REQUIRE(x != y, "decode_linear: y may not alias x");
+    const int cols = kLinWaves * kLinCols;
+    const dim3 grid((unsigned)ceil_div(N, cols)), block(64 * kLinWaves);
+    hipStream_t s = (hipStream_t)stream;
+    if (M <= 8)
+        hipLaunchKernelGGL(decode_linear_kernel<8>, grid, block, 0, s, x, ldx, gather, w, bias, res, ldr, y, ldy, (int)M, N, K,
+                           relu);
+    else
+        hipLaunchKernelGGL(decode_linear_kernel<32>, grid, block, 0, s, x, ldx, gather, w, bias, res, ldr, y, ldy, (int)M, N, K,
+                           relu);
+    VQ_CHECK_LAUNCH("decode_linear");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_attn(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
+                      const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
+                      const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, void* stream) {
+    VQ_REQUIRE(q && k_cache && v_cache && e1 && e2 && ctx && pos && M >= 1 && M <= kDecMaxRows && Lk >= 1 && Lk <= kDecMaxLk &&
+               ratio >= 1 && H >= 1 && mask >= 0 && mask <= 2,
+               "decode_attn: bad arguments (1 <= M <= 64, 1 <= Lk <= 1024, mask in {0, 1, 2})");
+    VQ_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "decode_attn: hd must be 16, 32, 64 or 128 (got %d)", hd);
+    const int64_t d = (int64_t)H * hd;
+    VQ_REQUIRE(ldq >= d && ldc >= d && ldo >= d && ldq % 4 == 0 && ldc % 4 == 0 && aligned16(q) && aligned16(k_cache) &&
+               aligned16(e1) && aligned16(e2), "decode_attn: bad leading dimensions or alignment");
+    VQ_REQUIRE((k_new == nullptr) == (v_new == nullptr), "decode_attn: k_new and v_new go together");
+    if (k_new)
+        VQ_REQUIRE(mask == 1 && ratio == 1 && ldn >= d && ldn % 4 == 0 && aligned16(k_new),
+                   "decode_attn: self mode (k_new given) is causal with ratio 1");
+    const float scale = 1.0f / sqrtf((float)hd);
+    const dim3 grid((unsigned)(M * H)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define DEC_ATTN(HD)                                                                                                           \
+    hipLaunchKernelGGL(decode_attn_kernel<HD>, grid, block, 0, s, q, ldq, k_cache, v_cache, ldc, k_new, v_new, ldn, e1, e2,   \
+                       ctx, ldo, pos, Lk, ratio, H, mask, scale)
+    switch (hd) {
+        case 16: DEC_ATTN(16); break;
+        case 32: DEC_ATTN(32); break;
+        case 64: DEC_ATTN(64); break;
+        default: DEC_ATTN(128); break;
+    }
+#undef DEC_ATTN
+    VQ_CHECK_LAUNCH("decode_attn");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
+                        int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
+                        int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,
+                        int U, float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream) {
+    VQ_REQUIRE(logits && voice_offsets && tokens && table && next_in && pos && nc >= 1 && nc <= kDecMaxVoices && M >= 1 &&
+               M <= kDecMaxRows && T >= 1 && d >= 1 && d <= kDecMaxDim && U >= 1 && table_rows >= 1,
+               "decode_sample: bad arguments (1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)");
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "decode_sample: temperature > 0, top_k >= 0");
+    VQ_REQUIRE(teacher || seeds, "decode_sample: seeds are needed unless the tokens are teacher-forced");
+    VoiceOffsets vo;
+    vo.off[0] = voice_offsets[0];
+    VQ_REQUIRE(vo.off[0] >= 0, "decode_sample: negative voice offset");
+    int vmax = 0;
+    for (int c = 0; c < nc; ++c) {
+        const int V = voice_offsets[c + 1] - voice_offsets[c];
+        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "decode_sample: voice %d has %d tokens (1 <= V_c <= 256)", c, V);
+        vo.off[c + 1] = voice_offsets[c + 1];
+        vmax = std::max(vmax, V);
+    }
+    for (int c = nc + 1; c <= kDecMaxVoices; ++c) vo.off[c] = vo.off[nc];
+    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!teacher || ldteach >= T) && (!probs || ldp >= vmax),
+               "decode_sample: bad leading dimensions");
+    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "decode_sample: the table has too few rows for V_c * U");
+    hipLaunchKernelGGL(decode_sample_kernel, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc, (int)M,
+                       temperature, top_k, top_p, exclude, seeds, teacher, ldteach, tokens, ldtok, T, table, table_rows, d, U,
+                       next_in, ldn, probs, ldp, pos);
+    VQ_CHECK_LAUNCH("decode_sample");
+    return VQCPC_OK;
+}
+
+}  // extern "C"

@@ -4,8 +4,9 @@ relative transformer that reconstructs the token sequence from the frozen encode
 Covered: `transformer_type='relative'` with causal target self-attention, anticausal or full source self-attention and
 anticausal or full cross-attention -- getters.py decoder_type 'transformer_relative' / 'transformer_relative_fullCross'.
 `__init__`, `forward`, `epoch`, `train_model`, `init_optimizers`, `save` / `load` keep the reference's names, argument
-meaning, state_dict keys and return contracts.  Generation / re-harmonisation (:552-1062), the absolute-position and
-'diagonal' variants are out of scope and raise.
+meaning, state_dict keys and return contracts.  `generate` / `generate_from_codes` / `init_generation` (:552-726) run
+KV-cached incremental decoding on the GPU (decoders/generation.py); the sliding-window and re-harmonisation generators
+(:728-1062), the absolute-position and 'diagonal' variants are out of scope and raise.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
   * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient);
@@ -20,6 +21,7 @@ Reference defect fixed: `epoch` (:327-344) passes the quantizer's (B, S, num_cod
 raises; the codes are merged with `Encoder.merge_codes` first, as `generate` (:600) does.
 """
 import os
+from datetime import datetime
 from itertools import islice
 
 import numpy as np
@@ -218,18 +220,25 @@ class Decoder(GraphedTraining, nn.Module):
         return self
 
     # ---- forward ---------------------------------------------------------------------------------------------------
-    def _target_rows(self, x):
-        """(B, events, channels) int64 on the device -> (B * T, d_model) shifted target rows (see module docstring)."""
-        B = x.shape[0]
+    def _target_table(self, dev):
+        """(vmax * U + 1, d_model) rows of `linear_target(cat[embed(token), channel emb, event-in-code emb])`: row v * U + u
+        holds token v at position u of a code block, the last row is the start-of-sentence row (see module docstring)."""
         nc, U, d = self.num_channels, self.total_upscaling, self.d_model
         tables = self.data_processor.stacked_tables()                                       # (nc, vmax, emb)
         vmax = tables.shape[1]
-        dev = x.device
         syn = torch.arange(vmax, device=dev).repeat_interleave(U)                            # table row v * U + u holds token v
         x_table = ops.EmbedPosFn.apply(syn, tables, self.target_channel_embeddings.view(nc, -1),
                                        self.target_events_positioning_embeddings.view(self.num_events_per_code, -1), U)
         tgt_table = ops.linear(x_table, self.linear_target.weight, self.linear_target.bias)  # (vmax * U, d)
-        table = torch.cat([tgt_table, self.sos.view(1, d)], dim=0)                           # + start-of-sentence row
+        return torch.cat([tgt_table, self.sos.view(1, d)], dim=0)                            # + start-of-sentence row
+
+    def _target_rows(self, x):
+        """(B, events, channels) int64 on the device -> (B * T, d_model) shifted target rows (see module docstring)."""
+        B = x.shape[0]
+        U = self.total_upscaling
+        dev = x.device
+        table = self._target_table(dev)
+        vmax = (table.shape[0] - 1) // U
         tok = flatten(x)                                                                     # (B, T), t = event * nc + voice
         T = tok.shape[1]
         idx = tok * U + (torch.arange(T, device=dev) % U)
@@ -357,8 +366,101 @@ class Decoder(GraphedTraining, nn.Module):
             history.append((train, val))
         return history
 
-    def generate(self, *a, **k):
-        raise NotImplementedError('generation / re-harmonisation (decoder.py:552-1062) is out of scope: SURVEY.md section 2')
+    # ---- generation (:552-726): KV-cached incremental decoding on the GPU, decoders/generation.py --------------------
+    def init_generation(self, num_events):
+        """:723-726: an all-zero (1, num_events, num_channels) token tensor on the device."""
+        return torch.zeros(1, num_events, self.num_channels, dtype=torch.int64, device=self.sos.device)
 
-    generate_from_code_long = generate_reharmonisation = generate_alla_mano = check_duplicate = compute_start_end_times = \
-        init_generation = plot = generate
+    def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
+                            use_graph=True):
+        """Samples target sequences from MERGED codes (B, S) (what `forward` takes): each row repeated `num_decodings` times
+        (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
+        temperature / top-k / top-p rule (utils.py:101-128) on the GPU.
+        exclude_tokens: per voice, token ids never drawn (the meta symbols of exclude_meta_symbols); seed: an int (per-row
+        seeds derived from it), a per-row int64 tensor, or None (drawn from torch's generator).  use_graph=False runs the
+        steps eagerly (same tokens).  -> int64 tokens (B * num_decodings, events, channels) on the device."""
+        from .generation import MAX_ROWS, IncrementalDecoder, row_seeds
+        dev = self.sos.device
+        codes = torch.as_tensor(codes).to(dev, torch.int64)
+        if codes.dim() != 2 or codes.shape[1] != self.num_tokens_source:
+            raise ValueError(f'codes: (batch, {self.num_tokens_source}) merged codes expected, got {tuple(codes.shape)}')
+        if num_decodings > 1:
+            codes = codes.repeat_interleave(num_decodings, dim=0)
+        B, T, nc = codes.shape[0], self.num_tokens_target, self.num_channels
+        seeds = row_seeds(seed, B)
+        out = torch.empty(B, T, dtype=torch.int64, device=dev)
+        with STEP_LOCK, torch.no_grad():               # never interleaved with a training step of another thread
+            was_training = self.training
+            self.eval()
+            try:
+                for b0 in range(0, B, MAX_ROWS):
+                    n = min(MAX_ROWS, B - b0)
+                    inc = IncrementalDecoder(self, n)
+                    inc.prefill(codes[b0:b0 + n])
+                    inc.start(seeds=seeds[b0:b0 + n], temperature=temperature, top_k=top_k, top_p=top_p,
+                              exclude=exclude_tokens)
+                    out[b0:b0 + n] = inc.run(use_graph=use_graph)
+                    del inc
+            finally:
+                self.train(was_training)
+        return out.view(B, T // nc, nc)
+
+    def _meta_symbol_ids(self):
+        ds = getattr(self.dataloader_generator, 'dataset', None)
+        n2i = getattr(ds, 'note2index_dicts', None)
+        if n2i is None:
+            raise ValueError('exclude_meta_symbols=True needs dataset.note2index_dicts with the START / END / PAD symbols; '
+                             'this dataset (e.g. the synthetic one) has no meta symbols')
+        syms = ('START', 'END', 'XX')                  # START_SYMBOL, END_SYMBOL, PAD_SYMBOL (datasets/helpers.py:5-9)
+        return [[n2i[c][s] for s in syms if s in n2i[c]] for c in range(self.num_channels)]
+
+    def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
+                 plot_attentions=False, code_juxtaposition=False, seed=None):
+        """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
+        second half of another), its merged codes, `batch_size` generations from them, the codes of original +
+        generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
+        code_juxtaposition) as the reference writes them.  Returns {'original', 'generation', 'codes', 'recoding'} tensors
+        instead of music21 scores (no score writing here).  seed: as generate_from_codes."""
+        if plot_attentions:
+            raise NotImplementedError('plot_attentions: attention plots need the full forward per token (matplotlib); '
+                                      'not available on the incremental path')
+        exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
+        generator_train, generator_val, _ = self.dataloader_generator.dataloaders(batch_size=1, shuffle_val=True)
+        if seed_set == 'val':
+            stream = generator_val
+        elif seed_set == 'train':
+            stream = generator_train
+        else:
+            raise Exception('Need to indicate seeds dataset')
+        dev = self.sos.device
+        if code_juxtaposition:
+            beginning, end = next(iter(stream)), next(iter(stream))
+            half = beginning['x'].shape[1] // 2
+            x_original_single = torch.cat([beginning['x'][:, :half], end['x'][:, half:]], dim=1)
+        else:
+            x_original_single = next(iter(stream))['x']
+        x_original_single = x_original_single.to(dev).long()
+        x_original = x_original_single.repeat(batch_size, 1, 1)
+        was_training = self.training
+        self.eval()
+        try:
+            codes = self.encode(x_original)
+            x = self.generate_from_codes(codes, temperature=temperature, top_k=top_k, top_p=top_p, exclude_tokens=exclude,
+                                         seed=seed)
+            recoding = self.encode(torch.cat([x_original_single, x], dim=0))
+        finally:
+            self.train(was_training)
+        timestamp = datetime.now().strftime('%Y-%m-%d_%H-%M-%S')
+        save_dir = f'{self.model_dir}/juxtapositions' if code_juxtaposition else f'{self.model_dir}/generations'
+        os.makedirs(save_dir, exist_ok=True)
+        with open(f'{save_dir}/{timestamp}.txt', 'w') as ff:
+            for aa in recoding.cpu().numpy():
+                ff.write(' , '.join(map(str, list(aa))))
+                ff.write('\n')
+        print(f'Saved in {save_dir}/{timestamp}')
+        return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': recoding}
+
+    def generate_from_code_long(self, *a, **k):
+        raise NotImplementedError('sliding-window generation / re-harmonisation (decoder.py:728-1062) is out of scope')
+
+    generate_reharmonisation = generate_alla_mano = check_duplicate = compute_start_end_times = plot = generate_from_code_long

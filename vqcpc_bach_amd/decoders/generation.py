@@ -1,0 +1,195 @@
+"""KV-cached autoregressive generation of the decoder (reference: VQCPCB/decoders/decoder.py:552-723, which runs one full
+seq2seq forward per generated token and samples on the host).
+
+Position t's logits depend on tokens < t only (causal target self-attention, a memory that does not depend on the target,
+row-wise embedding / LayerNorm / FFN), so one incremental step per token computes the same function:
+
+  prefill (once per call, existing kernels): source embedding + source encoder stack -> memory; per decoder layer the
+  cross-attention k | v of the memory; the target table of `Decoder._target_rows`; the per-voice heads concatenated into
+  one [sum V_c, d] weight.
+
+  step (csrc/decode.hip, 11 launches per layer + 2):  in_proj -> self-attention on the layer's K/V cache (the step's k / v row
+  is stored at row pos) -> out_proj + residual -> add & LayerNorm -> cross q -> cross-attention -> out_proj + residual ->
+  add & LayerNorm -> linear1 + ReLU -> linear2 + residual -> add & LayerNorm;  then the heads and the sampler, which draws
+  the token of position pos, writes the input row of position pos + 1 and advances the device counter `pos`.
+
+Every kernel of the step reads `pos` from device memory, so ONE captured step (torch.cuda.CUDAGraph) is replayed T times.
+Rows are independent and every kernel reduces in an order that does not depend on the number of rows, so a row's tokens
+do not depend on which other rows share the call (given the same memory rows and seed)."""
+import ctypes
+
+import torch
+
+from .. import hip, ops
+from ..transformer.transformer_custom import mask_code
+
+MAX_ROWS = 64                # rows of one incremental decoder (vqcpc_decode_*); larger batches run in chunks
+
+
+def _splitmix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
+def row_seeds(seed, n):
+    """int -> n per-row int64 seeds (splitmix64 of (seed, row)); a tensor of n int64 is taken as it is; None draws one
+    int from torch's CPU generator."""
+    if torch.is_tensor(seed):
+        s = seed.reshape(-1).to(torch.int64)
+        if s.numel() != n:
+            raise ValueError(f'seed: {s.numel()} per-row seeds for {n} rows')
+        return s.cpu()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    vals = [_splitmix64((int(seed) * 0x100000001B3 + r) & 0xFFFFFFFFFFFFFFFF) for r in range(n)]
+    return torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
+
+
+class IncrementalDecoder:
+    """One generation of `batch` <= 64 rows of `decoder` (a Decoder in eval mode; the caller holds utils.STEP_LOCK).
+
+        inc = IncrementalDecoder(dec, B)
+        inc.prefill(codes)                                        # (B, S) merged codes
+        tokens = inc.run(seeds, temperature, top_k, top_p)        # (B, T) int64, position-major (t = event * nc + voice)
+
+    `start` + `step` expose the single steps (teacher forcing, the sampler's inputs `logits` and its optional
+    probability output `probs`) for the tests."""
+
+    def __init__(self, decoder, batch):
+        if not 1 <= batch <= MAX_ROWS:
+            raise ValueError(f'IncrementalDecoder: 1 <= batch <= {MAX_ROWS} (got {batch})')
+        dec = self.dec = decoder
+        self.M = M = int(batch)
+        self.dev = dev = dec.sos.device
+        self.nc, self.U, self.d = dec.num_channels, dec.total_upscaling, dec.d_model
+        self.T, self.S = dec.num_tokens_target, dec.num_tokens_source
+        self.layers = list(dec.transformer.decoder.layers)
+        a = self.layers[0].self_attn
+        self.H, self.hd = a.num_heads, a.head_dim
+        self.ff = self.layers[0].linear1.weight.shape[0]
+        self.cross_mask = mask_code(dec.cross_attention_type)
+        sizes = [int(n) for n in dec.num_tokens_per_channel]
+        self.offsets = [0]
+        for n in sizes:
+            self.offsets.append(self.offsets[-1] + n)
+        self._offsets_c = (ctypes.c_int32 * (self.nc + 1))(*self.offsets)
+        self.vmax = max(sizes)
+        f32 = dict(dtype=torch.float32, device=dev)
+        d, T, L = self.d, self.T, len(self.layers)
+        self.x = torch.empty(M, d, **f32)                     # input rows of the current position
+        self.hb = [torch.empty(M, d, **f32) for _ in range(2)]
+        self.h1, self.h2, self.s, self.att, self.qc = (torch.empty(M, d, **f32) for _ in range(5))
+        self.qkv = torch.empty(M, 3 * d, **f32)
+        self.f = torch.empty(M, self.ff, **f32)
+        self.logits = torch.empty(M, self.offsets[-1], **f32)
+        self.mean, self.rstd = torch.empty(M, **f32), torch.empty(M, **f32)
+        self.kcache = torch.empty(L, M, T, d, **f32)
+        self.vcache = torch.empty(L, M, T, d, **f32)
+        self.tokens = torch.zeros(M, T, dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.seeds = torch.zeros(M, dtype=torch.int64, device=dev)
+        self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
+        self.teacher = None
+        self.probs = None
+        self.memkv = None
+
+    # ---- prefill ---------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prefill(self, codes):
+        dec, M, d = self.dec, self.M, self.d
+        codes = codes.to(self.dev, torch.int64)
+        assert codes.shape == (M, self.S), (codes.shape, (M, self.S))
+        src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
+        memory, _ = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
+        self.memkv = [ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:])
+                      for lay in self.layers]                                           # (M * S, 2d): k | v
+        self.table = dec._target_table(self.dev).contiguous()                          # (vmax * U + 1, d)
+        self.head_w = torch.cat([m.weight for m in dec.pre_softmaxes], dim=0).contiguous()
+        self.head_b = torch.cat([m.bias for m in dec.pre_softmaxes], dim=0).contiguous()
+
+    def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False):
+        """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
+        never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
+        probabilities of the last step in `probs` (M, max V_c)."""
+        if not temperature > 0:
+            raise ValueError('temperature must be > 0')
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        if seeds is not None:
+            self.seeds.copy_(row_seeds(seeds, self.M))
+        bits = torch.zeros(self.nc, 8, dtype=torch.int64)
+        for c, toks in enumerate(exclude or []):
+            for t in toks:
+                bits[c, int(t) // 32] |= 1 << (int(t) % 32)
+        self.exclude.copy_(torch.where(bits >= 1 << 31, bits - (1 << 32), bits).to(torch.int32))
+        self.excluding = bool((bits != 0).any())
+        if teacher is not None:
+            self.teacher = teacher.to(self.dev, torch.int64).reshape(self.M, self.T).contiguous()
+        else:
+            self.teacher = None
+        self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
+        self.reset()
+
+    def reset(self):
+        self.pos.zero_()
+        self.tokens.zero_()
+        self.x.copy_(self.table[-1].expand(self.M, self.d))                            # start-of-sentence row
+
+    # ---- one step ----------------------------------------------------------------------------------------------------
+    def _ln(self, s, norm, out):
+        hip.call('vqcpc_add_layernorm_fwd', s, self.d, None, norm.weight, norm.bias, out, self.mean, self.rstd, self.M, self.d,
+                 1e-5, 0.0, 0)
+
+    def _linear(self, x, w, b, out, res=None, relu=0):
+        N, K = w.shape
+        hip.call('vqcpc_decode_linear', x, x.shape[1], None, w, b, res, out.shape[1] if res is not None else 0, out,
+                 out.shape[1], self.M, N, K, relu)
+
+    def step(self):
+        M, d, T, S, H, hd = self.M, self.d, self.T, self.S, self.H, self.hd
+        hin = self.x
+        for li, lay in enumerate(self.layers):
+            sa, ca = lay.self_attn, lay.multihead_attn
+            hout = self.hb[li % 2]
+            self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
+            q0 = self.qkv.data_ptr()
+            hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
+                     sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, T, 1, H, hd, ops.MASK_CAUSAL)
+            self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
+            self._ln(self.s, lay.norm1, self.h1)
+            hip.call('vqcpc_decode_linear', self.h1, d, None, ca.in_proj_weight, ca.in_proj_bias, None, 0, self.qc, d, M, d, d, 0)
+            kv = self.memkv[li]
+            hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                     ca.attn_bias.e2, self.att, d, self.pos, M, S, T // S, H, hd, self.cross_mask)
+            self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
+            self._ln(self.s, lay.norm2, self.h2)
+            self._linear(self.h2, lay.linear1.weight, lay.linear1.bias, self.f, relu=1)
+            self._linear(self.f, lay.linear2.weight, lay.linear2.bias, self.s, res=self.h2)
+            self._ln(self.s, lay.norm3, hout)
+            hin = hout
+        self._linear(hin, self.head_w, self.head_b, self.logits)
+        teacher = self.teacher
+        hip.call('vqcpc_decode_sample', self.logits, self.logits.shape[1], self._offsets_c, self.nc, M, self.temperature,
+                 self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds, teacher, T, self.tokens, T, T,
+                 self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
+
+    # ---- a whole generation --------------------------------------------------------------------------------------------
+    def run(self, use_graph=True):
+        """T steps from position 0 (after `start`): one captured step replayed T times, or (use_graph=False) T eager
+        steps.  Returns the (M, T) token buffer."""
+        if use_graph:
+            self.step()                       # first launches outside the capture
+            torch.cuda.synchronize(self.dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                self.step()
+            self.reset()
+            for _ in range(self.T):
+                graph.replay()
+            torch.cuda.current_stream(self.dev).synchronize()
+            del graph
+        else:
+            for _ in range(self.T):
+                self.step()
+        return self.tokens

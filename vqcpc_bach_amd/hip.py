@@ -185,6 +185,12 @@ SIGNATURES = {
     'vqcpc_upscale_fwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr]),
     'vqcpc_upscale_bwd_workspace': (c_i64, [c_i64, c_int, c_int]),
     'vqcpc_upscale_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr]),
+    'vqcpc_decode_linear': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int,
+                                    c_ptr]),
+    'vqcpc_decode_attn': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                                  c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    'vqcpc_decode_sample': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                                    c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
 }
 
 # Entry points of LAB builds only (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so, the `#ifdef VQCPC_LAB`
