@@ -674,6 +674,24 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
  *   teacher[b * ldteach + pos].  Writes tokens[b * ldtok + pos], next_in row b = table row token * U + pos % U (the
  *   input of position pos + 1, decoders/decoder.py:_target_rows), optionally the filtered probabilities probs[b][0..V_c),
  *   and finally pos[0] = pos + 1.  Nothing happens once pos >= T.  M <= 64, nc <= 16, V_c <= 256, d <= 4096.
+ *
+ * Sliding-window generation (decoders/decoder.py:729-854): the window moves by one code, the caches of its P prefix rows
+ * are rebuilt teacher-forced (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_block_table_gather for the row-wise parts).
+ * vqcpc_decode_prefill_attn: query rows i in [0, P) of each of M sequences, q row b * P + i (stride ldq), at position i
+ *   of an Lq = ratio * Lk problem whose tables e1, e2 have Lk rows.  Self mode (k_cache, v_cache != NULL; mask 1, ratio 1):
+ *   k / v rows b * P + j (stride ldk; the in_proj output) are stored into k_cache / v_cache at row b * Lk + j (stride ldc),
+ *   keys 0..i are attended with the bias q.e1[h, Lk-1-(i-j)]; ctx == NULL stores the rows and stops.  Cross mode
+ *   (k_cache == NULL): k / v rows b * Lk + j of the memory, p = i / ratio, masks and bias as vqcpc_decode_attn's cross
+ *   mode.  ctx row b * P + i (stride ldo).  Tiled (16 query rows per workgroup, K / V / table tiles in LDS, masked key
+ *   tiles skipped), online fp32 softmax, no probabilities written, no dropout.  hd in {16, 32, 64, 128}.
+ * vqcpc_decode_window: ONE workgroup; win (device int32 [2]) = {next window's first code, live window's first code or
+ *   -1}.  First the live window's tokens [0, pos) go back into chorale[M][ldch] (token t of window w is chorale column
+ *   w * U + t).  Then, unless win[0] < 0 or win[0] + S > nb (commit only): codes_win[M][S] = codes_full[M][nb] columns
+ *   win[0].., tokens[M][T] = the chorale's columns win[0] * U.., prefix_rows[b * P + j] = the table row of input j
+ *   (start-of-sentence row table_rows - 1 at j = 0, else token[j-1] * U + (j-1) % U), x row b = the input row of position
+ *   P, seeds_out[b] = seeds_in[b] for window 0, otherwise splitmix64(seeds_in[b] ^ win[0] * 0xD1B54A32D192ED03) -- the
+ *   sampler keys its draw by (seed, window position), so the seed must change with the window --, pos[0] = P,
+ *   win = {win[0] + advance, win[0]}.  T == S * U, 0 <= P < T.
  * ------------------------------------------------------------------------------------------------------------------ */
 int vqcpc_decode_linear(const float* x, int64_t ldx, const int64_t* gather, const float* w, const float* bias, const float* res,
                         int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int relu, void* stream);
@@ -684,6 +702,13 @@ int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_o
                         int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
                         int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,
                         int U, float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream);
+int vqcpc_decode_prefill_attn(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldk, float* k_cache,
+                              float* v_cache, int64_t ldc, const float* e1, const float* e2, float* ctx, int64_t ldo, int64_t M,
+                              int P, int Lk, int ratio, int H, int hd, int mask, void* stream);
+int vqcpc_decode_window(const int64_t* codes_full, int64_t nb, int64_t* chorale, int64_t ldch, int32_t* win, int advance,
+                        int64_t* codes_win, int S, int64_t* tokens, int T, int U, int P, int64_t* prefix_rows,
+                        const float* table, int64_t table_rows, int d, float* x, int64_t ldx, const int64_t* seeds_in,
+                        int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
 
 #ifdef VQCPC_LAB
 /* ==================================================================================================================

@@ -14,6 +14,16 @@
 //   * vqcpc_decode_sample: temperature, exclusion mask, top-k, top-p, softmax and one counter-based draw per row; writes the
 //     token, the next step's input row (a row of the target table) and advances `pos`.  ONE workgroup: the position
 //     counter is read by every kernel of the step and written here once, after a barrier.
+//
+// Sliding-window generation (reference: decoder.py:729-854) moves the model window by one code at a time; the caches of
+// the new window's prefix are rebuilt by a teacher-forced pass over its P prefix rows (GEMMs + LayerNorm of the training
+// path, row-wise) whose attention is
+//   * vqcpc_decode_prefill_attn: the multi-query companion of vqcpc_decode_attn.  A workgroup owns a strip of 16 query rows
+//     of one (sequence, head); K / V / relative-table tiles go through LDS and are shared by the strip, key tiles the mask
+//     rules out are skipped, the softmax is online in fp32.  Self mode also stores the prefix's k / v rows into the cache.
+//   * vqcpc_decode_window: ONE workgroup.  Puts the live window's tokens back into the chorale, loads the next window's
+//     codes and tokens (its index is read from device memory and advanced), the prefix's table-row indices, the input row
+//     of position P, the window's effective sampling seeds and `pos`.
 #include <algorithm>
 
 #include "common.h"
@@ -226,6 +236,177 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const float* __restric
         float t = part[cc];
         for (int gg = 1; gg < G; ++gg) t += part[gg * HD + cc];
         ctx[b * ldo + hoff + cc] = t;
+    }
+}
+
+// =====================================================================================================================
+// decode_prefill_attn: grid (strips of kPfRows query rows, M * H); 256 threads.  Thread (r, l) = (tid / 16, tid % 16) owns
+// keys l, l + 16 of the tile in the score phase and HD / 16 output columns of row r in the P.V phase; the 16 lanes of a row
+// are consecutive lanes of one wavefront, so the row statistics are xor-shuffles of width 16.
+constexpr int kPfRows = 16;
+
+template <int HD, int KT>
+__global__ __launch_bounds__(256) void decode_prefill_attn_kernel(
+    const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, const float* __restrict__ v, int64_t ldk,
+    float* __restrict__ kc, float* __restrict__ vc, int64_t ldc, const float* __restrict__ e1, const float* __restrict__ e2,
+    float* __restrict__ ctx, int64_t ldo, int P, int Lk, int ratio, int H, int mask, float scale) {
+    constexpr int QR = kPfRows, LD = HD + 4, NJ = KT / 16, CPT = HD / 16, ER = KT + QR - 1;
+    __shared__ __attribute__((aligned(16))) float qs[QR * LD];
+    __shared__ __attribute__((aligned(16))) float ks[KT * LD];
+    __shared__ __attribute__((aligned(16))) float vs[KT * HD];
+    __shared__ __attribute__((aligned(16))) float es[ER * LD];
+    __shared__ float sc[QR][KT + 1];
+    const int tid = threadIdx.x, r = tid >> 4, l = tid & 15;
+    const int64_t b = blockIdx.y / H;
+    const int h = (int)(blockIdx.y % H);
+    const int64_t hoff = (int64_t)h * HD;
+    const int i0 = blockIdx.x * QR;
+    const int i1 = min(i0 + QR, P) - 1;                      // last live row of the strip (i0 < P by the grid)
+    const bool self = kc != nullptr;
+    const int64_t kvrow0 = self ? b * P : b * Lk;            // self: the prefix rows of the in_proj output; cross: the memory
+    const int nkeys = self ? P : Lk;
+    if (self) {                                              // the strip's own k / v rows join the cache [M][Lk][ldc]
+        for (int e = tid; e < QR * (HD / 4); e += 256) {
+            const int rr = e / (HD / 4), c = (e % (HD / 4)) * 4;
+            if (i0 + rr <= i1) {
+                const int64_t src = (kvrow0 + i0 + rr) * ldk + hoff + c, dst = (b * Lk + i0 + rr) * ldc + hoff + c;
+                *reinterpret_cast<float4*>(kc + dst) = *reinterpret_cast<const float4*>(k + src);
+                *reinterpret_cast<float4*>(vc + dst) = *reinterpret_cast<const float4*>(v + src);
+            }
+        }
+        if (!ctx) return;                                    // the last layer: nothing reads its prefix outputs
+    }
+    for (int e = tid; e < QR * (HD / 4); e += 256) {
+        const int rr = e / (HD / 4), c = (e % (HD / 4)) * 4;
+        float4 t = *reinterpret_cast<const float4*>(q + (b * P + min(i0 + rr, i1)) * ldq + hoff + c);
+        t.x *= scale, t.y *= scale, t.z *= scale, t.w *= scale;
+        *reinterpret_cast<float4*>(qs + rr * LD + c) = t;
+    }
+    // key range of the strip under the mask: p = i / ratio (self: ratio 1)
+    const int p_lo = i0 / ratio, p_hi = i1 / ratio;
+    const int j_lo = mask == 2 ? p_lo : 0, j_hi = mask == 1 ? min(p_hi, nkeys - 1) : nkeys - 1;
+    const int i = min(i0 + r, i1), p = i / ratio;
+    float m_run = kDecNegBig, l_run = 0.0f, o[CPT];
+#pragma unroll
+    for (int t = 0; t < CPT; ++t) o[t] = 0.0f;
+    for (int j0 = (j_lo / KT) * KT; j0 <= j_hi; j0 += KT) {
+        __syncthreads();                                     // the previous tile's readers are done (and qs is written)
+        for (int e = tid; e < KT * (HD / 4); e += 256) {
+            const int jj = e / (HD / 4), c = (e % (HD / 4)) * 4;
+            const int64_t src = (kvrow0 + min(j0 + jj, nkeys - 1)) * ldk + hoff + c;
+            *reinterpret_cast<float4*>(ks + jj * LD + c) = *reinterpret_cast<const float4*>(k + src);
+            *reinterpret_cast<float4*>(vs + jj * HD + c) = *reinterpret_cast<const float4*>(v + src);
+        }
+        // relative rows xr = j - p + Lk - 1 of the tile: [j0 - p_hi + Lk - 1, j0 + KT - 1 - p_lo + Lk - 1], clamped to the
+        // tables' 2 Lk - 1 rows (e1 rows 0 .. Lk - 1, then e2 rows 1 .. Lk - 1, the rule of vqcpc_decode_attn)
+        const int xr0 = j0 - p_hi + Lk - 1;
+        for (int e = tid; e < ER * (HD / 4); e += 256) {
+            const int rr = e / (HD / 4), c = (e % (HD / 4)) * 4;
+            const int xr = min(max(xr0 + rr, 0), 2 * Lk - 2);
+            const float* er = xr < Lk ? e1 + ((int64_t)h * Lk + xr) * HD : e2 + ((int64_t)h * Lk + (xr - Lk + 1)) * HD;
+            *reinterpret_cast<float4*>(es + rr * LD + c) = *reinterpret_cast<const float4*>(er + c);
+        }
+        __syncthreads();
+        float s[NJ], mx = kDecNegBig;
+#pragma unroll
+        for (int u = 0; u < NJ; ++u) {
+            const int jj = l + 16 * u, j = j0 + jj;
+            const bool keep = j < nkeys && ((mask == 0) | ((mask == 1) & (j <= p)) | ((mask == 2) & (j >= p)));
+            float sk = 0.0f, se = 0.0f;
+            if (keep) dot_rows<HD>(qs + r * LD, ks + jj * LD, es + (j - p + Lk - 1 - xr0) * LD, sk, se);
+            s[u] = keep ? sk + se : kDecNegBig;
+            mx = fmaxf(mx, s[u]);
+        }
+#pragma unroll
+        for (int w = 8; w > 0; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w, 64));
+        const float m_new = fmaxf(m_run, mx);
+        float sum = 0.0f;
+#pragma unroll
+        for (int u = 0; u < NJ; ++u) {
+            const float e = s[u] > 0.5f * kDecNegBig ? __expf(s[u] - m_new) : 0.0f;
+            sc[r][l + 16 * u] = e;
+            sum += e;
+        }
+#pragma unroll
+        for (int w = 8; w > 0; w >>= 1) sum += __shfl_xor(sum, w, 64);
+        const float alpha = __expf(m_run - m_new);           // 1 while every key so far was masked (m_run == m_new)
+        l_run = l_run * alpha + sum;
+        m_run = m_new;
+#pragma unroll
+        for (int t = 0; t < CPT; ++t) o[t] *= alpha;
+        __syncthreads();                                     // sc rows are read by the row's 16 lanes (one wavefront), and
+                                                             // uniformly by every row: a barrier keeps it simple
+        const int jn = min(KT, j_hi - j0 + 1);
+        for (int jj = 0; jj < jn; ++jj) {
+            const float pj = sc[r][jj];
+#pragma unroll
+            for (int t = 0; t < CPT; ++t) o[t] = fmaf(pj, vs[jj * HD + l * CPT + t], o[t]);
+        }
+    }
+    if (i0 + r <= i1) {
+        const float inv = 1.0f / l_run;                      // every live row keeps at least one key (host-checked masks)
+#pragma unroll
+        for (int t = 0; t < CPT; ++t) ctx[(b * P + i0 + r) * ldo + hoff + l * CPT + t] = o[t] * inv;
+    }
+}
+
+// =====================================================================================================================
+// decode_window: ONE workgroup of 1024 threads (integer plumbing of M * T tokens and one input row per sequence)
+__device__ __forceinline__ uint64_t splitmix64_dev(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__global__ __launch_bounds__(1024) void decode_window_kernel(
+    const int64_t* __restrict__ codes_full, int64_t nb, int64_t* __restrict__ chorale, int64_t ldch, int32_t* __restrict__ win,
+    int advance, int64_t* __restrict__ codes_win, int S, int64_t* __restrict__ tokens, int T, int U, int P,
+    int64_t* __restrict__ prefix_rows, const float* __restrict__ table, int64_t table_rows, int d, float* __restrict__ x,
+    int64_t ldx, const int64_t* __restrict__ seeds_in, int64_t* __restrict__ seeds_out, int32_t* __restrict__ posp, int M) {
+    const int tid = threadIdx.x;
+    const int next = win[0], live = win[1], cur = min(max(*posp, 0), T);
+    __syncthreads();                                         // every thread has read win and pos
+    if (live >= 0 && (int64_t)live + S <= nb) {              // commit: the live window's tokens [0, pos) back into the chorale
+        for (int e = tid; e < M * cur; e += 1024) {
+            const int m = e / cur, j = e % cur;
+            chorale[(int64_t)m * ldch + (int64_t)live * U + j] = tokens[(int64_t)m * T + j];
+        }
+    }
+    __threadfence_block();
+    __syncthreads();                                         // the load below reads what the commit wrote
+    if (next < 0 || (int64_t)next + S > nb) return;          // commit only (uniform)
+    const int64_t sos = table_rows - 1;
+    for (int e = tid; e < M * S; e += 1024) {
+        const int m = e / S, s = e % S;
+        codes_win[e] = codes_full[(int64_t)m * nb + next + s];
+    }
+    for (int e = tid; e < M * T; e += 1024) {
+        const int m = e / T, j = e % T;
+        const int64_t tok = chorale[(int64_t)m * ldch + (int64_t)next * U + j];
+        tokens[e] = tok;
+        // the input row of position j + 1 (decoders/decoder.py:_target_rows): table row token * U + j % U
+        if (j + 1 < P) prefix_rows[(int64_t)m * P + j + 1] = min(max(tok * U + j % U, (int64_t)0), sos - 1);
+    }
+    for (int m = tid; m < M; m += 1024) {
+        if (P > 0) prefix_rows[(int64_t)m * P] = sos;
+        const uint64_t sd = (uint64_t)seeds_in[m];
+        // window 0 keeps the row's seed: a generation that never slides draws what the fixed-window generation draws
+        seeds_out[m] = (int64_t)(next == 0 ? sd : splitmix64_dev(sd ^ ((uint64_t)next * 0xD1B54A32D192ED03ull)));
+    }
+    for (int e = tid; e < M * d; e += 1024) {                // the input row of position P
+        const int m = e / d, c = e % d;
+        int64_t row = sos;
+        if (P > 0) {
+            const int64_t tok = chorale[(int64_t)m * ldch + (int64_t)next * U + P - 1];
+            row = min(max(tok * U + (P - 1) % U, (int64_t)0), sos - 1);
+        }
+        x[(int64_t)m * ldx + c] = table[row * d + c];
+    }
+    if (tid == 0) {
+        *posp = P;
+        win[0] = next + advance;
+        win[1] = next;
     }
 }
 
@@ -481,6 +662,56 @@ int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_o
                        temperature, top_k, top_p, exclude, seeds, teacher, ldteach, tokens, ldtok, T, table, table_rows, d, U,
                        next_in, ldn, probs, ldp, pos);
     VQ_CHECK_LAUNCH("decode_sample");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_prefill_attn(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldk, float* k_cache,
+                              float* v_cache, int64_t ldc, const float* e1, const float* e2, float* ctx, int64_t ldo, int64_t M,
+                              int P, int Lk, int ratio, int H, int hd, int mask, void* stream) {
+    VQ_REQUIRE(k && v && e1 && e2 && M >= 1 && M <= kDecMaxRows && Lk >= 1 && Lk <= kDecMaxLk && ratio >= 1 && H >= 1 &&
+               mask >= 0 && mask <= 2 && P >= 0 && (int64_t)P <= (int64_t)ratio * Lk,
+               "decode_prefill_attn: bad arguments (1 <= M <= 64, 1 <= Lk <= 1024, 0 <= P <= ratio * Lk, mask in {0, 1, 2})");
+    VQ_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "decode_prefill_attn: hd must be 16, 32, 64 or 128 (got %d)", hd);
+    const int64_t d = (int64_t)H * hd;
+    VQ_REQUIRE((k_cache == nullptr) == (v_cache == nullptr), "decode_prefill_attn: k_cache and v_cache go together");
+    VQ_REQUIRE(ctx || k_cache, "decode_prefill_attn: ctx may be NULL in self mode only (store the prefix k | v and stop)");
+    VQ_REQUIRE(!ctx || (q && ldq >= d && ldq % 4 == 0 && ldo >= d && aligned16(q)), "decode_prefill_attn: bad q / ctx");
+    VQ_REQUIRE(ldk >= d && ldk % 4 == 0 && aligned16(k) && aligned16(v) && aligned16(e1) && aligned16(e2),
+               "decode_prefill_attn: bad leading dimensions or alignment");
+    if (k_cache)
+        VQ_REQUIRE(mask == 1 && ratio == 1 && ldc >= d && ldc % 4 == 0 && aligned16(k_cache) && aligned16(v_cache),
+                   "decode_prefill_attn: self mode (k_cache given) is causal with ratio 1");
+    if (P == 0) return VQCPC_OK;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const dim3 grid((unsigned)ceil_div(P, kPfRows), (unsigned)(M * H)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define DEC_PF(HD, KT)                                                                                                         \
+    hipLaunchKernelGGL((decode_prefill_attn_kernel<HD, KT>), grid, block, 0, s, q, ldq, k, v, ldk, k_cache, v_cache, ldc, e1,  \
+                       e2, ctx, ldo, P, Lk, ratio, H, mask, scale)
+    switch (hd) {
+        case 16: DEC_PF(16, 32); break;
+        case 32: DEC_PF(32, 32); break;
+        case 64: DEC_PF(64, 32); break;
+        default: DEC_PF(128, 16); break;
+    }
+#undef DEC_PF
+    VQ_CHECK_LAUNCH("decode_prefill_attn");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_window(const int64_t* codes_full, int64_t nb, int64_t* chorale, int64_t ldch, int32_t* win, int advance,
+                        int64_t* codes_win, int S, int64_t* tokens, int T, int U, int P, int64_t* prefix_rows,
+                        const float* table, int64_t table_rows, int d, float* x, int64_t ldx, const int64_t* seeds_in,
+                        int64_t* seeds_out, int32_t* pos, int64_t M, void* stream) {
+    VQ_REQUIRE(codes_full && chorale && win && codes_win && tokens && table && x && seeds_in && seeds_out && pos && M >= 1 &&
+               M <= kDecMaxRows, "decode_window: bad arguments (1 <= M <= 64)");
+    VQ_REQUIRE(S >= 1 && U >= 1 && T == S * U && nb >= S && ldch >= nb * U && P >= 0 && P < T && (P == 0 || prefix_rows) &&
+               d >= 1 && d <= kDecMaxDim && ldx >= d && table_rows >= 2 && advance >= 0,
+               "decode_window: T == S * U, nb >= S, ldch >= nb * U, 0 <= P < T, 1 <= d <= 4096");
+    hipLaunchKernelGGL(decode_window_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, codes_full, nb, chorale, ldch, win,
+                       advance, codes_win, S, tokens, T, U, P, prefix_rows, table, table_rows, d, x, ldx, seeds_in, seeds_out,
+                       pos, (int)M);
+    VQ_CHECK_LAUNCH("decode_window");
     return VQCPC_OK;
 }
 

@@ -5,8 +5,11 @@ Covered: `transformer_type='relative'` with causal target self-attention, antica
 anticausal or full cross-attention -- getters.py decoder_type 'transformer_relative' / 'transformer_relative_fullCross'.
 `__init__`, `forward`, `epoch`, `train_model`, `init_optimizers`, `save` / `load` keep the reference's names, argument
 meaning, state_dict keys and return contracts.  `generate` / `generate_from_codes` / `init_generation` (:552-726) run
-KV-cached incremental decoding on the GPU (decoders/generation.py); the sliding-window and re-harmonisation generators
-(:728-1062), the absolute-position and 'diagonal' variants are out of scope and raise.
+KV-cached incremental decoding on the GPU (decoders/generation.py); `generate_from_code_long`, `generate_alla_mano`,
+`compute_start_end_times`, `init_generation_chorale` (:728-854, :960-981, :1054-1062) decode code sequences of any length
+by sliding the window, with a K/V-cache re-prefill per move; `reharmonise_tokens` is the body of
+`generate_reharmonisation` (:856-958) on a token tensor (the music21 corpus it reads is absent, so that method raises).
+Duplicate checks, plots, the absolute-position and 'diagonal' variants are out of scope and raise.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
   * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient);
@@ -460,7 +463,158 @@ class Decoder(GraphedTraining, nn.Module):
         print(f'Saved in {save_dir}/{timestamp}')
         return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': recoding}
 
-    def generate_from_code_long(self, *a, **k):
-        raise NotImplementedError('sliding-window generation / re-harmonisation (decoder.py:728-1062) is out of scope')
+    # ---- long-form generation (:728-1062): sliding-window decoding with KV-cache re-prefill, decoders/generation.py --
+    @staticmethod
+    def compute_start_end_times(t, num_blocks, num_blocks_model):
+        """:831-854: the model window [t_begin, t_end) of codes used to generate code t of a sequence of `num_blocks`
+        codes, and t's index in it.  Head (t < S // 2): the first window, t_relative = t; middle: t sits at S // 2 of a
+        window that moves with it; tail (t >= num_blocks - S // 2): the last window."""
+        half = num_blocks_model // 2
+        if half <= t < num_blocks - half:
+            t_relative = half
+        elif t < half:
+            t_relative = t
+        else:
+            t_relative = num_blocks_model - (num_blocks - t)
+        t_begin = min(max(0, t - half), num_blocks - num_blocks_model)
+        return t_begin, t_begin + num_blocks_model, t_relative
 
-    generate_reharmonisation = generate_alla_mano = check_duplicate = compute_start_end_times = plot = generate_from_code_long
+    def _meta_symbol(self, name, given, symbol):
+        if given is not None:
+            ids = [int(v) for v in given]
+            if len(ids) != self.num_channels:
+                raise ValueError(f'{name}: one token id per voice expected ({self.num_channels}), got {len(ids)}')
+            return ids
+        ds = getattr(self.dataloader_generator, 'dataset', None)
+        n2i = getattr(ds, 'note2index_dicts', None)
+        if n2i is None or any(symbol not in n2i[c] for c in range(self.num_channels)):
+            raise ValueError(f"init_generation_chorale needs dataset.note2index_dicts with the '{symbol}' symbol, or explicit "
+                             'per-voice lists pad= and start=; this dataset (e.g. the synthetic one) has no meta symbols')
+        return [int(n2i[c][symbol]) for c in range(self.num_channels)]
+
+    def init_generation_chorale(self, num_events, start_index, pad=None, start=None):
+        """:1054-1062: (1, num_events, num_channels) int64 on the device, PAD everywhere and START at event
+        start_index - 1.  pad / start: per-voice token ids for datasets without meta symbols (default: the dataset's 'XX' /
+        'START').  start_index = 0 puts no START (the reference fails there on a negative repeat count)."""
+        if not 0 <= start_index <= num_events:
+            raise ValueError(f'init_generation_chorale: 0 <= start_index <= {num_events} (got {start_index})')
+        PAD = self._meta_symbol('pad', pad, 'XX')
+        out = torch.tensor(PAD, dtype=torch.int64).view(1, 1, -1).repeat(1, num_events, 1)
+        if start_index >= 1:
+            out[0, start_index - 1] = torch.tensor(self._meta_symbol('start', start, 'START'), dtype=torch.int64)
+        return out.to(self.sos.device)
+
+    def generate_from_code_long(self, encoding_indices=None, temperature=None, top_k=0, top_p=1., exclude_meta_symbols=False,
+                                num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
+                                use_graph=True):
+        """:729-829: decodes MERGED codes (B, nb) of any length nb >= S by sliding the model window one code at a time
+        (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
+        full forward on the window per token; here the window's prefix is re-prefilled into the K/V caches when it moves
+        and the tokens come from incremental steps (decoders/generation.py), which computes the same function.
+        Returns int64 tokens (B * num_decodings, events, channels) on the device, sliced to the events of codes
+        [code_index_start, code_index_end) -- tensors, not music21 scores, as `generate`.
+        Differences from the reference: code_index_start / code_index_end = None mean the whole sequence (the reference
+        multiplies them before applying its own default, :747-755, and crashes); code_index_start = 0 works (no START
+        token, an all-PAD chorale and an empty first prefill); exclude_meta_symbols=True is honoured as in `generate` (the
+        reference ignores it, its code is commented out, :786-793; the default False is its behaviour).  pad / start: see
+        `init_generation_chorale`.  seed: as `generate_from_codes`; a row's draw is a function of (row seed, absolute
+        chorale position).  A bare call without codes raises NotImplementedError, as before this method existed."""
+        if encoding_indices is None or temperature is None:
+            raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
+                                      'is not implemented')
+        from .generation import MAX_ROWS, IncrementalDecoder, row_seeds
+        dev = self.sos.device
+        codes = torch.as_tensor(encoding_indices).to(dev, torch.int64)
+        S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
+        if codes.dim() != 2:
+            raise ValueError(f'encoding_indices: (batch, num_codes) merged codes expected, got {tuple(codes.shape)}')
+        nb = codes.shape[1]
+        if nb < S:
+            raise ValueError(f'encoding_indices: at least {S} codes (one model window) are needed, got {nb}')
+        code_index_start = 0 if code_index_start is None else int(code_index_start)
+        code_index_end = nb if code_index_end is None else int(code_index_end)
+        if not 0 <= code_index_start <= code_index_end <= nb:
+            raise ValueError(f'0 <= code_index_start <= code_index_end <= {nb} expected, got {code_index_start}, {code_index_end}')
+        epc = self.num_events_per_code
+        exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
+        chorale = self.init_generation_chorale(num_events=nb * epc, start_index=code_index_start * epc, pad=pad, start=start)
+        if num_decodings > 1:
+            codes = codes.repeat_interleave(num_decodings, dim=0)
+        B = codes.shape[0]
+        seeds = row_seeds(seed, B)
+        out = torch.empty(B, nb * U, dtype=torch.int64, device=dev)
+        with STEP_LOCK, torch.no_grad():               # never interleaved with a training step of another thread
+            was_training = self.training
+            self.eval()
+            try:
+                for b0 in range(0, B, MAX_ROWS):
+                    n = min(MAX_ROWS, B - b0)
+                    inc = IncrementalDecoder(self, n)
+                    inc.start_long(codes[b0:b0 + n], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[b0:b0 + n],
+                                   temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude)
+                    out[b0:b0 + n] = inc.run_long(code_index_start, code_index_end, use_graph=use_graph)
+                    del inc
+            finally:
+                self.train(was_training)
+        return out.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
+
+    def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
+        """:960-981: start_codes + body_codes + end_codes (lists of merged codes) decoded as one sequence, the body's
+        events returned: int64 (num_decodings, events, channels).  kwargs go to `generate_from_code_long`."""
+        if start_codes is None or end_codes is None or body_codes is None or temperature is None:
+            raise NotImplementedError('generate_alla_mano(start_codes, end_codes, body_codes, temperature): generation '
+                                      'without codes is not implemented')
+        start_codes, body_codes, end_codes = list(start_codes), list(body_codes), list(end_codes)
+        codes = torch.tensor(start_codes + body_codes + end_codes, dtype=torch.int64).unsqueeze(0)
+        return self.generate_from_code_long(codes, temperature=temperature, num_decodings=num_decodings,
+                                            code_index_start=len(start_codes),
+                                            code_index_end=len(start_codes) + len(body_codes), **kwargs)
+
+    def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False, **kwargs):
+        """The body of generate_reharmonisation (:871-941) on a (1, events, channels) token tensor: the chorale is cut into
+        model-sized chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD),
+        every chunk is encoded, the codes are glued and the chorale's own codes are decoded `num_reharmonisations` times.
+        Needs the dataset's START / END / XX symbols.  -> int64 (num_reharmonisations, events', channels), or with
+        return_bounds=True (tokens, code_index_start, code_index_end, number of codes).  kwargs go to
+        `generate_from_code_long`."""
+        n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
+        if n2i is None:
+            raise ValueError('reharmonise_tokens needs dataset.note2index_dicts with the START / END / XX symbols')
+        nc, E, dev = self.num_channels, self.data_processor.num_events, self.sos.device
+        x = torch.as_tensor(x).long().cpu()
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[2] != nc or x.shape[1] < 1:
+            raise ValueError(f'x: (1, events, {nc}) tokens expected, got {tuple(x.shape)}')
+        PAD, START, END = ([int(n2i[c][sym]) for c in range(nc)] for sym in ('XX', 'START', 'END'))
+        row = lambda ids, n: torch.tensor(ids, dtype=torch.int64).view(1, 1, nc).repeat(1, n, 1)
+        x_chunks = list(x.split(E, 1))
+        last_chunk = x_chunks[-1]
+        start_chunk = torch.cat([row(PAD, E - 1), row(START, 1)], 1)
+        completion_length = E - last_chunk.size(1)
+        if completion_length >= 1:
+            x_chunks[-1] = torch.cat([last_chunk, row(END, 1), row(PAD, completion_length - 1)], 1)
+            end_chunk = row(PAD, E)
+        else:
+            end_chunk = torch.cat([row(END, 1), row(PAD, E - 1)], 1)
+        chunks = torch.cat([start_chunk] + x_chunks + [end_chunk], dim=0).to(dev)
+        was_training = self.training
+        self.eval()
+        try:
+            codes = self.encode(chunks).reshape(1, -1)                                # glued: (1, chunks * S)
+        finally:
+            self.train(was_training)
+        U = self.total_upscaling
+        code_index_start = start_chunk.size(1) * nc // U
+        code_index_end = codes.size(1) - (end_chunk.size(1) + completion_length) * nc // U
+        tokens = self.generate_from_code_long(codes, temperature=temperature, top_k=top_k, top_p=top_p,
+                                              num_decodings=num_reharmonisations, code_index_start=code_index_start,
+                                              code_index_end=code_index_end, **kwargs)
+        return (tokens, code_index_start, code_index_end, codes.size(1)) if return_bounds else tokens
+
+    def generate_reharmonisation(self, *a, **k):
+        raise NotImplementedError('generate_reharmonisation (:856-958) reads its chorale from the music21 corpus, which this '
+                                  'package does not ship; pass the token tensor to reharmonise_tokens instead')
+
+    def _not_implemented(self, *a, **k):
+        raise NotImplementedError('duplicate checks and plots (decoder.py:983-1052) are out of scope')
+
+    check_duplicate = plot = _not_implemented

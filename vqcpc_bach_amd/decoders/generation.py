@@ -15,7 +15,20 @@ row-wise embedding / LayerNorm / FFN), so one incremental step per token compute
 
 Every kernel of the step reads `pos` from device memory, so ONE captured step (torch.cuda.CUDAGraph) is replayed T times.
 Rows are independent and every kernel reduces in an order that does not depend on the number of rows, so a row's tokens
-do not depend on which other rows share the call (given the same memory rows and seed)."""
+do not depend on which other rows share the call (given the same memory rows and seed).
+
+Long mode (reference: generate_from_code_long, decoder.py:729-854, one full forward on the moved window per token): a code
+sequence of any length nb >= S is decoded by sliding the window one code at a time.  The chorale (M, nb * U) and the codes
+(M, nb) live on the device.  When the window moves, its first position gets the start-of-sentence row and every row loses U
+tokens of context, so every cache is stale:
+
+  slide: vqcpc_decode_window (commit the live window's tokens, load the next window's codes / tokens / prefix rows / seeds,
+  pos = P) -> memory and cross k | v of the new source window -> the decoder stack teacher-forced over the P = t_relative * U
+  prefix rows of every sequence (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_decode_prefill_attn), which leaves every
+  layer's K/V cache rows [0, P) filled; the last layer stops after its self-attention k | v.  Then U steps as above.
+
+The window index is read from device memory and advanced by the window kernel, so ONE captured slide serves every middle
+window of a generation (all have P = (S // 2) * U), next to the one captured step."""
 import ctypes
 
 import torch
@@ -101,13 +114,21 @@ class IncrementalDecoder:
         dec, M, d = self.dec, self.M, self.d
         codes = codes.to(self.dev, torch.int64)
         assert codes.shape == (M, self.S), (codes.shape, (M, self.S))
-        src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
-        memory, _ = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
-        self.memkv = [ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:])
-                      for lay in self.layers]                                           # (M * S, 2d): k | v
+        self._encode_memory(codes)
         self.table = dec._target_table(self.dev).contiguous()                          # (vmax * U + 1, d)
         self.head_w = torch.cat([m.weight for m in dec.pre_softmaxes], dim=0).contiguous()
         self.head_b = torch.cat([m.bias for m in dec.pre_softmaxes], dim=0).contiguous()
+
+    def _encode_memory(self, codes):
+        """codes (M, S) -> memory -> every layer's cross k | v, written into buffers that keep their address (a captured
+        step reads them)."""
+        dec, M, d = self.dec, self.M, self.d
+        if self.memkv is None:
+            self.memkv = [torch.empty(M * self.S, 2 * d, dtype=torch.float32, device=self.dev) for _ in self.layers]
+        src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
+        memory, _ = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
+        for lay, kv in zip(self.layers, self.memkv):                                    # (M * S, 2d): k | v
+            ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:], out=kv)
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
@@ -193,3 +214,136 @@ class IncrementalDecoder:
             for _ in range(self.T):
                 self.step()
         return self.tokens
+
+    # ---- long mode: sliding window -----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def start_long(self, codes_full, chorale, seeds=None, **sampling):
+        """codes_full (M, nb) merged codes, nb >= S; chorale (M, nb * U) int64 tokens, position-major (the initial PAD /
+        START sequence; generated tokens are written into it).  sampling: the keywords of `start`."""
+        M, S, U = self.M, self.S, self.U
+        codes_full = codes_full.to(self.dev, torch.int64).contiguous()
+        if codes_full.dim() != 2 or codes_full.shape[0] != M or codes_full.shape[1] < S:
+            raise ValueError(f'codes_full: ({M}, nb >= {S}) expected, got {tuple(codes_full.shape)}')
+        self.nb = nb = codes_full.shape[1]
+        self.codes_full = codes_full
+        self.chorale = chorale.to(self.dev, torch.int64).reshape(M, nb * U).contiguous().clone()
+        self.codes_win = torch.zeros(M, S, dtype=torch.int64, device=self.dev)
+        self.win = torch.tensor([0, -1], dtype=torch.int32, device=self.dev)       # {next window, live window}
+        self.prefix_rows = torch.zeros(M * self.T, dtype=torch.int64, device=self.dev)
+        self.row_seeds = torch.zeros(M, dtype=torch.int64, device=self.dev)
+        if self.memkv is None:
+            self.prefill(codes_full[:, :S])
+        self.start(seeds=seeds, **sampling)
+        self.row_seeds.copy_(self.seeds)
+
+    def _window(self, P, advance):
+        hip.call('vqcpc_decode_window', self.codes_full, self.nb, self.chorale, self.nb * self.U, self.win, int(advance),
+                 self.codes_win, self.S, self.tokens, self.T, self.U, int(P), self.prefix_rows, self.table, self.table.shape[0],
+                 self.d, self.x, self.d, self.row_seeds, self.seeds, self.pos, self.M)
+
+    def _prefix_ln(self, x, r, norm):
+        y = torch.empty_like(x)
+        n = x.shape[0]
+        hip.call('vqcpc_add_layernorm_fwd', x, self.d, r, norm.weight, norm.bias, y, self._pmean[:n], self._prstd[:n], n, self.d,
+                 1e-5, 0.0, 0)
+        return y
+
+    def prefill_prefix(self, P):
+        """The decoder stack, teacher-forced over prefix rows [0, P) of every sequence (inputs: table rows `prefix_rows`):
+        fills every layer's K/V cache rows [0, P)."""
+        if P == 0:
+            return
+        M, d, T, S, H, hd = self.M, self.d, self.T, self.S, self.H, self.hd
+        if getattr(self, '_pmean', None) is None:
+            self._pmean = torch.empty(M * T, dtype=torch.float32, device=self.dev)
+            self._prstd = torch.empty(M * T, dtype=torch.float32, device=self.dev)
+        h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
+        last = len(self.layers) - 1
+        for li, lay in enumerate(self.layers):
+            sa, ca = lay.self_attn, lay.multihead_attn
+            qkv = ops.gemm_nt(h, sa.in_proj_weight, bias=sa.in_proj_bias)
+            att = torch.empty(M * P, d, dtype=torch.float32, device=self.dev) if li < last else None
+            hip.call('vqcpc_decode_prefill_attn', qkv, 3 * d, qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, 3 * d,
+                     self.kcache[li], self.vcache[li], d, sa.attn_bias.e1, sa.attn_bias.e2, att, d, M, P, T, 1, H, hd,
+                     ops.MASK_CAUSAL)
+            if li == last:
+                break                                     # nothing reads the last layer's prefix outputs
+            h1 = self._prefix_ln(h, ops.gemm_nt(att, sa.out_proj.weight, bias=sa.out_proj.bias), lay.norm1)
+            qc = ops.gemm_nt(h1, ca.in_proj_weight[:d], bias=ca.in_proj_bias[:d])
+            kv = self.memkv[li]
+            hip.call('vqcpc_decode_prefill_attn', qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                     ca.attn_bias.e2, att, d, M, P, S, T // S, H, hd, self.cross_mask)
+            h2 = self._prefix_ln(h1, ops.gemm_nt(att, ca.out_proj.weight, bias=ca.out_proj.bias), lay.norm2)
+            f = ops.gemm_nt(h2, lay.linear1.weight, bias=lay.linear1.bias, act=1)
+            h = self._prefix_ln(h2, ops.gemm_nt(f, lay.linear2.weight, bias=lay.linear2.bias), lay.norm3)
+
+    @torch.no_grad()
+    def slide(self, t_begin=None, t_relative=0, advance=1):
+        """Moves the generation to the window of codes [t_begin, t_begin + S) at position P = t_relative * U: commits the
+        live window, loads the new one, recomputes the memory and the cross k | v of its codes and re-prefills the
+        prefix.  t_begin=None takes the window index the device holds (the previous window's + `advance`)."""
+        if t_begin is not None:
+            if not 0 <= t_begin <= self.nb - self.S:
+                raise ValueError(f'slide: 0 <= t_begin <= {self.nb - self.S} (got {t_begin})')
+            self.win[0:1].fill_(int(t_begin))
+        P = int(t_relative) * self.U
+        if not 0 <= P < self.T:
+            raise ValueError(f'slide: 0 <= t_relative < {self.S} (got {t_relative})')
+        self._window(P, advance)
+        self._encode_memory(self.codes_win)
+        self.prefill_prefix(P)
+
+    def commit(self):
+        """Puts the live window's tokens back into the chorale (no new window is loaded)."""
+        self.win[0:1].fill_(-1)
+        self._window(0, 0)
+
+    @torch.no_grad()
+    def run_long(self, code_index_start, code_index_end, use_graph=True, graph_slides=None):
+        """Generates the codes [code_index_start, code_index_end) (after `start_long`): head / middle / tail regimes of
+        `Decoder.compute_start_end_times`; a slide whenever the window of a code differs from the live one, then U steps.
+        use_graph: the step is one captured graph; graph_slides (default: use_graph): the middle slides, which all have
+        P = (S // 2) * U and windows that advance by one, are ONE captured graph too.  Returns the chorale (M, nb * U)."""
+        from .decoder import Decoder
+        S, U, nb = self.S, self.U, self.nb
+        if not 0 <= code_index_start <= code_index_end <= nb:
+            raise ValueError(f'run_long: 0 <= code_index_start <= code_index_end <= {nb}')
+        plan = [(ci,) + tuple(Decoder.compute_start_end_times(ci, nb, S)) for ci in range(code_index_start, code_index_end)]
+        if not plan:
+            return self.chorale
+        graph_slides = use_graph if graph_slides is None else graph_slides
+        step_graph = slide_graph = None
+        tr_mid = S // 2
+        if use_graph or graph_slides:
+            chorale0 = self.chorale.clone()
+            _, tb0, _, tr0 = plan[0]
+            self.slide(tb0, tr0)                  # a live state for the first launches, which stay outside the captures
+            if use_graph:
+                self.step()
+                torch.cuda.synchronize(self.dev)
+                step_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(step_graph, capture_error_mode='thread_local'):
+                    self.step()
+            n_mid = sum(1 for k in range(1, len(plan)) if plan[k][1] == plan[k - 1][1] + 1 and plan[k][3] == tr_mid)
+            if graph_slides and n_mid >= 2:
+                self.slide(tb0, tr_mid)
+                torch.cuda.synchronize(self.dev)
+                slide_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(slide_graph, capture_error_mode='thread_local'):
+                    self.slide(None, tr_mid, advance=1)
+            self.chorale.copy_(chorale0)          # the warm-up launches drew and committed tokens: start again
+            self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
+        live = None
+        for _, tb, _, tr in plan:
+            if tb != live:
+                if slide_graph is not None and live is not None and tb == live + 1 and tr == tr_mid:
+                    slide_graph.replay()          # the device's window index is live + 1 already
+                else:
+                    self.slide(tb, tr)
+                live = tb
+            for _ in range(U):
+                step_graph.replay() if step_graph is not None else self.step()
+        self.commit()
+        torch.cuda.current_stream(self.dev).synchronize()
+        del step_graph, slide_graph
+        return self.chorale
