@@ -710,6 +710,37 @@ int vqcpc_decode_window(const int64_t* codes_full, int64_t nb, int64_t* chorale,
                         const float* table, int64_t table_rows, int d, float* x, int64_t ldx, const int64_t* seeds_in,
                         int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sampling code sequences from the prior (VQCPCB/priors/prior_relative.py:308-353: one full forward per code, softmax,
+ * p ** temperature renormalised, np.random.choice on the host).  The prior's KV-cached step is made of vqcpc_decode_linear,
+ * vqcpc_decode_attn (self mode), vqcpc_add_layernorm_fwd and, for the re-prefill of a moved window, vqcpc_gemm_nt and
+ * vqcpc_decode_prefill_attn (vqcpc_bach_amd/priors/generation.py); the two entry points below are its tail and its window
+ * bookkeeping (csrc/prior.hip).  Adding them left the ABI version alone.
+ *
+ * vqcpc_prior_sample: one workgroup per row b < M <= 64, V <= 4096 codes.  The position is read from pos[0] (device
+ *   int32); nothing happens once pos >= N.  Per row: logits[b][0..V) * temperature -- the reference's sense (:346,
+ *   p ** temperature renormalised == softmax(temperature * logits)), the OPPOSITE of vqcpc_decode_sample's division --,
+ *   top-k (drop logits < the k-th largest; 0 = off), top-p (utils.py:116-126; top_p <= 0 or >= 1 = off), softmax, one draw
+ *   from the counter-based hash keyed by (seeds[b], pos) -- or, teacher != NULL, the code teacher[b * ldteach + pos].
+ *   Writes codes[b * ldc + pos], next_in row b = table row `code` (the input of position pos + 1; table [table_rows][d],
+ *   table_rows >= V), optionally the filtered probabilities probs[b][0..V).  The last workgroup to finish (ticket: device
+ *   int32, zero before the first call, zero again after every call) writes pos[0] = pos + 1.  Every reduction runs inside
+ *   the row's workgroup in an order that depends on V only: a row's codes do not depend on M.
+ * vqcpc_prior_window: ONE workgroup; win (device int32 [2]) = {next window's first code, live window's first code or -1}.
+ *   First the live window's codes [0, pos) go back into seq[M][ldseq] (code j of window w is column w + j).  Then, unless
+ *   win[0] < 0 or win[0] + N > num_tokens (commit only): codes_win[M][N] = seq columns win[0].., prefix_rows[b * P + j] =
+ *   the table row of input j (start-of-sentence row table_rows - 1 at j = 0, else code j - 1 of the window), x row b = the
+ *   input row of position P, seeds_out[b] by the rule of vqcpc_decode_window, pos[0] = P, win = {win[0] + advance, win[0]}.
+ *   0 <= P < N <= 1024.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_prior_sample(const float* logits, int64_t ldl, int V, int64_t M, float temperature, int top_k, float top_p,
+                       const int64_t* seeds, const int64_t* teacher, int64_t ldteach, int64_t* codes, int64_t ldc, int N,
+                       const float* table, int64_t table_rows, int d, float* next_in, int64_t ldn, float* probs, int64_t ldp,
+                       int32_t* pos, int32_t* ticket, void* stream);
+int vqcpc_prior_window(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t* win, int advance, int64_t* codes_win, int N,
+                       int P, int64_t* prefix_rows, const float* table, int64_t table_rows, int d, float* x, int64_t ldx,
+                       const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

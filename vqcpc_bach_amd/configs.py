@@ -67,7 +67,27 @@ def make_decoder_config(dropout=0.2, **over):
     return cfg
 
 
+def make_prior_config(dropout=0.2, **over):
+    """The code prior (VQCPCB/priors/prior_relative.py) on the DEC configuration's frozen encoder (1 x 32 codes, 24 codes per
+    24-beat window).  The reference ships NO prior configuration: `prior_kwargs` (d_model 512, 8 heads, 6 layers, ff 1024,
+    embedding 32, dropout 0.2 -- the decoder's widths with its 3 + 3 layers in one stack) is this package's own choice."""
+    dec = make_decoder_config()
+    cfg = {
+        'config_encoder': dec['config_encoder'], 'training_method': 'prior', 'dataset': 'bach',
+        'dataloader_generator_kwargs': dict(sequences_size=24),
+        'prior_type': 'transformer_relative',
+        'prior_kwargs': dict(d_model=512, n_head=8, num_layers=6, dim_feedforward=1024, embedding_size=32, dropout=dropout),
+        'lr': 1e-4, 'batch_size': 32, 'num_batches': 2048, 'num_epochs': 1, 'timestamp': None, 'savename': 'prior_relative',
+    }
+    cfg = copy.deepcopy(cfg)
+    for k, v in over.items():
+        cfg[k] = v
+    return cfg
+
+
 def make_config(name='C1', dropout=0.1, **over):
+    if name == 'PRI':
+        return make_prior_config(dropout=dropout, **over)
     if name == 'C3':
         return make_student_config(dropout=dropout, **over)
     if name == 'DEC':

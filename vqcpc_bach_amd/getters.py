@@ -1,6 +1,6 @@
 """Factories with the reference's names and config schema (reference: VQCPCB/getters.py:24-45,48-175,221-270,431-514),
 restricted to the encoder branches (vqcpc, student) that `main_encoder.py` reaches, plus `get_decoder` (:274-392) for
-the relative decoder training step."""
+the relative decoder training step and `get_prior` (:398-428) for the code prior."""
 import numpy as np
 
 from .auxiliary_decoders.auxiliary_decoder_relative import AuxiliaryDecoderRelative
@@ -12,6 +12,7 @@ from .decoders.decoder import Decoder
 from .downscalers.relative_transformer_downscaler import RelativeTransformerDownscaler
 from .downscalers.relative_transformer_downscaler_linear import RelativeTransformerDownscalerLinear
 from .encoder import Encoder
+from .priors.prior_relative import PriorRelative
 from .student_encoder_trainer import StudentEncoderTrainer
 from .teachers.teacher_relative import TeacherRelative
 from .quantizer.vector_quantizer import NoQuantization, ProductVectorQuantizer
@@ -23,9 +24,9 @@ def get_dataloader_generator(dataset, training_method, dataloader_generator_kwar
     if dataset.lower() in ('bach', 'synthetic') and training_method.lower() == 'vqcpc':
         # the music21 Bach corpus is replaced by a synthetic generator with the same tensor contract
         return SyntheticCPCDataloaderGenerator(**dataloader_generator_kwargs)
-    if dataset.lower() in ('bach', 'synthetic') and training_method.lower() in ('student', 'decoder'):
+    if dataset.lower() in ('bach', 'synthetic') and training_method.lower() in ('student', 'decoder', 'prior'):
         return SyntheticStudentDataloaderGenerator(**dataloader_generator_kwargs)     # {'x': (B, events, voices)}
-    raise NotImplementedError('only the vqcpc, student and decoder training methods are on the path (prior: out of scope)')
+    raise NotImplementedError('only the vqcpc, student, decoder and prior training methods are on the path')
 
 
 def get_downscaler(downscaler_type, downscaler_kwargs):
@@ -172,3 +173,25 @@ def get_decoder(model_dir, dataloader_generator, data_processor, encoder, decode
                    positional_embedding_size=k['positional_embedding_size'], num_channels_encoder=num_channels_encoder,
                    num_events_encoder=num_events_encoder, num_channels_decoder=num_channels_decoder,
                    num_events_decoder=num_events_decoder)
+
+
+def get_prior(model_dir, dataloader_generator, encoder, prior_type, prior_kwargs):
+    """getters.py:398-428.  'transformer_relative': one channel of merged codes, one event per code of the model window:
+    the window's tokens divided by the encoder's total downscaling.  The reference reads the window from the encoder's data
+    processor (:406-411); a CPC-trained encoder's describes ONE block, so the window of the prior's own dataloader (the
+    sequences it will be fed, as `get_decoder` takes the decoder's) is used where it has one.  `prior_kwargs['num_events']`
+    (optional, ours) states N explicitly and wins over both."""
+    if prior_type != 'transformer_relative':
+        raise NotImplementedError(f'prior_type {prior_type}: only the relative prior is built')
+    num_channels = 1
+    tokens = encoder.data_processor.num_tokens
+    if getattr(dataloader_generator, 'num_events', None) and getattr(dataloader_generator, 'num_channels', None):
+        tokens = dataloader_generator.num_events * dataloader_generator.num_channels
+    num_events = int(tokens // (np.prod(encoder.downscaler.downscale_factors) * num_channels))
+    k = prior_kwargs
+    if k.get('num_events') is not None:
+        num_events = int(k['num_events'])
+    return PriorRelative(model_dir=model_dir, dataloader_generator=dataloader_generator, encoder=encoder,
+                         d_model=k['d_model'], num_layers=k['num_layers'], n_head=k['n_head'],
+                         dim_feedforward=k['dim_feedforward'], embedding_size=k['embedding_size'], num_channels=num_channels,
+                         num_events=num_events, dropout=k['dropout'])

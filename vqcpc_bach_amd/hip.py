@@ -195,6 +195,10 @@ SIGNATURES = {
                                           c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     'vqcpc_decode_window': (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_ptr,
                                     c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_prior_sample': (c_int, [c_ptr, c_i64, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_int,
+                                   c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_window': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr,
+                                   c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
 }
 
 # Entry points of LAB builds only (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so, the `#ifdef VQCPC_LAB`

@@ -1,0 +1,305 @@
+"""KV-cached sampling of code sequences from the prior (reference: VQCPCB/priors/prior_relative.py:308-353, which runs one
+full forward on the model window per code and samples on the host).
+
+The prior is one causal stack: position e's logits depend on codes < e of the window only (row-wise table lookup /
+LayerNorm / FFN, causal self-attention), so an incremental step per code computes the same function.  The step is the
+decoder's (decoders/generation.py) without the cross-attention, 7 launches per layer + 2:
+
+  in_proj -> self-attention on the layer's K/V cache (the step's k / v row is stored at row pos) -> out_proj + residual ->
+  add & LayerNorm -> linear1 + ReLU -> linear2 + residual -> add & LayerNorm;  then the head and vqcpc_prior_sample, which
+  draws the code of position pos, writes the input row of position pos + 1 and advances the device counter `pos`.
+
+Two regimes, as in the reference (:331-336):
+
+  head (e < N): the first window.  One step per code; ONE captured step replayed N times.
+  sliding (e >= N): the reference's window is [e - N + 1, e] and the code comes from its LAST position, i.e. the window
+  moves by one code per code.  The window's first input row becomes the start-of-sentence row and every other row loses
+  one code of context, so EVERY cache row is stale.  Per move: vqcpc_prior_window (commit the live window's codes, load the
+  next window's, the prefix's table rows, the input row of position P, the window's seeds, pos = P) -> the stack
+  teacher-forced over the P prefix rows of every sequence (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd,
+  vqcpc_decode_prefill_attn; the last layer stops after its k | v) -> N - P cached steps.
+  window_stride = 1 is the reference exactly: P = N - 1, one step per move.  At that stride the cache saves only the last
+  layer's prefix outputs and the head over the window's rows; a move costs about one full forward minus those, and what the
+  captured move buys is host launch time.  window_stride = k > 1 (opt-in) moves k codes at a time: P = N - k, k steps per
+  move, 1 / k of the re-prefills, but code e then sees N - k .. N - 1 previous codes instead of always N - 1 -- a slightly
+  different model context, not the reference's.
+
+Window index, position and seeds live in device memory and the window kernel advances the index by the stride, so ONE
+captured move (window kernel + re-prefill) and the ONE captured step serve every move of a generation.  A last, shorter
+move (when (num_tokens - N) % stride != 0) runs eagerly.
+
+Two forms of a step.  The CACHED form above streams every weight once per step and applies it row by row
+(vqcpc_decode_linear), which is the cheap form for a few rows.  The FORWARD form (`step_forward`) runs the training path's
+stack over all N rows of the window (table lookup, `forward_rows_masked`: well-filled GEMMs at 24 rows per sequence), the head
+on the one row of the position (vqcpc_decode_linear reading that row of every sequence through its leading dimension) and
+the same sampler: the reference's algorithm on this package's kernels.  In the sliding regime at stride 1 a cached move is a
+re-prefill of N - 1 rows (about one forward) PLUS one cached step, so the forward form is never more work there: a move is
+the window kernel + forward + head + sampler.  Its launches are not captured: the stack is GPU-bound from one row on (650 us
+eager, 654 us replayed at B = 1), so a graph returns nothing and its capture costs a few ms per generation.  In the head
+regime the forward form recomputes the rows before the position, so it wins only when the cached step's row-by-row linears
+dominate (measured: from 32 rows).  `run(method='auto')` picks per regime and batch from the
+measurements in profiles/generate_prior_perf_log.md (`FORWARD_HEAD_MIN_ROWS`, `FORWARD_SLIDE_MIN_ROWS`); 'cached' and
+'forward' force one form.  Strides > 1 always use the cached form.
+
+Rows are independent and every kernel reduces in an order that does not depend on the number of rows, so a row's codes do
+not depend on which other rows share the call (given the same seed and the same form; the two forms agree to rounding, so
+a draw that sits within ~1e-6 of a cumulative-probability boundary can differ between them)."""
+import torch
+
+from .. import hip, ops
+from ..decoders.generation import MAX_ROWS, row_seeds
+
+# method='auto': rows from which the forward form replaces the cached step (profiles/generate_prior_perf_log.md: at the PRI
+# shape the head step costs 376 / 1 096 us cached against 735 / 995 us forward at 8 / 32 rows; a stride-1 move 651 / 910 / 1 916 us
+# cached against 650 / 742 / 1 012 us forward at 1 / 8 / 32 rows)
+FORWARD_HEAD_MIN_ROWS = 32
+FORWARD_SLIDE_MIN_ROWS = 1
+
+
+class IncrementalPrior:
+    """One generation of `batch` <= 64 rows of `prior` (a PriorRelative in eval mode; the caller holds utils.STEP_LOCK).
+
+        inc = IncrementalPrior(prior, B)
+        inc.start(num_tokens, seeds, temperature, top_k, top_p)
+        codes = inc.run(use_graph, window_stride)                 # (B, num_tokens) int64
+
+    `start` + `slide` + `step` expose the single launches (teacher forcing, the sampler's input `logits` and its optional
+    probability output `probs`) for the tests."""
+
+    def __init__(self, prior, batch):
+        if not 1 <= batch <= MAX_ROWS:
+            raise ValueError(f'IncrementalPrior: 1 <= batch <= {MAX_ROWS} (got {batch})')
+        pr = self.prior = prior
+        self.M = M = int(batch)
+        self.dev = dev = pr.sos.device
+        self.d, self.N, self.V = pr.d_model, pr.num_tokens, pr.num_tokens_per_channel[0]
+        self.layers = list(pr.transformer.layers)
+        a = self.layers[0].self_attn
+        self.H, self.hd = a.num_heads, a.head_dim
+        self.ff = self.layers[0].linear1.weight.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        d, N, L = self.d, self.N, len(self.layers)
+        self.x = torch.empty(M, d, **f32)                     # input rows of the current position
+        self.hb = [torch.empty(M, d, **f32) for _ in range(2)]
+        self.h1, self.s, self.att = (torch.empty(M, d, **f32) for _ in range(3))
+        self.qkv = torch.empty(M, 3 * d, **f32)
+        self.f = torch.empty(M, self.ff, **f32)
+        self.logits = torch.empty(M, self.V, **f32)
+        self.mean, self.rstd = torch.empty(M, **f32), torch.empty(M, **f32)
+        self.kcache = torch.empty(L, M, N, d, **f32)
+        self.vcache = torch.empty(L, M, N, d, **f32)
+        self.codes_win = torch.zeros(M, N, dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.seeds = torch.zeros(M, dtype=torch.int64, device=dev)        # the live window's effective seeds
+        self.row_seeds = torch.zeros(M, dtype=torch.int64, device=dev)
+        self.win = torch.tensor([0, -1], dtype=torch.int32, device=dev)   # {next window, live window}
+        self.prefix_rows = torch.zeros(M * N, dtype=torch.int64, device=dev)
+        self._pmean = torch.empty(M * N, **f32)
+        self._prstd = torch.empty(M * N, **f32)
+        self.teacher = None
+        self.probs = None
+        self._sos_col = torch.full((M, 1), self.V, dtype=torch.int64, device=dev)    # table row of the start-of-sentence input
+        with torch.no_grad():
+            self.table = pr._input_table().contiguous()                    # (V + 1, d)
+        head = pr.pre_softmaxes[0]
+        self.head_w, self.head_b = head.weight, head.bias
+
+    def start(self, num_tokens, seeds=None, temperature=1.0, top_k=0, top_p=1.0, teacher=None, want_probs=False):
+        """A new generation of `num_tokens` >= N codes per row.  teacher: (M, N) codes of the live window to force instead
+        of drawing (single-step use); want_probs: keep the filtered probabilities of the last step in `probs` (M, V)."""
+        if not temperature > 0:
+            raise ValueError('temperature must be > 0')
+        if num_tokens < self.N:
+            raise ValueError(f'IncrementalPrior: num_tokens >= {self.N} (got {num_tokens})')
+        self.nt = int(num_tokens)
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        if seeds is not None:
+            self.row_seeds.copy_(row_seeds(seeds, self.M))
+        self.teacher = None if teacher is None else teacher.to(self.dev, torch.int64).reshape(self.M, self.N).contiguous()
+        self.probs = torch.zeros(self.M, self.V, dtype=torch.float32, device=self.dev) if want_probs else None
+        self.seq = torch.zeros(self.M, self.nt, dtype=torch.int64, device=self.dev)
+        self.reset()
+
+    def reset(self):
+        """Back to the head regime's first position; the sequence is cleared."""
+        self.seq.zero_()
+        self.codes_win.zero_()
+        self.ticket.zero_()
+        self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
+        self._window(0, 0)                                    # window 0, P = 0: start-of-sentence row, the rows' own seeds
+
+    # ---- one step ----------------------------------------------------------------------------------------------------
+    def _ln(self, s, norm, out):
+        hip.call('vqcpc_add_layernorm_fwd', s, self.d, None, norm.weight, norm.bias, out, self.mean, self.rstd, self.M, self.d,
+                 1e-5, 0.0, 0)
+
+    def _linear(self, x, w, b, out, res=None, relu=0):
+        N, K = w.shape
+        hip.call('vqcpc_decode_linear', x, x.shape[1], None, w, b, res, out.shape[1] if res is not None else 0, out,
+                 out.shape[1], self.M, N, K, relu)
+
+    def step(self):
+        M, d, N, H, hd = self.M, self.d, self.N, self.H, self.hd
+        hin = self.x
+        for li, lay in enumerate(self.layers):
+            sa = lay.self_attn
+            hout = self.hb[li % 2]
+            self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
+            q0 = self.qkv.data_ptr()
+            hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
+                     sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, N, 1, H, hd, ops.MASK_CAUSAL)
+            self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
+            self._ln(self.s, lay.norm1, self.h1)
+            self._linear(self.h1, lay.linear1.weight, lay.linear1.bias, self.f, relu=1)
+            self._linear(self.f, lay.linear2.weight, lay.linear2.bias, self.s, res=self.h1)
+            self._ln(self.s, lay.norm2, hout)
+            hin = hout
+        self._linear(hin, self.head_w, self.head_b, self.logits)
+        self._sample()
+
+    def _sample(self):
+        N = self.N
+        hip.call('vqcpc_prior_sample', self.logits, self.V, self.V, self.M, self.temperature, self.top_k, self.top_p,
+                 self.seeds, self.teacher, N, self.codes_win, N, N, self.table, self.table.shape[0], self.d, self.x, self.d,
+                 self.probs, self.V, self.pos, self.ticket)
+
+    def step_forward(self, p):
+        """The forward form of the step at position p (the caller's p must be the device's `pos`): the training path's
+        stack over the window's N rows, the head on row p of every sequence, the sampler."""
+        M, N, d, V = self.M, self.N, self.d, self.V
+        if not 0 <= p < N:
+            raise ValueError(f'step_forward: 0 <= p < {N} (got {p})')
+        idx = torch.cat([self._sos_col, self.codes_win[:, :N - 1]], dim=1).reshape(-1)       # the shift by one
+        rows = ops.EmbeddingFn.apply(self.table, idx)                                        # (M * N, d)
+        out, _ = self.prior.transformer.forward_rows_masked(rows, M, ops.MASK_CAUSAL)
+        hip.call('vqcpc_decode_linear', out.data_ptr() + 4 * p * d, N * d, None, self.head_w, self.head_b, None, 0, self.logits,
+                 V, M, V, d, 0)
+        self._sample()
+
+    def _move_forward(self):
+        """One stride-1 move in the forward form: commit / load the next window at position N - 1, then its one code."""
+        self._window(self.N - 1, 1)
+        self.step_forward(self.N - 1)
+
+    # ---- moving the window ---------------------------------------------------------------------------------------------
+    def _window(self, P, advance):
+        hip.call('vqcpc_prior_window', self.seq, self.nt, self.nt, self.win, int(advance), self.codes_win, self.N, int(P),
+                 self.prefix_rows, self.table, self.table.shape[0], self.d, self.x, self.d, self.row_seeds, self.seeds,
+                 self.pos, self.M)
+
+    def _prefix_ln(self, x, r, norm):
+        y = torch.empty_like(x)
+        n = x.shape[0]
+        hip.call('vqcpc_add_layernorm_fwd', x, self.d, r, norm.weight, norm.bias, y, self._pmean[:n], self._prstd[:n], n, self.d,
+                 1e-5, 0.0, 0)
+        return y
+
+    def prefill_prefix(self, P):
+        """The stack, teacher-forced over prefix rows [0, P) of every sequence (inputs: table rows `prefix_rows`): fills
+        every layer's K/V cache rows [0, P)."""
+        if P == 0:
+            return
+        M, d, N, H, hd = self.M, self.d, self.N, self.H, self.hd
+        h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
+        last = len(self.layers) - 1
+        for li, lay in enumerate(self.layers):
+            sa = lay.self_attn
+            qkv = ops.gemm_nt(h, sa.in_proj_weight, bias=sa.in_proj_bias)
+            att = torch.empty(M * P, d, dtype=torch.float32, device=self.dev) if li < last else None
+            hip.call('vqcpc_decode_prefill_attn', qkv, 3 * d, qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, 3 * d,
+                     self.kcache[li], self.vcache[li], d, sa.attn_bias.e1, sa.attn_bias.e2, att, d, M, P, N, 1, H, hd,
+                     ops.MASK_CAUSAL)
+            if li == last:
+                break                                     # nothing reads the last layer's prefix outputs
+            h1 = self._prefix_ln(h, ops.gemm_nt(att, sa.out_proj.weight, bias=sa.out_proj.bias), lay.norm1)
+            f = ops.gemm_nt(h1, lay.linear1.weight, bias=lay.linear1.bias, act=1)
+            h = self._prefix_ln(h1, ops.gemm_nt(f, lay.linear2.weight, bias=lay.linear2.bias), lay.norm2)
+
+    @torch.no_grad()
+    def slide(self, w=None, P=0, advance=1):
+        """Moves the generation to the window of codes [w, w + N) at position P: commits the live window, loads the new one
+        and re-prefills its prefix.  w=None takes the window index the device holds (the previous window's + its advance)."""
+        if w is not None:
+            if not 0 <= w <= self.nt - self.N:
+                raise ValueError(f'slide: 0 <= w <= {self.nt - self.N} (got {w})')
+            self.win[0:1].fill_(int(w))
+        if not 0 <= P < self.N:
+            raise ValueError(f'slide: 0 <= P < {self.N} (got {P})')
+        self._window(P, advance)
+        self.prefill_prefix(int(P))
+
+    def commit(self):
+        """Puts the live window's codes into the sequence (no new window is loaded)."""
+        self.win[0:1].fill_(-1)
+        self._window(0, 0)
+
+    # ---- a whole generation --------------------------------------------------------------------------------------------
+    def _forms(self, method, stride):
+        if method not in ('auto', 'cached', 'forward'):
+            raise ValueError(f"method: 'auto', 'cached' or 'forward' (got {method!r})")
+        if method == 'forward' and stride != 1:
+            raise ValueError("method='forward' moves the window one code at a time (window_stride = 1)")
+        if method == 'auto':
+            head = 'forward' if self.M >= FORWARD_HEAD_MIN_ROWS else 'cached'
+            slide = 'forward' if stride == 1 and self.M >= FORWARD_SLIDE_MIN_ROWS else 'cached'
+            return head, slide
+        return method, method
+
+    @torch.no_grad()
+    def run(self, use_graph=True, window_stride=1, graph_slides=None, method='auto'):
+        """Generates the `num_tokens` codes of `start`: N steps in window 0, then moves of `window_stride` codes.
+        method: the form of the steps per regime (module docstring).  use_graph: the cached step is a captured graph (the
+        forward form's launches are always eager); graph_slides (default: use_graph): the cached form's full-stride moves are ONE captured graph
+        too.  Returns the sequence (M, num_tokens)."""
+        N, nt, k = self.N, self.nt, int(window_stride)
+        if not 1 <= k < max(N, 2):
+            raise ValueError(f'run: 1 <= window_stride < {N} (got {window_stride})')
+        head_form, slide_form = self._forms(method, k)
+        n_full, rem = divmod(nt - N, k)
+        graph_slides = use_graph if graph_slides is None else graph_slides
+        step_graph = slide_graph = None
+        warmed = False
+        if use_graph and (head_form == 'cached' or (slide_form == 'cached' and nt > N)):
+            self.step()                           # first launches outside the capture
+            torch.cuda.synchronize(self.dev)
+            step_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(step_graph, capture_error_mode='thread_local'):
+                self.step()
+            warmed = True
+        if slide_form == 'cached' and graph_slides and n_full >= 2:
+            self.slide(0, N - k, advance=k)
+            torch.cuda.synchronize(self.dev)
+            slide_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(slide_graph, capture_error_mode='thread_local'):
+                self.slide(None, N - k, advance=k)
+            warmed = True
+        if warmed:
+            self.reset()                          # the warm-up launches drew and committed codes: start again
+        step = step_graph.replay if step_graph is not None else self.step
+        if head_form == 'forward':
+            for p in range(N):
+                self.step_forward(p)
+        else:
+            for _ in range(N):
+                step()
+        for i in range(n_full):
+            if slide_form == 'forward':
+                if i == 0:
+                    self.win[0:1].fill_(1)        # afterwards the window kernel advances the device's index by one per move
+                self._move_forward()
+            elif slide_graph is not None and i >= 1:
+                slide_graph.replay()              # the device's window index is (i + 1) * k already
+            else:
+                self.slide((i + 1) * k, N - k, advance=k)
+            if slide_form == 'cached':
+                for _ in range(k):
+                    step()
+        if rem:
+            self.slide(nt - N, N - rem, advance=0)
+            for _ in range(rem):
+                step()
+        self.commit()
+        torch.cuda.current_stream(self.dev).synchronize()
+        del step_graph, slide_graph
+        return self.seq
