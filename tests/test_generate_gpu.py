@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import load_golden, sub_state
+from decode_reference import filter_ref as _filtered_probs
 from oracle import decoder_oracle as D
 from test_decoder_gpu import build_decoder, seeded_decoder
 
@@ -132,22 +133,6 @@ def test_filter_equals_the_reference():
                     assert torch.equal(pr > 0, ref_keep), (V, k, p, temp)
                     f = f.masked_fill(~ref_keep, -float('inf'))
                     assert float((pr - torch.softmax(f, dim=-1)).abs().max()) < 1e-6, (V, k, p, temp)
-
-
-def _filtered_probs(row, temperature, top_k, top_p, exclude):
-    """The reference rule (utils.py:101-128, excluded tokens -inf first) in float64."""
-    lg = torch.tensor(row, dtype=torch.float64) / temperature
-    lg[list(exclude)] = -float('inf')
-    if top_k > 0:
-        lg[lg < torch.topk(lg, top_k)[0][-1]] = -float('inf')
-    if 0 < top_p < 1:
-        srt, idx = torch.sort(lg, descending=True)
-        cum = torch.cumsum(torch.softmax(srt, dim=-1), dim=-1)
-        rm = cum > top_p
-        rm[1:] = rm[:-1].clone()
-        rm[0] = False
-        lg[idx[rm]] = -float('inf')
-    return torch.softmax(lg, dim=-1)
 
 
 @pytest.mark.parametrize('temperature', [0.5, 1.0, 2.0])

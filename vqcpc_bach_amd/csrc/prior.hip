@@ -31,9 +31,12 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
-// order-preserving map float -> uint32 (a < b  <=>  key(a) < key(b); -inf is the smallest key of a non-NaN value)
+// order-preserving map float -> uint32 (a < b  <=>  key(a) < key(b); -inf is the smallest key of a non-NaN value).  -0.0 takes
+// the key of +0.0: the two compare equal as floats (the reference's `logits < kth`, utils.py:113, keeps a -0.0 next to a k-th
+// largest +0.0), and their bit patterns would order them strictly
 __device__ __forceinline__ uint32_t float_key(float v) {
-    const uint32_t u = __float_as_uint(v);
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
