@@ -199,7 +199,9 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict
         }
         const int64_t nrow = row + step;
         LNF_FETCH(nrow)
-        const float mu = wave_sum(sum) * inv_d;
+        // a true division: `sum * (1 / d)` with the rounded reciprocal puts the mean of a CONSTANT row one ulp off the constant when
+        // d is no power of two, and rstd = 1 / sqrt(eps) turns that ulp into an output error of 316 ulp (y != beta)
+        const float mu = wave_sum(sum) / (float)d;
         float sq = 0.0f;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {

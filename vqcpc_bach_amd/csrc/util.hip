@@ -279,9 +279,13 @@ __global__ __launch_bounds__(256) void transpose_many_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float selu_f(float x) {
-    const float alpha = 1.6732632423543772848170429916717f, scale = 1.0507009873554804934193349852946f;
-    return scale * (x > 0.0f ? x : alpha * (__expf(x) - 1.0f));
+// x = h * mask scale, formed and evaluated in double and rounded ONCE: `alpha * (__expf(x) - 1)` in fp32 loses all relative
+// accuracy as x -> 0- (6e-5 at x = -1e-3, several per cent at -1e-6); the kernel is bandwidth-trivial and only the student
+// step's MlpUpscaler runs it, so the fp64 expm1 costs nothing that can be measured
+__device__ __forceinline__ float selu_f(float h, float s) {
+    const double alpha = 1.6732632423543772848170429916717, scale = 1.0507009873554804934193349852946;
+    const double x = (double)h * (double)s;
+    return (float)(scale * (x > 0.0 ? x : alpha * expm1(x)));
 }
 __device__ __forceinline__ float selu_grad(float x) {
     const float alpha = 1.6732632423543772848170429916717f, scale = 1.0507009873554804934193349852946f;
@@ -292,7 +296,7 @@ __global__ __launch_bounds__(256) void dropout_selu_fwd_kernel(const float* __re
                                                                int64_t n, uint32_t thr, float inv_keep, uint64_t seed) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += step) out[i] = selu_f(h[i] * drop_scale(seed, (uint64_t)i, thr, inv_keep));
+    for (; i < n; i += step) out[i] = selu_f(h[i], drop_scale(seed, (uint64_t)i, thr, inv_keep));
 }
 
 __global__ __launch_bounds__(256) void dropout_selu_bwd_kernel(const float* __restrict__ h, const float* __restrict__ g,
