@@ -536,6 +536,39 @@ int vqcpc_gru_step_bwd(const float* dgh_next, const float* whh_t, float* dhp, co
                        uint64_t seed, uint64_t idx_base, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * First layer of the GRU block downscaler (LstmDownscaler.compute_z, lstm_downscaler.py:73-94: g_enc_fwd on the blocks,
+ * g_enc_bwd on x.flip(dims=[1]); x = BachCPCDataProcessor.embed, bach_cpc_data_processor.py:24-28: a per-voice table
+ * lookup without a positional term).  gi = x W_ih^T + b_ih of nn.GRU's first layer then takes n_voices * vmax distinct
+ * rows, so it is computed once on the stacked embedding tables, gi_table [n_voices * vmax][3H], and the step kernels read
+ *   gi of row b  =  gi_table[(p % n_voices) * vmax + tokens[b * L + p]][0 .. 3H)
+ * for the step at block position p (p = t for the forward stack, L - 1 - t for the flipped one); tokens [B][L] int64,
+ * clamped into [0, vmax).  Everything else -- arguments, arithmetic, dropout indices -- is that of the four entry points
+ * above: their results are bit-identical when gi holds the gathered rows.  d_gi stays a [B][3H] buffer of the step.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_gru_tok_cell_fwd(const float* gi_table, const int64_t* tokens, int L, int p, int n_voices, int vmax, const float* gh,
+                           const float* h_prev, float* h_out, float* y_out, int64_t B, int H, float drop_p, uint64_t seed,
+                           uint64_t idx_base, void* stream);
+int vqcpc_gru_tok_cell_bwd(const float* gi_table, const int64_t* tokens, int L, int p, int n_voices, int vmax, const float* gh,
+                           const float* h_prev, const float* d_y, const float* d_h, float* d_gi, float* d_gh, float* d_hprev,
+                           int64_t B, int H, float drop_p, uint64_t seed, uint64_t idx_base, void* stream);
+int vqcpc_gru_tok_step_fwd(const float* gi_table, const int64_t* tokens, int L, int p, int n_voices, int vmax, const float* w_hh,
+                           const float* b_hh, const float* h_prev, float* gh, float* h_out, float* y_out, int64_t B, int H,
+                           float drop_p, uint64_t seed, uint64_t idx_base, void* stream);
+int vqcpc_gru_tok_step_bwd(const float* dgh_next, const float* whh_t, float* dhp, const float* gi_table, const int64_t* tokens,
+                           int L, int p, int n_voices, int vmax, const float* gh, const float* h_prev, const float* d_y,
+                           float* d_gi, float* d_gh, int64_t B, int H, float drop_p, uint64_t seed, uint64_t idx_base,
+                           void* stream);
+/* Gradient of gi_table from ONE step's d_gi [R][C] (C = 3H): for every v in [0, vmax)
+ *   d_table[(p % n_voices) * vmax + v][:]  (accumulate ? += : =)  sum of d_gi[b][:] over the rows b with tokens[b * L + p] == v,
+ * rows added in ascending order within 64 row chunks at the most, the chunks in ascending order (no float atomics: two calls
+ * give the same bits); a v that no row holds gets 0 (accumulate = 0) or stays (accumulate = 1).  The backward pass calls it
+ * once per step: the first visit of a voice writes, later ones accumulate (the embedding backward that nn.GRU's first
+ * layer ends in, lstm_downscaler.py:79,84). */
+int64_t vqcpc_gru_tok_segsum_workspace(int64_t R, int vmax, int C);
+int vqcpc_gru_tok_segsum(const float* d_gi, const int64_t* tokens, int L, int p, int n_voices, int vmax, float* d_table, int64_t R,
+                         int C, int accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Student (distilled VQ-VAE) step, SURVEY.md section 8 row A23.
  *
  * vqcpc_softmax_ce: one row = one (batch row, masked event, channel) logit vector.

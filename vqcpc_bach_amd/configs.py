@@ -46,8 +46,9 @@ def make_decoder_config(dropout=0.2, **over):
     """VQCPCB/configs/decoder_relative_AC_AC_C_random.py:4-46 (24 beats = 96 ticks = 384
     target tokens, d_model 512, 8 heads, 3 + 3 layers, ff 1024, dropout 0.2, batch 32, scheduled lr) on the frozen
     transformer encoder of VQCPCB/configs/encoder_random_transfo_config.py:26-63 (d_model 512, 8 heads, [2, 2] layers,
-    ff 2048, 1 x 32 codes of dim 3) -- the shipped decoder configs point at LSTM-downscaler encoders, which are out of
-    scope."""
+    ff 2048, 1 x 32 codes of dim 3).  The shipped decoder configs point at LSTM-downscaler encoders; that encoder is
+    `make_config('SAMESEQ')` and can be passed as `config_encoder=...` -- the default stays the transformer encoder the DEC
+    measurements were taken with."""
     enc = make_config('C1', dropout=0.1)
     enc['downscaler_kwargs'].update(d_model=512, n_head=8, list_of_num_layers=[2, 2], dim_feedforward=2048)
     enc['quantizer_kwargs'].update(num_codebooks=1, codebook_size=32, codebook_dim=3, initialize=False)
@@ -85,7 +86,39 @@ def make_prior_config(dropout=0.2, **over):
     return cfg
 
 
+def make_sameseq_config(dropout=0.1, **over):
+    """VQCPCB/configs/encoder_sameSeq.py:11-86 in this package's schema: the GRU block downscaler ('lstm_downscaler':
+    hidden 512, 2 layers, bidirectional, one 16-token block per code), 1 x 32 codes of dim 3, MLP upscaler 32 / 512, context
+    network 512 x 2, quantization weighting 1.0, batch 16, 6 + 6 blocks, same-sequence negatives (num_negative_samples = 15
+    is stated and unused there)."""
+    cfg = {
+        'training_method': 'vqcpc', 'dataset': 'bach',
+        'dataloader_generator_kwargs': dict(num_tokens_per_block=16, num_blocks_left=6, num_blocks_right=6,
+                                            negative_sampling_method='same_sequence', num_negative_samples=15,
+                                            sequences_size=1),
+        'subdivision': 4,
+        'data_processor_type': 'bach_cpc', 'data_processor_kwargs': dict(embedding_size=32),
+        'downscaler_type': 'lstm_downscaler',
+        'downscaler_kwargs': dict(downscale_factors=[16], hidden_size=512, num_layers=2, dropout=dropout, bidirectional=True),
+        'quantizer_type': 'commitment',
+        'quantizer_kwargs': dict(num_codebooks=1, codebook_size=32, codebook_dim=3, commitment_cost=0.25,
+                                 use_batch_norm=False, squared_l2_norm=True, initialize=True),
+        'upscaler_type': 'mlp_upscaler', 'upscaler_kwargs': dict(output_dim=32, hidden_size=512, dropout=dropout),
+        'auxiliary_networks_kwargs': {'quantization_weighting': 1.0,
+                                      'c_net_kwargs': dict(output_dim=32, hidden_size=512, num_layers=2, dropout=dropout,
+                                                           bidirectional=False)},
+        'lr': 1e-4, 'schedule_lr': False, 'batch_size': 16, 'num_batches': 256, 'num_epochs': 1,
+        'quantizer_regularization': dict(corrupt_labels=False), 'timestamp': None, 'savename': 'encoder_sameSeq',
+    }
+    cfg = copy.deepcopy(cfg)
+    for k, v in over.items():
+        cfg[k] = v
+    return cfg
+
+
 def make_config(name='C1', dropout=0.1, **over):
+    if name == 'SAMESEQ':
+        return make_sameseq_config(dropout=dropout, **over)
     if name == 'PRI':
         return make_prior_config(dropout=dropout, **over)
     if name == 'C3':

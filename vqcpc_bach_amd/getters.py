@@ -9,6 +9,7 @@ from .data_processor.bach_data_processor import BachDataProcessor
 from .dataloaders.synthetic_cpc_dataloader import SyntheticCPCDataloaderGenerator
 from .dataloaders.synthetic_student_dataloader import SyntheticStudentDataloaderGenerator
 from .decoders.decoder import Decoder
+from .downscalers.lstm_downscaler import LstmDownscaler
 from .downscalers.relative_transformer_downscaler import RelativeTransformerDownscaler
 from .downscalers.relative_transformer_downscaler_linear import RelativeTransformerDownscalerLinear
 from .encoder import Encoder
@@ -44,7 +45,13 @@ def get_downscaler(downscaler_type, downscaler_kwargs):
                                                    num_channels=k['num_channels'], d_model=k['d_model'],
                                                    n_head=k['n_head'], list_of_num_layers=k['list_of_num_layers'],
                                                    dim_feedforward=k['dim_feedforward'], dropout=k['dropout'])
-    raise NotImplementedError(f'{downscaler_type}: only the relative transformer downscalers are on the path')
+    if downscaler_type == 'lstm_downscaler':                                           # getters.py:74-85
+        k = downscaler_kwargs
+        return LstmDownscaler(input_dim=k['input_dim'], output_dim=k['output_dim'], num_channels=k['num_channels'],
+                              downscale_factors=k['downscale_factors'], hidden_size=k['hidden_size'],
+                              num_layers=k['num_layers'], dropout=k['dropout'], bidirectional=k['bidirectional'])
+    raise NotImplementedError(f'{downscaler_type}: only the relative transformer and the GRU block ("lstm") downscalers '
+                              'are on the path')
 
 
 def get_upscaler(upscaler_type, upscaler_kwargs):

@@ -2038,6 +2038,90 @@ class GRULayerFn(torch.autograd.Function):
         return dx, dw_ih, dw_hh, db_ih, db_hh, None, None, None, None
 
 
+# Most rows at which GRUTokLayerFn runs a step as the fused tok-step launch; above it a step is vqcpc_gemm_nt + the tok-cell
+# kernel.  The fused launch splits the contraction over the 8 waves of a 32 x 32 tile and re-reads W_hh per tile: built for
+# the context network's few hundred rows.  Measured at H = 512 (profiles/lstm_downscaler_perf_log.md): fused no slower at 256
+# and 1 632 rows, 1.7 x (forward) / 2.7 x (backward) slower at 2 304 and worse above; sizes in between are unmeasured and take
+# the baseline form.  GRULayerFn (context network) does not read it.
+GRU_TOK_FUSED_MAX_ROWS = 1632
+
+
+class GRUTokLayerFn(torch.autograd.Function):
+    """First nn.GRU layer (h0 = 0) of the GRU block downscaler on token blocks: tokens (R, L) int64, gi_table
+    (n_voices, vmax, 3H) = W_ih . (stacked embedding tables) + b_ih.  Step t reads gi of row b from the table row of
+    (voice p % n_voices, token tokens[b, p]), p = t (reverse = False) or L - 1 - t (the stack fed x.flip(dims=[1])), so the
+    (R L, 3H) input projection is never formed.  Outputs as GRULayerFn: y (L R, H) time-major in STEP order with dropout(p)
+    (last_only = False) or the last step (R, H).  Backward: d_gi is ONE (R, 3H) buffer, folded into d gi_table after every step
+    by the deterministic segment sum vqcpc_gru_tok_segsum; dW_ih, db_ih and the embedding gradients follow from d gi_table
+    through the small product that built the table."""
+
+    @staticmethod
+    def forward(ctx, tokens, gi_table, w_hh, b_hh, L, reverse, drop_p, seed, last_only):
+        nv, vmax, H3 = gi_table.shape
+        H = H3 // 3
+        tokens = tokens.reshape(-1, L).contiguous()
+        gi_table = _f32(gi_table).contiguous()
+        w_hh = w_hh.contiguous()
+        B, T = tokens.shape[0], int(L)
+        dev = gi_table.device
+        p = 0.0 if last_only else float(drop_p)
+        gh = torch.empty(T * B, 3 * H, dtype=torch.float32, device=dev)
+        h = torch.empty(T * B + B, H, dtype=torch.float32, device=dev)       # rows [t*B, (t+1)*B) = h_{t-1}; h_{-1} = 0
+        h[:B].zero_()
+        y = None if last_only else torch.empty(T * B, H, dtype=torch.float32, device=dev)
+        fused = bool(hip.query('vqcpc_gru_step_supported', B, H)) and B <= GRU_TOK_FUSED_MAX_ROWS
+        for t in range(T):
+            sl = slice(t * B, (t + 1) * B)
+            pos = T - 1 - t if reverse else t
+            if fused:
+                hip.call('vqcpc_gru_tok_step_fwd', gi_table, tokens, T, pos, nv, vmax, w_hh, b_hh, h[sl] if t > 0 else None, gh[sl],
+                         h[(t + 1) * B:(t + 2) * B], None if y is None else y[sl], B, H, p, int(seed), t * B * H)
+                continue
+            gemm_nt(h[sl], w_hh, bias=b_hh, out=gh[sl])
+            hip.call('vqcpc_gru_tok_cell_fwd', gi_table, tokens, T, pos, nv, vmax, gh[sl], h[sl], h[(t + 1) * B:(t + 2) * B],
+                     None if y is None else y[sl], B, H, p, int(seed), t * B * H)
+        ctx.save_for_backward(tokens, gi_table, w_hh, gh, h)
+        ctx.b_hh = b_hh
+        ctx.meta = (T, B, H, nv, vmax, bool(reverse), p, int(seed), bool(last_only), fused)
+        return h[T * B:].clone() if last_only else y
+
+    @staticmethod
+    def backward(ctx, g):
+        tokens, gi_table, w_hh, gh, h = ctx.saved_tensors
+        T, B, H, nv, vmax, reverse, p, seed, last_only, fused = ctx.meta
+        dev = gh.device
+        g = g.contiguous()
+        dgi = torch.empty(B, 3 * H, dtype=torch.float32, device=dev)        # one step's d_gi, reused
+        dgh = torch.empty_like(gh)
+        whh_t = transpose(w_hh)
+        # a voice that no position of the block belongs to (L < n_voices) is never visited: its rows must still be 0
+        d_table = (torch.empty if T >= nv else torch.zeros)(nv, vmax, 3 * H, dtype=torch.float32, device=dev)
+        nbytes = hip.query('vqcpc_gru_tok_segsum_workspace', B, vmax, 3 * H)
+        ws = hip.workspace(nbytes, dev)
+        seen = set()
+        dh = None
+        dhp = torch.empty(B, H, dtype=torch.float32, device=dev)
+        for t in range(T - 1, -1, -1):
+            sl = slice(t * B, (t + 1) * B)
+            pos = T - 1 - t if reverse else t
+            d_y = (g if t == T - 1 else None) if last_only else g[sl]
+            hp = h[sl] if t > 0 else None
+            if fused and t < T - 1:
+                nx = slice((t + 1) * B, (t + 2) * B)
+                hip.call('vqcpc_gru_tok_step_bwd', dgh[nx], whh_t, dhp, gi_table, tokens, T, pos, nv, vmax, gh[sl], hp, d_y, dgi,
+                         dgh[sl], B, H, p, seed, t * B * H)
+            else:
+                hip.call('vqcpc_gru_tok_cell_bwd', gi_table, tokens, T, pos, nv, vmax, gh[sl], h[sl], d_y, dh, dgi, dgh[sl], dhp,
+                         B, H, p, seed, t * B * H)
+                if t > 0 and not fused:
+                    dh = gemm_nt(dgh[sl], whh_t, add=dhp)                    # d h_{t-1} = dgh W_hh + dh * u
+            voice = pos % nv
+            hip.call('vqcpc_gru_tok_segsum', dgi, tokens, T, pos, nv, vmax, d_table, B, 3 * H, 1 if voice in seen else 0, ws, nbytes)
+            seen.add(voice)
+        dw_hh, db_hh = wgrad(dgh, h[:T * B], w_hh, ctx.b_hh)                 # step 0 multiplies the zero rows h_{-1}
+        return None, d_table, dw_hh, db_hh, None, None, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # A16/A17: bilinear scores + InfoNCE + hits
 # ------------------------------------------------------------------------------------------------------------------
