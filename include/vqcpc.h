@@ -460,7 +460,8 @@ int vqcpc_reduce_grouped(int n, const void* const* ws, const int64_t* stride, co
  * squared != 0: loss = (1 + beta) * sum (q - z)^2 computed as q_latent + beta * e_latent;
  * squared == 0: loss = (1 + beta) * || (q - z) + 1e-5 ||_2.
  * bwd: d_z = g_zq + g_loss * d(loss)/dz ; d_codebooks [ncb][K][dsub] = segment-sum of g_loss * d(loss)/dq
- * (this is the slot the north_star calls "codebook update": the reference trains codebooks by Adam, not EMA).
+ * (the reference trains codebooks by Adam through this gradient; the EMA codebook update the north_star names is the
+ * opt-in second quantiser below: vqcpc_vq_ema_stats / vqcpc_vq_commit_bwd / vqcpc_vq_ema_update).
  * ------------------------------------------------------------------------------------------------------------------  * zq_sg == loss == NULL (with assign = 1): index-only mode for inference consumers (decoders/decoder.py:327-336,
  * encoder.py:137-159 only read encoding_indices).
  */
@@ -470,6 +471,26 @@ int64_t vqcpc_vq_bwd_workspace(int64_t R, int ncb, int K, int dsub);
 int vqcpc_vq_bwd(const float* z, const float* codebooks, const int64_t* idx, const float* g_zq, const float* g_loss,
                  int64_t R, int ncb, int K, int dsub, float beta, int squared, float* d_z, float* d_codebooks,
                  void* workspace, int64_t workspace_bytes, void* stream);
+
+/* EMA codebooks (quantizer_type 'ema', EMAProductVectorQuantizer; no counterpart in the reference).  The forward search is
+ * vqcpc_vq_fwd with beta = 0 (loss = l exactly; the host scales it by beta).
+ * ema_stats: stats [ncb][K][1 + dsub], per code the COUNT of rows assigned to it (column 0) and the SUM of their sub-vectors
+ *   (columns 1..dsub), from z [R][D] and idx [R][ncb]: a deterministic segment sum (256-row chunks, one owning lane per LDS
+ *   cell, rows in ascending order, chunk partials reduced in chunk order; no float atomics), counts exact.  Refuses
+ *   R >= 2^24, dsub + 1 > 256 and K * (1 + dsub) floats that do not fit the LDS next to the staged chunk.  A row whose index
+ *   is outside [0, K) is skipped, never dereferenced.
+ * commit_bwd: d_z = g_zq + g_loss * beta * dl/dz for l = sum (q - z)^2 (squared) or ||(q - z) + 1e-5||; no codebook gradient
+ *   and no segment sum.  In the squared form d_z equals what vqcpc_vq_bwd writes for the same inputs, bit for bit.
+ * ema_update, in place, per codebook:  N_k <- g N_k + h n_k ;  m_k <- g m_k + h s_k ;  T = sum_k N_k (pairwise tree over K
+ *   padded to a power of two: a function of K alone) ;  Nt_k = (N_k + eps) / (T + K eps) * T ;  e_k <- m_k / Nt_k.
+ *   cluster_size [ncb][K], ema_sum and codebooks [ncb][K][dsub]; g = float(decay), h = float(1 - decay) rounded on the host. */
+int64_t vqcpc_vq_ema_stats_workspace(int64_t R, int ncb, int K, int dsub);
+int vqcpc_vq_ema_stats(const float* z, const int64_t* idx, int64_t R, int ncb, int K, int dsub, float* stats, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int vqcpc_vq_commit_bwd(const float* z, const float* codebooks, const int64_t* idx, const float* g_zq, const float* g_loss,
+                        int64_t R, int ncb, int K, int dsub, float beta, int squared, float* d_z, void* stream);
+int vqcpc_vq_ema_update(const float* stats, float* cluster_size, float* ema_sum, float* codebooks, int ncb, int K, int dsub,
+                        float g, float h, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * MlpUpscaler middle: h' = SELU(dropout(h))  (VQCPCB/upscalers/mlp_upscaler.py:21-34); element index = flat index.

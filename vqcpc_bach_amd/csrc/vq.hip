@@ -220,6 +220,140 @@ __global__ __launch_bounds__(kVqThreads) void vq_bwd_kernel(const float* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// EMA codebooks (EMAProductVectorQuantizer).  Three kernels; vq_fwd / vq_bwd above are untouched.
+//
+// statistics.  Per codebook c and code k: the number of rows assigned to k and the sum of their sub-vectors,
+// stats [ncb][K][W], W = 1 + dsub (column 0 = count, columns 1.. = sum).  The scheme of vq_bwd_kernel's phase B: workgroup =
+// chunk of 256 rows, the chunk's rows staged in LDS as val[256][W] = (1.0f, z sub-vector), cell (k, t) of the LDS accumulator
+// owned by exactly one lane (lane (k % kgroups) * W + t), rows applied in ascending order -> deterministic segment sum, no
+// atomics; partials go to the workspace and launch_reduce_splits adds the chunks in chunk order.  k % kgroups is taken once
+// per row by the row's own lane (kgroups = 256 / W is rarely a power of two here: 15 at dsub = 16).  A row whose index is
+// outside [0, K) is skipped (its group is -1: no lane owns it), never dereferenced.
+__global__ __launch_bounds__(kVqThreads) void vq_ema_stats_kernel(const float* __restrict__ z, const int64_t* __restrict__ idx,
+                                                                  int64_t R, int ncb, int K, int dsub, float* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int W = dsub + 1;
+    const int D = ncb * dsub;
+    float* acc = lds;                                              // [K][W]
+    float* val = lds + (size_t)K * W;                              // [256][W]
+    int* sidx = reinterpret_cast<int*>(val + kVqThreads * W);      // [256] code of the row
+    int* sgrp = sidx + kVqThreads;                                 // [256] code % kgroups, -1: skip the row
+    const int64_t r = (int64_t)blockIdx.x * kVqThreads + threadIdx.x;
+    const bool live = r < R;
+    const int rows_here = (int)min((int64_t)kVqThreads, R - (int64_t)blockIdx.x * kVqThreads);
+    const int kgroups = kVqThreads / W;                            // W <= 256 checked on the host
+    const int my_t = threadIdx.x % W, my_g = threadIdx.x / W;
+
+    for (int c = 0; c < ncb; ++c) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < K * W; i += kVqThreads) acc[i] = 0.0f;
+        if (live) {
+            const int64_t k64 = idx[r * ncb + c];
+            const bool ok = k64 >= 0 && k64 < (int64_t)K;
+            sidx[threadIdx.x] = ok ? (int)k64 : 0;
+            sgrp[threadIdx.x] = ok ? (int)(k64 % kgroups) : -1;
+            val[threadIdx.x * W] = 1.0f;
+            for (int t = 0; t < dsub; ++t) val[threadIdx.x * W + 1 + t] = z[r * D + c * dsub + t];
+        }
+        __syncthreads();
+        if (my_g < kgroups) {
+            for (int row = 0; row < rows_here; ++row) {
+                if (sgrp[row] == my_g) acc[sidx[row] * W + my_t] += val[row * W + my_t];
+            }
+        }
+        __syncthreads();
+        float* dst = ws + ((int64_t)blockIdx.x * ncb + c) * K * W;
+        for (int i = threadIdx.x; i < K * W; i += kVqThreads) dst[i] = acc[i];
+    }
+}
+
+// commitment backward: d_z = g_zq + g_loss * beta * dl/dz only (lane = row, the arithmetic of vq_bwd_kernel's phase A, so the
+// squared form gives vq_bwd's d_z bit for bit); no segment sum, no LDS.  A row with an index outside [0, K) gets d_z = g_zq.
+__global__ __launch_bounds__(kVqThreads) void vq_commit_bwd_kernel(const float* __restrict__ z, const float* __restrict__ cb,
+                                                                   const int64_t* __restrict__ idx,
+                                                                   const float* __restrict__ g_zq,
+                                                                   const float* __restrict__ g_loss, int64_t R, int ncb, int K,
+                                                                   int dsub, float beta, int squared, float* __restrict__ d_z) {
+    const int D = ncb * dsub;
+    const int64_t r = (int64_t)blockIdx.x * kVqThreads + threadIdx.x;
+    if (r >= R) return;
+    bool ok = true;
+    for (int c = 0; c < ncb; ++c) {
+        const int64_t k = idx[r * ncb + c];
+        ok = ok && k >= 0 && k < (int64_t)K;
+    }
+    if (!ok) {
+        for (int col = 0; col < D; ++col) d_z[r * D + col] = g_zq[r * D + col];
+        return;
+    }
+    float inv_n = 0.0f;
+    if (!squared) {
+        float s = 0.0f;
+        for (int c = 0; c < ncb; ++c) {
+            const float* q = cb + ((int64_t)c * K + idx[r * ncb + c]) * dsub;
+            for (int t = 0; t < dsub; ++t) {
+                const float v = (q[t] - z[r * D + c * dsub + t]) + 1e-5f;
+                s += v * v;
+            }
+        }
+        inv_n = 1.0f / sqrtf(s);
+    }
+    const float gl = g_loss[r];
+    for (int c = 0; c < ncb; ++c) {
+        const float* q = cb + ((int64_t)c * K + idx[r * ncb + c]) * dsub;
+        for (int t = 0; t < dsub; ++t) {
+            const int col = c * dsub + t;
+            const float diff = q[t] - z[r * D + col];
+            const float dq = squared ? 2.0f * diff : (diff + 1e-5f) * inv_n;
+            d_z[r * D + col] = g_zq[r * D + col] - gl * beta * dq;
+        }
+    }
+}
+
+// update, one workgroup per codebook:  N_k <- g N_k + h n_k ;  m_k <- g m_k + h s_k ;  T = sum_k N_k ;
+// Nt_k = (N_k + eps) / (T + K eps) * T ;  e_k <- m_k / Nt_k.  Every product, sum and quotient is rounded separately
+// (-ffp-contract=off, IEEE division).  T is a pairwise tree over the K values padded with zeros to P = 2^ceil(log2 K):
+// level by level a[i] += a[i + half]; the order is a function of K alone, whatever the launch geometry.
+__global__ __launch_bounds__(kVqThreads) void vq_ema_update_kernel(const float* __restrict__ stats, float* __restrict__ N,
+                                                                   float* __restrict__ m, float* __restrict__ cb, int K,
+                                                                   int dsub, int P, float g, float h, float eps) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* tree = lds;            // [P]
+    float* nt = lds + P;          // [K]
+    const int c = blockIdx.x;
+    const int W = dsub + 1;
+    const float* st = stats + (int64_t)c * K * W;
+    float* Nc = N + (int64_t)c * K;
+    for (int k = threadIdx.x; k < P; k += kVqThreads) {
+        float v = 0.0f;
+        if (k < K) {
+            v = g * Nc[k] + h * st[(int64_t)k * W];
+            Nc[k] = v;
+            nt[k] = v;
+        }
+        tree[k] = v;
+    }
+    __syncthreads();
+    for (int half = P >> 1; half >= 1; half >>= 1) {
+        for (int i = threadIdx.x; i < half; i += kVqThreads) tree[i] += tree[i + half];
+        __syncthreads();
+    }
+    const float T = tree[0];
+    const float denom = T + (float)K * eps;
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += kVqThreads) nt[k] = (nt[k] + eps) / denom * T;
+    __syncthreads();
+    float* mc = m + (int64_t)c * K * dsub;
+    float* ec = cb + (int64_t)c * K * dsub;
+    for (int i = threadIdx.x; i < K * dsub; i += kVqThreads) {
+        const int k = i / dsub, t = i - k * dsub;
+        const float v = g * mc[i] + h * st[(int64_t)k * W + 1 + t];
+        mc[i] = v;
+        ec[i] = v / nt[k];
+    }
+}
+
 }  // namespace vq
 
 using namespace vq;
@@ -281,6 +415,63 @@ int vqcpc_vq_bwd(const float* z, const float* codebooks, const int64_t* idx, con
     VQ_CHECK_LAUNCH("vq_bwd");
     const int64_t count = (int64_t)ncb * K * dsub;
     return launch_reduce_splits((const float*)workspace, count, nchunks, d_codebooks, count, 0, s);
+}
+
+int64_t vqcpc_vq_ema_stats_workspace(int64_t R, int ncb, int K, int dsub) {
+    return ceil_div(std::max<int64_t>(R, 1), kVqThreads) * ncb * K * (dsub + 1) * (int64_t)sizeof(float);
+}
+
+int vqcpc_vq_ema_stats(const float* z, const int64_t* idx, int64_t R, int ncb, int K, int dsub, float* stats, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+    VQ_REQUIRE(z && idx && stats && workspace, "vq_ema_stats: null pointer");
+    VQ_REQUIRE(R >= 1 && ncb >= 1 && K >= 1 && dsub >= 1, "vq_ema_stats: bad shape R=%lld ncb=%d K=%d dsub=%d", (long long)R, ncb,
+               K, dsub);
+    VQ_REQUIRE(R < ((int64_t)1 << 24), "vq_ema_stats: %lld rows: the counts of 2^24 rows and more are not exact in fp32",
+               (long long)R);
+    VQ_REQUIRE(dsub + 1 <= kVqThreads, "vq_ema_stats: dsub + 1 = %d columns exceed the %d lanes of a workgroup", dsub + 1,
+               kVqThreads);
+    const int W = dsub + 1;
+    const size_t lds = ((size_t)K * W + (size_t)kVqThreads * W + 2 * kVqThreads) * sizeof(float);
+    VQ_REQUIRE(lds <= 160 * 1024, "vq_ema_stats: accumulator of %d x %d floats does not fit the LDS", K, W);
+    if (workspace_bytes < vqcpc_vq_ema_stats_workspace(R, ncb, K, dsub)) {
+        set_error("vq_ema_stats: workspace too small");
+        return VQCPC_EWORKSPACE;
+    }
+    const int nchunks = (int)ceil_div(R, kVqThreads);
+    hipStream_t s = (hipStream_t)stream;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)vq_ema_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(vq_ema_stats_kernel, dim3(nchunks), dim3(kVqThreads), lds, s, z, idx, R, ncb, K, dsub, (float*)workspace);
+    VQ_CHECK_LAUNCH("vq_ema_stats");
+    const int64_t count = (int64_t)ncb * K * W;
+    return launch_reduce_splits((const float*)workspace, count, nchunks, stats, count, 0, s);
+}
+
+int vqcpc_vq_commit_bwd(const float* z, const float* codebooks, const int64_t* idx, const float* g_zq, const float* g_loss,
+                        int64_t R, int ncb, int K, int dsub, float beta, int squared, float* d_z, void* stream) {
+    VQ_REQUIRE(z && codebooks && idx && g_zq && g_loss && d_z, "vq_commit_bwd: null pointer");
+    VQ_REQUIRE(R >= 1 && ncb >= 1 && K >= 1 && dsub >= 1, "vq_commit_bwd: bad shape R=%lld ncb=%d K=%d dsub=%d", (long long)R, ncb,
+               K, dsub);
+    hipLaunchKernelGGL(vq_commit_bwd_kernel, dim3((unsigned)ceil_div(R, kVqThreads)), dim3(kVqThreads), 0, (hipStream_t)stream, z,
+                       codebooks, idx, g_zq, g_loss, R, ncb, K, dsub, beta, squared, d_z);
+    VQ_CHECK_LAUNCH("vq_commit_bwd");
+    return VQCPC_OK;
+}
+
+int vqcpc_vq_ema_update(const float* stats, float* cluster_size, float* ema_sum, float* codebooks, int ncb, int K, int dsub,
+                        float g, float h, float eps, void* stream) {
+    VQ_REQUIRE(stats && cluster_size && ema_sum && codebooks, "vq_ema_update: null pointer");
+    VQ_REQUIRE(ncb >= 1 && K >= 1 && dsub >= 1, "vq_ema_update: bad shape ncb=%d K=%d dsub=%d", ncb, K, dsub);
+    VQ_REQUIRE(K <= 16 * 1024, "vq_ema_update: %d codes do not fit the LDS", K);
+    int P = 1;
+    while (P < K) P <<= 1;
+    const size_t lds = ((size_t)P + K) * sizeof(float);
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)vq_ema_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(vq_ema_update_kernel, dim3(ncb), dim3(kVqThreads), lds, (hipStream_t)stream, stats, cluster_size, ema_sum,
+                       codebooks, K, dsub, P, g, h, eps);
+    VQ_CHECK_LAUNCH("vq_ema_update");
+    return VQCPC_OK;
 }
 
 }  // extern "C"

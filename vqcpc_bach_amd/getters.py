@@ -16,7 +16,7 @@ from .encoder import Encoder
 from .priors.prior_relative import PriorRelative
 from .student_encoder_trainer import StudentEncoderTrainer
 from .teachers.teacher_relative import TeacherRelative
-from .quantizer.vector_quantizer import NoQuantization, ProductVectorQuantizer
+from .quantizer.vector_quantizer import EMAProductVectorQuantizer, NoQuantization, ProductVectorQuantizer
 from .upscalers.mlp_upscaler import MlpUpscaler
 from .vqcpc_encoder_trainer import VQCPCEncoderTrainer
 
@@ -123,6 +123,17 @@ def get_encoder(model_dir, dataloader_generator, config):
                                            squared_l2_norm=quantizer_kwargs['squared_l2_norm'],
                                            use_batch_norm=quantizer_kwargs['use_batch_norm'],
                                            commitment_cost=quantizer_kwargs['commitment_cost'])
+    elif config['quantizer_type'] == 'ema':                # this package's extension: EMA codebooks, no codebook gradient
+        if quantizer_kwargs.get('use_batch_norm', False):
+            raise NotImplementedError('use_batch_norm=True: out of scope')
+        quantizer = EMAProductVectorQuantizer(codebook_size=quantizer_kwargs['codebook_size'],
+                                              num_codebooks=quantizer_kwargs['num_codebooks'],
+                                              codebook_dim=quantizer_kwargs['codebook_dim'],
+                                              initialize=quantizer_kwargs['initialize'],
+                                              squared_l2_norm=quantizer_kwargs['squared_l2_norm'],
+                                              commitment_cost=quantizer_kwargs['commitment_cost'],
+                                              decay=quantizer_kwargs.get('ema_decay', 0.99),
+                                              epsilon=quantizer_kwargs.get('ema_epsilon', 1e-5))
     elif config['quantizer_type'] is None:
         quantizer = NoQuantization(codebook_dim=quantizer_kwargs['codebook_dim'])
     else:

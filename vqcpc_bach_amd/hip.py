@@ -148,6 +148,10 @@ SIGNATURES = {
     'vqcpc_vq_bwd_workspace': (c_i64, [c_i64, c_int, c_int, c_int]),
     'vqcpc_vq_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr,
                              c_ptr, c_i64, c_ptr]),
+    'vqcpc_vq_ema_stats_workspace': (c_i64, [c_i64, c_int, c_int, c_int]),
+    'vqcpc_vq_ema_stats': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_vq_commit_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr]),
+    'vqcpc_vq_ema_update': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_f32, c_f32, c_ptr]),
     'vqcpc_dropout_selu_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_f32, c_u64, c_ptr]),
     'vqcpc_dropout_selu_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_u64, c_ptr]),
     'vqcpc_nce_fwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr,

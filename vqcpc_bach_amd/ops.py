@@ -1928,6 +1928,61 @@ class VQFn(torch.autograd.Function):
         return dz, dcb, None, None, None
 
 
+class VQEmaFn(torch.autograd.Function):
+    """The EMA quantiser's forward / backward (quantizer.vector_quantizer.EMAProductVectorQuantizer): nearest-code search,
+    straight-through output and the commitment loss beta * l; the codebooks receive NO gradient (their update is
+    vqcpc_vq_ema_update on the statistics).  `stats` (ncb, K, 1 + dsub) is filled with this call's per-code counts and sums when
+    given (training); `stats_idx` is the uncorrupted nearest-code assignment when `given_idx` forces another (label corruption)."""
+
+    @staticmethod
+    def forward(ctx, z, codebooks, beta, squared, given_idx=None, stats=None, stats_idx=None):
+        z = _f32(z).contiguous()
+        codebooks = _f32(codebooks).contiguous()
+        R, D = z.shape
+        ncb, K, dsub = codebooks.shape
+        assert ncb * dsub == D
+        idx = (torch.empty(R, ncb, dtype=torch.int64, device=z.device) if given_idx is None
+               else given_idx.to(torch.int64).contiguous().clone())
+        zq = torch.empty_like(z)
+        loss = torch.empty(R, dtype=torch.float32, device=z.device)
+        # beta = 0: loss = l + 0 * l = l exactly
+        hip.call('vqcpc_vq_fwd', z, codebooks, R, ncb, K, dsub, 0.0, int(bool(squared)), int(given_idx is None), idx, zq, loss)
+        loss.mul_(float(beta))
+        if stats is not None:
+            assert stats.shape == (ncb, K, dsub + 1) and stats.is_contiguous() and stats.dtype == torch.float32
+            sidx = idx if given_idx is None else stats_idx.to(torch.int64).contiguous()
+            nbytes = hip.query('vqcpc_vq_ema_stats_workspace', R, ncb, K, dsub)
+            ws = hip.workspace(nbytes, z.device)
+            hip.call('vqcpc_vq_ema_stats', z, sidx, R, ncb, K, dsub, stats, ws, nbytes)
+        ctx.save_for_backward(z, codebooks, idx)
+        ctx.meta = (float(beta), int(bool(squared)))
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return zq, idx, loss
+
+    @staticmethod
+    def backward(ctx, g_zq, _g_idx, g_loss):
+        z, codebooks, idx = ctx.saved_tensors
+        beta, squared = ctx.meta
+        R, D = z.shape
+        ncb, K, dsub = codebooks.shape
+        g_zq = g_zq.contiguous() if g_zq is not None else torch.zeros_like(z)
+        g_loss = g_loss.contiguous() if g_loss is not None else torch.zeros(R, dtype=torch.float32, device=z.device)
+        dz = torch.empty_like(z)
+        hip.call('vqcpc_vq_commit_bwd', z, codebooks, idx, g_zq, g_loss, R, ncb, K, dsub, beta, squared, dz)
+        return dz, None, None, None, None, None, None
+
+
+def vq_ema_update(stats, cluster_size, ema_sum, codebooks, decay, epsilon):
+    """In-place EMA update of (cluster_size, ema_sum, codebooks) from `stats` (include/vqcpc.h: vqcpc_vq_ema_update).
+    g = float32(decay); h = float32(1 - decay) with the difference taken in double on the host."""
+    ncb, K, dsub = codebooks.shape
+    assert stats.shape == (ncb, K, dsub + 1) and cluster_size.shape == (ncb, K) and ema_sum.shape == codebooks.shape
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (stats, cluster_size, ema_sum, codebooks))
+    hip.call('vqcpc_vq_ema_update', stats, cluster_size, ema_sum, codebooks, ncb, K, dsub, float(decay), 1.0 - float(decay),
+             float(epsilon))
+
+
 def vq_assign(z, codebooks):
     """Index-only product-VQ assignment (no straight-through output, no loss): z (R, D) -> (R, ncb) int64."""
     z = _f32(z).contiguous()

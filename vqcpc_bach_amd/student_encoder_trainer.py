@@ -33,6 +33,10 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
     def __init__(self, model_dir, dataloader_generator, encoder, num_events_masked, teacher, auxiliary_decoder,
                  quantization_weighting, num_gpus=1):
         super().__init__(dataloader_generator=dataloader_generator)
+        if hasattr(encoder.quantizer, 'apply_update'):
+            raise NotImplementedError("quantizer_type 'ema' is not supported by the student step: it has two optimisers, and where "
+                                      'the codebook update goes between them is undecided; use VQCPCEncoderTrainer or '
+                                      "quantizer_type 'commitment'")
         self.model_dir = model_dir
         self.dataloader_generator = dataloader_generator
         self.encoder = encoder

@@ -59,6 +59,12 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
         self.lr = None
         self.global_step = 0
 
+    @property
+    def _ema(self):
+        """The quantiser when its codebooks are EMA buffers (EMAProductVectorQuantizer), else None."""
+        q = self.encoder.quantizer
+        return q if hasattr(q, 'apply_update') else None
+
     # ---- optimiser ---------------------------------------------------------------------------------------------
     def _modules_with_params(self):
         mods = [self.c_module, self.fks_module, self.encoder]
@@ -84,6 +90,10 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
         self.dp.broadcast_(self.flat.flat, src=0)                       # identical replicas
         if self.dp.distributed:
             self.encoder.quantizer.init_broadcast = lambda tensors: [self.dp.broadcast_(t.data, 0) for t in tensors]
+        # EMA codebooks are buffers, not parameters: outside the flat buffer, so rank 0's go to every rank on their own
+        if self._ema is not None:
+            for t in self._ema.ema_buffers():
+                self.dp.broadcast_(t, src=0)
         self.lr, self.schedule_lr = lr, schedule_lr
         self.optimizer = ops.FlatAdam(self.flat.flat, self.flat.flat_grad, lr=lr, max_norm=5.0)
         self.scheduler = self.lr_lambda if schedule_lr else None
@@ -239,7 +249,15 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
     def _step_apply(self, out):
         """clip + Adam (:313-316) on the (all-reduced) flat gradient; the rank sum becomes a mean inside the kernels."""
         self.optimizer.step(lr=self.current_lr(), grad_scale=1.0 / self.dp.world_size)
+        if self._ema is not None:
+            self._ema.apply_update()          # EMA codebooks: counts and sums of the step (summed over ranks, not averaged)
         return out
+
+    def _all_reduce_gradients(self):
+        """The flat gradient bucket and, with EMA codebooks, the step's per-code counts and sums next to it."""
+        self.dp.all_reduce_sum_(self.flat.flat_grad)
+        if self._ema is not None:
+            self.dp.all_reduce_sum_(self._ema.stats)
 
     def _train_step_body(self, tensor_dict, corrupt_labels=False):
         """Everything a step enqueues on the device: compute, ONE all-reduce of the gradient bucket, apply."""
