@@ -795,6 +795,30 @@ int vqcpc_prior_window(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t*
                        int P, int64_t* prefix_rows, const float* table, int64_t table_rows, int d, float* x, int64_t ldx,
                        const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The aligned ("diagonal") cross block of the decoder (TransformerAlignedDecoderLayerCustom,
+ * VQCPCB/transformer/transformer_custom.py:389-492; csrc/aligned.hip).  C = cross_attn(memory rows) is [n * S][nc * d] with
+ * feature index j * nc + v (feature j of voice v, the reshape of :476); a code covers U = epc * nc target tokens
+ * t = event * nc + voice.  fp32, no atomics, fixed summation order, graph-capture safe.  Adding them left the ABI version
+ * alone.  nc * d <= 16384, U % nc == 0.
+ *
+ * vqcpc_aligned_expand (:476-481, reshape / permute / repeat_interleave / reshape): out [n * P][d], row b * P + i =
+ *   C[b * S + i / U][(.) * nc + i % nc]; P <= S * U rows per sequence (a trailing partial code is written in part).
+ * vqcpc_aligned_reduce (the backward of the above for P = S * U): d_C[b * S + s][j * nc + v] =
+ *   sum_{e < epc} d_out[b * S * U + (s * epc + e) * nc + v][j], e ascending.
+ * vqcpc_elu_fwd / vqcpc_elu_bwd (nn.ELU of cross_attn, :428, alpha = 1): y = x > 0 ? x : expm1(x);
+ *   g_x = x > 0 ? g_out : g_out * exp(x), x the PRE-activation.  expm1 / exp in double, one rounding.
+ * vqcpc_decode_aligned_add (:475-482 at one position, eval mode): s[b][j] = h[b][j] + C[b * S + pos / U][j * nc + pos % nc],
+ *   pos read from pos[0] (device int32) as the kernels of the generation step do; nothing happens unless
+ *   0 <= pos < S * U.  M <= 64 rows.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_aligned_expand(const float* C, float* out, int64_t n, int S, int P, int U, int nc, int d, void* stream);
+int vqcpc_aligned_reduce(const float* d_out, float* d_C, int64_t n, int S, int U, int nc, int d, void* stream);
+int vqcpc_elu_fwd(const float* x, float* y, int64_t n, void* stream);
+int vqcpc_elu_bwd(const float* x, const float* g_out, float* g_x, int64_t n, void* stream);
+int vqcpc_decode_aligned_add(const float* h, int64_t ldh, const float* C, float* s, int64_t lds, const int32_t* pos, int64_t M,
+                             int S, int U, int nc, int d, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

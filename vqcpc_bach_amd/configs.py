@@ -48,7 +48,9 @@ def make_decoder_config(dropout=0.2, **over):
     transformer encoder of VQCPCB/configs/encoder_random_transfo_config.py:26-63 (d_model 512, 8 heads, [2, 2] layers,
     ff 2048, 1 x 32 codes of dim 3).  The shipped decoder configs point at LSTM-downscaler encoders; that encoder is
     `make_config('SAMESEQ')` and can be passed as `config_encoder=...` -- the default stays the transformer encoder the DEC
-    measurements were taken with."""
+    measurements were taken with.  `decoder_type=` (like every key) is an override: 'transformer_relative_diagonal' is the DEC
+    shape of VQCPCB/configs/decoder_relative_AC_D_C_*.py, 'transformer_relative_full' that of decoder_relative_F_F_C_*.py,
+    'transformer_relative_fullCross'; the default 'transformer_relative' is unchanged."""
     enc = make_config('C1', dropout=0.1)
     enc['downscaler_kwargs'].update(d_model=512, n_head=8, list_of_num_layers=[2, 2], dim_feedforward=2048)
     enc['quantizer_kwargs'].update(num_codebooks=1, codebook_size=32, codebook_dim=3, initialize=False)

@@ -2,14 +2,17 @@
 relative transformer that reconstructs the token sequence from the frozen encoder's codes.
 
 Covered: `transformer_type='relative'` with causal target self-attention, anticausal or full source self-attention and
-anticausal or full cross-attention -- getters.py decoder_type 'transformer_relative' / 'transformer_relative_fullCross'.
+anticausal or full cross-attention, or the aligned ('diagonal') cross block -- getters.py decoder_type 'transformer_relative' /
+'transformer_relative_fullCross' / 'transformer_relative_full' / 'transformer_relative_diagonal'.  The diagonal decoder
+(TransformerAlignedDecoderLayerCustom, transformer_custom.py:389-492) has no cross-attention: an MLP on the memory gives
+every code one vector per voice, which every target token of that code and voice receives (csrc/aligned.hip).
 `__init__`, `forward`, `epoch`, `train_model`, `init_optimizers`, `save` / `load` keep the reference's names, argument
 meaning, state_dict keys and return contracts.  `generate` / `generate_from_codes` / `init_generation` (:552-726) run
 KV-cached incremental decoding on the GPU (decoders/generation.py); `generate_from_code_long`, `generate_alla_mano`,
 `compute_start_end_times`, `init_generation_chorale` (:728-854, :960-981, :1054-1062) decode code sequences of any length
 by sliding the window, with a K/V-cache re-prefill per move; `reharmonise_tokens` is the body of
 `generate_reharmonisation` (:856-958) on a token tensor (the music21 corpus it reads is absent, so that method raises).
-Duplicate checks, plots, the absolute-position and 'diagonal' variants are out of scope and raise.
+Duplicate checks, plots, the absolute-position variant and continuous (NoQuantization) sources are out of scope and raise.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
   * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient);
@@ -34,8 +37,9 @@ from torch import nn
 from .. import ops
 from ..graphs import GraphedTraining
 from ..parallel import DataParallelContext, FlatParameters
-from ..transformer.transformer_custom import (TransformerCustom, TransformerDecoderCustom, TransformerDecoderLayerCustom,
-                                              TransformerEncoderCustom, TransformerEncoderLayerCustom, mask_code)
+from ..transformer.transformer_custom import (TransformerAlignedDecoderLayerCustom, TransformerCustom, TransformerDecoderCustom,
+                                              TransformerDecoderLayerCustom, TransformerEncoderCustom,
+                                              TransformerEncoderLayerCustom, mask_code)
 from ..utils import dict_pretty_print, flatten, SEEDS, STEP_LOCK
 
 
@@ -87,8 +91,6 @@ class Decoder(GraphedTraining, nn.Module):
                                       'relative bias) is not on the path: SURVEY.md section 8(f) N4 covers the relative decoder')
         assert encoder_attention_type in ['anticausal', 'causal', 'full']
         assert cross_attention_type in ['anticausal', 'causal', 'diagonal', 'full']
-        if cross_attention_type == 'diagonal':
-            raise NotImplementedError("cross_attention_type 'diagonal' (TransformerAlignedDecoderLayerCustom) is out of scope")
         if cross_attention_type == 'causal':
             raise NotImplementedError                      # as the reference (decoder.py:487-488)
         self.transformer_type = transformer_type
@@ -116,14 +118,13 @@ class Decoder(GraphedTraining, nn.Module):
                                                       attention_bias_type='relative_attention',
                                                       num_channels=num_channels_encoder, num_events=num_events_encoder,
                                                       dim_feedforward=dim_feedforward, dropout=dropout)
-        decoder_layer = TransformerDecoderLayerCustom(d_model=d_model, nhead=n_head,
-                                                      attention_bias_type_self='relative_attention',
-                                                      attention_bias_type_cross='relative_attention_target_source',
-                                                      num_channels_encoder=num_channels_encoder,
-                                                      num_events_encoder=num_events_encoder,
-                                                      num_channels_decoder=num_channels_decoder,
-                                                      num_events_decoder=num_events_decoder,
-                                                      dim_feedforward=dim_feedforward, dropout=dropout)
+        diagonal = cross_attention_type == 'diagonal'                                        # :161-186
+        layer_class = TransformerAlignedDecoderLayerCustom if diagonal else TransformerDecoderLayerCustom
+        decoder_layer = layer_class(d_model=d_model, nhead=n_head, attention_bias_type_self='relative_attention',
+                                    attention_bias_type_cross=None if diagonal else 'relative_attention_target_source',
+                                    num_channels_encoder=num_channels_encoder, num_events_encoder=num_events_encoder,
+                                    num_channels_decoder=num_channels_decoder, num_events_decoder=num_events_decoder,
+                                    dim_feedforward=dim_feedforward, dropout=dropout)
         self.transformer = TransformerCustom(
             d_model=self.d_model, nhead=n_head,
             custom_encoder=TransformerEncoderCustom(encoder_layer=encoder_layer, num_layers=num_encoder_layers),
@@ -255,8 +256,9 @@ class Decoder(GraphedTraining, nn.Module):
         assert S == self.num_tokens_source and x.shape[1] * nc == self.num_tokens_target
         src = ops.EmbeddingFn.apply(self.source_embeddings.weight, source.reshape(-1))      # (B * S, d)
         tgt = self._target_rows(x)
+        memory_mask = ops.MASK_NONE if self.cross_attention_type == 'diagonal' else mask_code(self.cross_attention_type)   # :487-488
         out, att_dec, att_enc = self.transformer.forward_rows(
-            src, tgt, B, mask_code(self.encoder_attention_type), ops.MASK_CAUSAL, mask_code(self.cross_attention_type))
+            src, tgt, B, mask_code(self.encoder_attention_type), ops.MASK_CAUSAL, memory_mask)
         params = [t for m in self.pre_softmaxes for t in (m.weight, m.bias)]
         logits = HeadsFn.apply(out, nc, *params)                                            # nc x (B * events, V_c)
         ce = sum(ops.SoftmaxCEFn.apply(lg, x[:, :, c].reshape(-1), None) for c, lg in enumerate(logits))

@@ -28,7 +28,13 @@ tokens of context, so every cache is stale:
   layer's K/V cache rows [0, P) filled; the last layer stops after its self-attention k | v.  Then U steps as above.
 
 The window index is read from device memory and advanced by the window kernel, so ONE captured slide serves every middle
-window of a generation (all have P = (S // 2) * U), next to the one captured step."""
+window of a generation (all have P = (S // 2) * U), next to the one captured step.
+
+Diagonal decoder (cross_attention_type 'diagonal', TransformerAlignedDecoderLayerCustom): the layer has no cross-attention.
+The prefill computes per layer C_l = cross_attn_l(memory) (n * S, nc * d) instead of the cross k | v; the step replaces its
+three cross launches (q projection, attention, out-projection + residual) by ONE vqcpc_decode_aligned_add, which adds the
+position's code-and-voice vector of C_l to the row (9 launches per layer + 2); the re-prefill expands C_l over the P prefix
+rows with vqcpc_aligned_expand.  Everything else -- one captured step, one captured slide -- is as above."""
 import ctypes
 
 import torch
@@ -82,7 +88,8 @@ class IncrementalDecoder:
         a = self.layers[0].self_attn
         self.H, self.hd = a.num_heads, a.head_dim
         self.ff = self.layers[0].linear1.weight.shape[0]
-        self.cross_mask = mask_code(dec.cross_attention_type)
+        self.diagonal = dec.cross_attention_type == 'diagonal'
+        self.cross_mask = None if self.diagonal else mask_code(dec.cross_attention_type)
         sizes = [int(n) for n in dec.num_tokens_per_channel]
         self.offsets = [0]
         for n in sizes:
@@ -120,13 +127,20 @@ class IncrementalDecoder:
         self.head_b = torch.cat([m.bias for m in dec.pre_softmaxes], dim=0).contiguous()
 
     def _encode_memory(self, codes):
-        """codes (M, S) -> memory -> every layer's cross k | v, written into buffers that keep their address (a captured
-        step reads them)."""
+        """codes (M, S) -> memory -> every layer's cross k | v (diagonal decoder: its C = cross_attn(memory), (M * S, nc * d)),
+        written into buffers that keep their address (a captured step reads them)."""
         dec, M, d = self.dec, self.M, self.d
         if self.memkv is None:
-            self.memkv = [torch.empty(M * self.S, 2 * d, dtype=torch.float32, device=self.dev) for _ in self.layers]
+            width = self.nc * d if self.diagonal else 2 * d
+            self.memkv = [torch.empty(M * self.S, width, dtype=torch.float32, device=self.dev) for _ in self.layers]
         src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
         memory, _ = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
+        if self.diagonal:
+            for lay, C in zip(self.layers, self.memkv):
+                l1, l2 = lay.cross_attn[0], lay.cross_attn[2]
+                h = ops.gemm_nt(memory.reshape(-1, l1.weight.shape[1]), l1.weight, bias=l1.bias)
+                ops.gemm_nt(ops.EluFn.apply(h), l2.weight, bias=l2.bias, out=C)
+            return
         for lay, kv in zip(self.layers, self.memkv):                                    # (M * S, 2d): k | v
             ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:], out=kv)
 
@@ -171,7 +185,7 @@ class IncrementalDecoder:
         M, d, T, S, H, hd = self.M, self.d, self.T, self.S, self.H, self.hd
         hin = self.x
         for li, lay in enumerate(self.layers):
-            sa, ca = lay.self_attn, lay.multihead_attn
+            sa = lay.self_attn
             hout = self.hb[li % 2]
             self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
             q0 = self.qkv.data_ptr()
@@ -179,11 +193,15 @@ class IncrementalDecoder:
                      sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, T, 1, H, hd, ops.MASK_CAUSAL)
             self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
             self._ln(self.s, lay.norm1, self.h1)
-            hip.call('vqcpc_decode_linear', self.h1, d, None, ca.in_proj_weight, ca.in_proj_bias, None, 0, self.qc, d, M, d, d, 0)
             kv = self.memkv[li]
-            hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
-                     ca.attn_bias.e2, self.att, d, self.pos, M, S, T // S, H, hd, self.cross_mask)
-            self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
+            if self.diagonal:
+                hip.call('vqcpc_decode_aligned_add', self.h1, d, kv, self.s, d, self.pos, M, S, self.U, self.nc, d)
+            else:
+                ca = lay.multihead_attn
+                hip.call('vqcpc_decode_linear', self.h1, d, None, ca.in_proj_weight, ca.in_proj_bias, None, 0, self.qc, d, M, d, d, 0)
+                hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                         ca.attn_bias.e2, self.att, d, self.pos, M, S, T // S, H, hd, self.cross_mask)
+                self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
             self._ln(self.s, lay.norm2, self.h2)
             self._linear(self.h2, lay.linear1.weight, lay.linear1.bias, self.f, relu=1)
             self._linear(self.f, lay.linear2.weight, lay.linear2.bias, self.s, res=self.h2)
@@ -260,7 +278,7 @@ class IncrementalDecoder:
         h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
         last = len(self.layers) - 1
         for li, lay in enumerate(self.layers):
-            sa, ca = lay.self_attn, lay.multihead_attn
+            sa = lay.self_attn
             qkv = ops.gemm_nt(h, sa.in_proj_weight, bias=sa.in_proj_bias)
             att = torch.empty(M * P, d, dtype=torch.float32, device=self.dev) if li < last else None
             hip.call('vqcpc_decode_prefill_attn', qkv, 3 * d, qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, 3 * d,
@@ -269,11 +287,16 @@ class IncrementalDecoder:
             if li == last:
                 break                                     # nothing reads the last layer's prefix outputs
             h1 = self._prefix_ln(h, ops.gemm_nt(att, sa.out_proj.weight, bias=sa.out_proj.bias), lay.norm1)
-            qc = ops.gemm_nt(h1, ca.in_proj_weight[:d], bias=ca.in_proj_bias[:d])
             kv = self.memkv[li]
-            hip.call('vqcpc_decode_prefill_attn', qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
-                     ca.attn_bias.e2, att, d, M, P, S, T // S, H, hd, self.cross_mask)
-            h2 = self._prefix_ln(h1, ops.gemm_nt(att, ca.out_proj.weight, bias=ca.out_proj.bias), lay.norm2)
+            if self.diagonal:
+                hip.call('vqcpc_aligned_expand', kv, att, M, S, P, self.U, self.nc, d)        # att: (M * P, d), free here
+                h2 = self._prefix_ln(h1, att, lay.norm2)
+            else:
+                ca = lay.multihead_attn
+                qc = ops.gemm_nt(h1, ca.in_proj_weight[:d], bias=ca.in_proj_bias[:d])
+                hip.call('vqcpc_decode_prefill_attn', qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                         ca.attn_bias.e2, att, d, M, P, S, T // S, H, hd, self.cross_mask)
+                h2 = self._prefix_ln(h1, ops.gemm_nt(att, ca.out_proj.weight, bias=ca.out_proj.bias), lay.norm2)
             f = ops.gemm_nt(h2, lay.linear1.weight, bias=lay.linear1.bias, act=1)
             h = self._prefix_ln(h2, ops.gemm_nt(f, lay.linear2.weight, bias=lay.linear2.bias), lay.norm3)
 

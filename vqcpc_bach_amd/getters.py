@@ -1,6 +1,7 @@
 """Factories with the reference's names and config schema (reference: VQCPCB/getters.py:24-45,48-175,221-270,431-514),
 restricted to the encoder branches (vqcpc, student) that `main_encoder.py` reaches, plus `get_decoder` (:274-392) for
-the relative decoder training step and `get_prior` (:398-428) for the code prior."""
+the relative decoder training step (the attention decoders AC-AC-C, AC-F-C, F-F-C and the
+aligned AC-D-C one) and `get_prior` (:398-428) for the code prior."""
 import numpy as np
 
 from .auxiliary_decoders.auxiliary_decoder_relative import AuxiliaryDecoderRelative
@@ -172,9 +173,11 @@ def get_encoder_trainer(model_dir, dataloader_generator, training_method, encode
 
 
 def get_decoder(model_dir, dataloader_generator, data_processor, encoder, decoder_type, decoder_kwargs):
-    """getters.py:274-392.  'transformer_relative' (anticausal source / anticausal cross / causal target) and
-    'transformer_relative_fullCross'; the absolute and diagonal variants are out of scope."""
-    kinds = {'transformer_relative': ('anticausal', 'anticausal'), 'transformer_relative_fullCross': ('anticausal', 'full')}
+    """getters.py:274-392.  'transformer_relative' (anticausal source / anticausal cross / causal target),
+    'transformer_relative_fullCross', 'transformer_relative_full' (full source / full cross) and
+    'transformer_relative_diagonal' (anticausal source, the aligned cross block); the absolute variant is out of scope."""
+    kinds = {'transformer_relative': ('anticausal', 'anticausal'), 'transformer_relative_fullCross': ('anticausal', 'full'),
+             'transformer_relative_full': ('full', 'full'), 'transformer_relative_diagonal': ('anticausal', 'diagonal')}
     if decoder_type not in kinds:
         raise NotImplementedError(f'decoder_type {decoder_type}: only the relative decoders {sorted(kinds)} are built')
     num_channels_decoder = data_processor.num_channels

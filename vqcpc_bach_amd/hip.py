@@ -213,6 +213,11 @@ SIGNATURES = {
                                    c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     'vqcpc_prior_window': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr,
                                    c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_aligned_expand': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    'vqcpc_aligned_reduce': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr]),
+    'vqcpc_elu_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_elu_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_decode_aligned_add': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr]),
 }
 
 # Entry points of LAB builds only (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so, the `#ifdef VQCPC_LAB`

@@ -2287,6 +2287,50 @@ class UpscaleFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# aligned ("diagonal") cross block of the decoder (transformer_custom.py:389-492), csrc/aligned.hip
+# ------------------------------------------------------------------------------------------------------------------
+class AlignedExpandFn(torch.autograd.Function):
+    """C (n * S, nc * d), feature index j * nc + v -> (n * S * U, d): target row b * T + t takes C[b * S + t // U, (.) * nc + t % nc]
+    (the reshape / permute / repeat_interleave of :476-481); the backward sums the U // nc events of every (code, voice)."""
+
+    @staticmethod
+    def forward(ctx, C, n, S, U, nc):
+        C = _f32(C).contiguous()
+        d = C.shape[1] // nc
+        assert C.shape == (n * S, nc * d), (C.shape, n, S, nc)
+        out = torch.empty(n * S * U, d, dtype=torch.float32, device=C.device)
+        hip.call('vqcpc_aligned_expand', C, out, n, S, S * U, U, nc, d)
+        ctx.meta = (n, S, U, nc, d)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n, S, U, nc, d = ctx.meta
+        dC = torch.empty(n * S, nc * d, dtype=torch.float32, device=g.device)
+        hip.call('vqcpc_aligned_reduce', g.contiguous(), dC, n, S, U, nc, d)
+        return dC, None, None, None, None
+
+
+class EluFn(torch.autograd.Function):
+    """nn.ELU (alpha = 1); the backward reads the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _f32(x).contiguous()
+        y = torch.empty_like(x)
+        hip.call('vqcpc_elu_fwd', x, y, x.numel())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        hip.call('vqcpc_elu_bwd', x, g.contiguous(), gx, x.numel())
+        return gx
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # flat-buffer optimiser
 # ------------------------------------------------------------------------------------------------------------------
 class FlatAdam:

@@ -182,6 +182,74 @@ class TransformerDecoderLayerCustom(nn.Module):
         return y.view(N, T, E).transpose(0, 1), att
 
 
+class TransformerAlignedDecoderLayerCustom(nn.Module):
+    """transformer_custom.py:389-492: the decoder layer without cross-attention.  An MLP on the memory gives every code one
+    vector per voice, C = cross_attn(memory rows) of shape (n * S, d * nc) with feature index j * nc + v, and target token
+    t = event * nc + voice receives C[b * S + t // U, (.) * nc + t % nc] (U = seq_len_tgt / seq_len_src tokens per code) where
+    the attention layer adds its cross-attention output.  `attention_bias_type_cross` is accepted and unused, as there."""
+
+    def __init__(self, d_model, nhead, attention_bias_type_self, attention_bias_type_cross, num_channels_encoder,
+                 num_events_encoder, num_channels_decoder, num_events_decoder, dim_feedforward=2048, dropout=0.1,
+                 activation='relu'):
+        super().__init__()
+        if activation != 'relu':
+            raise NotImplementedError('the decoder path uses relu')
+        self.self_attn = MultiheadAttentionCustom(embed_dim=d_model, num_heads=nhead,
+                                                  attention_bias_type=attention_bias_type_self,
+                                                  num_channels_k=num_channels_decoder, num_events_k=num_events_decoder,
+                                                  num_channels_q=num_channels_decoder, num_events_q=num_events_decoder,
+                                                  dropout=dropout)
+        self.cross_attn = nn.Sequential(nn.Linear(num_channels_encoder * d_model, d_model * 2), nn.ELU(),
+                                        nn.Linear(d_model * 2, d_model * num_channels_decoder))
+        self.num_channels_encoder = num_channels_encoder
+        self.num_channels_decoder = num_channels_decoder
+        self.linear1 = nn.Linear(d_model, dim_feedforward)
+        self.dropout = nn.Dropout(dropout)
+        self.linear2 = nn.Linear(dim_feedforward, d_model)
+        self.norm1 = nn.LayerNorm(d_model)
+        self.norm2 = nn.LayerNorm(d_model)
+        self.norm3 = nn.LayerNorm(d_model)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+        self.dropout3 = nn.Dropout(dropout)
+        self.p = dropout
+
+    def cross_rows(self, memory):
+        """memory (n * S, d) batch-major rows -> C (n * S / nce, d * nc): the two cross_attn GEMMs with the ELU between them.
+        The nce memory rows of one event are adjacent, so (:468-474) is a view."""
+        l1, l2 = self.cross_attn[0], self.cross_attn[2]
+        h = ops.linear(memory.reshape(-1, l1.weight.shape[1]), l1.weight, l1.bias)
+        return ops.linear(ops.EluFn.apply(h), l2.weight, l2.bias)
+
+    def forward_rows(self, tgt, memory, n, tgt_mask, memory_mask=None):
+        """tgt (n * T, d), memory (n * S, d) batch-major rows -> (tgt, {'a_self_decoder', 'a_cross': None}); the memory mask
+        has no meaning here (the reference passes None)."""
+        p = self.p if self.training else 0.0
+        s = [SEEDS.next() if p > 0 else 0 for _ in range(5)]
+        a, p_self = self.self_attn.forward_rows(tgt, n, tgt_mask, drop_p=p, seed=s[0])
+        tgt = ops.AddLayerNormFn.apply(tgt, a, self.norm1.weight, self.norm1.bias, p, s[1])
+        nc = self.num_channels_decoder
+        C = self.cross_rows(memory)
+        S = C.shape[0] // n
+        T = tgt.shape[0] // n
+        assert T % S == 0 and (T // S) % nc == 0, (T, S, nc)
+        tgt2 = ops.AlignedExpandFn.apply(C, n, S, T // S, nc)
+        tgt = ops.AddLayerNormFn.apply(tgt, tgt2, self.norm2.weight, self.norm2.bias, p, s[2])
+        f = ops.FFNFn.apply(tgt, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, p, s[3])
+        tgt = ops.AddLayerNormFn.apply(tgt, f, self.norm3.weight, self.norm3.bias, p, s[4])
+        return tgt, dict(a_self_decoder=p_self, a_cross=None)
+
+    def forward(self, tgt, memory, tgt_mask=None, memory_mask=None, tgt_key_padding_mask=None,
+                memory_key_padding_mask=None):
+        """API-compatible entry, time-first (T, N, E) / (S, N, E); masks as in TransformerEncoderLayerCustom.forward."""
+        assert tgt_key_padding_mask is None and memory_key_padding_mask is None
+        T, N, E = tgt.shape
+        S = memory.shape[0]
+        y, att = self.forward_rows(tgt.transpose(0, 1).reshape(N * T, E), memory.transpose(0, 1).reshape(N * S, E), N,
+                                   mask_code(tgt_mask))
+        return y.view(N, T, E).transpose(0, 1), att
+
+
 class TransformerDecoderCustom(nn.Module):
     def __init__(self, decoder_layer, num_layers, norm=None):
         super().__init__()
