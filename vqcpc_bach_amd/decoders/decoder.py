@@ -384,7 +384,8 @@ class Decoder(GraphedTraining, nn.Module):
         exclude_tokens: per voice, token ids never drawn (the meta symbols of exclude_meta_symbols); seed: an int (per-row
         seeds derived from it), a per-row int64 tensor, or None (drawn from torch's generator).  use_graph=False runs the
         steps eagerly (same tokens).  -> int64 tokens (B * num_decodings, events, channels) on the device."""
-        from .generation import MAX_ROWS, IncrementalDecoder, row_seeds
+        from ..transformer.incremental import generate_in_chunks, row_seeds
+        from .generation import IncrementalDecoder
         dev = self.sos.device
         codes = torch.as_tensor(codes).to(dev, torch.int64)
         if codes.dim() != 2 or codes.shape[1] != self.num_tokens_source:
@@ -393,22 +394,13 @@ class Decoder(GraphedTraining, nn.Module):
             codes = codes.repeat_interleave(num_decodings, dim=0)
         B, T, nc = codes.shape[0], self.num_tokens_target, self.num_channels
         seeds = row_seeds(seed, B)
-        out = torch.empty(B, T, dtype=torch.int64, device=dev)
-        with STEP_LOCK, torch.no_grad():               # never interleaved with a training step of another thread
-            was_training = self.training
-            self.eval()
-            try:
-                for b0 in range(0, B, MAX_ROWS):
-                    n = min(MAX_ROWS, B - b0)
-                    inc = IncrementalDecoder(self, n)
-                    inc.prefill(codes[b0:b0 + n])
-                    inc.start(seeds=seeds[b0:b0 + n], temperature=temperature, top_k=top_k, top_p=top_p,
-                              exclude=exclude_tokens)
-                    out[b0:b0 + n] = inc.run(use_graph=use_graph)
-                    del inc
-            finally:
-                self.train(was_training)
-        return out.view(B, T // nc, nc)
+
+        def chunk(n, rows):
+            inc = IncrementalDecoder(self, n)
+            inc.prefill(codes[rows])
+            inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens)
+            return inc.run(use_graph=use_graph)
+        return generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
 
     def _meta_symbol_ids(self):
         ds = getattr(self.dataloader_generator, 'dataset', None)
@@ -524,7 +516,8 @@ class Decoder(GraphedTraining, nn.Module):
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
-        from .generation import MAX_ROWS, IncrementalDecoder, row_seeds
+        from ..transformer.incremental import generate_in_chunks, row_seeds
+        from .generation import IncrementalDecoder
         dev = self.sos.device
         codes = torch.as_tensor(encoding_indices).to(dev, torch.int64)
         S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
@@ -544,20 +537,13 @@ class Decoder(GraphedTraining, nn.Module):
             codes = codes.repeat_interleave(num_decodings, dim=0)
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
-        out = torch.empty(B, nb * U, dtype=torch.int64, device=dev)
-        with STEP_LOCK, torch.no_grad():               # never interleaved with a training step of another thread
-            was_training = self.training
-            self.eval()
-            try:
-                for b0 in range(0, B, MAX_ROWS):
-                    n = min(MAX_ROWS, B - b0)
-                    inc = IncrementalDecoder(self, n)
-                    inc.start_long(codes[b0:b0 + n], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[b0:b0 + n],
-                                   temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude)
-                    out[b0:b0 + n] = inc.run_long(code_index_start, code_index_end, use_graph=use_graph)
-                    del inc
-            finally:
-                self.train(was_training)
+
+        def chunk(n, rows):
+            inc = IncrementalDecoder(self, n)
+            inc.start_long(codes[rows], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[rows], temperature=temperature,
+                           top_k=top_k, top_p=top_p, exclude=exclude)
+            return inc.run_long(code_index_start, code_index_end, use_graph=use_graph)
+        out = generate_in_chunks(self, B, nb * U, chunk)
         return out.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):

@@ -1,21 +1,15 @@
 """KV-cached autoregressive generation of the decoder (reference: VQCPCB/decoders/decoder.py:552-723, which runs one full
 seq2seq forward per generated token and samples on the host).
 
-Position t's logits depend on tokens < t only (causal target self-attention, a memory that does not depend on the target,
-row-wise embedding / LayerNorm / FFN), so one incremental step per token computes the same function:
+The incremental step, the prefix re-prefill and the captured graphs are the shared stack's (transformer/incremental.py);
+this module adds what the decoder has on top of it:
 
   prefill (once per call, existing kernels): source embedding + source encoder stack -> memory; per decoder layer the
   cross-attention k | v of the memory; the target table of `Decoder._target_rows`; the per-voice heads concatenated into
   one [sum V_c, d] weight.
 
-  step (csrc/decode.hip, 11 launches per layer + 2):  in_proj -> self-attention on the layer's K/V cache (the step's k / v row
-  is stored at row pos) -> out_proj + residual -> add & LayerNorm -> cross q -> cross-attention -> out_proj + residual ->
-  add & LayerNorm -> linear1 + ReLU -> linear2 + residual -> add & LayerNorm;  then the heads and the sampler, which draws
-  the token of position pos, writes the input row of position pos + 1 and advances the device counter `pos`.
-
-Every kernel of the step reads `pos` from device memory, so ONE captured step (torch.cuda.CUDAGraph) is replayed T times.
-Rows are independent and every kernel reduces in an order that does not depend on the number of rows, so a row's tokens
-do not depend on which other rows share the call (given the same memory rows and seed).
+  the step's cross hook (csrc/decode.hip, 11 launches per layer + 2 in all): cross q -> cross-attention on the memory's k | v
+  -> out_proj + residual -> add & LayerNorm;  and vqcpc_decode_sample, which draws the token of position pos.
 
 Long mode (reference: generate_from_code_long, decoder.py:729-854, one full forward on the moved window per token): a code
 sequence of any length nb >= S is decoded by sliding the window one code at a time.  The chorale (M, nb * U) and the codes
@@ -24,8 +18,7 @@ tokens of context, so every cache is stale:
 
   slide: vqcpc_decode_window (commit the live window's tokens, load the next window's codes / tokens / prefix rows / seeds,
   pos = P) -> memory and cross k | v of the new source window -> the decoder stack teacher-forced over the P = t_relative * U
-  prefix rows of every sequence (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_decode_prefill_attn), which leaves every
-  layer's K/V cache rows [0, P) filled; the last layer stops after its self-attention k | v.  Then U steps as above.
+  prefix rows of every sequence (`prefill_prefix`).  Then U steps as above.
 
 The window index is read from device memory and advanced by the window kernel, so ONE captured slide serves every middle
 window of a generation (all have P = (S // 2) * U), next to the one captured step.
@@ -40,33 +33,11 @@ import ctypes
 import torch
 
 from .. import hip, ops
+from ..transformer.incremental import MAX_ROWS, IncrementalStack, _splitmix64, row_seeds       # noqa: F401 (re-exported)
 from ..transformer.transformer_custom import mask_code
 
-MAX_ROWS = 64                # rows of one incremental decoder (vqcpc_decode_*); larger batches run in chunks
 
-
-def _splitmix64(z):
-    z = (z + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    return z ^ (z >> 31)
-
-
-def row_seeds(seed, n):
-    """int -> n per-row int64 seeds (splitmix64 of (seed, row)); a tensor of n int64 is taken as it is; None draws one
-    int from torch's CPU generator."""
-    if torch.is_tensor(seed):
-        s = seed.reshape(-1).to(torch.int64)
-        if s.numel() != n:
-            raise ValueError(f'seed: {s.numel()} per-row seeds for {n} rows')
-        return s.cpu()
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    vals = [_splitmix64((int(seed) * 0x100000001B3 + r) & 0xFFFFFFFFFFFFFFFF) for r in range(n)]
-    return torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
-
-
-class IncrementalDecoder:
+class IncrementalDecoder(IncrementalStack):
     """One generation of `batch` <= 64 rows of `decoder` (a Decoder in eval mode; the caller holds utils.STEP_LOCK).
 
         inc = IncrementalDecoder(dec, B)
@@ -80,16 +51,16 @@ class IncrementalDecoder:
         if not 1 <= batch <= MAX_ROWS:
             raise ValueError(f'IncrementalDecoder: 1 <= batch <= {MAX_ROWS} (got {batch})')
         dec = self.dec = decoder
-        self.M = M = int(batch)
-        self.dev = dev = dec.sos.device
-        self.nc, self.U, self.d = dec.num_channels, dec.total_upscaling, dec.d_model
+        M, dev, d = int(batch), dec.sos.device, dec.d_model
+        layers = list(dec.transformer.decoder.layers)
         self.T, self.S = dec.num_tokens_target, dec.num_tokens_source
-        self.layers = list(dec.transformer.decoder.layers)
-        a = self.layers[0].self_attn
-        self.H, self.hd = a.num_heads, a.head_dim
-        self.ff = self.layers[0].linear1.weight.shape[0]
+        super().__init__(dev, M, layers, [lay.norm3 for lay in layers], self.T, d)
+        self.nc, self.U = dec.num_channels, dec.total_upscaling
         self.diagonal = dec.cross_attention_type == 'diagonal'
         self.cross_mask = None if self.diagonal else mask_code(dec.cross_attention_type)
+        cls = IncrementalDecoder
+        self._cross = cls._cross_aligned if self.diagonal else cls._cross_attention
+        self._prefix_cross = cls._prefix_cross_aligned if self.diagonal else cls._prefix_cross_attention
         sizes = [int(n) for n in dec.num_tokens_per_channel]
         self.offsets = [0]
         for n in sizes:
@@ -97,22 +68,10 @@ class IncrementalDecoder:
         self._offsets_c = (ctypes.c_int32 * (self.nc + 1))(*self.offsets)
         self.vmax = max(sizes)
         f32 = dict(dtype=torch.float32, device=dev)
-        d, T, L = self.d, self.T, len(self.layers)
-        self.x = torch.empty(M, d, **f32)                     # input rows of the current position
-        self.hb = [torch.empty(M, d, **f32) for _ in range(2)]
-        self.h1, self.h2, self.s, self.att, self.qc = (torch.empty(M, d, **f32) for _ in range(5))
-        self.qkv = torch.empty(M, 3 * d, **f32)
-        self.f = torch.empty(M, self.ff, **f32)
+        self.h2, self.qc = torch.empty(M, d, **f32), torch.empty(M, d, **f32)
         self.logits = torch.empty(M, self.offsets[-1], **f32)
-        self.mean, self.rstd = torch.empty(M, **f32), torch.empty(M, **f32)
-        self.kcache = torch.empty(L, M, T, d, **f32)
-        self.vcache = torch.empty(L, M, T, d, **f32)
-        self.tokens = torch.zeros(M, T, dtype=torch.int64, device=dev)
-        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.seeds = torch.zeros(M, dtype=torch.int64, device=dev)
+        self.tokens = torch.zeros(M, self.T, dtype=torch.int64, device=dev)
         self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
-        self.teacher = None
-        self.probs = None
         self.memkv = None
 
     # ---- prefill ---------------------------------------------------------------------------------------------------
@@ -171,46 +130,27 @@ class IncrementalDecoder:
         self.tokens.zero_()
         self.x.copy_(self.table[-1].expand(self.M, self.d))                            # start-of-sentence row
 
-    # ---- one step ----------------------------------------------------------------------------------------------------
-    def _ln(self, s, norm, out):
-        hip.call('vqcpc_add_layernorm_fwd', s, self.d, None, norm.weight, norm.bias, out, self.mean, self.rstd, self.M, self.d,
-                 1e-5, 0.0, 0)
+    # ---- one step: the cross hooks and the sampler ----------------------------------------------------------------------
+    def _cross_attention(self, li, lay):
+        d, ca, kv = self.d, lay.multihead_attn, self.memkv[li]
+        hip.call('vqcpc_decode_linear', self.h1, d, None, ca.in_proj_weight, ca.in_proj_bias, None, 0, self.qc, d, self.M, d, d,
+                 0)
+        hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                 ca.attn_bias.e2, self.att, d, self.pos, self.M, self.S, self.T // self.S, self.H, self.hd, self.cross_mask)
+        self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
+        self._ln(self.s, lay.norm2, self.h2)
+        return self.h2
 
-    def _linear(self, x, w, b, out, res=None, relu=0):
-        N, K = w.shape
-        hip.call('vqcpc_decode_linear', x, x.shape[1], None, w, b, res, out.shape[1] if res is not None else 0, out,
-                 out.shape[1], self.M, N, K, relu)
+    def _cross_aligned(self, li, lay):
+        d = self.d
+        hip.call('vqcpc_decode_aligned_add', self.h1, d, self.memkv[li], self.s, d, self.pos, self.M, self.S, self.U, self.nc, d)
+        self._ln(self.s, lay.norm2, self.h2)
+        return self.h2
 
-    def step(self):
-        M, d, T, S, H, hd = self.M, self.d, self.T, self.S, self.H, self.hd
-        hin = self.x
-        for li, lay in enumerate(self.layers):
-            sa = lay.self_attn
-            hout = self.hb[li % 2]
-            self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
-            q0 = self.qkv.data_ptr()
-            hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
-                     sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, T, 1, H, hd, ops.MASK_CAUSAL)
-            self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
-            self._ln(self.s, lay.norm1, self.h1)
-            kv = self.memkv[li]
-            if self.diagonal:
-                hip.call('vqcpc_decode_aligned_add', self.h1, d, kv, self.s, d, self.pos, M, S, self.U, self.nc, d)
-            else:
-                ca = lay.multihead_attn
-                hip.call('vqcpc_decode_linear', self.h1, d, None, ca.in_proj_weight, ca.in_proj_bias, None, 0, self.qc, d, M, d, d, 0)
-                hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
-                         ca.attn_bias.e2, self.att, d, self.pos, M, S, T // S, H, hd, self.cross_mask)
-                self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
-            self._ln(self.s, lay.norm2, self.h2)
-            self._linear(self.h2, lay.linear1.weight, lay.linear1.bias, self.f, relu=1)
-            self._linear(self.f, lay.linear2.weight, lay.linear2.bias, self.s, res=self.h2)
-            self._ln(self.s, lay.norm3, hout)
-            hin = hout
-        self._linear(hin, self.head_w, self.head_b, self.logits)
-        teacher = self.teacher
-        hip.call('vqcpc_decode_sample', self.logits, self.logits.shape[1], self._offsets_c, self.nc, M, self.temperature,
-                 self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds, teacher, T, self.tokens, T, T,
+    def _sample(self):
+        T, d = self.T, self.d
+        hip.call('vqcpc_decode_sample', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.temperature,
+                 self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds, self.teacher, T, self.tokens, T, T,
                  self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
 
     # ---- a whole generation --------------------------------------------------------------------------------------------
@@ -219,10 +159,7 @@ class IncrementalDecoder:
         steps.  Returns the (M, T) token buffer."""
         if use_graph:
             self.step()                       # first launches outside the capture
-            torch.cuda.synchronize(self.dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                self.step()
+            graph = self.capture(self.step)
             self.reset()
             for _ in range(self.T):
                 graph.replay()
@@ -246,9 +183,8 @@ class IncrementalDecoder:
         self.codes_full = codes_full
         self.chorale = chorale.to(self.dev, torch.int64).reshape(M, nb * U).contiguous().clone()
         self.codes_win = torch.zeros(M, S, dtype=torch.int64, device=self.dev)
-        self.win = torch.tensor([0, -1], dtype=torch.int32, device=self.dev)       # {next window, live window}
-        self.prefix_rows = torch.zeros(M * self.T, dtype=torch.int64, device=self.dev)
-        self.row_seeds = torch.zeros(M, dtype=torch.int64, device=self.dev)
+        self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
+        self.prefix_rows.zero_()
         if self.memkv is None:
             self.prefill(codes_full[:, :S])
         self.start(seeds=seeds, **sampling)
@@ -259,46 +195,16 @@ class IncrementalDecoder:
                  self.codes_win, self.S, self.tokens, self.T, self.U, int(P), self.prefix_rows, self.table, self.table.shape[0],
                  self.d, self.x, self.d, self.row_seeds, self.seeds, self.pos, self.M)
 
-    def _prefix_ln(self, x, r, norm):
-        y = torch.empty_like(x)
-        n = x.shape[0]
-        hip.call('vqcpc_add_layernorm_fwd', x, self.d, r, norm.weight, norm.bias, y, self._pmean[:n], self._prstd[:n], n, self.d,
-                 1e-5, 0.0, 0)
-        return y
+    def _prefix_cross_attention(self, li, lay, h1, att, P):
+        d, ca, kv = self.d, lay.multihead_attn, self.memkv[li]
+        qc = ops.gemm_nt(h1, ca.in_proj_weight[:d], bias=ca.in_proj_bias[:d])
+        hip.call('vqcpc_decode_prefill_attn', qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                 ca.attn_bias.e2, att, d, self.M, P, self.S, self.T // self.S, self.H, self.hd, self.cross_mask)
+        return self._prefix_ln(h1, ops.gemm_nt(att, ca.out_proj.weight, bias=ca.out_proj.bias), lay.norm2)
 
-    def prefill_prefix(self, P):
-        """The decoder stack, teacher-forced over prefix rows [0, P) of every sequence (inputs: table rows `prefix_rows`):
-        fills every layer's K/V cache rows [0, P)."""
-        if P == 0:
-            return
-        M, d, T, S, H, hd = self.M, self.d, self.T, self.S, self.H, self.hd
-        if getattr(self, '_pmean', None) is None:
-            self._pmean = torch.empty(M * T, dtype=torch.float32, device=self.dev)
-            self._prstd = torch.empty(M * T, dtype=torch.float32, device=self.dev)
-        h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
-        last = len(self.layers) - 1
-        for li, lay in enumerate(self.layers):
-            sa = lay.self_attn
-            qkv = ops.gemm_nt(h, sa.in_proj_weight, bias=sa.in_proj_bias)
-            att = torch.empty(M * P, d, dtype=torch.float32, device=self.dev) if li < last else None
-            hip.call('vqcpc_decode_prefill_attn', qkv, 3 * d, qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, 3 * d,
-                     self.kcache[li], self.vcache[li], d, sa.attn_bias.e1, sa.attn_bias.e2, att, d, M, P, T, 1, H, hd,
-                     ops.MASK_CAUSAL)
-            if li == last:
-                break                                     # nothing reads the last layer's prefix outputs
-            h1 = self._prefix_ln(h, ops.gemm_nt(att, sa.out_proj.weight, bias=sa.out_proj.bias), lay.norm1)
-            kv = self.memkv[li]
-            if self.diagonal:
-                hip.call('vqcpc_aligned_expand', kv, att, M, S, P, self.U, self.nc, d)        # att: (M * P, d), free here
-                h2 = self._prefix_ln(h1, att, lay.norm2)
-            else:
-                ca = lay.multihead_attn
-                qc = ops.gemm_nt(h1, ca.in_proj_weight[:d], bias=ca.in_proj_bias[:d])
-                hip.call('vqcpc_decode_prefill_attn', qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
-                         ca.attn_bias.e2, att, d, M, P, S, T // S, H, hd, self.cross_mask)
-                h2 = self._prefix_ln(h1, ops.gemm_nt(att, ca.out_proj.weight, bias=ca.out_proj.bias), lay.norm2)
-            f = ops.gemm_nt(h2, lay.linear1.weight, bias=lay.linear1.bias, act=1)
-            h = self._prefix_ln(h2, ops.gemm_nt(f, lay.linear2.weight, bias=lay.linear2.bias), lay.norm3)
+    def _prefix_cross_aligned(self, li, lay, h1, att, P):
+        hip.call('vqcpc_aligned_expand', self.memkv[li], att, self.M, self.S, P, self.U, self.nc, self.d)
+        return self._prefix_ln(h1, att, lay.norm2)
 
     @torch.no_grad()
     def slide(self, t_begin=None, t_relative=0, advance=1):
@@ -343,17 +249,11 @@ class IncrementalDecoder:
             self.slide(tb0, tr0)                  # a live state for the first launches, which stay outside the captures
             if use_graph:
                 self.step()
-                torch.cuda.synchronize(self.dev)
-                step_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(step_graph, capture_error_mode='thread_local'):
-                    self.step()
+                step_graph = self.capture(self.step)
             n_mid = sum(1 for k in range(1, len(plan)) if plan[k][1] == plan[k - 1][1] + 1 and plan[k][3] == tr_mid)
             if graph_slides and n_mid >= 2:
                 self.slide(tb0, tr_mid)
-                torch.cuda.synchronize(self.dev)
-                slide_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(slide_graph, capture_error_mode='thread_local'):
-                    self.slide(None, tr_mid, advance=1)
+                slide_graph = self.capture(lambda: self.slide(None, tr_mid, advance=1))
             self.chorale.copy_(chorale0)          # the warm-up launches drew and committed tokens: start again
             self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
         live = None

@@ -3,11 +3,9 @@ full forward on the model window per code and samples on the host).
 
 The prior is one causal stack: position e's logits depend on codes < e of the window only (row-wise table lookup /
 LayerNorm / FFN, causal self-attention), so an incremental step per code computes the same function.  The step is the
-decoder's (decoders/generation.py) without the cross-attention, 7 launches per layer + 2:
-
-  in_proj -> self-attention on the layer's K/V cache (the step's k / v row is stored at row pos) -> out_proj + residual ->
-  add & LayerNorm -> linear1 + ReLU -> linear2 + residual -> add & LayerNorm;  then the head and vqcpc_prior_sample, which
-  draws the code of position pos, writes the input row of position pos + 1 and advances the device counter `pos`.
+shared stack's (transformer/incremental.py) with no cross block, i.e. the decoder's without the cross-attention, 7 launches
+per layer + 2; its sampler is vqcpc_prior_sample, which draws the code of position pos, writes the input row of position
+pos + 1 and advances the device counter `pos`.
 
 Two regimes, as in the reference (:331-336):
 
@@ -16,8 +14,7 @@ Two regimes, as in the reference (:331-336):
   moves by one code per code.  The window's first input row becomes the start-of-sentence row and every other row loses
   one code of context, so EVERY cache row is stale.  Per move: vqcpc_prior_window (commit the live window's codes, load the
   next window's, the prefix's table rows, the input row of position P, the window's seeds, pos = P) -> the stack
-  teacher-forced over the P prefix rows of every sequence (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd,
-  vqcpc_decode_prefill_attn; the last layer stops after its k | v) -> N - P cached steps.
+  teacher-forced over the P prefix rows of every sequence (`prefill_prefix`) -> N - P cached steps.
   window_stride = 1 is the reference exactly: P = N - 1, one step per move.  At that stride the cache saves only the last
   layer's prefix outputs and the head over the window's rows; a move costs about one full forward minus those, and what the
   captured move buys is host launch time.  window_stride = k > 1 (opt-in) moves k codes at a time: P = N - k, k steps per
@@ -47,7 +44,7 @@ a draw that sits within ~1e-6 of a cumulative-probability boundary can differ be
 import torch
 
 from .. import hip, ops
-from ..decoders.generation import MAX_ROWS, row_seeds
+from ..transformer.incremental import MAX_ROWS, IncrementalStack, row_seeds
 
 # method='auto': rows from which the forward form replaces the cached step (profiles/generate_prior_perf_log.md: at the PRI
 # shape the head step costs 376 / 1 096 us cached against 735 / 995 us forward at 8 / 32 rows; a stride-1 move 651 / 910 / 1 916 us
@@ -56,7 +53,7 @@ FORWARD_HEAD_MIN_ROWS = 32
 FORWARD_SLIDE_MIN_ROWS = 1
 
 
-class IncrementalPrior:
+class IncrementalPrior(IncrementalStack):
     """One generation of `batch` <= 64 rows of `prior` (a PriorRelative in eval mode; the caller holds utils.STEP_LOCK).
 
         inc = IncrementalPrior(prior, B)
@@ -70,35 +67,14 @@ class IncrementalPrior:
         if not 1 <= batch <= MAX_ROWS:
             raise ValueError(f'IncrementalPrior: 1 <= batch <= {MAX_ROWS} (got {batch})')
         pr = self.prior = prior
-        self.M = M = int(batch)
-        self.dev = dev = pr.sos.device
-        self.d, self.N, self.V = pr.d_model, pr.num_tokens, pr.num_tokens_per_channel[0]
-        self.layers = list(pr.transformer.layers)
-        a = self.layers[0].self_attn
-        self.H, self.hd = a.num_heads, a.head_dim
-        self.ff = self.layers[0].linear1.weight.shape[0]
-        f32 = dict(dtype=torch.float32, device=dev)
-        d, N, L = self.d, self.N, len(self.layers)
-        self.x = torch.empty(M, d, **f32)                     # input rows of the current position
-        self.hb = [torch.empty(M, d, **f32) for _ in range(2)]
-        self.h1, self.s, self.att = (torch.empty(M, d, **f32) for _ in range(3))
-        self.qkv = torch.empty(M, 3 * d, **f32)
-        self.f = torch.empty(M, self.ff, **f32)
-        self.logits = torch.empty(M, self.V, **f32)
-        self.mean, self.rstd = torch.empty(M, **f32), torch.empty(M, **f32)
-        self.kcache = torch.empty(L, M, N, d, **f32)
-        self.vcache = torch.empty(L, M, N, d, **f32)
+        M, dev = int(batch), pr.sos.device
+        N = self.N = pr.num_tokens
+        self.V = pr.num_tokens_per_channel[0]
+        layers = list(pr.transformer.layers)
+        super().__init__(dev, M, layers, [lay.norm2 for lay in layers], N, pr.d_model)
+        self.logits = torch.empty(M, self.V, dtype=torch.float32, device=dev)
         self.codes_win = torch.zeros(M, N, dtype=torch.int64, device=dev)
-        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.seeds = torch.zeros(M, dtype=torch.int64, device=dev)        # the live window's effective seeds
-        self.row_seeds = torch.zeros(M, dtype=torch.int64, device=dev)
-        self.win = torch.tensor([0, -1], dtype=torch.int32, device=dev)   # {next window, live window}
-        self.prefix_rows = torch.zeros(M * N, dtype=torch.int64, device=dev)
-        self._pmean = torch.empty(M * N, **f32)
-        self._prstd = torch.empty(M * N, **f32)
-        self.teacher = None
-        self.probs = None
         self._sos_col = torch.full((M, 1), self.V, dtype=torch.int64, device=dev)    # table row of the start-of-sentence input
         with torch.no_grad():
             self.table = pr._input_table().contiguous()                    # (V + 1, d)
@@ -129,35 +105,7 @@ class IncrementalPrior:
         self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
         self._window(0, 0)                                    # window 0, P = 0: start-of-sentence row, the rows' own seeds
 
-    # ---- one step ----------------------------------------------------------------------------------------------------
-    def _ln(self, s, norm, out):
-        hip.call('vqcpc_add_layernorm_fwd', s, self.d, None, norm.weight, norm.bias, out, self.mean, self.rstd, self.M, self.d,
-                 1e-5, 0.0, 0)
-
-    def _linear(self, x, w, b, out, res=None, relu=0):
-        N, K = w.shape
-        hip.call('vqcpc_decode_linear', x, x.shape[1], None, w, b, res, out.shape[1] if res is not None else 0, out,
-                 out.shape[1], self.M, N, K, relu)
-
-    def step(self):
-        M, d, N, H, hd = self.M, self.d, self.N, self.H, self.hd
-        hin = self.x
-        for li, lay in enumerate(self.layers):
-            sa = lay.self_attn
-            hout = self.hb[li % 2]
-            self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
-            q0 = self.qkv.data_ptr()
-            hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
-                     sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, N, 1, H, hd, ops.MASK_CAUSAL)
-            self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
-            self._ln(self.s, lay.norm1, self.h1)
-            self._linear(self.h1, lay.linear1.weight, lay.linear1.bias, self.f, relu=1)
-            self._linear(self.f, lay.linear2.weight, lay.linear2.bias, self.s, res=self.h1)
-            self._ln(self.s, lay.norm2, hout)
-            hin = hout
-        self._linear(hin, self.head_w, self.head_b, self.logits)
-        self._sample()
-
+    # ---- one step: the sampler, and the forward form ---------------------------------------------------------------------
     def _sample(self):
         N = self.N
         hip.call('vqcpc_prior_sample', self.logits, self.V, self.V, self.M, self.temperature, self.top_k, self.top_p,
@@ -187,34 +135,6 @@ class IncrementalPrior:
         hip.call('vqcpc_prior_window', self.seq, self.nt, self.nt, self.win, int(advance), self.codes_win, self.N, int(P),
                  self.prefix_rows, self.table, self.table.shape[0], self.d, self.x, self.d, self.row_seeds, self.seeds,
                  self.pos, self.M)
-
-    def _prefix_ln(self, x, r, norm):
-        y = torch.empty_like(x)
-        n = x.shape[0]
-        hip.call('vqcpc_add_layernorm_fwd', x, self.d, r, norm.weight, norm.bias, y, self._pmean[:n], self._prstd[:n], n, self.d,
-                 1e-5, 0.0, 0)
-        return y
-
-    def prefill_prefix(self, P):
-        """The stack, teacher-forced over prefix rows [0, P) of every sequence (inputs: table rows `prefix_rows`): fills
-        every layer's K/V cache rows [0, P)."""
-        if P == 0:
-            return
-        M, d, N, H, hd = self.M, self.d, self.N, self.H, self.hd
-        h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
-        last = len(self.layers) - 1
-        for li, lay in enumerate(self.layers):
-            sa = lay.self_attn
-            qkv = ops.gemm_nt(h, sa.in_proj_weight, bias=sa.in_proj_bias)
-            att = torch.empty(M * P, d, dtype=torch.float32, device=self.dev) if li < last else None
-            hip.call('vqcpc_decode_prefill_attn', qkv, 3 * d, qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, 3 * d,
-                     self.kcache[li], self.vcache[li], d, sa.attn_bias.e1, sa.attn_bias.e2, att, d, M, P, N, 1, H, hd,
-                     ops.MASK_CAUSAL)
-            if li == last:
-                break                                     # nothing reads the last layer's prefix outputs
-            h1 = self._prefix_ln(h, ops.gemm_nt(att, sa.out_proj.weight, bias=sa.out_proj.bias), lay.norm1)
-            f = ops.gemm_nt(h1, lay.linear1.weight, bias=lay.linear1.bias, act=1)
-            h = self._prefix_ln(h1, ops.gemm_nt(f, lay.linear2.weight, bias=lay.linear2.bias), lay.norm2)
 
     @torch.no_grad()
     def slide(self, w=None, P=0, advance=1):
@@ -262,17 +182,11 @@ class IncrementalPrior:
         warmed = False
         if use_graph and (head_form == 'cached' or (slide_form == 'cached' and nt > N)):
             self.step()                           # first launches outside the capture
-            torch.cuda.synchronize(self.dev)
-            step_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(step_graph, capture_error_mode='thread_local'):
-                self.step()
+            step_graph = self.capture(self.step)
             warmed = True
         if slide_form == 'cached' and graph_slides and n_full >= 2:
             self.slide(0, N - k, advance=k)
-            torch.cuda.synchronize(self.dev)
-            slide_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(slide_graph, capture_error_mode='thread_local'):
-                self.slide(None, N - k, advance=k)
+            slide_graph = self.capture(lambda: self.slide(None, N - k, advance=k))
             warmed = True
         if warmed:
             self.reset()                          # the warm-up launches drew and committed codes: start again

@@ -268,8 +268,8 @@ class PriorRelative(GraphedTraining, nn.Module):
         launches eagerly (same codes).  method: 'auto' picks per regime and batch between the KV-cached step and the
         full-stack step on the window (priors/generation.py: the faster of the two as measured), 'cached' / 'forward' force
         one; both compute the same logits to rounding.  -> int64 (num_generated_codes, num_tokens) on the device."""
-        from ..decoders.generation import row_seeds
-        from .generation import MAX_ROWS, IncrementalPrior
+        from ..transformer.incremental import generate_in_chunks, row_seeds
+        from .generation import IncrementalPrior
         V, N = self.num_tokens_per_channel[0], self.num_tokens
         if V > MAX_SAMPLED_VOCAB:
             raise ValueError(f'generate_codes: {V} merged codes, the sampling kernel (vqcpc_prior_sample) takes at most '
@@ -283,22 +283,13 @@ class PriorRelative(GraphedTraining, nn.Module):
             raise ValueError(f'generate_codes: 1 <= window_stride < {N} (got {window_stride})')
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
-        dev = self.sos.device
         seeds = row_seeds(seed, B)
-        out = torch.empty(B, num_tokens, dtype=torch.int64, device=dev)
-        with STEP_LOCK, torch.no_grad():               # never interleaved with a training step of another thread
-            was_training = self.training
-            self.eval()
-            try:
-                for b0 in range(0, B, MAX_ROWS):
-                    n = min(MAX_ROWS, B - b0)
-                    inc = IncrementalPrior(self, n)
-                    inc.start(num_tokens, seeds=seeds[b0:b0 + n], temperature=temperature, top_k=top_k, top_p=top_p)
-                    out[b0:b0 + n] = inc.run(use_graph=use_graph, window_stride=stride, method=method)
-                    del inc
-            finally:
-                self.train(was_training)
-        return out
+
+        def chunk(n, rows):
+            inc = IncrementalPrior(self, n)
+            inc.start(num_tokens, seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p)
+            return inc.run(use_graph=use_graph, window_stride=stride, method=method)
+        return generate_in_chunks(self, B, num_tokens, chunk)
 
     def generate(self, num_tokens, decoder, temperature=1.0, num_generated_codes=1, num_decodings_per_generating_code=1,
                  decoder_temperature=None, seed=None, **decoder_sampling):

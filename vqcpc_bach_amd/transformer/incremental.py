@@ -1,0 +1,178 @@
+"""The incremental (KV-cached) transformer stack that the decoder's and the prior's generation share
+(decoders/generation.py, priors/generation.py; kernels: csrc/decode.hip, csrc/prior.hip).
+
+Both generators run one causal stack a position at a time over a window of W positions (the decoder's T target tokens, the
+prior's N codes): position t's output depends on positions < t only (causal self-attention, row-wise embedding / LayerNorm
+/ FFN), so one incremental step per position computes the same function as the full forward.
+
+  step, per layer:  in_proj -> self-attention on the layer's K/V cache (the step's k / v row is stored at row pos) ->
+  out_proj + residual -> add & LayerNorm -> the cross hook -> linear1 + ReLU -> linear2 + residual -> add & LayerNorm;  then
+  the head(s) and the subclass's sampler, which draws the position's token, writes the input row of position pos + 1 and
+  advances the device counter `pos`.  7 launches per layer + 2 plus the cross hook's: none (prior, whose stack has no
+  cross block), 3 + a LayerNorm (decoder: cross q -> cross-attention -> out_proj + residual), 1 + a LayerNorm (diagonal
+  decoder: vqcpc_decode_aligned_add).
+
+  prefix (`prefill_prefix`): when a window moves, every cache row is stale.  The stack is teacher-forced over the P prefix
+  rows of every sequence (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_decode_prefill_attn, the prefix-side cross hook),
+  which leaves every layer's K/V cache rows [0, P) filled; the last layer stops after its self-attention k | v.
+
+Every kernel of the step reads `pos` from device memory, so ONE captured step (`capture`) is replayed for every position.
+Rows are independent and every kernel reduces in an order that does not depend on the number of rows, so a row's tokens do
+not depend on which other rows share the call (given the same inputs and seed)."""
+import torch
+
+from .. import hip, ops
+from ..utils import STEP_LOCK
+
+MAX_ROWS = 64                # rows of one incremental stack (vqcpc_decode_*); larger batches run in chunks
+
+
+def _splitmix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
+def row_seeds(seed, n):
+    """int -> n per-row int64 seeds (splitmix64 of (seed, row)); a tensor of n int64 is taken as it is; None draws one
+    int from torch's CPU generator."""
+    if torch.is_tensor(seed):
+        s = seed.reshape(-1).to(torch.int64)
+        if s.numel() != n:
+            raise ValueError(f'seed: {s.numel()} per-row seeds for {n} rows')
+        return s.cpu()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    vals = [_splitmix64((int(seed) * 0x100000001B3 + r) & 0xFFFFFFFFFFFFFFFF) for r in range(n)]
+    return torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
+
+
+def generate_in_chunks(model, B, width, chunk):
+    """The public generation methods' loop: `chunk(n, rows)` -> (n, width) int64 tokens of the rows `rows` (a slice of
+    n <= MAX_ROWS of the B rows), from an incremental stack that lives for that chunk only.  Runs under STEP_LOCK (never
+    interleaved with a training step of another thread), without gradients and with `model` in eval mode.  -> (B, width)."""
+    out = torch.empty(B, width, dtype=torch.int64, device=model.sos.device)
+    with STEP_LOCK, torch.no_grad():
+        was_training = model.training
+        model.eval()
+        try:
+            for b0 in range(0, B, MAX_ROWS):
+                n = min(MAX_ROWS, B - b0)
+                out[b0:b0 + n] = chunk(n, slice(b0, b0 + n))
+        finally:
+            model.train(was_training)
+    return out
+
+
+class IncrementalStack:
+    """The buffers, the step and the prefix re-prefill of M <= 64 rows of a stack `layers` over a window of W positions.
+    last_norms: per layer, the LayerNorm after the FFN (the decoder's norm3, the prior's norm2).  A subclass provides
+    `table`, `head_w`, `head_b`, `logits` and `_sample`, and, where its layers have a cross block, sets the hooks `_cross` /
+    `_prefix_cross` once at construction.  The hooks are plain functions of (stack, layer index, layer, ...), not bound
+    methods: an instance that held its own bound methods would be a reference cycle, and its caches would outlive `del`."""
+
+    def __init__(self, dev, M, layers, last_norms, W, d):
+        self.dev, self.M, self.W, self.d = dev, M, W, d
+        self.layers, self.last_norms = layers, last_norms
+        a = layers[0].self_attn
+        self.H, self.hd = a.num_heads, a.head_dim
+        self.ff = layers[0].linear1.weight.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.x = torch.empty(M, d, **f32)                     # input rows of the current position
+        self.hb = [torch.empty(M, d, **f32) for _ in range(2)]
+        self.h1, self.s, self.att = (torch.empty(M, d, **f32) for _ in range(3))
+        self.qkv = torch.empty(M, 3 * d, **f32)
+        self.f = torch.empty(M, self.ff, **f32)
+        self.mean, self.rstd = torch.empty(M, **f32), torch.empty(M, **f32)
+        self.kcache = torch.empty(len(layers), M, W, d, **f32)
+        self.vcache = torch.empty(len(layers), M, W, d, **f32)
+        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.seeds = torch.zeros(M, dtype=torch.int64, device=dev)        # the live window's effective seeds
+        self.row_seeds = torch.zeros(M, dtype=torch.int64, device=dev)
+        self.win = torch.tensor([0, -1], dtype=torch.int32, device=dev)   # {next window, live window}
+        self.prefix_rows = torch.zeros(M * W, dtype=torch.int64, device=dev)
+        self._pmean, self._prstd = torch.empty(M * W, **f32), torch.empty(M * W, **f32)
+        self.teacher = None
+        self.probs = None
+        self._cross, self._prefix_cross = IncrementalStack._no_cross, IncrementalStack._no_prefix_cross
+
+    # ---- one step ----------------------------------------------------------------------------------------------------
+    def _ln(self, s, norm, out):
+        hip.call('vqcpc_add_layernorm_fwd', s, self.d, None, norm.weight, norm.bias, out, self.mean, self.rstd, self.M, self.d,
+                 1e-5, 0.0, 0)
+
+    def _linear(self, x, w, b, out, res=None, relu=0):
+        N, K = w.shape
+        hip.call('vqcpc_decode_linear', x, x.shape[1], None, w, b, res, out.shape[1] if res is not None else 0, out,
+                 out.shape[1], self.M, N, K, relu)
+
+    def _no_cross(self, li, lay):
+        """The step's cross hook of layer li: reads `h1`, returns the rows the FFN reads."""
+        return self.h1
+
+    def step(self):
+        M, d, W, H, hd = self.M, self.d, self.W, self.H, self.hd
+        cross = self._cross
+        hin = self.x
+        for li, lay in enumerate(self.layers):
+            sa = lay.self_attn
+            hout = self.hb[li % 2]
+            self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
+            q0 = self.qkv.data_ptr()
+            hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
+                     sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, W, 1, H, hd, ops.MASK_CAUSAL)
+            self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
+            self._ln(self.s, lay.norm1, self.h1)
+            h = cross(self, li, lay)
+            self._linear(h, lay.linear1.weight, lay.linear1.bias, self.f, relu=1)
+            self._linear(self.f, lay.linear2.weight, lay.linear2.bias, self.s, res=h)
+            self._ln(self.s, self.last_norms[li], hout)
+            hin = hout
+        self._linear(hin, self.head_w, self.head_b, self.logits)
+        self._sample()
+
+    # ---- the prefix of a moved window ----------------------------------------------------------------------------------
+    def _prefix_ln(self, x, r, norm):
+        y = torch.empty_like(x)
+        n = x.shape[0]
+        hip.call('vqcpc_add_layernorm_fwd', x, self.d, r, norm.weight, norm.bias, y, self._pmean[:n], self._prstd[:n], n, self.d,
+                 1e-5, 0.0, 0)
+        return y
+
+    def _no_prefix_cross(self, li, lay, h1, att, P):
+        """The prefix's cross hook of layer li on the (M * P, d) rows h1 (att: (M * P, d), free here): returns the rows the
+        FFN reads."""
+        return h1
+
+    def prefill_prefix(self, P):
+        """The stack, teacher-forced over prefix rows [0, P) of every sequence (inputs: table rows `prefix_rows`): fills
+        every layer's K/V cache rows [0, P)."""
+        if P == 0:
+            return
+        M, d, W, H, hd = self.M, self.d, self.W, self.H, self.hd
+        h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
+        last = len(self.layers) - 1
+        for li, lay in enumerate(self.layers):
+            sa = lay.self_attn
+            qkv = ops.gemm_nt(h, sa.in_proj_weight, bias=sa.in_proj_bias)
+            att = torch.empty(M * P, d, dtype=torch.float32, device=self.dev) if li < last else None
+            hip.call('vqcpc_decode_prefill_attn', qkv, 3 * d, qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, 3 * d,
+                     self.kcache[li], self.vcache[li], d, sa.attn_bias.e1, sa.attn_bias.e2, att, d, M, P, W, 1, H, hd,
+                     ops.MASK_CAUSAL)
+            if li == last:
+                break                                     # nothing reads the last layer's prefix outputs
+            h1 = self._prefix_ln(h, ops.gemm_nt(att, sa.out_proj.weight, bias=sa.out_proj.bias), lay.norm1)
+            h2 = self._prefix_cross(self, li, lay, h1, att, P)
+            f = ops.gemm_nt(h2, lay.linear1.weight, bias=lay.linear1.bias, act=1)
+            h = self._prefix_ln(h2, ops.gemm_nt(f, lay.linear2.weight, bias=lay.linear2.bias), self.last_norms[li])
+
+    # ---- graphs --------------------------------------------------------------------------------------------------------
+    def capture(self, fn):
+        """fn's launches as a captured graph.  The caller has run them eagerly once already: first launches (module
+        loading, workspace and buffer allocation) stay outside the capture."""
+        torch.cuda.synchronize(self.dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+            fn()
+        return graph
