@@ -746,6 +746,13 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
  *   P, seeds_out[b] = seeds_in[b] for window 0, otherwise splitmix64(seeds_in[b] ^ win[0] * 0xD1B54A32D192ED03) -- the
  *   sampler keys its draw by (seed, window position), so the seed must change with the window --, pos[0] = P,
  *   win = {win[0] + advance, win[0]}.  T == S * U, 0 <= P < T.
+ * vqcpc_decode_source_rows: the source rows of a decoder on CONTINUOUS latents (a NoQuantization encoder; decoder.py:222-229
+ *   makes source_embeddings an nn.Linear(dz, d_model)): for b < M, j < S, n < N
+ *     src[(b * S + j) * lds + n] = bias[n] + sum_k z_full[(b * nb + w0 + j) * dz + k] * w[n * dz + k],
+ *   w0 = win ? win[1] : 0 -- the live window's first code as vqcpc_decode_window leaves it, read from device memory, so a
+ *   captured slide serves every middle window.  Nothing is written if w0 < 0 or w0 + S > nb.  Plain fp32 FMA, k ascending
+ *   from 0, the bias added last: a row's result depends on its own latents and W only (not on M, b, w0 or other rows).
+ *   bias may be NULL.  M <= 64, S <= 1024, 4 <= dz <= 256, dz % 4 == 0, N <= 4096, lds >= N, nb >= S.
  * ------------------------------------------------------------------------------------------------------------------ */
 int vqcpc_decode_linear(const float* x, int64_t ldx, const int64_t* gather, const float* w, const float* bias, const float* res,
                         int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int relu, void* stream);
@@ -763,6 +770,8 @@ int vqcpc_decode_window(const int64_t* codes_full, int64_t nb, int64_t* chorale,
                         int64_t* codes_win, int S, int64_t* tokens, int T, int U, int P, int64_t* prefix_rows,
                         const float* table, int64_t table_rows, int d, float* x, int64_t ldx, const int64_t* seeds_in,
                         int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
+int vqcpc_decode_source_rows(const float* z_full, int64_t nb, int dz, const int32_t* win, const float* w, const float* bias,
+                             float* src, int64_t lds, int64_t M, int S, int N, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Sampling code sequences from the prior (VQCPCB/priors/prior_relative.py:308-353: one full forward per code, softmax,

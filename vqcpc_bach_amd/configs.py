@@ -88,11 +88,14 @@ def make_prior_config(dropout=0.2, **over):
     return cfg
 
 
-def make_sameseq_config(dropout=0.1, **over):
+def make_sameseq_config(dropout=0.1, quantizer_type='commitment', **over):
     """VQCPCB/configs/encoder_sameSeq.py:11-86 in this package's schema: the GRU block downscaler ('lstm_downscaler':
     hidden 512, 2 layers, bidirectional, one 16-token block per code), 1 x 32 codes of dim 3, MLP upscaler 32 / 512, context
     network 512 x 2, quantization weighting 1.0, batch 16, 6 + 6 blocks, same-sequence negatives (num_negative_samples = 15
-    is stated and unused there)."""
+    is stated and unused there).
+    quantizer_type=None ('SAMESEQ_NOQ') is VQCPCB/configs/encoder_sameSeq_no_quantization_config.py: no quantiser
+    (`codebook_dim` 32 is the dimension of the continuous latent z, no codebook keys), no upscaler, quantization weighting
+    0.5 -- the encoder of the decoders on continuous latents (decoder_relative_AC_D_C_*_noQuantization.py)."""
     cfg = {
         'training_method': 'vqcpc', 'dataset': 'bach',
         'dataloader_generator_kwargs': dict(num_tokens_per_block=16, num_blocks_left=6, num_blocks_right=6,
@@ -112,6 +115,12 @@ def make_sameseq_config(dropout=0.1, **over):
         'lr': 1e-4, 'schedule_lr': False, 'batch_size': 16, 'num_batches': 256, 'num_epochs': 1,
         'quantizer_regularization': dict(corrupt_labels=False), 'timestamp': None, 'savename': 'encoder_sameSeq',
     }
+    if quantizer_type is None:
+        cfg.update(quantizer_type=None, quantizer_kwargs=dict(codebook_dim=32), upscaler_type=None,
+                   savename='encoder_sameSeq_no_quantization_config')
+        cfg['auxiliary_networks_kwargs']['quantization_weighting'] = 0.5
+    elif quantizer_type != 'commitment':
+        cfg['quantizer_type'] = quantizer_type
     cfg = copy.deepcopy(cfg)
     for k, v in over.items():
         cfg[k] = v
@@ -121,6 +130,8 @@ def make_sameseq_config(dropout=0.1, **over):
 def make_config(name='C1', dropout=0.1, **over):
     if name == 'SAMESEQ':
         return make_sameseq_config(dropout=dropout, **over)
+    if name == 'SAMESEQ_NOQ':
+        return make_sameseq_config(dropout=dropout, quantizer_type=None, **over)
     if name == 'PRI':
         return make_prior_config(dropout=dropout, **over)
     if name == 'C3':

@@ -24,6 +24,10 @@
 //   * vqcpc_decode_window: ONE workgroup.  Puts the live window's tokens back into the chorale, loads the next window's
 //     codes and tokens (its index is read from device memory and advanced), the prefix's table-row indices, the input row
 //     of position P, the window's effective sampling seeds and `pos`.
+//
+// A decoder on continuous latents (a NoQuantization encoder) has a linear layer where the others have an embedding table:
+//   * vqcpc_decode_source_rows: src = z W^T + b on the S latents of the live window of every sequence; the window's first
+//     code is read from the device memory that vqcpc_decode_window maintains.
 #include <algorithm>
 
 #include "common.h"
@@ -411,6 +415,60 @@ __global__ __launch_bounds__(1024) void decode_window_kernel(
 }
 
 // =====================================================================================================================
+// decode_source_rows: the source rows of a decoder on continuous latents, src = z W^T + b on the live window of z_full.
+// A workgroup owns kSrcRows source rows x kSrcThreads output columns: the latents of its rows go through LDS (every lane
+// reads the same address: a broadcast), a thread streams its own row of W as float4 and keeps one accumulator per row.
+// Per output element: acc = 0, fmaf over k ascending, + bias -- a function of the row's latents and W's row alone.
+constexpr int kSrcRows = 8;
+constexpr int kSrcThreads = 128;
+constexpr int kSrcMaxDz = 256;
+constexpr int kSrcMaxS = 1024;
+
+__global__ __launch_bounds__(kSrcThreads) void decode_source_rows_kernel(const float* __restrict__ z_full, int64_t nb, int dz,
+                                                                         const int32_t* __restrict__ win,
+                                                                         const float* __restrict__ w,
+                                                                         const float* __restrict__ bias,
+                                                                         float* __restrict__ src, int64_t lds, int64_t rows_all,
+                                                                         int S, int N) {
+    __shared__ float4 zs[kSrcRows * (kSrcMaxDz / 4)];
+    const int w0 = win ? win[1] : 0;
+    if (w0 < 0 || (int64_t)w0 + S > nb) return;              // no live window (uniform): src stays as it is
+    const int64_t r0 = (int64_t)blockIdx.y * kSrcRows;
+    const int rows = (int)min((int64_t)kSrcRows, rows_all - r0);
+    const int q = dz / 4;
+    for (int e = threadIdx.x; e < rows * q; e += kSrcThreads) {
+        const int64_t row = r0 + e / q;
+        const int64_t b = row / S, j = row % S;
+        zs[(e / q) * (kSrcMaxDz / 4) + e % q] = reinterpret_cast<const float4*>(z_full + (b * nb + w0 + j) * dz)[e % q];
+    }
+    __syncthreads();
+    const int n = blockIdx.x * kSrcThreads + threadIdx.x;
+    if (n >= N) return;
+    const float4* wr = reinterpret_cast<const float4*>(w + (int64_t)n * dz);
+    float acc[kSrcRows];
+#pragma unroll
+    for (int r = 0; r < kSrcRows; ++r) acc[r] = 0.0f;
+#pragma unroll 4
+    for (int k = 0; k < q; ++k) {
+        const float4 wv = wr[k];
+#pragma unroll
+        for (int r = 0; r < kSrcRows; ++r) {
+            const float4 zv = zs[r * (kSrcMaxDz / 4) + k];   // rows past `rows` hold stale LDS: computed, never stored
+            float a = acc[r];
+            a = fmaf(zv.x, wv.x, a);
+            a = fmaf(zv.y, wv.y, a);
+            a = fmaf(zv.z, wv.z, a);
+            a = fmaf(zv.w, wv.w, a);
+            acc[r] = a;
+        }
+    }
+    const float bn = bias ? bias[n] : 0.0f;
+#pragma unroll
+    for (int r = 0; r < kSrcRows; ++r)
+        if (r < rows) src[(r0 + r) * lds + n] = bn + acc[r];
+}
+
+// =====================================================================================================================
 // decode_sample: one workgroup of 16 wavefronts; wavefront w takes rows w, w + 16, ...  Lane l owns tokens 4l .. 4l + 3
 // of the row (V_c <= 256), so the cumulative sums are a lane-serial scan of four plus a wave scan of the lane totals.
 constexpr int kSampWaves = 16;
@@ -712,6 +770,21 @@ int vqcpc_decode_window(const int64_t* codes_full, int64_t nb, int64_t* chorale,
                        advance, codes_win, S, tokens, T, U, P, prefix_rows, table, table_rows, d, x, ldx, seeds_in, seeds_out,
                        pos, (int)M);
     VQ_CHECK_LAUNCH("decode_window");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_source_rows(const float* z_full, int64_t nb, int dz, const int32_t* win, const float* w, const float* bias,
+                             float* src, int64_t lds, int64_t M, int S, int N, void* stream) {
+    VQ_REQUIRE(z_full && w && src && M >= 1 && M <= kDecMaxRows && S >= 1 && S <= kSrcMaxS && N >= 1 && N <= kDecMaxDim &&
+               dz >= 4 && dz <= kSrcMaxDz && dz % 4 == 0,
+               "decode_source_rows: bad arguments (1 <= M <= 64, 1 <= S <= 1024, 1 <= N <= 4096, 4 <= dz <= 256, dz %% 4 == 0)");
+    VQ_REQUIRE(nb >= S && lds >= N && aligned16(z_full) && aligned16(w),
+               "decode_source_rows: nb >= S, lds >= N, z_full and w 16-byte aligned");
+    const int64_t rows = M * S;
+    const dim3 grid((unsigned)ceil_div(N, kSrcThreads), (unsigned)ceil_div(rows, (int64_t)kSrcRows)), block(kSrcThreads);
+    hipLaunchKernelGGL(decode_source_rows_kernel, grid, block, 0, (hipStream_t)stream, z_full, nb, dz, win, w, bias, src, lds,
+                       rows, S, N);
+    VQ_CHECK_LAUNCH("decode_source_rows");
     return VQCPC_OK;
 }
 

@@ -12,10 +12,13 @@ KV-cached incremental decoding on the GPU (decoders/generation.py); `generate_fr
 `compute_start_end_times`, `init_generation_chorale` (:728-854, :960-981, :1054-1062) decode code sequences of any length
 by sliding the window, with a K/V-cache re-prefill per move; `reharmonise_tokens` is the body of
 `generate_reharmonisation` (:856-958) on a token tensor (the music21 corpus it reads is absent, so that method raises).
-Duplicate checks, plots, the absolute-position variant and continuous (NoQuantization) sources are out of scope and raise.
+A decoder on continuous latents (a `NoQuantization` encoder without upscaler, decoder.py:222-229, :327-336, :595-600) has
+`source_embeddings = nn.Linear(dz, d_model)` and takes the encoder's (B, S, dz) latents wherever the others take merged codes.
+Duplicate checks, plots and the absolute-position variant are out of scope and raise.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
-  * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient);
+  * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient), or, on continuous
+    latents, `ops.linear(z, W, b)` (z is the frozen encoder's output: no input gradient);
   * target: `linear_target(cat[embed(x), channel emb, event-in-code emb])` depends only on (token, position in a code
     block), so it is evaluated on the vmax * U table rows (U = total_upscaling) by ONE small GEMM and looked up per
     token -- with the start-of-sentence row appended, the reference's shift-by-one (:474-480) is the same lookup with
@@ -131,10 +134,19 @@ class Decoder(GraphedTraining, nn.Module):
             custom_decoder=TransformerDecoderCustom(decoder_layer=decoder_layer, num_layers=num_decoder_layers))
         self.linear_target = nn.Linear(self.data_processor.embedding_size + positional_embedding_size * 2, self.d_model)
         self.sos = nn.Parameter(torch.randn((1, 1, self.d_model)))
-        if type(self.encoder.quantizer).__name__ == 'NoQuantization':
-            raise NotImplementedError('continuous (NoQuantization) sources are out of scope')
-        codebook_size = self.encoder.quantizer.codebook_size ** self.encoder.quantizer.num_codebooks
-        self.source_embeddings = nn.Embedding(codebook_size, self.d_model)
+        self.continuous_source = type(self.encoder.quantizer).__name__ == 'NoQuantization'
+        if self.continuous_source:                                                           # :222-229
+            if self.encoder.upscaler is not None:
+                raise NotImplementedError('a NoQuantization encoder WITH an upscaler: the decoder reads the latents before the '
+                                          'upscaler, which the reference does only when upscaler_type is None')
+            self.source_dim = int(self.encoder.quantizer.codebook_dim)
+            if self.source_dim % 4 != 0 or not 4 <= self.source_dim <= 256:
+                raise NotImplementedError(f'continuous source of dimension {self.source_dim}: a multiple of 4 in [4, 256] is needed')
+            self.source_embeddings = nn.Linear(self.source_dim, self.d_model)
+        else:
+            self.source_dim = None
+            codebook_size = self.encoder.quantizer.codebook_size ** self.encoder.quantizer.num_codebooks
+            self.source_embeddings = nn.Embedding(codebook_size, self.d_model)
         self.pre_softmaxes = nn.ModuleList([nn.Linear(self.d_model, n) for n in self.num_tokens_per_channel])
         self.num_tokens_source = num_channels_encoder * num_events_encoder
         self.optimizer = None
@@ -249,12 +261,29 @@ class Decoder(GraphedTraining, nn.Module):
         shifted = torch.cat([torch.full((B, 1), vmax * U, dtype=idx.dtype, device=dev), idx[:, :-1]], dim=1)
         return ops.EmbeddingFn.apply(table, shifted.reshape(-1))
 
+    def _check_source(self, source, name, length=None):
+        """The source of this decoder's kind: (B, n) integer merged codes, or (B, n, dz) floating-point latents for a
+        continuous decoder; n == length unless length is None.  ValueError otherwise."""
+        cont = self.continuous_source
+        want = (f'(batch, {length or "num_codes"}, {self.source_dim}) floating-point latents (continuous decoder)' if cont else
+                f'(batch, {length or "num_codes"}) merged codes')
+        ok = source.dim() == (3 if cont else 2) and source.is_floating_point() == cont and not source.is_complex()
+        ok = ok and (not cont or source.shape[2] == self.source_dim) and (length is None or source.shape[1] == length)
+        if not ok:
+            raise ValueError(f'{name}: {want} expected, got {tuple(source.shape)} {source.dtype}')
+
     def compute_loss(self, source, x):
-        """source (B, S) merged codes, x (B, events, channels) device int64 -> (loss, logits per voice, attentions)."""
-        B, S = source.shape
+        """source (B, S) merged codes [continuous decoder: (B, S, dz) latents], x (B, events, channels) device int64 ->
+        (loss, logits per voice, attentions)."""
+        self._check_source(source, 'source', self.num_tokens_source)
+        B, S = source.shape[:2]
         nc = self.num_channels
-        assert S == self.num_tokens_source and x.shape[1] * nc == self.num_tokens_target
-        src = ops.EmbeddingFn.apply(self.source_embeddings.weight, source.reshape(-1))      # (B * S, d)
+        assert x.shape[1] * nc == self.num_tokens_target
+        if self.continuous_source:                                                          # :327-336: no gradient into z
+            z = source.detach().to(torch.float32).reshape(-1, self.source_dim)
+            src = ops.linear(z, self.source_embeddings.weight, self.source_embeddings.bias)
+        else:
+            src = ops.EmbeddingFn.apply(self.source_embeddings.weight, source.reshape(-1))  # (B * S, d)
         tgt = self._target_rows(x)
         memory_mask = ops.MASK_NONE if self.cross_attention_type == 'diagonal' else mask_code(self.cross_attention_type)   # :487-488
         out, att_dec, att_enc = self.transformer.forward_rows(
@@ -267,14 +296,18 @@ class Decoder(GraphedTraining, nn.Module):
         return loss, [lg.reshape(B, E, -1) for lg in logits], att_dec, att_enc
 
     def forward(self, source, target):
-        """API-compatible `Decoder.forward` (:431-543): source (B, S) merged codes, target (B, events, channels)."""
+        """API-compatible `Decoder.forward` (:431-543): source (B, S) merged codes [continuous decoder: (B, S, dz) latents],
+        target (B, events, channels)."""
         target = self.data_processor.checked(self.data_processor.preprocess(target))
         loss, logits, att_dec, att_enc = self.compute_loss(source.to(target.device), target)
         return {'loss': loss, 'attentions_decoder': att_dec, 'attentions_encoder': att_enc,
                 'weights_per_category': logits, 'monitored_quantities': {'loss': loss.item()}}
 
     def encode(self, x):
-        """:327-336 + the merge the reference forgot: frozen encoder, inference only -> merged codes (B, S)."""
+        """:327-336 + the merge the reference forgot: frozen encoder, inference only -> merged codes (B, S); continuous
+        decoder: the encoder's latents (B, S, dz) float32."""
+        if self.continuous_source:
+            return self.encoder.encode_latents(x)
         return self.encoder.encode_indices(x, merged=True)
 
     def _step_compute(self, tensor_dict):
@@ -378,7 +411,8 @@ class Decoder(GraphedTraining, nn.Module):
 
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
                             use_graph=True):
-        """Samples target sequences from MERGED codes (B, S) (what `forward` takes): each row repeated `num_decodings` times
+        """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
+        latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
         temperature / top-k / top-p rule (utils.py:101-128) on the GPU.
         exclude_tokens: per voice, token ids never drawn (the meta symbols of exclude_meta_symbols); seed: an int (per-row
@@ -387,9 +421,7 @@ class Decoder(GraphedTraining, nn.Module):
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
-        codes = torch.as_tensor(codes).to(dev, torch.int64)
-        if codes.dim() != 2 or codes.shape[1] != self.num_tokens_source:
-            raise ValueError(f'codes: (batch, {self.num_tokens_source}) merged codes expected, got {tuple(codes.shape)}')
+        codes = self._source_on_device(codes, 'codes', self.num_tokens_source)
         if num_decodings > 1:
             codes = codes.repeat_interleave(num_decodings, dim=0)
         B, T, nc = codes.shape[0], self.num_tokens_target, self.num_channels
@@ -401,6 +433,11 @@ class Decoder(GraphedTraining, nn.Module):
             inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens)
             return inc.run(use_graph=use_graph)
         return generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
+
+    def _source_on_device(self, source, name, length=None):
+        source = torch.as_tensor(source)
+        self._check_source(source, name, length)
+        return source.to(self.sos.device, torch.float32 if self.continuous_source else torch.int64).contiguous()
 
     def _meta_symbol_ids(self):
         ds = getattr(self.dataloader_generator, 'dataset', None)
@@ -417,7 +454,8 @@ class Decoder(GraphedTraining, nn.Module):
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
         code_juxtaposition) as the reference writes them.  Returns {'original', 'generation', 'codes', 'recoding'} tensors
-        instead of music21 scores (no score writing here).  seed: as generate_from_codes."""
+        instead of music21 scores (no score writing here).  seed: as generate_from_codes.  A continuous decoder returns
+        the latents as 'codes', 'recoding' None and writes no file (:674-701)."""
         if plot_attentions:
             raise NotImplementedError('plot_attentions: attention plots need the full forward per token (matplotlib); '
                                       'not available on the incremental path')
@@ -444,9 +482,11 @@ class Decoder(GraphedTraining, nn.Module):
             codes = self.encode(x_original)
             x = self.generate_from_codes(codes, temperature=temperature, top_k=top_k, top_p=top_p, exclude_tokens=exclude,
                                          seed=seed)
-            recoding = self.encode(torch.cat([x_original_single, x], dim=0))
+            recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
             self.train(was_training)
+        if recoding is None:
+            return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': None}
         timestamp = datetime.now().strftime('%Y-%m-%d_%H-%M-%S')
         save_dir = f'{self.model_dir}/juxtapositions' if code_juxtaposition else f'{self.model_dir}/generations'
         os.makedirs(save_dir, exist_ok=True)
@@ -501,7 +541,8 @@ class Decoder(GraphedTraining, nn.Module):
     def generate_from_code_long(self, encoding_indices=None, temperature=None, top_k=0, top_p=1., exclude_meta_symbols=False,
                                 num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
                                 use_graph=True):
-        """:729-829: decodes MERGED codes (B, nb) of any length nb >= S by sliding the model window one code at a time
+        """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
+        the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
         full forward on the window per token; here the window's prefix is re-prefilled into the K/V caches when it moves
         and the tokens come from incremental steps (decoders/generation.py), which computes the same function.
@@ -519,10 +560,8 @@ class Decoder(GraphedTraining, nn.Module):
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
-        codes = torch.as_tensor(encoding_indices).to(dev, torch.int64)
+        codes = self._source_on_device(encoding_indices, 'encoding_indices')
         S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
-        if codes.dim() != 2:
-            raise ValueError(f'encoding_indices: (batch, num_codes) merged codes expected, got {tuple(codes.shape)}')
         nb = codes.shape[1]
         if nb < S:
             raise ValueError(f'encoding_indices: at least {S} codes (one model window) are needed, got {nb}')
@@ -547,13 +586,20 @@ class Decoder(GraphedTraining, nn.Module):
         return out.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
-        """:960-981: start_codes + body_codes + end_codes (lists of merged codes) decoded as one sequence, the body's
-        events returned: int64 (num_decodings, events, channels).  kwargs go to `generate_from_code_long`."""
+        """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent
+        tensors, concatenated along time) decoded as one sequence, the body's events returned: int64 (num_decodings, events,
+        channels).  kwargs go to `generate_from_code_long`."""
         if start_codes is None or end_codes is None or body_codes is None or temperature is None:
             raise NotImplementedError('generate_alla_mano(start_codes, end_codes, body_codes, temperature): generation '
                                       'without codes is not implemented')
-        start_codes, body_codes, end_codes = list(start_codes), list(body_codes), list(end_codes)
-        codes = torch.tensor(start_codes + body_codes + end_codes, dtype=torch.int64).unsqueeze(0)
+        if self.continuous_source:
+            parts = [torch.as_tensor(c, dtype=torch.float32).reshape(-1, self.source_dim).cpu()
+                     for c in (start_codes, body_codes, end_codes)]
+            start_codes, body_codes, end_codes = parts
+            codes = torch.cat(parts, dim=0).unsqueeze(0)
+        else:
+            start_codes, body_codes, end_codes = list(start_codes), list(body_codes), list(end_codes)
+            codes = torch.tensor(start_codes + body_codes + end_codes, dtype=torch.int64).unsqueeze(0)
         return self.generate_from_code_long(codes, temperature=temperature, num_decodings=num_decodings,
                                             code_index_start=len(start_codes),
                                             code_index_end=len(start_codes) + len(body_codes), **kwargs)
@@ -587,7 +633,8 @@ class Decoder(GraphedTraining, nn.Module):
         was_training = self.training
         self.eval()
         try:
-            codes = self.encode(chunks).reshape(1, -1)                                # glued: (1, chunks * S)
+            codes = self.encode(chunks)                                               # glued: (1, chunks * S [, dz])
+            codes = codes.reshape(1, -1, self.source_dim) if self.continuous_source else codes.reshape(1, -1)
         finally:
             self.train(was_training)
         U = self.total_upscaling

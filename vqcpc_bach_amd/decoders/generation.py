@@ -27,7 +27,13 @@ Diagonal decoder (cross_attention_type 'diagonal', TransformerAlignedDecoderLaye
 The prefill computes per layer C_l = cross_attn_l(memory) (n * S, nc * d) instead of the cross k | v; the step replaces its
 three cross launches (q projection, attention, out-projection + residual) by ONE vqcpc_decode_aligned_add, which adds the
 position's code-and-voice vector of C_l to the row (9 launches per layer + 2); the re-prefill expands C_l over the P prefix
-rows with vqcpc_aligned_expand.  Everything else -- one captured step, one captured slide -- is as above."""
+rows with vqcpc_aligned_expand.  Everything else -- one captured step, one captured slide -- is as above.
+
+Continuous decoder (`Decoder.continuous_source`, a NoQuantization encoder): the source is the latents (M, nb, dz) and
+`source_embeddings` a linear layer.  The first launch of `_encode_memory` is then vqcpc_decode_source_rows instead of the
+embedding gather: it reads the live window's S latents of every sequence from `z_full` through the device window index `win`
+(NULL in the fixed-window prefill), so the captured slide still serves every middle window; vqcpc_decode_window gets a dummy
+all-zero code tensor and keeps its token / seed / position bookkeeping.  Everything after `src` is shared."""
 import ctypes
 
 import torch
@@ -41,7 +47,7 @@ class IncrementalDecoder(IncrementalStack):
     """One generation of `batch` <= 64 rows of `decoder` (a Decoder in eval mode; the caller holds utils.STEP_LOCK).
 
         inc = IncrementalDecoder(dec, B)
-        inc.prefill(codes)                                        # (B, S) merged codes
+        inc.prefill(codes)                                        # (B, S) merged codes [continuous decoder: (B, S, dz) latents]
         tokens = inc.run(seeds, temperature, top_k, top_p)        # (B, T) int64, position-major (t = event * nc + voice)
 
     `start` + `step` expose the single steps (teacher forcing, the sampler's inputs `logits` and its optional
@@ -73,26 +79,42 @@ class IncrementalDecoder(IncrementalStack):
         self.tokens = torch.zeros(M, self.T, dtype=torch.int64, device=dev)
         self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
         self.memkv = None
+        self.continuous = bool(getattr(dec, 'continuous_source', False))
+        if self.continuous:
+            self.dz = dec.source_dim
+            self.src = torch.empty(M * self.S, d, **f32)                          # fixed address: a captured slide writes it
+            self.z_full, self.z_nb = None, 0
 
     # ---- prefill ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def prefill(self, codes):
         dec, M, d = self.dec, self.M, self.d
-        codes = codes.to(self.dev, torch.int64)
-        assert codes.shape == (M, self.S), (codes.shape, (M, self.S))
-        self._encode_memory(codes)
+        if self.continuous:
+            assert tuple(codes.shape) == (M, self.S, self.dz) and codes.is_floating_point(), (codes.shape, (M, self.S, self.dz))
+            self.z_full, self.z_nb = codes.to(self.dev, torch.float32).contiguous(), self.S
+            self._encode_memory(None)
+        else:
+            codes = codes.to(self.dev, torch.int64)
+            assert codes.shape == (M, self.S), (codes.shape, (M, self.S))
+            self._encode_memory(codes)
         self.table = dec._target_table(self.dev).contiguous()                          # (vmax * U + 1, d)
         self.head_w = torch.cat([m.weight for m in dec.pre_softmaxes], dim=0).contiguous()
         self.head_b = torch.cat([m.bias for m in dec.pre_softmaxes], dim=0).contiguous()
 
-    def _encode_memory(self, codes):
+    def _encode_memory(self, codes, windowed=False):
         """codes (M, S) -> memory -> every layer's cross k | v (diagonal decoder: its C = cross_attn(memory), (M * S, nc * d)),
-        written into buffers that keep their address (a captured step reads them)."""
+        written into buffers that keep their address (a captured step reads them).  Continuous decoder: `codes` is unused, the
+        source rows come from the S latents of `z_full` at the live window of `win` (windowed) or at 0."""
         dec, M, d = self.dec, self.M, self.d
         if self.memkv is None:
             width = self.nc * d if self.diagonal else 2 * d
             self.memkv = [torch.empty(M * self.S, width, dtype=torch.float32, device=self.dev) for _ in self.layers]
-        src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
+        if self.continuous:
+            lin, src = dec.source_embeddings, self.src
+            hip.call('vqcpc_decode_source_rows', self.z_full, self.z_nb, self.dz, self.win if windowed else None, lin.weight,
+                     lin.bias, src, d, M, self.S, d)
+        else:
+            src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
         memory, _ = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
         if self.diagonal:
             for lay, C in zip(self.layers, self.memkv):
@@ -173,9 +195,17 @@ class IncrementalDecoder(IncrementalStack):
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
     def start_long(self, codes_full, chorale, seeds=None, **sampling):
-        """codes_full (M, nb) merged codes, nb >= S; chorale (M, nb * U) int64 tokens, position-major (the initial PAD /
-        START sequence; generated tokens are written into it).  sampling: the keywords of `start`."""
+        """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
+        tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  sampling: the
+        keywords of `start`."""
         M, S, U = self.M, self.S, self.U
+        z_full = None
+        if self.continuous:
+            if codes_full.dim() != 3 or not codes_full.is_floating_point() or codes_full.shape[0] != M or \
+                    codes_full.shape[1] < S or codes_full.shape[2] != self.dz:
+                raise ValueError(f'codes_full: ({M}, nb >= {S}, {self.dz}) latents expected, got {tuple(codes_full.shape)}')
+            z_full = codes_full.to(self.dev, torch.float32).contiguous()
+            codes_full = torch.zeros(M, z_full.shape[1], dtype=torch.int64, device=self.dev)   # the window kernel's dummy codes
         codes_full = codes_full.to(self.dev, torch.int64).contiguous()
         if codes_full.dim() != 2 or codes_full.shape[0] != M or codes_full.shape[1] < S:
             raise ValueError(f'codes_full: ({M}, nb >= {S}) expected, got {tuple(codes_full.shape)}')
@@ -186,7 +216,9 @@ class IncrementalDecoder(IncrementalStack):
         self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
         self.prefix_rows.zero_()
         if self.memkv is None:
-            self.prefill(codes_full[:, :S])
+            self.prefill(z_full[:, :S] if self.continuous else codes_full[:, :S])
+        if self.continuous:
+            self.z_full, self.z_nb = z_full, nb
         self.start(seeds=seeds, **sampling)
         self.row_seeds.copy_(self.seeds)
 
@@ -219,7 +251,7 @@ class IncrementalDecoder(IncrementalStack):
         if not 0 <= P < self.T:
             raise ValueError(f'slide: 0 <= t_relative < {self.S} (got {t_relative})')
         self._window(P, advance)
-        self._encode_memory(self.codes_win)
+        self._encode_memory(self.codes_win, windowed=True)
         self.prefill_prefix(P)
 
     def commit(self):

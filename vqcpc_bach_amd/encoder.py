@@ -115,6 +115,23 @@ class Encoder(nn.Module):
         idx = idx.view(z.shape[0], z.shape[1], -1)
         return self.merge_codes(idx) if merged else idx
 
+    @torch.no_grad()
+    def encode_latents(self, x):
+        """The latents a decoder on continuous sources consumes (decoders/decoder.py:327-336 with a NoQuantization
+        quantizer): token tensor (batch, ticks, voices) -> z (batch, nb, D) float32, the downscaler's output; no quantizer, no
+        upscaler.  Inference only, in eval mode (the caller's train / eval state is put back)."""
+        was_training = self.training
+        self.eval()
+        try:
+            tpb = self.downscaler.sequence_length
+            t = self.data_processor.preprocess(x)
+            t = t if t.shape[-1] == tpb else t.reshape(t.shape[0], -1, tpb)
+            t = self.data_processor.checked(t)
+            z = self.downscaler.forward_tokens(t.unsqueeze(0), self.data_processor)[0]         # (batch, nb, D)
+        finally:
+            self.train(was_training)
+        return z.detach().to(torch.float32).contiguous()
+
     def quantizer_needs_init(self):
         """True while the codebooks still wait for their data-dependent initialisation (first training batch)."""
         return bool(getattr(self.quantizer, 'initialize', False))

@@ -209,6 +209,7 @@ SIGNATURES = {
                                           c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     'vqcpc_decode_window': (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_ptr,
                                     c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_decode_source_rows': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr]),
     'vqcpc_prior_sample': (c_int, [c_ptr, c_i64, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_int,
                                    c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     'vqcpc_prior_window': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr,
