@@ -127,7 +127,7 @@ def main():
         twin.train_step({k: v[lo:hi].cuda() for k, v in b.items()}, train=True)
     g = tr._graph
     graph_replays = g.replays if g is not None else 0
-    graph_two = bool(g is not None and g.finish_fn is not None)
+    graph_two = bool(g is not None and len(g.stages) == 2)
     graph_vs_eager = float((tr.flat.flat - twin.flat.flat).abs().max() / twin.flat.flat.abs().max())
     torch.cuda.synchronize()
     torch.save(dict(rank=rank, world=world, init_equal=init_equal, codebook_equal=codebook_equal, grad_worst=grad_worst,

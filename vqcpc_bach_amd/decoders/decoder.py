@@ -31,19 +31,17 @@ raises; the codes are merged with `Encoder.merge_codes` first, as `generate` (:6
 """
 import os
 from datetime import datetime
-from itertools import islice
 
 import numpy as np
 import torch
 from torch import nn
 
 from .. import ops
-from ..graphs import GraphedTraining
-from ..parallel import DataParallelContext, FlatParameters
+from ..training import FlatTraining
 from ..transformer.transformer_custom import (TransformerAlignedDecoderLayerCustom, TransformerCustom, TransformerDecoderCustom,
                                               TransformerDecoderLayerCustom, TransformerEncoderCustom,
                                               TransformerEncoderLayerCustom, mask_code)
-from ..utils import dict_pretty_print, flatten, SEEDS, STEP_LOCK
+from ..utils import flatten, STEP_LOCK
 
 
 class HeadsFn(torch.autograd.Function):
@@ -83,7 +81,7 @@ class HeadsFn(torch.autograd.Function):
         return (d_out, None, *d_params)
 
 
-class Decoder(GraphedTraining, nn.Module):
+class Decoder(FlatTraining, nn.Module):
     def __init__(self, model_dir, dataloader_generator, data_processor, encoder, transformer_type, encoder_attention_type,
                  cross_attention_type, d_model, num_encoder_layers, num_decoder_layers, n_head, dim_feedforward,
                  positional_embedding_size, num_channels_encoder, num_events_encoder, num_channels_decoder,
@@ -149,11 +147,7 @@ class Decoder(GraphedTraining, nn.Module):
             self.source_embeddings = nn.Embedding(codebook_size, self.d_model)
         self.pre_softmaxes = nn.ModuleList([nn.Linear(self.d_model, n) for n in self.num_tokens_per_channel])
         self.num_tokens_source = num_channels_encoder * num_events_encoder
-        self.optimizer = None
         self.scheduler = None
-        self.dp = None
-        self.is_main = True
-        self.global_step = 0
 
     def __repr__(self):
         names = dict(anticausal='AC', causal='C', full='F', diagonal='D')
@@ -179,56 +173,27 @@ class Decoder(GraphedTraining, nn.Module):
         return [self.data_processor, self.target_channel_embeddings, self.target_events_positioning_embeddings,
                 self.transformer, self.linear_target, self.sos, self.source_embeddings, self.pre_softmaxes]
 
-    @staticmethod
-    def lr_lambda(step):
-        """LambdaLR factor of init_optimizers (:237-249)."""
-        warmup, lo, hi = 10000, 0.1, 1.0
-        s1 = (hi - lo) / warmup
-        return max(min(lo + s1 * step, hi + (step - warmup) * (-s1 * 0.1)), lo)
-
     def init_optimizers(self, lr, schedule_lr, dp=None):
-        dev = self.sos.device
-        assert dev.type == 'cuda', 'call .to(device) first: the training step has no CPU path'
-        self.dp = dp if dp is not None else (self.dp or DataParallelContext(device=dev))
-        self.is_main = self.dp.rank == 0
-        SEEDS.set_rank(self.dp.rank)            # per-rank dropout masks, whatever the launcher seeded
-        self.flat = FlatParameters(self._trainable())
-        self.dp.broadcast_(self.flat.flat, src=0)
+        self._init_flat(self._trainable(), self.sos.device, dp)
         self.lr, self.schedule_lr = lr, schedule_lr
         self.optimizer = ops.FlatAdam(self.flat.flat, self.flat.flat_grad, lr=lr, max_norm=5.0)
         self.scheduler = self.lr_lambda if schedule_lr else None
         self.global_step = 0
-        st = getattr(self, '_resume_state', None)
-        if st is not None and st['m'].numel() == self.optimizer.m.numel():
-            self.optimizer.m.copy_(st['m'])
-            self.optimizer.v.copy_(st['v'])
-            self.optimizer.step_count = int(st['step'])
-            self.global_step = int(st['global_step'])
-            self.restore_dropout_stream(st.get('dropout_stream'))
-        self._resume_state = None
-
-    def current_lr(self):
-        return self.lr * (self.lr_lambda(self.global_step) if self.schedule_lr else 1.0)
+        self._apply_resume_state()
 
     # ---- checkpoints (:254-274): one file `decoder` holding the whole state_dict, encoder included -------------------
-    def _dir(self, early_stopped):
-        return f'{self.model_dir}/early_stopped' if early_stopped else f'{self.model_dir}/overfitted'
-
     def save(self, early_stopped):
         model_dir = self._dir(early_stopped)
         os.makedirs(model_dir, exist_ok=True)
         torch.save(self.state_dict(), f'{model_dir}/decoder')
-        if self.optimizer is not None:       # extension: the reference restarts Adam on every resume
-            torch.save(dict(m=self.optimizer.m, v=self.optimizer.v, step=self.optimizer.step_count,
-                            global_step=self.global_step, dropout_stream=self.dropout_stream_state()), f'{model_dir}/decoder_optimizer')
+        self._save_optimizer_state(f'{model_dir}/decoder_optimizer')
 
     def load(self, early_stopped, device):
         print(f'Loading models {self.__repr__()}')
         model_dir = self._dir(early_stopped)
         ml = torch.device(device)
         self.load_state_dict(torch.load(f'{model_dir}/decoder', map_location=ml))
-        opt = f'{model_dir}/decoder_optimizer'
-        self._resume_state = torch.load(opt, map_location=ml) if os.path.exists(opt) else None
+        self._load_optimizer_state(f'{model_dir}/decoder_optimizer', ml)
 
     def train(self, mode=True):
         super().train(mode)
@@ -313,26 +278,11 @@ class Decoder(GraphedTraining, nn.Module):
     def _step_compute(self, tensor_dict):
         x = self.data_processor.checked(self.data_processor.preprocess(tensor_dict['x']))
         codes = self.encode(tensor_dict['x'])
-        # (round 6: the decoder's forward products inside ops.forward_arithmetic -- f16x3 scale table + the weights' fp16 planes of this
-        # step; the frozen encoder above is inference and stays outside, on six products)
-        with torch.enable_grad(), ops.forward_arithmetic(self.flat):      # whatever the caller's ambient grad mode: this IS the training step
-            loss, _, _, _ = self.compute_loss(codes, x)
-        self.flat.zero_grad()
-        with ops.direct_weight_gradients(self.flat):
-            loss.backward()
-        return loss.detach()
-
-    def _step_apply(self, loss):
-        self.optimizer.step(lr=self.current_lr(), grad_scale=1.0 / self.dp.world_size)       # clip 5 + Adam (:345-346)
-        return loss
-
-    def _train_step_body(self, tensor_dict):
-        loss = self._step_compute(tensor_dict)
-        self._all_reduce_gradients()
-        return self._step_apply(loss)
-
-    def _graph_optimizers(self):
-        return [self.optimizer]
+        # (the frozen encoder above is inference and stays outside the step's forward arithmetic, on six products)
+        def forward():
+            loss = self.compute_loss(codes, x)[0]
+            return loss, loss.detach()
+        return self._forward_backward(forward)
 
     def train_step(self, tensor_dict, train=True):
         if not train:
@@ -341,68 +291,18 @@ class Decoder(GraphedTraining, nn.Module):
                 codes = self.encode(tensor_dict['x'])
                 with torch.no_grad():
                     return self.compute_loss(codes, x)[0].detach()
-        with SEEDS.stream_of(self):            # this trainer's own dropout-seed stream (utils.DropoutSeeds.stream_of)
-            out = self._graphed_step(tensor_dict, self._train_step_body, parts=(self._step_compute, self._step_apply))
-            if out is None:
-                out = self._train_step_body(tensor_dict)
-        self.global_step += 1
-        return out
+        return self._train_step(tensor_dict)
 
     def epoch(self, data_loader, train=True, num_batches=None):
         assert self.optimizer is not None, 'call init_optimizers(lr, schedule_lr) first'
-        self.train() if train else self.eval()
-        total = torch.zeros((), dtype=torch.float32, device=self.sos.device)
-        n = 0
-        for tensor_dict in islice(data_loader, num_batches):
-            total += self.train_step(tensor_dict, train=train)
-            n += 1
-        total /= max(n, 1)
-        if self.dp.distributed:
-            self.dp.all_reduce_sum_(total)
-            total /= self.dp.world_size
-        means = {'loss': float(total.item())}                    # the host sync of the epoch
-        self.data_processor.raise_if_bad_tokens(dp=self.dp)
-        self.encoder.data_processor.raise_if_bad_tokens(dp=self.dp)
-        if train:
-            self._report_scale_saturation(means)
-        return means
+        return self._scalar_loss_epoch(data_loader, train, num_batches, [self.data_processor, self.encoder.data_processor])
 
     def train_model(self, batch_size, num_batches, num_epochs, lr, schedule_lr, plot=False, num_workers=0, **kwargs):
-        from .. import hip, ops
-        mode_before, arith_before = hip.gemm_mode_state(), ops.gradient_arithmetic_state()
-        self.use_training_defaults()               # bf16x6 GEMMs + step-graph replay unless the caller chose otherwise
-        self.trained_gemm_mode = hip.get_gemm_mode()
-        try:
-            return self._train_epochs(batch_size, num_batches, num_epochs, lr, schedule_lr, num_workers)
-        finally:
-            hip.restore_gemm_mode_state(mode_before)      # process-wide settings: put back what the caller had (encoder.py)
-            ops.restore_gradient_arithmetic_state(arith_before)
-
-    def _train_epochs(self, batch_size, num_batches, num_epochs, lr, schedule_lr, num_workers):
-        best_val = 1e8
-        self.init_optimizers(lr=lr, schedule_lr=schedule_lr)
-        history = []
-        for epoch_id in range(num_epochs):
-            gen_train, gen_val, _ = self.dataloader_generator.dataloaders(batch_size=batch_size, num_workers=num_workers)
-            train = self.epoch(data_loader=gen_train, train=True, num_batches=num_batches)
-            del gen_train
-            val = self.epoch(data_loader=gen_val, train=False,
-                             num_batches=num_batches // 2 if num_batches is not None else None)
-            del gen_val
-            if self.is_main:
-                print(f'======= Epoch {epoch_id} =======')
-                print('---Train---')
-                dict_pretty_print(train, endstr=' ' * 5)
-                print()
-                print('---Val---')
-                dict_pretty_print(val, endstr=' ' * 5)
-                print('\n')
-                self.save(early_stopped=False)
-                if val['loss'] < best_val:
-                    self.save(early_stopped=True)
-                    best_val = val['loss']
-            history.append((train, val))
-        return history
+        with self._training_defaults():
+            self.init_optimizers(lr=lr, schedule_lr=schedule_lr)
+            return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss',
+                                      save_best=lambda: self.save(early_stopped=True),
+                                      save_every=lambda: self.save(early_stopped=False))
 
     # ---- generation (:552-726): KV-cached incremental decoding on the GPU, decoders/generation.py --------------------
     def init_generation(self, num_events):

@@ -5,7 +5,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .utils import dict_pretty_print, flatten
+from .training import FlatTraining, checkpoint_dir
+from .utils import flatten
 
 
 class Encoder(nn.Module):
@@ -21,7 +22,7 @@ class Encoder(nn.Module):
 
     # ---- checkpoints: one torch.save(state_dict) per sub-module, reference file names (encoder.py:47-74) --------
     def _dir(self, early_stopped):
-        return f'{self.model_dir}/early_stopped' if early_stopped else f'{self.model_dir}/overfitted'
+        return checkpoint_dir(self.model_dir, early_stopped)
 
     def save(self, early_stopped):
         model_dir = self._dir(early_stopped)
@@ -149,13 +150,26 @@ class Encoder(nn.Module):
     show_nn_clusters = scatterplot_clusters_3d = plot_clusters
 
 
-class EncoderTrainer(nn.Module):
-    """Epoch loop, checkpoints, logging (encoder.py:216-325)."""
+class EncoderTrainer(FlatTraining, nn.Module):
+    """Epoch loop, checkpoints, logging (encoder.py:216-325); the step protocol is training.FlatTraining's."""
 
     def __init__(self, dataloader_generator):
         super().__init__()
         self.dataloader_generator = dataloader_generator
         self.writer = None
+
+    def to(self, device):
+        for m in self._modules_with_params():
+            m.to(device)
+        return self
+
+    def train(self, mode=True):
+        for m in self._modules_with_params():
+            m.train(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
 
     def train_model(self, batch_size, num_batches, num_epochs, lr, corrupt_labels, schedule_lr, plot=False, num_workers=0,
                     **kwargs):
@@ -165,49 +179,13 @@ class EncoderTrainer(nn.Module):
                 self.writer = SummaryWriter(f'{self.model_dir}')
             except Exception:                  # tensorboard is optional (not installed in the ROCm image)
                 self.writer = None
-        best_val = 1e8
-        from . import hip
-        from . import ops
-        mode_before, arith_before = hip.gemm_mode_state(), ops.gradient_arithmetic_state()
-        if hasattr(self, 'use_training_defaults'):
-            self.use_training_defaults()           # bf16x6 GEMMs + step-graph replay unless the caller chose otherwise
-        self.trained_gemm_mode = hip.get_gemm_mode()        # what the epochs below run in (0 fp32 MFMA / 1 bf16x6 / 2 bf16)
-        try:
-            return self._train_epochs(batch_size, num_batches, num_epochs, lr, corrupt_labels, schedule_lr, plot, num_workers,
-                                      best_val)
-        finally:
-            # the GEMM arithmetic is a process-wide setting: a caller who chose nothing gets back what was there before
-            # (evaluation / generation code that runs after training sees the mode it would have seen without it)
-            hip.restore_gemm_mode_state(mode_before)
-            ops.restore_gradient_arithmetic_state(arith_before)
-
-    def _train_epochs(self, batch_size, num_batches, num_epochs, lr, corrupt_labels, schedule_lr, plot, num_workers, best_val):
-        self.init_optimizers(lr=lr, schedule_lr=schedule_lr)
-        history = []
-        for epoch_id in range(num_epochs):
-            gen_train, gen_val, _ = self.dataloader_generator.dataloaders(batch_size=batch_size, num_workers=num_workers)
-            train = self.epoch(data_loader=gen_train, train=True, num_batches=num_batches, corrupt_labels=corrupt_labels)
-            del gen_train
-            val = self.epoch(data_loader=gen_val, train=False,
-                             num_batches=num_batches // 2 if num_batches is not None else None,
-                             corrupt_labels=corrupt_labels)
-            del gen_val
-            if getattr(self, 'is_main', True):
-                print(f'======= Epoch {epoch_id} =======')
-                print('---Train---')
-                dict_pretty_print(train, endstr=' ' * 5)
-                print()
-                print('---Val---')
-                dict_pretty_print(val, endstr=' ' * 5)
-                print('\n')
-                self.save(early_stopped=False)
-                if val['loss_monitor'] < best_val:
-                    self.save(early_stopped=True)
-                    best_val = val['loss_monitor']
-                if plot and self.writer is not None:
-                    self.plot(epoch_id, train, val)
-            history.append((train, val))
-        return history
+        with self._training_defaults():
+            self.init_optimizers(lr=lr, schedule_lr=schedule_lr)
+            return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss_monitor',
+                                      save_best=lambda: self.save(early_stopped=True),
+                                      save_every=lambda: self.save(early_stopped=False),
+                                      after_epoch=self.plot if plot and self.writer is not None else None,
+                                      corrupt_labels=corrupt_labels)
 
     def plot(self, epoch_id, monitored_quantities_train, monitored_quantities_val, index_encoder=None):
         suffix = f'_{index_encoder})' if index_encoder is not None else ''

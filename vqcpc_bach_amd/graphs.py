@@ -45,27 +45,15 @@ def dp_graph_mode():
 
 
 class StepGraph:
-    def __init__(self, step_fn, optimizers, lr_fn, device, key_fn=None, seed_base=0x5EED5A17, between_fn=None,
-                 finish_fn=None, stages=None, betweens=None):
-        """step_fn(batch_dict) -> outputs (tensor / dict / tuple of tensors): one full training step on device tensors.
+    def __init__(self, stages, betweens, optimizers, lr_fn, device, key_fn=None, seed_base=0x5EED5A17):
+        """stages = [f0, f1, .., fk], one graph each: f0(batch_dict) -> outputs (tensor / dict / tuple of tensors),
+        fi(outputs) -> outputs; together one full training step on device tensors.  betweens = [b0, .., b(k-1)] run EAGERLY
+        between consecutive replays (the all-reduces of the gradient buckets); one stage and no betweens is the single-graph step.
         optimizers: the ops.FlatAdam objects the step uses; lr_fn() -> current learning rate (host float);
-        key_fn(batch) -> extra hashable that selects the graph (the student step's masked event index).
-        Two-graph form (multi-rank): step_fn records everything up to the gradients, `between_fn()` runs EAGERLY between the
-        two replays (the all-reduce of the gradient bucket), finish_fn(outputs of step_fn) -> outputs records the rest."""
-        self.step_fn, self.optimizers, self.lr_fn, self.key_fn = step_fn, list(optimizers), lr_fn, key_fn
-        self.between_fn, self.finish_fn = between_fn, finish_fn
-        assert (between_fn is None) == (finish_fn is None)
-        # General form: `stages` = [f0, f1, .., fk] (f0(batch) -> outputs, fi(outputs) -> outputs), one graph each, and
-        # `betweens` = [b0, .., b(k-1)] run EAGERLY between consecutive replays (bucketed all-reduces).  The two-graph form
-        # above is stages = [step_fn, finish_fn], betweens = [between_fn].
-        if stages is not None:
-            assert step_fn is None and between_fn is None and len(betweens) == len(stages) - 1 >= 1
-            self.step_fn, self.finish_fn, self.between_fn = stages[0], stages[-1], betweens[0]
-            self.stages, self.betweens = list(stages), list(betweens)
-        elif finish_fn is not None:
-            self.stages, self.betweens = [step_fn, finish_fn], [between_fn]
-        else:
-            self.stages, self.betweens = [step_fn], []
+        key_fn(batch) -> extra hashable that selects the graph (the student step's masked event index)."""
+        assert len(betweens) == len(stages) - 1
+        self.stages, self.betweens = list(stages), list(betweens)
+        self.optimizers, self.lr_fn, self.key_fn = list(optimizers), lr_fn, key_fn
         self.device = torch.device(device)
         self.seed_base = int(seed_base)
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)       # device step counter (uint64 bits)
@@ -132,7 +120,6 @@ class StepGraph:
         finally:
             for opt, c in zip(self.optimizers, counts):  # capture ran the Python side of optimizer.step(): undo its count
                 opt.step_count = c
-        graph2 = graphs[1] if len(graphs) > 1 else None
         entry = (tuple(graphs), static, out)
         self.graphs[self._signature(batch)] = entry
         return entry
@@ -168,8 +155,9 @@ class StepGraph:
 
 
 class GraphedTraining:
-    """Mixin of the trainers: `enable_step_graph()` makes `train_step(train=True)` replay a captured step after a few
-    eager steps (lazy initialisations -- codebook data init, kernel attributes, allocator -- happen there)."""
+    """The switches of step-graph replay and the dropout-seed stream of a trainer: `enable_step_graph()` makes a training step
+    replay a captured step after a few eager steps (lazy initialisations -- codebook data init, kernel attributes, allocator --
+    happen there).  training.FlatTraining, which owns the step, builds and replays the StepGraph (`_graphed_step`)."""
 
     graph_warmup_steps = 2
     _graph_on = False
@@ -189,31 +177,6 @@ class GraphedTraining:
         if not self._graph_explicit and os.environ.get('VQCPC_STEP_GRAPH', '1') != '0':
             self.enable_step_graph(True)
             self._graph_explicit = False
-
-    def _report_scale_saturation(self, means):
-        """End of a TRAINING epoch, every trainer (the host has just synchronised for the metric means): the f16x3 scale tables of
-        this trainer's flat parameters are asked whether a tensor outgrew the 16-32 x head-room of its previous-step scale (its
-        largest elements were clamped to 65504 / scale for that ONE step -- in a forward product that can move a loss or a code
-        assignment of that step; the next step already runs under the followed scale).  `means['f16x3_scale_saturations']` = the
-        number of (call site, operand) pairs it happened to during THIS epoch (0.0 in every run of this repository); when non-zero
-        the marked step indices are logged through `warnings` and kept in `self.scale_saturation_log`."""
-        from . import ops
-        flat = getattr(self, 'flat', None)
-        if flat is None or not getattr(flat, '_grad_scales', None):
-            return means
-        total = ops.scale_saturations(flat)
-        seen = getattr(self, '_scale_saturations_seen', 0)
-        means['f16x3_scale_saturations'] = float(total - seen)
-        if total > seen:
-            import warnings
-            rep = ops.scale_saturation_report(flat)
-            self.scale_saturation_log = rep
-            warnings.warn(f'f16x3 GEMM arithmetic: {total - seen} operand tensors outgrew the fp16 range under their previous-step scale '
-                          f'during this epoch (clamped for one step each; marked steps by scale table: '
-                          f'{ {k: v["step_indices"] for k, v in rep.items()} }); '
-                          'ops.set_gradient_arithmetic("six") / ops.set_forward_arithmetic("six") select the scale-free arithmetic')
-            self._scale_saturations_seen = total
-        return means
 
     def seed_dropout(self, base):
         """Re-seeds THIS trainer's dropout-seed stream (utils.DropoutSeeds.stream_of): the per-trainer counterpart of
@@ -236,53 +199,3 @@ class GraphedTraining:
             self._graph.release()
             self._graph = None
         return self
-
-    def _graph_optimizers(self):
-        raise NotImplementedError
-
-    def _graph_key(self, batch):
-        return None
-
-    def _all_reduce_gradients(self):
-        self.dp.all_reduce_sum_(self.flat.flat_grad)
-
-    def _dp_stages(self, parts):
-        """(stages, betweens) of the multi-rank step: by default [compute, apply] around ONE all-reduce of the flat gradient
-        bucket.  A trainer whose step has independent halves overrides this (student: bucketed all-reduces)."""
-        return [parts[0], parts[1]], [self._all_reduce_gradients]
-
-    def _new_step_graph(self, body, parts):
-        """parts = (compute, apply): the halves of `body` before / after the gradient all-reduce."""
-        dev = self.flat.flat.device
-        if self.dp.distributed and not (dp_graph_mode() == 'capture' and self.dp.backend == 'nccl'):
-            stages, betweens = self._dp_stages(parts)
-            return StepGraph(None, self._graph_optimizers(), self.current_lr, dev, key_fn=self._graph_key, stages=stages,
-                             betweens=betweens)
-        return StepGraph(body, self._graph_optimizers(), self.current_lr, dev, key_fn=self._graph_key)
-
-    def _graphed_step(self, batch, body, parts=None):
-        """Returns body's outputs from a graph replay, or None when this step has to run eagerly."""
-        if not self._graph_on:
-            return None
-        if self.dp.distributed and (parts is None or dp_graph_mode() == 'off'):
-            return None
-        if self._graph_eager_steps < self.graph_warmup_steps:
-            self._graph_eager_steps += 1
-            return None
-        if self._graph is None:
-            self._graph = self._new_step_graph(body, parts)
-        try:
-            return self._graph(batch)
-        except RuntimeError as e:
-            # a failed CAPTURE (e.g. a runtime that cannot record one of the step's calls) must not take the training run
-            # down: fall back to eager steps for good and say so once.  Errors of a replayed step are real errors.
-            if self._graph.replays > 0:
-                raise
-            import warnings
-            warnings.warn(f'step-graph capture failed ({str(e)[:200]}); continuing with eager steps')
-            torch.cuda.synchronize()
-            hip.clear_runtime_error()       # the failed capture's HIP error must not be reported by the next kernel launch check
-            self._graph_on = False
-            self._graph.release()
-            self._graph = None
-            return None

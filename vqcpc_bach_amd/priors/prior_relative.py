@@ -3,9 +3,9 @@ frozen encoder's merged codes.  It is what makes generation unconditional: sampl
 (`generate_codes`), hand it to `Decoder.generate_from_code_long`, get a chorale (`generate`).
 
 `__init__`, `forward`, `epoch`, `train_model`, `init_optimizers`, `save` / `load` keep the reference's names, argument
-meaning, state_dict keys (a reference state_dict loads with strict=True) and return contracts; the training step follows
-`decoders.decoder.Decoder` (GraphedTraining step graph, utils.STEP_LOCK, flat parameters + FlatAdam, data-parallel
-all-reduce through parallel.py, frozen encoder).
+meaning, state_dict keys (a reference state_dict loads with strict=True) and return contracts; the training step is
+`training.FlatTraining`'s, shared with the other three trainers (step graph, utils.STEP_LOCK, flat parameters + FlatAdam,
+data-parallel all-reduce through parallel.py); what is this class's own is the loss on the frozen encoder's codes.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so: `linear(embedding)` depends on the code only, so it is
 evaluated on the V table rows by ONE small GEMM; with the start-of-sentence row appended, the reference's shift-by-one
@@ -29,22 +29,20 @@ for the prior what the reference makes it mean and goes to the decoder unchanged
 The reference ships no prior configuration; `configs.make_prior_config()` is this package's own.
 """
 import os
-from itertools import islice
 
 import torch
 from torch import nn
 
 from .. import ops
 from ..decoders.decoder import HeadsFn
-from ..graphs import GraphedTraining
-from ..parallel import DataParallelContext, FlatParameters
+from ..training import FlatTraining
 from ..transformer.transformer_custom import TransformerEncoderCustom, TransformerEncoderLayerCustom
-from ..utils import dict_pretty_print, SEEDS, STEP_LOCK
+from ..utils import STEP_LOCK
 
 MAX_SAMPLED_VOCAB = 4096         # vqcpc_prior_sample: codes per step of `generate_codes`
 
 
-class PriorRelative(GraphedTraining, nn.Module):
+class PriorRelative(FlatTraining, nn.Module):
     def __init__(self, model_dir, dataloader_generator, encoder, d_model, num_layers, n_head, dim_feedforward, embedding_size,
                  num_channels, num_events, dropout):
         super().__init__()
@@ -69,10 +67,6 @@ class PriorRelative(GraphedTraining, nn.Module):
         self.linear = nn.Linear(embedding_size, self.d_model)
         self.sos = nn.Parameter(torch.randn((1, 1, self.d_model)))
         self.pre_softmaxes = nn.ModuleList([nn.Linear(self.d_model, n) for n in self.num_tokens_per_channel])
-        self.optimizer = None
-        self.dp = None
-        self.is_main = True
-        self.global_step = 0
         self.lr = 1e-3
 
     def __repr__(self):
@@ -88,24 +82,11 @@ class PriorRelative(GraphedTraining, nn.Module):
         return [self.transformer, self.embedding, self.linear, self.sos, self.pre_softmaxes]
 
     def init_optimizers(self, lr=1e-3, dp=None):
-        dev = self.sos.device
-        assert dev.type == 'cuda', 'call .to(device) first: the training step has no CPU path'
-        self.dp = dp if dp is not None else (self.dp or DataParallelContext(device=dev))
-        self.is_main = self.dp.rank == 0
-        SEEDS.set_rank(self.dp.rank)            # per-rank dropout masks, whatever the launcher seeded
-        self.flat = FlatParameters(self._trainable())
-        self.dp.broadcast_(self.flat.flat, src=0)
+        self._init_flat(self._trainable(), self.sos.device, dp)
         self.lr = lr
         self.optimizer = ops.FlatAdam(self.flat.flat, self.flat.flat_grad, lr=lr, max_norm=5.0)
         self.global_step = 0
-        st = getattr(self, '_resume_state', None)
-        if st is not None and st['m'].numel() == self.optimizer.m.numel():
-            self.optimizer.m.copy_(st['m'])
-            self.optimizer.v.copy_(st['v'])
-            self.optimizer.step_count = int(st['step'])
-            self.global_step = int(st['global_step'])
-            self.restore_dropout_stream(st.get('dropout_stream'))
-        self._resume_state = None
+        self._apply_resume_state()
 
     def current_lr(self):
         return self.lr
@@ -114,17 +95,13 @@ class PriorRelative(GraphedTraining, nn.Module):
     def save(self):
         os.makedirs(self.model_dir, exist_ok=True)
         torch.save(self.state_dict(), f'{self.model_dir}/prior')
-        if self.optimizer is not None:       # extension: the reference restarts Adam on every resume
-            torch.save(dict(m=self.optimizer.m, v=self.optimizer.v, step=self.optimizer.step_count,
-                            global_step=self.global_step, dropout_stream=self.dropout_stream_state()),
-                       f'{self.model_dir}/prior_optimizer')
+        self._save_optimizer_state(f'{self.model_dir}/prior_optimizer')
 
     def load(self, device):
         print(f'Loading models {self.__repr__()}')
         ml = torch.device(device)
         self.load_state_dict(torch.load(f'{self.model_dir}/prior', map_location=ml))
-        opt = f'{self.model_dir}/prior_optimizer'
-        self._resume_state = torch.load(opt, map_location=ml) if os.path.exists(opt) else None
+        self._load_optimizer_state(f'{self.model_dir}/prior_optimizer', ml)
 
     def train(self, mode=True):
         super().train(mode)
@@ -169,24 +146,11 @@ class PriorRelative(GraphedTraining, nn.Module):
 
     def _step_compute(self, tensor_dict):
         codes = self.encode(tensor_dict['x'])
-        with torch.enable_grad(), ops.forward_arithmetic(self.flat):      # whatever the caller's ambient grad mode
-            loss, _ = self.compute_loss(codes)
-        self.flat.zero_grad()
-        with ops.direct_weight_gradients(self.flat):
-            loss.backward()
-        return loss.detach()
 
-    def _step_apply(self, loss):
-        self.optimizer.step(lr=self.current_lr(), grad_scale=1.0 / self.dp.world_size)       # clip 5 + Adam
-        return loss
-
-    def _train_step_body(self, tensor_dict):
-        loss = self._step_compute(tensor_dict)
-        self._all_reduce_gradients()
-        return self._step_apply(loss)
-
-    def _graph_optimizers(self):
-        return [self.optimizer]
+        def forward():
+            loss = self.compute_loss(codes)[0]
+            return loss, loss.detach()
+        return self._forward_backward(forward)
 
     def train_step(self, tensor_dict, train=True):
         if not train:
@@ -194,66 +158,16 @@ class PriorRelative(GraphedTraining, nn.Module):
                 codes = self.encode(tensor_dict['x'])
                 with torch.no_grad():
                     return self.compute_loss(codes)[0].detach()
-        with SEEDS.stream_of(self):            # this trainer's own dropout-seed stream (utils.DropoutSeeds.stream_of)
-            out = self._graphed_step(tensor_dict, self._train_step_body, parts=(self._step_compute, self._step_apply))
-            if out is None:
-                out = self._train_step_body(tensor_dict)
-        self.global_step += 1
-        return out
+        return self._train_step(tensor_dict)
 
     def epoch(self, data_loader, train=True, num_batches=None):
         assert self.optimizer is not None, 'call init_optimizers(lr) first'
-        self.train() if train else self.eval()
-        total = torch.zeros((), dtype=torch.float32, device=self.sos.device)
-        n = 0
-        for tensor_dict in islice(data_loader, num_batches):
-            total += self.train_step(tensor_dict, train=train)
-            n += 1
-        total /= max(n, 1)
-        if self.dp.distributed:
-            self.dp.all_reduce_sum_(total)
-            total /= self.dp.world_size
-        means = {'loss': float(total.item())}                    # the host sync of the epoch
-        self.encoder.data_processor.raise_if_bad_tokens(dp=self.dp)
-        if train:
-            self._report_scale_saturation(means)
-        return means
+        return self._scalar_loss_epoch(data_loader, train, num_batches, [self.encoder.data_processor])
 
     def train_model(self, batch_size, num_batches=None, num_epochs=10, lr=1e-3, plot=False, num_workers=0, **kwargs):
-        from .. import hip
-        mode_before, arith_before = hip.gemm_mode_state(), ops.gradient_arithmetic_state()
-        self.use_training_defaults()               # bf16x6 GEMMs + step-graph replay unless the caller chose otherwise
-        self.trained_gemm_mode = hip.get_gemm_mode()
-        try:
-            return self._train_epochs(batch_size, num_batches, num_epochs, lr, num_workers)
-        finally:
-            hip.restore_gemm_mode_state(mode_before)      # process-wide settings: put back what the caller had
-            ops.restore_gradient_arithmetic_state(arith_before)
-
-    def _train_epochs(self, batch_size, num_batches, num_epochs, lr, num_workers):
-        best_val = 1e8
-        self.init_optimizers(lr=lr)
-        history = []
-        for epoch_id in range(num_epochs):
-            gen_train, gen_val, _ = self.dataloader_generator.dataloaders(batch_size=batch_size, num_workers=num_workers)
-            train = self.epoch(data_loader=gen_train, train=True, num_batches=num_batches)
-            del gen_train
-            val = self.epoch(data_loader=gen_val, train=False,
-                             num_batches=num_batches // 2 if num_batches is not None else None)
-            del gen_val
-            if self.is_main:
-                print(f'======= Epoch {epoch_id} =======')
-                print('---Train---')
-                dict_pretty_print(train, endstr=' ' * 5)
-                print()
-                print('---Val---')
-                dict_pretty_print(val, endstr=' ' * 5)
-                print('\n')
-                if val['loss'] < best_val:                 # :292-294
-                    self.save()
-                    best_val = val['loss']
-            history.append((train, val))
-        return history
+        with self._training_defaults():
+            self.init_optimizers(lr=lr)
+            return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss', save_best=self.save)     # :292-294
 
     # ---- generation (:308-368): KV-cached sampling on the GPU, priors/generation.py -----------------------------------
     def generate_codes(self, num_tokens, temperature=1.0, num_generated_codes=1, top_k=0, top_p=1.0, seed=None, use_graph=True,

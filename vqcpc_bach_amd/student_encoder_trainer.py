@@ -23,13 +23,10 @@ import torch
 
 from . import ops
 from .encoder import EncoderTrainer
-from .graphs import GraphedTraining
-from .utils import SEEDS, STEP_LOCK
-from .parallel import DataParallelContext, FlatParameters
-from .vqcpc_encoder_trainer import VQCPCEncoderTrainer
+from .utils import STEP_LOCK
 
 
-class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
+class StudentEncoderTrainer(EncoderTrainer):
     def __init__(self, model_dir, dataloader_generator, encoder, num_events_masked, teacher, auxiliary_decoder,
                  quantization_weighting, num_gpus=1):
         super().__init__(dataloader_generator=dataloader_generator)
@@ -53,26 +50,13 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         self.optimizer_teacher = None
         self.scheduler_enc_dec = None
         self.scheduler_teacher = None
-        self.schedule_lr = False
-        self.flat = None
-        self.dp = None
-        self.lr = None
-        self.global_step = 0
 
     # ---- optimiser (:49-76) --------------------------------------------------------------------------------------
     def _modules_with_params(self):
         return [self.teacher, self.auxiliary_decoder, self.encoder]
 
-    lr_lambda = staticmethod(VQCPCEncoderTrainer.lr_lambda)
-
     def init_optimizers(self, lr, schedule_lr, dp=None):
-        dev = next(self.encoder.parameters()).device
-        assert dev.type == 'cuda', 'call .to(device) first: the training step has no CPU path'
-        self.dp = dp if dp is not None else (self.dp or DataParallelContext(device=dev))
-        self.is_main = self.dp.rank == 0
-        SEEDS.set_rank(self.dp.rank)            # per-rank dropout masks, whatever the launcher seeded
-        self.flat = FlatParameters(self._modules_with_params())
-        self.dp.broadcast_(self.flat.flat, src=0)
+        self._init_flat(self._modules_with_params(), next(self.encoder.parameters()).device, dp)
         if self.dp.distributed:
             self.encoder.quantizer.init_broadcast = lambda tensors: [self.dp.broadcast_(t.data, 0) for t in tensors]
         self.lr, self.schedule_lr = lr, schedule_lr
@@ -85,42 +69,16 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         self.optimizer_enc_dec = (adam(self.auxiliary_decoder), adam(self.encoder))
         self.scheduler_enc_dec = self.scheduler_teacher = self.lr_lambda if schedule_lr else None
         self.global_step = 0
-        st = getattr(self, '_resume_state', None)      # extension: Adam moments + schedule position survive a resume
-        if st is not None and st['m'].numel() == self.flat.numel:
-            for opt in (self.optimizer_teacher,) + self.optimizer_enc_dec:
-                opt.step_count = int(st['step'])
-            m, v = st['m'].to(dev), st['v'].to(dev)
-            for opt, mod in zip((self.optimizer_teacher,) + self.optimizer_enc_dec, self._modules_with_params()):
-                a, b = self.flat.range_of(mod)
-                opt.m.copy_(m[a:b])
-                opt.v.copy_(v[a:b])
-            self.global_step = int(st['global_step'])
-            self.restore_dropout_stream(st.get('dropout_stream'))
-            self._resume_state = None
-
-    def current_lr(self):
-        return self.lr * (self.lr_lambda(self.global_step) if self.schedule_lr else 1.0)
-
-    def to(self, device):
-        for m in self._modules_with_params():
-            m.to(device)
-        return self
+        self._apply_resume_state()      # extension: Adam moments + schedule position survive a resume
 
     # ---- checkpoints (:85-107): encoder files + `decoder` + `teacher` -------------------------------------------------
-    def _dir(self, early_stopped):
-        return f'{self.model_dir}/early_stopped' if early_stopped else f'{self.model_dir}/overfitted'
-
     def save(self, early_stopped):
         model_dir = self._dir(early_stopped)
         os.makedirs(model_dir, exist_ok=True)
         self.encoder.save(early_stopped=early_stopped)
         torch.save(self.auxiliary_decoder.state_dict(), f'{model_dir}/decoder')
         torch.save(self.teacher.state_dict(), f'{model_dir}/teacher')
-        if self.optimizer_teacher is not None:      # extension: the reference drops optimiser state on resume
-            opts = (self.optimizer_teacher,) + self.optimizer_enc_dec
-            torch.save(dict(m=torch.cat([o.m for o in opts]), v=torch.cat([o.v for o in opts]),
-                            step=self.optimizer_teacher.step_count, global_step=self.global_step, dropout_stream=self.dropout_stream_state()),
-                       f'{model_dir}/optimizer')
+        self._save_optimizer_state(f'{model_dir}/optimizer')
 
     def load(self, early_stopped, device):
         print(f'Loading models {self.__repr__()}')
@@ -130,16 +88,7 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         self.encoder.load(early_stopped=early_stopped, device=device)
         self.auxiliary_decoder.load_state_dict(torch.load(f'{model_dir}/decoder', map_location=ml))
         self.teacher.load_state_dict(torch.load(f'{model_dir}/teacher', map_location=ml))
-        opt = f'{model_dir}/optimizer'
-        self._resume_state = torch.load(opt, map_location=ml) if os.path.exists(opt) else None
-
-    def train(self, mode=True):
-        for m in self._modules_with_params():
-            m.train(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+        self._load_optimizer_state(f'{model_dir}/optimizer', ml)
 
     # ---- masking (:144-184) --------------------------------------------------------------------------------------
     def draw_masked_event(self, num_events):
@@ -226,21 +175,12 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
 
     def _step_compute(self, tensor_dict, masked_event_index=None):
         m = self._graph_m if masked_event_index is None else masked_event_index
-        # (round 6: the forward products of the step inside ops.forward_arithmetic, as in the CPC trainer -- their f16x3 scale table
-        # and the weights' fp16 planes for this step; the masked event index selects rows, not shapes: one table serves every index)
-        with torch.enable_grad(), ops.forward_arithmetic(self.flat):      # whatever the caller's ambient grad mode: this IS the training step
-            loss_teacher, loss_encdec, out = self.compute_losses(tensor_dict, m)
-        self.flat.zero_grad()
-        with ops.direct_weight_gradients(self.flat):
-            (loss_teacher + loss_encdec).backward()          # disjoint graphs: the teacher logits are detached
-        return out
 
-    def _step_apply(self, out):
-        lr, scale = self.current_lr(), 1.0 / self.dp.world_size
-        self.optimizer_teacher.step(lr=lr, grad_scale=scale)
-        for opt in self.optimizer_enc_dec:
-            opt.step(lr=lr, grad_scale=scale)
-        return out
+        # (the masked event index selects rows, not shapes: one f16x3 scale table of the forward scope serves every index)
+        def forward():
+            loss_teacher, loss_encdec, out = self.compute_losses(tensor_dict, m)
+            return loss_teacher + loss_encdec, out           # disjoint graphs: the teacher logits are detached
+        return self._forward_backward(forward)
 
     def _train_step_body(self, tensor_dict, masked_event_index=None):
         if self._dp_bucketed():
@@ -253,9 +193,7 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
                 raise
             self._all_reduce_encdec_and_join()
             return self._step_apply(out)
-        out = self._step_compute(tensor_dict, masked_event_index)
-        self._all_reduce_gradients()
-        return self._step_apply(out)
+        return super()._train_step_body(tensor_dict, masked_event_index)
 
     # ---- bucketed data-parallel step (bucketed + overlapped all-reduce) ---------------------------
     # The flat gradient of this step is 327 MB at C3 (82 M parameters): one blocking all-reduce of it behind the backward
@@ -281,23 +219,22 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         m = self._graph_m if masked_event_index is None else masked_event_index
         x = self.teacher.data_processor.checked(self.teacher.data_processor.preprocess(tensor_dict['x']))
         m = self.draw_masked_event(x.shape[1]) if m is None else int(m)
-        self.flat.zero_grad()
-        with torch.enable_grad(), ops.forward_arithmetic(self.flat, tag='teacher'):
+
+        def forward():
             t = self.forward_teacher(x, m)
-        with ops.direct_weight_gradients(self.flat, tag='teacher'):       # own f16x3 scale table: two backward passes per step
-            t['loss'].backward()
-        return dict(x=x, m=m, teacher_logits=[lg.detach() for lg in t['weights_per_category']],
-                    monitored=dict(t['monitored_quantities']))
+            return t['loss'], dict(x=x, m=m, teacher_logits=[lg.detach() for lg in t['weights_per_category']],
+                                   monitored=dict(t['monitored_quantities']))
+        self.flat.zero_grad()                  # of the whole bucket, here: the other half's backward adds to it after this one
+        return self._forward_backward(forward, tag='teacher', zero_grad=False)    # own f16x3 scale table: two backward passes per step
 
     def _step_compute_encdec(self, st):
-        with torch.enable_grad(), ops.forward_arithmetic(self.flat, tag='encdec'):
+        def forward():
             e = self._encdec_losses(*self._encode_decode(st['x'], st['m']), st['teacher_logits'])
-        with ops.direct_weight_gradients(self.flat, tag='encdec'):
-            e['loss'].backward()
-        out = dict(st['monitored'], **e['monitored_quantities'])
-        out.update(masked_event_index=st['m'], encoding_indices=e['encoding_indices'], teacher_logits=st['teacher_logits'],
-                   student_logits=[lg.detach() for lg in e['weights_per_category']])
-        return out
+            out = dict(st['monitored'], **e['monitored_quantities'])
+            out.update(masked_event_index=st['m'], encoding_indices=e['encoding_indices'], teacher_logits=st['teacher_logits'],
+                       student_logits=[lg.detach() for lg in e['weights_per_category']])
+            return e['loss'], out
+        return self._forward_backward(forward, tag='encdec', zero_grad=False)
 
     def _all_reduce_teacher_async(self):
         import torch.distributed as dist
@@ -321,16 +258,16 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         if work is not None:
             work.wait()                       # the current stream waits for the collective (no host block with RCCL)
 
-    def _dp_stages(self, parts):
+    def _dp_stages(self):
         if self._dp_bucketed():
             return ([self._step_compute_teacher, self._step_compute_encdec, self._step_apply],
                     [self._all_reduce_teacher_async, self._all_reduce_encdec_and_join])
-        return super()._dp_stages(parts)
+        return super()._dp_stages()
 
     _graph_m = None
 
     def _graph_optimizers(self):
-        return [self.optimizer_teacher] + list(self.optimizer_enc_dec)
+        return [self.optimizer_teacher, *(self.optimizer_enc_dec or ())]
 
     def _graph_key(self, batch):
         return self._graph_m           # one captured step per masked event index (it selects rows by host-side slicing)
@@ -340,7 +277,7 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         pool), so that no capture happens later inside a training loop.  Call after the warm-up steps."""
         assert self._graph_on and not self.encoder.quantizer_needs_init()
         if self._graph is None:
-            self._graph = self._new_step_graph(self._train_step_body, (self._step_compute, self._step_apply))
+            self._graph = self._new_step_graph()
         self._graph_eager_steps = self.graph_warmup_steps
         for m in range(tensor_dict['x'].shape[1]):
             self._graph_m = m
@@ -355,14 +292,7 @@ class StudentEncoderTrainer(GraphedTraining, EncoderTrainer):
         # the masked event is drawn on the host exactly as the reference does (student_encoder_trainer.py:159-160)
         x = tensor_dict['x']
         self._graph_m = self.draw_masked_event(x.shape[1]) if masked_event_index is None else int(masked_event_index)
-        out = None
-        with SEEDS.stream_of(self):            # this trainer's own dropout-seed stream (utils.DropoutSeeds.stream_of)
-            if not self.encoder.quantizer_needs_init():
-                out = self._graphed_step(tensor_dict, self._train_step_body, parts=(self._step_compute, self._step_apply))
-            if out is None:
-                out = self._train_step_body(tensor_dict, self._graph_m)
-        self.global_step += 1
-        return out
+        return self._train_step(tensor_dict, self._graph_m, eager=self.encoder.quantizer_needs_init())
 
     KEYS = ('loss_teacher', 'loss_quantization', 'loss_reconstruction', 'loss_encdec', 'loss_monitor')
 

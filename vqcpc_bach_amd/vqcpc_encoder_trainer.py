@@ -16,13 +16,11 @@ import torch
 
 from . import hip, ops, vqcpc_helper
 from .encoder import EncoderTrainer
-from .graphs import GraphedTraining
-from .utils import SEEDS, STEP_LOCK
-from .parallel import DataParallelContext, FlatParameters
+from .utils import STEP_LOCK
 from .vqcpc_helper import cpc_scores_and_loss
 
 
-class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
+class VQCPCEncoderTrainer(EncoderTrainer):
     def __init__(self, model_dir, dataloader_generator, encoder, c_net_kwargs, quantization_weighting):
         super().__init__(dataloader_generator=dataloader_generator)
         self.model_dir = model_dir
@@ -51,13 +49,7 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
         else:
             self.c_module_back = None
         self.quantization_weighting = quantization_weighting
-        self.optimizer = None
         self.scheduler = None
-        self.schedule_lr = False
-        self.flat = None
-        self.dp = None
-        self.lr = None
-        self.global_step = 0
 
     @property
     def _ema(self):
@@ -72,22 +64,8 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
             mods += [self.fks_module_back, self.c_module_back]
         return mods
 
-    @staticmethod
-    def lr_lambda(step):
-        """init_optimizers' LambdaLR factor (:96-107): linear warm-up 0.1 -> 1 over 10 000 steps, then a 10x slower
-        linear decay, floored at 0.1."""
-        warmup, lo, hi = 10000, 0.1, 1.0
-        s1 = (hi - lo) / warmup
-        return max(min(lo + s1 * step, hi + (step - warmup) * (-s1 * 0.1)), lo)
-
     def init_optimizers(self, lr, schedule_lr, dp=None):
-        dev = next(self.encoder.parameters()).device
-        assert dev.type == 'cuda', 'call .to(device) first: the training step has no CPU path'
-        self.dp = dp if dp is not None else (self.dp or DataParallelContext(device=dev))
-        self.is_main = self.dp.rank == 0
-        SEEDS.set_rank(self.dp.rank)            # per-rank dropout masks, whatever the launcher seeded
-        self.flat = FlatParameters(self._modules_with_params())
-        self.dp.broadcast_(self.flat.flat, src=0)                       # identical replicas
+        self._init_flat(self._modules_with_params(), next(self.encoder.parameters()).device, dp)
         if self.dp.distributed:
             self.encoder.quantizer.init_broadcast = lambda tensors: [self.dp.broadcast_(t.data, 0) for t in tensors]
         # EMA codebooks are buffers, not parameters: outside the flat buffer, so rank 0's go to every rank on their own
@@ -100,34 +78,7 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
         self.global_step = 0
         self._apply_resume_state()
 
-    def _apply_resume_state(self):
-        """Extension over the reference (which restarts Adam and the LR schedule on every resume):
-        `save` writes `optimizer`; `load` stashes it; it is applied here once the flat buffers exist."""
-        st = getattr(self, '_resume_state', None)
-        if st is None:
-            return
-        if st['m'].numel() != self.optimizer.m.numel():
-            print('optimizer state ignored: parameter count differs from the checkpoint')
-            return
-        self.optimizer.m.copy_(st['m'])
-        self.optimizer.v.copy_(st['v'])
-        self.optimizer.step_count = int(st['step'])
-        self.global_step = int(st['global_step'])
-        self.restore_dropout_stream(st.get('dropout_stream'))
-        self._resume_state = None
-
-    def current_lr(self):
-        return self.lr * (self.lr_lambda(self.global_step) if self.schedule_lr else 1.0)
-
-    def to(self, device):
-        for m in self._modules_with_params():
-            m.to(device)
-        return self
-
     # ---- checkpoints (:117-151) ----------------------------------------------------------------------------------
-    def _dir(self, early_stopped):
-        return f'{self.model_dir}/early_stopped' if early_stopped else f'{self.model_dir}/overfitted'
-
     def save(self, early_stopped):
         model_dir = self._dir(early_stopped)
         os.makedirs(model_dir, exist_ok=True)
@@ -137,10 +88,7 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
         if self.c_module_back is not None:
             torch.save(self.c_module_back.state_dict(), f'{model_dir}/c_module_back')
             torch.save(self.fks_module_back.state_dict(), f'{model_dir}/fks_module_back')
-        if self.optimizer is not None:       # extension: the reference drops optimiser state on resume
-            torch.save(dict(m=self.optimizer.m, v=self.optimizer.v, step=self.optimizer.step_count,
-                            global_step=self.global_step, dropout_stream=self.dropout_stream_state()),
-                       f'{model_dir}/optimizer')
+        self._save_optimizer_state(f'{model_dir}/optimizer')
 
     def load(self, early_stopped, device):
         print(f'Loading models {self.__repr__()}')
@@ -154,16 +102,7 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
         if self.c_module_back is not None:
             self.c_module_back.load_state_dict(torch.load(f'{model_dir}/c_module_back', map_location=ml))
             self.fks_module_back.load_state_dict(torch.load(f'{model_dir}/fks_module_back', map_location=ml))
-        opt = f'{model_dir}/optimizer'
-        self._resume_state = torch.load(opt, map_location=ml) if os.path.exists(opt) else None
-
-    def train(self, mode=True):
-        for m in self._modules_with_params():
-            m.train(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+        self._load_optimizer_state(f'{model_dir}/optimizer', ml)
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def compute_losses(self, tensor_dict, corrupt_labels=False):
@@ -238,35 +177,22 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
 
     def _step_compute(self, tensor_dict, corrupt_labels=False):
         """zero_grad / forward / backward (:310-312) + the step's metric vector: everything before the gradient all-reduce."""
-        with torch.enable_grad(), ops.forward_arithmetic(self.flat):     # whatever the caller's ambient grad mode: this IS the training step
-            loss, out = self.compute_losses(tensor_dict, corrupt_labels)
-        self.flat.zero_grad()
-        with ops.direct_weight_gradients(self.flat):
-            loss.backward()
+        out = self._forward_backward(lambda: self.compute_losses(tensor_dict, corrupt_labels))
         out['metrics'] = self._step_metrics(out)
         return out
 
     def _step_apply(self, out):
-        """clip + Adam (:313-316) on the (all-reduced) flat gradient; the rank sum becomes a mean inside the kernels."""
-        self.optimizer.step(lr=self.current_lr(), grad_scale=1.0 / self.dp.world_size)
+        """clip + Adam (:313-316), then the EMA codebooks' update."""
+        super()._step_apply(out)
         if self._ema is not None:
             self._ema.apply_update()          # EMA codebooks: counts and sums of the step (summed over ranks, not averaged)
         return out
 
     def _all_reduce_gradients(self):
         """The flat gradient bucket and, with EMA codebooks, the step's per-code counts and sums next to it."""
-        self.dp.all_reduce_sum_(self.flat.flat_grad)
+        super()._all_reduce_gradients()
         if self._ema is not None:
             self.dp.all_reduce_sum_(self._ema.stats)
-
-    def _train_step_body(self, tensor_dict, corrupt_labels=False):
-        """Everything a step enqueues on the device: compute, ONE all-reduce of the gradient bucket, apply."""
-        out = self._step_compute(tensor_dict, corrupt_labels)
-        self._all_reduce_gradients()
-        return self._step_apply(out)
-
-    def _graph_optimizers(self):
-        return [self.optimizer]
 
     def train_step(self, tensor_dict, train=True, corrupt_labels=False):
         """One iteration.  Returns device-side metrics.  With `enable_step_graph()` a training step is a HIP-graph replay
@@ -276,14 +202,8 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
                 out = self.compute_losses(tensor_dict, corrupt_labels)[1]
                 out['metrics'] = self._step_metrics(out)
                 return out
-        out = None
-        with SEEDS.stream_of(self):            # this trainer's own dropout-seed stream (utils.DropoutSeeds.stream_of)
-            if not corrupt_labels and not self.encoder.quantizer_needs_init():
-                out = self._graphed_step(tensor_dict, self._train_step_body, parts=(self._step_compute, self._step_apply))
-            if out is None:
-                out = self._train_step_body(tensor_dict, corrupt_labels)
-        self.global_step += 1
-        return out
+        # label corruption is not in the captured step, and the codebooks' data init must have happened before a capture
+        return self._train_step(tensor_dict, corrupt_labels, eager=corrupt_labels or self.encoder.quantizer_needs_init())
 
     def epoch(self, data_loader, train, num_batches, corrupt_labels):
         assert self.optimizer is not None, 'call init_optimizers(lr, schedule_lr) first'
@@ -313,5 +233,5 @@ class VQCPCEncoderTrainer(GraphedTraining, EncoderTrainer):
                      num_codewords=host[3], num_codewords_negative=host[4])
         means['loss_monitor'] = -sum(means['accuracy']) / len(means['accuracy'])
         if train:
-            self._report_scale_saturation(means)      # graphs.GraphedTraining: means['f16x3_scale_saturations'] + marked steps
+            self._report_scale_saturation(means)      # training.FlatTraining: means['f16x3_scale_saturations'] + marked steps
         return means
