@@ -828,6 +828,25 @@ int vqcpc_elu_bwd(const float* x, const float* g_out, float* g_x, int64_t n, voi
 int vqcpc_decode_aligned_add(const float* h, int64_t ldh, const float* C, float* s, int64_t lds, const int32_t* pos, int64_t M,
                              int S, int U, int nc, int d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Device-resident window sampler over a tokenised corpus (csrc/corpus.hip, vqcpc_bach_amd/dataloaders/corpus.py; the window
+ * rule restates VQCPCB/datasets/chorale_dataset.py:124-129, 418-470).  Device tables: tokens (total_ticks, 4) int32, 16-byte
+ * aligned, the pieces concatenated; piece_start (P + 1) tick offsets; special = START[4] END[4] PAD[4]; win_cum (P + 1), the
+ * cumulative window counts of ONE window length W (beats of `subdivision` ticks): piece p has last[p] + W windows, start beats
+ * o = -(W - 1) .. last[p], 0 <= last[p] <= beats(p) - 1.
+ * vqcpc_corpus_permute: ids[i] = lo + pi_key((q0 + i) mod n), i < count; pi_key is a bijection of [0, n) for every n >= 1
+ *   (a cycle-walked 6-round Feistel network whose round keys are a splitmix64 sequence started at `key`).
+ * vqcpc_corpus_gather: window ids[r] = win_cum[p] + j (found by binary search) starts at beat o = j - (W - 1) of piece p; its tick
+ *   t < W * subdivision is tick rel = o * subdivision + t of the piece: rel < -1 PAD, rel == -1 START, 0 <= rel < length the
+ *   corpus row, rel == length END, rel > length PAD.  The 4 voices of tick t < split go, as int64, to out[r * ld_row + t * ld_tick
+ *   + 0..3], those of t >= split to out2[r * ld_row2 + (t - split) * ld_tick2 + 0..3] (strides in int64 words; split =
+ *   W * subdivision: out only, out2 may be null).  An id outside [0, win_cum[P]) writes nothing and stores 1 to *flag (int32).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_corpus_permute(int64_t* ids, int64_t lo, int64_t n, uint64_t key, int64_t q0, int64_t count, void* stream);
+int vqcpc_corpus_gather(const int32_t* tokens, const int64_t* piece_start, const int64_t* win_cum, const int32_t* special, int P,
+                        int W, int subdivision, const int64_t* ids, int64_t count, int64_t* out, int64_t ld_row, int64_t ld_tick,
+                        int split, int64_t* out2, int64_t ld_row2, int64_t ld_tick2, int32_t* flag, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

@@ -7,6 +7,7 @@ import numpy as np
 from .auxiliary_decoders.auxiliary_decoder_relative import AuxiliaryDecoderRelative
 from .data_processor.bach_cpc_data_processor import BachCPCDataProcessor
 from .data_processor.bach_data_processor import BachDataProcessor
+from .dataloaders.corpus import CorpusCPCDataloaderGenerator, CorpusDataloaderGenerator
 from .dataloaders.synthetic_cpc_dataloader import SyntheticCPCDataloaderGenerator
 from .dataloaders.synthetic_student_dataloader import SyntheticStudentDataloaderGenerator
 from .decoders.decoder import Decoder
@@ -28,6 +29,12 @@ def get_dataloader_generator(dataset, training_method, dataloader_generator_kwar
         return SyntheticCPCDataloaderGenerator(**dataloader_generator_kwargs)
     if dataset.lower() in ('bach', 'synthetic') and training_method.lower() in ('student', 'decoder', 'prior'):
         return SyntheticStudentDataloaderGenerator(**dataloader_generator_kwargs)     # {'x': (B, events, voices)}
+    if dataset.lower() == 'corpus':
+        # a tokenised corpus file (dataloader_generator_kwargs['corpus_path']) sampled on the device: dataloaders/corpus.py
+        if training_method.lower() == 'vqcpc':
+            return CorpusCPCDataloaderGenerator(**dataloader_generator_kwargs)
+        if training_method.lower() in ('student', 'decoder', 'prior'):
+            return CorpusDataloaderGenerator(**dataloader_generator_kwargs)
     raise NotImplementedError('only the vqcpc, student, decoder and prior training methods are on the path')
 
 
