@@ -847,6 +847,35 @@ int vqcpc_corpus_gather(const int32_t* tokens, const int64_t* piece_start, const
                         int W, int subdivision, const int64_t* ids, int64_t count, int64_t* out, int64_t ld_row, int64_t ld_tick,
                         int split, int64_t* out2, int64_t ld_row2, int64_t ld_tick2, int32_t* flag, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Duplicate check: the longest common run of a token sequence against the corpus (csrc/duplicates.hip,
+ * DeviceCorpus.longest_common_run; in place of the difflib loop of VQCPCB/decoders/decoder.py:983-1017).
+ * DEFINITION.  Tokens are compared voice by voice in the flattened order (tick-major, voice-minor): query position
+ *   i = 4 tick + voice is matched with corpus position j = 4 tick' + voice of the SAME voice, so j - i is a multiple of 4.  A run
+ *   is a maximal stretch of consecutive equal tokens; it may begin and end in the middle of a tick and never crosses a piece
+ *   boundary.  Only stored corpus ticks take part: the virtual PAD / START / END ticks of the window rule never match.  The
+ *   answer per query row is the longest run; among equals the smallest i; among those the smallest j.  This is what
+ *   difflib.SequenceMatcher(None, a, b, autojunk=False).find_longest_match gives per piece on lists of (voice, token) pairs,
+ *   combined by (longest, smallest a, earliest piece).  The reference counts CHARACTERS of the dumped note names (so a long name
+ *   counts more, a run may end inside a name, and its "(size - 1) / 3" assumes three characters per token) and compares with the
+ *   padded windows, so padding in a generation counts as copied there; neither is reproduced.
+ * FRAMED CORPUS.  One 64-bit word per tick, voice v in bits 16 v .. 16 v + 15, with one sentinel tick (all ones) in front of
+ *   every piece and after the last: piece p starts at framed tick piece_start[p] + p + 1, n_framed = total_ticks + P + 1.  Tokens
+ *   of queries and corpus are < 0xFFFF (the caller checks), so a sentinel equals nothing and runs break at piece boundaries.
+ *   Any sub-array that starts and ends on a sentinel is the framed corpus of a contiguous piece range.
+ * vqcpc_dup_frame: tokens (total_ticks, 4) int32, 16-byte aligned, and piece_start (P + 1) int64 -> framed (n_framed words).
+ * vqcpc_dup_pack: int64 tokens x[g * ld_row + t * ld_tick + v] -> query[g * ld_query + t] in the word layout above.
+ * vqcpc_dup_longest_run: out[g] = max(out[g], key) over the n_ticks + n_framed - 1 diagonals of row g, key =
+ *   length << 48 | (0xFFFF - i) << 32 | (0xFFFFFFFF - j), j the token position inside `framed` (4 framed tick + voice); out
+ *   (G uint64) is zeroed by the caller and 0 means no common token.  The maximum is order-independent: the result is
+ *   deterministic.  Limits: n_ticks >= 1, 4 n_ticks <= 65535, 1 <= G <= 65535, 1 <= n_framed < 2^30, ld_query >= n_ticks.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_dup_frame(const int32_t* tokens, const int64_t* piece_start, int P, int64_t total_ticks, uint64_t* framed, void* stream);
+int vqcpc_dup_pack(const int64_t* x, int64_t ld_row, int64_t ld_tick, int n_ticks, int G, uint64_t* query, int64_t ld_query,
+                   void* stream);
+int vqcpc_dup_longest_run(const uint64_t* framed, int64_t n_framed, const uint64_t* query, int64_t ld_query, int n_ticks, int G,
+                          uint64_t* out, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

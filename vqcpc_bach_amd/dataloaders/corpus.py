@@ -40,6 +40,17 @@ starts the next epoch.
 THE IDS.  The window ids behind the last batch are `loader.last_ids` / `generator.last_ids` (CPC: a dict 'positive', 'negative',
 'negative_back'; the 'x' loaders: one tensor).  They are NOT a key of the batch dict: the trainers' step graph (graphs.py) bakes
 every batch entry into its signature and copies every tensor entry per replay, so an unknown key is not free there.
+
+THE DUPLICATE CHECK (`DeviceCorpus.longest_common_run`, csrc/duplicates.hip): how much of a generation is copied from the corpus, in
+place of the difflib loop over every training window of decoder.py:983-1017.  Tokens are compared voice by voice in the flattened
+order (tick-major, voice-minor): query position i = 4 tick + voice faces corpus position j = 4 tick' + voice of the SAME voice.  A
+run is a maximal stretch of consecutive equal tokens; it may begin and end in the middle of a tick and never crosses a piece
+boundary.  Only stored corpus ticks take part: the virtual PAD / START / END ticks of the window rule never match, so padding in a
+generation is never counted as copied (the reference compares with the padded windows and counts it).  The answer per query row
+is the longest run; among equals the smallest i; among those the smallest j (the earliest piece, then the earliest tick) -- what
+`difflib.SequenceMatcher(None, a, b, autojunk=False).find_longest_match` returns per piece on lists of (voice, token) pairs,
+combined by (longest, smallest a, earliest piece).  The reference matches the CHARACTERS of the dumped note names instead, so its
+count depends on the names' lengths and a match may end inside a name; lengths here are tokens.
 """
 import numpy as np
 import torch
@@ -118,6 +129,18 @@ class Corpus:
         assert num_beats >= 1
         return self.last() + int(num_beats)
 
+    def window_at(self, piece, start_tick, ticks):
+        """int64 (ticks, 4): the ticks [start_tick, start_tick + ticks) of `piece` under the padding of the window rule (tick -1
+        START, the first tick past the piece END, every other tick outside PAD); any start tick, not only a beat."""
+        lo, hi = int(self.piece_start[piece]), int(self.piece_start[piece + 1])
+        rel = np.arange(int(start_tick), int(start_tick) + int(ticks))
+        out = np.repeat(self.pad[None, :], len(rel), axis=0)
+        out[rel == -1] = self.start
+        out[rel == hi - lo] = self.end
+        inside = (rel >= 0) & (rel < hi - lo)
+        out[inside] = self.tokens[lo + rel[inside]]
+        return out
+
     def index2note_dicts(self):
         if self.names is None:
             return [{i: i for i in range(int(v))} for v in self.vocab]
@@ -177,6 +200,60 @@ def mix_key(seed, split, stream, epoch):
     return z
 
 
+# ---- the duplicate check: framing arithmetic (include/vqcpc.h, "Duplicate check") -----------------------------------------------
+DUP_SENTINEL = 0xFFFF                  # the 16-bit voice value of a sentinel tick: every token of a query or a corpus is below it
+DUP_MAX_TICKS = 65535 // NUM_VOICES    # a query position must fit 16 bits of the key
+
+
+def pack_words(x):
+    """(..., 4) tokens -> (...) uint64 words, voice v in bits 16 v .. 16 v + 15 (the host twin of vqcpc_dup_pack)."""
+    x = np.asarray(x).astype(np.uint64)
+    return x[..., 0] | (x[..., 1] << np.uint64(16)) | (x[..., 2] << np.uint64(32)) | (x[..., 3] << np.uint64(48))
+
+
+def framed_start(piece_start):
+    """(P + 1,) framed tick of the sentinel in front of piece p (p = P: the one after the last piece); piece p's first tick is
+    the next one.  n_framed = framed_start[P] + 1."""
+    piece_start = np.asarray(piece_start, dtype=np.int64)
+    return piece_start + np.arange(piece_start.size, dtype=np.int64)
+
+
+def frame_words(tokens, piece_start):
+    """The framed, packed corpus as vqcpc_dup_frame builds it: (total_ticks + P + 1,) uint64."""
+    fs = framed_start(piece_start)
+    out = np.full(int(fs[-1]) + 1, np.iinfo(np.uint64).max, dtype=np.uint64)
+    words = pack_words(tokens)
+    for p in range(len(fs) - 1):
+        out[fs[p] + 1:fs[p + 1]] = words[piece_start[p]:piece_start[p + 1]]
+    return out
+
+
+def framed_range(piece_start, lo, hi):
+    """(first framed tick, framed ticks) of the pieces [lo, hi): a sub-array that starts and ends on a sentinel."""
+    fs = framed_start(piece_start)
+    if not 0 <= lo < hi <= len(fs) - 1:
+        raise ValueError(f'corpus: pieces=({lo}, {hi}) is not a non-empty range of the {len(fs) - 1} pieces')
+    return int(fs[lo]), int(fs[hi] - fs[lo]) + 1
+
+
+def unpack_key(key):
+    """A key of vqcpc_dup_longest_run -> (length in tokens, query position i, framed position j); (0, -1, -1) for key 0."""
+    key = int(key)
+    if key == 0:
+        return 0, -1, -1
+    return key >> 48, 0xFFFF - ((key >> 32) & 0xFFFF), 0xFFFFFFFF - (key & 0xFFFFFFFF)
+
+
+def unframe(j, piece_start, first=0):
+    """Token position j inside the framed sub-array that begins at framed tick `first` -> (piece, tick of the piece, voice)."""
+    fs = framed_start(piece_start)
+    f, voice = first + j // NUM_VOICES, j % NUM_VOICES
+    piece = int(np.searchsorted(fs, f, side='right')) - 1
+    tick = f - int(fs[piece]) - 1
+    assert 0 <= piece < len(fs) - 1 and 0 <= tick < piece_start[piece + 1] - piece_start[piece], 'a match on a sentinel tick'
+    return piece, int(tick), int(voice)
+
+
 # ---- the corpus on the device ---------------------------------------------------------------------------------------------
 def permute(ids, lo, n, key, q0):
     """ids[i] = lo + pi_key((q0 + i) mod n) for the whole int64 device tensor `ids`."""
@@ -200,6 +277,65 @@ class DeviceCorpus:
         self.special = torch.from_numpy(special).to(self.device)
         self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._tables = {}
+        self._framed = None
+
+    def framed(self):
+        """The framed, packed copy of the corpus for the duplicate check (vqcpc_dup_frame), built on first use."""
+        if self._framed is None:
+            c = self.corpus
+            if int(c.vocab.max()) > DUP_SENTINEL:
+                raise ValueError(f'corpus: the duplicate check packs a token into 16 bits below the sentinel {DUP_SENTINEL:#x}; '
+                                 f'the vocab {c.vocab.tolist()} does not fit')
+            total = int(c.piece_start[-1])
+            framed = torch.empty(total + c.num_pieces + 1, dtype=torch.int64, device=self.device)
+            hip.call('vqcpc_dup_frame', self.tokens, self.piece_start, c.num_pieces, total, framed)
+            self._framed = framed
+        return self._framed
+
+    def split_pieces(self, split, num_beats):
+        """(lo, hi): the pieces of `split` for windows of `num_beats` beats.  A piece belongs to the split that holds its first
+        window id, so the ranges of the three splits are contiguous and partition the pieces; a range may be empty."""
+        cum = np.concatenate([[0], np.cumsum(self.corpus.window_counts(num_beats))]).astype(np.int64)
+        lo, hi = split_bounds(int(cum[-1]))[split]
+        first = cum[:-1]
+        return int(np.searchsorted(first, lo, side='left')), int(np.searchsorted(first, hi, side='left'))
+
+    def longest_common_run(self, x, pieces=None):
+        """The longest common run (module docstring) of every row of x, int64 tokens (G, ticks, 4) or (ticks, 4) on the device or
+        the host, against the pieces [lo, hi) = `pieces` (default: all).  Returns a dict of host values, (G,) int64 arrays or, for
+        a (ticks, 4) query, ints: `length` in tokens, where the run starts in the query (`query_tick`, `query_voice`) and in
+        the corpus (`piece`, `piece_tick`, `voice`; voice == query_voice).  No common token: length 0 and -1 everywhere."""
+        x = torch.as_tensor(x)
+        single = x.dim() == 2
+        if single:
+            x = x.unsqueeze(0)
+        if x.dim() != 3 or x.shape[2] != NUM_VOICES or x.dtype != torch.int64:
+            raise ValueError(f'longest_common_run: int64 tokens (G, ticks, {NUM_VOICES}) or (ticks, {NUM_VOICES}) expected, got '
+                             f'{x.dtype} {tuple(x.shape)}')
+        G, ticks = int(x.shape[0]), int(x.shape[1])
+        if G < 1 or not 1 <= ticks <= DUP_MAX_TICKS:
+            raise ValueError(f'longest_common_run: at least one row of 1 .. {DUP_MAX_TICKS} ticks expected, got {tuple(x.shape)}')
+        x = x.to(self.device).contiguous()
+        lo_tok, hi_tok = torch.stack([x.amin(dim=(0, 1)), x.amax(dim=(0, 1))]).cpu().numpy()       # one copy, one wait
+        if (lo_tok < 0).any() or (hi_tok >= self.corpus.vocab).any():
+            raise ValueError(f'longest_common_run: tokens in [{lo_tok.tolist()}, {hi_tok.tolist()}] per voice are not all tokens of '
+                             f'the vocab {self.corpus.vocab.tolist()}')
+        ps = self.corpus.piece_start
+        first, n_framed = framed_range(ps, *((0, self.corpus.num_pieces) if pieces is None else map(int, pieces)))
+        framed = self.framed()[first:first + n_framed]
+        query = torch.empty(G, ticks, dtype=torch.int64, device=self.device)
+        keys = torch.zeros(G, dtype=torch.int64, device=self.device)
+        hip.call('vqcpc_dup_pack', x, x.stride(0), x.stride(1), ticks, G, query, ticks)
+        hip.call('vqcpc_dup_longest_run', framed, n_framed, query, ticks, ticks, G, keys)
+        names = ('length', 'query_tick', 'query_voice', 'piece', 'piece_tick', 'voice')
+        out = {k: np.full(G, -1, dtype=np.int64) for k in names}
+        for g, key in enumerate(keys.cpu().numpy().view(np.uint64).tolist()):
+            length, i, j = unpack_key(key)
+            out['length'][g] = length
+            if length:
+                out['query_tick'][g], out['query_voice'][g] = divmod(i, NUM_VOICES)
+                out['piece'][g], out['piece_tick'][g], out['voice'][g] = unframe(j, ps, first)
+        return {k: int(v[0]) for k, v in out.items()} if single else out
 
     def table(self, num_beats):
         """(win_cum on the device, number of windows) of the window set of `num_beats` beats."""

@@ -14,7 +14,9 @@ by sliding the window, with a K/V-cache re-prefill per move; `reharmonise_tokens
 `generate_reharmonisation` (:856-958) on a token tensor (the music21 corpus it reads is absent, so that method raises).
 A decoder on continuous latents (a `NoQuantization` encoder without upscaler, decoder.py:222-229, :327-336, :595-600) has
 `source_embeddings = nn.Linear(dz, d_model)` and takes the encoder's (B, S, dz) latents wherever the others take merged codes.
-Duplicate checks, plots and the absolute-position variant are out of scope and raise.
+`check_duplicate` / `check_duplicate_all_corpus` (:983-1017) report the longest run of tokens a generation shares with another
+sequence or with the training corpus (csrc/duplicates.hip; dataloaders/corpus.py states the definition and where it departs from
+the reference's character-level difflib match).  Plots and the absolute-position variant are out of scope and raise.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
   * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient), or, on continuous
@@ -549,7 +551,67 @@ class Decoder(FlatTraining, nn.Module):
         raise NotImplementedError('generate_reharmonisation (:856-958) reads its chorale from the music21 corpus, which this '
                                   'package does not ship; pass the token tensor to reharmonise_tokens instead')
 
-    def _not_implemented(self, *a, **k):
-        raise NotImplementedError('duplicate checks and plots (decoder.py:983-1052) are out of scope')
+    # ---- duplicate checks (:983-1017): the longest common run on the device, dataloaders/corpus.py, csrc/duplicates.hip ----------
+    def _print_duplicates(self, lengths, subdivision):
+        best = int(np.max(lengths))
+        print(f'Num tokens plagiarisms: {best}')
+        print(f'Num beats plagiarisms: {best / self.num_channels / subdivision}')
 
-    check_duplicate = plot = _not_implemented
+    def check_duplicate(self, generation=None, original=None):
+        """:983-991, pairwise: the longest common run (dataloaders/corpus.py: same voice, consecutive tokens in tick-major order,
+        ties to the earliest query position, then the earliest position of `original`) of two (events, channels) token tensors;
+        `original` is framed as a one-piece corpus on the fly.  Returns the dict of `DeviceCorpus.longest_common_run` (host ints;
+        `piece` is 0, or -1 without a common token) and prints the reference's two lines with the TRUE token count (the
+        reference prints (characters - 1) / 3 of a match on the dumped note names).  The two tensors carry no subdivision: the
+        beats line divides by the one of the decoder's dataloader generator, or by the reference's constant 4 (:1015) when the
+        generator states none.  A bare call raises NotImplementedError, as before this method existed."""
+        if generation is None or original is None:
+            raise NotImplementedError('check_duplicate(generation, original): two (events, channels) token tensors are needed')
+        from ..dataloaders.corpus import Corpus, DeviceCorpus
+        original = torch.as_tensor(original).cpu().numpy()
+        if original.ndim != 2 or original.shape[1] != self.num_channels or original.shape[0] < 1:
+            raise ValueError(f'original: (events, {self.num_channels}) tokens expected, got {original.shape}')
+        if original.min() < 0 or original.max() > np.iinfo(np.int32).max:
+            raise ValueError('original: a token is negative or does not fit 32 bits')
+        # START / END / PAD take no part in the check: only `longest_common_run` is called on this corpus, never `gather` or
+        # `window_at`, so any ids the constructor accepts will do; subdivision 1 lets `original` have any length
+        zero = np.zeros(self.num_channels, dtype=np.int64)
+        corpus = Corpus(original.astype(np.int32), [0, original.shape[0]], 1, self.num_tokens_per_channel, zero, zero, zero)
+        generation = torch.as_tensor(generation)
+        if generation.dim() != 2:
+            raise ValueError(f'generation: (events, {self.num_channels}) tokens expected, got {tuple(generation.shape)}')
+        out = DeviceCorpus(corpus, self.sos.device).longest_common_run(generation)
+        self._print_duplicates(out['length'], getattr(getattr(self.dataloader_generator, 'dataset', None), 'subdivision', 4))
+        return out
+
+    def check_duplicate_all_corpus(self, generation, split='train'):
+        """:993-1017 on the device-resident corpus: the longest common run of every row of `generation`, (events, channels) or
+        (G, events, channels), with the pieces of `split` ('train' / 'val' / 'test': a piece belongs to the split that holds its
+        first window; None: every piece).  Needs a corpus dataloader generator (dataloaders/corpus.py); the synthetic ones have no
+        corpus and raise ValueError.  Returns the dict of `DeviceCorpus.longest_common_run` plus 'best_x': int64 (events of the
+        decoder, channels) per row, host -- the ticks of the matched piece that face the decoder-sized chunk of the generation in
+        which the run begins (the run starts at row query_tick % events), padded by the window rule outside the piece; all PAD
+        for a row without a common token.  The reference returns the training window with the longest character match instead
+        and counts padding as copied."""
+        dc = getattr(self.dataloader_generator, 'device_corpus', None)
+        if dc is None:
+            raise ValueError('check_duplicate_all_corpus needs a corpus dataloader generator (dataloaders/corpus.py); '
+                             f'{type(self.dataloader_generator).__name__} has no corpus')
+        pieces = None
+        if split is not None:
+            pieces = dc.split_pieces(split, self.dataloader_generator.sequences_size)
+            if pieces[0] == pieces[1]:
+                raise ValueError(f'check_duplicate_all_corpus: no piece begins in the {split} split')
+        out = dc.longest_common_run(generation, pieces=pieces)
+        E = self.data_processor.num_events
+        single = np.ndim(out['length']) == 0
+        rows = []
+        for piece, tick, q in zip(*(np.atleast_1d(out[k]) for k in ('piece', 'piece_tick', 'query_tick'))):
+            rows.append(dc.corpus.window_at(int(piece), int(tick) - int(q) % E, E) if piece >= 0
+                        else np.repeat(dc.corpus.pad[None, :], E, axis=0))
+        out['best_x'] = rows[0] if single else np.stack(rows)
+        self._print_duplicates(out['length'], dc.corpus.subdivision)
+        return out
+
+    def plot(self, *a, **k):
+        raise NotImplementedError('plots (decoder.py:1019-1052) are out of scope')
