@@ -876,6 +876,44 @@ int vqcpc_dup_pack(const int64_t* x, int64_t ld_row, int64_t ld_tick, int n_tick
 int vqcpc_dup_longest_run(const uint64_t* framed, int64_t n_framed, const uint64_t* query, int64_t ld_query, int n_ticks, int G,
                           uint64_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Cluster census: which rows every codeword collects, E examples per codeword, and the codewords next to each other
+ * (csrc/clusters.hip, vqcpc_bach_amd/clusters.py; in place of the host loops of VQCPCB/encoder.py:112-185: `.item()` per block,
+ * dict-of-lists grouping, random.shuffle and a cap of 50 in plot_clusters, norm + topk in show_nn_clusters).
+ * DEFINITION.  A POPULATION is a set of rows, each with an id < 2^32 - 1 and one code per codebook, codes[row * ld + c] (int64,
+ *   c < ncb <= 64, ld >= ncb), a code being in [0, K), K <= 2^24 (the merged code of a product quantiser is ncb = 1,
+ *   K = codebook_size ** num_codebooks).  The COUNT of (c, k) is the number of rows whose code c is k.  The EXAMPLES of (c, k) are
+ *   its E members with the smallest PACKED KEY h(key, id) << 32 | id, ascending, where
+ *       h(key, id) = the low 32 bits of mix(key + id * 0x9E3779B97F4A7C15 mod 2^64),
+ *       mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31   (mod 2^64; the
+ *   splitmix64 finaliser of dataloaders/corpus.py mix_key; clusters.select_hash is the host twin).  Packed keys are unique -- the
+ *   id sits in the low bits -- and none is all ones, the EMPTY slot value, because id < 2^32 - 1.  Counts and examples are functions
+ *   of the SET of rows: the order of the rows, their split into calls and the scheduling of the threads do not enter.  The
+ *   NEIGHBOURS of codeword i of a codebook are the k other codewords j != i of that codebook with the smallest
+ *   (dist2(i, j), j), ascending; i is left out by index (the reference drops the first hit of topk(k + 1), which is another codeword
+ *   when two coincide), and dist2 is the canonical chain of vqcpc_vq_fwd: acc = 0; for t ascending: df = e[i][t] - e[j][t],
+ *   acc = acc + df * df, every operation rounded to fp32 on its own (no FMA), so a numpy float32 restatement gives the same bits.
+ * vqcpc_cluster_count: counts[c * K + k] += count of (c, k) over the n rows; counts (ncb * K int32) is zeroed by the caller, so
+ *   calls over disjoint row sets accumulate.  A code outside [0, K) is not counted and stores 1 to *flag (int32), as
+ *   vqcpc_corpus_gather does.  ncb * K <= 8192: per-workgroup counts in LDS, one flush; larger: global integer atomics.
+ *   Limits: 1 <= ncb <= 64, 1 <= K <= 2^24, ld >= ncb, 0 <= n < 2^31.
+ * vqcpc_cluster_select: slots (ncb * K * E uint64, slot e of (c, k) at (c * K + k) * E + e) are set to all ones by the caller.
+ *   After any number of calls over disjoint row sets slots[c][k][0 .. min(E, count) - 1] are the smallest packed keys of the
+ *   members of (c, k), ascending, and the rest are still all ones.  The id of row r is ids[r] (int64) or, ids == null, id0 + r.  A
+ *   row with a code outside [0, K) or an id outside [0, 2^32 - 1) takes no part and stores 1 to *flag.
+ *   Limits: as vqcpc_cluster_count, 1 <= E <= 64, and without ids 0 <= id0, id0 + n <= 2^32 - 1.
+ * vqcpc_codebook_knn: e (ncb, K, d) fp32, dense -> nn (ncb, K, k) int32 and dist2 (ncb, K, k) fp32, the neighbours above; finite
+ *   codewords whose distances do not overflow.  Codebooks of more than 8192 floats are streamed through LDS in tiles.
+ *   Limits: 1 <= ncb <= 65535, 2 <= K <= 2^24, 1 <= d <= 1024, 1 <= k <= 16, k < K.
+ * No allocation or synchronisation in the launch functions; integer atomics and minima only: the results are deterministic.
+ * Adding them left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_cluster_count(const int64_t* codes, int64_t ld, int64_t n, int ncb, int64_t K, int32_t* counts, int32_t* flag,
+                        void* stream);
+int vqcpc_cluster_select(const int64_t* codes, int64_t ld, int64_t n, int ncb, int64_t K, const int64_t* ids, int64_t id0,
+                         uint64_t key, int E, uint64_t* slots, int32_t* flag, void* stream);
+int vqcpc_codebook_knn(const float* e, int ncb, int K, int d, int k, int32_t* nn, float* dist2, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

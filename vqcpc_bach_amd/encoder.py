@@ -144,10 +144,45 @@ class Encoder(nn.Module):
             ret = ret + codes[..., c] * (self.quantizer.codebook_size ** c)
         return ret
 
-    def plot_clusters(self, *a, **k):
-        raise NotImplementedError('cluster visualisation needs the music21 corpus: out of scope (SURVEY.md section 2, #4)')
+    # ---- "Explore clusters" (main_encoder.py:100-118; encoder.py:112-200) ----------------------------------------------------------
+    def plot_clusters(self, dataloader_generator, split_name, batch_size=32, num_batches=64):
+        """What the codes of `split_name` stand for (encoder.py:112-176): the cluster census (clusters.cluster_census) of the
+        generator's corpus, written as `{model_dir}/clusters_{split_name}.npz` (ClusterCensus.save) and
+        `{model_dir}/clusters_{split_name}.txt` (its tables, every codebook), and returned.  The WHOLE split is visited:
+        `batch_size` and `num_batches` are accepted for the reference's signature and ignored.  Needs a corpus generator (one with
+        `device_corpus`): the synthetic generators have no corpus to show."""
+        from . import clusters
+        if split_name not in ('train', 'val', 'test'):
+            raise ValueError(f'{split_name} is not a valid split value. Choose between train, val or test')
+        dc = getattr(dataloader_generator, 'device_corpus', None)
+        if dc is None:
+            raise NotImplementedError('plot_clusters shows blocks of a corpus: it needs a corpus dataloader generator '
+                                      '(dataloaders/corpus.py), not a synthetic one')
+        census = clusters.cluster_census(self, dc, split=split_name)
+        os.makedirs(self.model_dir, exist_ok=True)
+        census.save(f'{self.model_dir}/clusters_{split_name}.npz')
+        with open(f'{self.model_dir}/clusters_{split_name}.txt', 'w') as f:
+            f.write('\n'.join(census.table(codebook=c) for c in range(census.num_codebooks)))
+        return census
 
-    show_nn_clusters = scatterplot_clusters_3d = plot_clusters
+    def show_nn_clusters(self, k=3):
+        """Prints, per codeword of codebook 0, its k nearest other codewords (encoder.py:178-185, same lines), then the further
+        codebooks under a header line each; returns the (num_codebooks, codebook_size, k) int32 array.  Neighbours are ordered by
+        (squared distance, index) and a codeword is left out of its own list by index (vqcpc_codebook_knn)."""
+        from . import clusters
+        if not hasattr(self.quantizer, 'embeddings'):
+            raise ValueError(f'show_nn_clusters: a {type(self.quantizer).__name__} encoder has no codebook')
+        nn_idx, _ = clusters.codebook_knn(torch.stack([e.detach() for e in self.quantizer.embeddings], dim=0), k)
+        nn_idx = nn_idx.cpu().numpy()
+        for c, book in enumerate(nn_idx):
+            print('Nearest neighbours list:' if c == 0 else f'Nearest neighbours list (codebook {c}):')
+            for i, res in enumerate(book):
+                print(f'{i}: {res}')
+        return nn_idx
+
+    def scatterplot_clusters_3d(self):
+        raise NotImplementedError('the 3-d scatter plot of a codebook of dimension 3 needs matplotlib: out of scope '
+                                  '(SURVEY.md section 2, #4)')
 
 
 class EncoderTrainer(FlatTraining, nn.Module):

@@ -225,6 +225,9 @@ SIGNATURES = {
     'vqcpc_dup_frame': (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr]),
     'vqcpc_dup_pack': (c_int, [c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr]),
     'vqcpc_dup_longest_run': (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
+    'vqcpc_cluster_count': (c_int, [c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_cluster_select': (c_int, [c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_i64, c_u64, c_int, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_codebook_knn': (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
 }
 
 # Entry points of LAB builds only (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so, the `#ifdef VQCPC_LAB`
