@@ -6,6 +6,7 @@ row = block * L + token (block-major), i.e. the reference's time-first `(L, N, E
 """
 import bisect
 import os
+from collections import namedtuple
 
 import torch
 
@@ -1287,11 +1288,11 @@ def _residual_sum_in_epilogue(M, N, K, nat):
     return (M // 256) * (N // 256) >= SFORM_MIN_TILES and M % 256 == 0 and N % 256 == 0 or SFORM_MIN_TILES == 0
 
 
-def _dgrad_plus_residual_bf16(g, wt, res, carrier=False):
-    """g @ wt^T + res on the bf16 path; `res` fp32 or -- the gradient of a residual branch kept in bf16 -- bf16.
+def _dgrad_plus_residual_bf16(g, wt, res, res_b16, carrier=False):
+    """g @ wt^T + res on the bf16 path; `res` fp32 or -- res_b16: the gradient of a residual branch kept in bf16 -- bf16.
     carrier: the layer that produced this layer's input reads its output gradient in bf16 (EncoderLayerFn.forward): the sum leaves
     the epilogue in bf16 only, wrapped for autograd by _bf16_grad_carrier."""
-    if res.dtype != torch.bfloat16:
+    if not res_b16:
         return gemm_nt_bf16(g, wt, add=res)
     if carrier:
         return _bf16_grad_carrier(gemm_nt_bf16(g, wt, add_b=res, out_f32=False, out_bf16=True))
@@ -1333,6 +1334,147 @@ def _bf16_grad_of(g):
     return gb if (gb is not None and tuple(gb.shape) == tuple(g.shape)) else None
 
 
+_LayerRoute = namedtuple('_LayerRoute', 'nat ext_qkv need_dx x_b16_only att_fwd att_bwd tab_b16 s16 x1_f32 sform1 sform2 gate_bits y_carrier '
+                                        'g16 g16_1 g16_stream dx_b16')
+_ATT_B16_ROUTES = ('b16', 'b16io', 'b16_L', 'sub_b16')      # attention routes whose context / d q | k | v are bf16 tensors
+
+
+def _layer_route(M, d, H, L, f, ffd, ext_qkv, tab_tokens, x_b16, x_b16_grad, out_b16_only, need_dx):
+    """Every decision of one EncoderLayerFn node, taken ONCE -- from the module switches, the library's `..._supported` answers and the
+    GEMM mode as they are when forward runs; forward and backward obey the record and read none of those again.
+    ext_qkv: qkv_in is given, tab_tokens: its block table's token count (0: per token); x_b16: x arrived as a bf16 activation carrier,
+    x_b16_grad: its producer reads a bf16 gradient; need_dx: ctx.needs_input_grad[0].  (drop_p selects no route.)"""
+    hd, Mq, own = d // H, M // f, not ext_qkv
+    # bf16 mode (configs[4]): the layer's GEMMs take bf16 operands from HBM; activations that only feed GEMMs get a bf16
+    # copy from the producing epilogue (FFN hidden) or from a cast pass (x, attention output, LayerNorm output)
+    nat = bool(bf16_native((M, 3 * d if (f == 1 and own) else 2 * d, d), (Mq, d, d), (Mq, ffd, d), (Mq, d, ffd))
+               and hip.query('vqcpc_gemm_tn_bf16_supported', Mq, d, d))
+    b16 = nat and ATT_B16_OUT
+    tab_b16 = False
+    if f > 1:
+        att_fwd = att_bwd = 'sub_b16' if b16 and hip.query('vqcpc_relattn_sub_b16_supported', L, f, H, hd) else 'sub'
+    else:
+        # bf16 path at L = 16: the attention context only feeds the out-proj GEMM, which reads bf16 -> the kernel writes
+        # bf16 directly (no fp32 tensor, no cast pass); where the projection runs here (no block table) q | k | v are
+        # bf16 as well -- the in_proj epilogue writes them so and the attention kernels read half the bytes
+        q16 = b16 and bool(hip.query('vqcpc_relattn16_b16_supported', L, H, hd))
+        if q16:
+            att_fwd = 'b16io' if (ATT_B16_IN and own) else 'b16'
+        elif b16 and not tab_tokens and hip.query('vqcpc_relattn_b16_supported', L, H, hd):
+            att_fwd = 'b16_L'                            # the other block lengths (L = 4)
+        else:
+            att_fwd = 'tab' if tab_tokens else 'f32'
+        # bf16 path, block table (first layer): d q | k | v only feeds the segment sum -> the attention backward writes it as bf16
+        # (the rounding the in_proj's bf16 input-gradient operand would get anyway), the segment sum reads half the bytes
+        tab_b16 = bool(q16 and tab_tokens and BF16_TAB_GRAD and L == 16 and tab_tokens <= 80)   # (80 tokens: the bf16 segment sum's LDS table)
+        # the projection lives outside (qkv_in): its gradient leaves in fp32, whatever forward read
+        att_bwd = att_fwd if own else (('b16' if tab_b16 else 'tab') if tab_tokens else 'f32')
+    # bf16 path: x1 = LN1(...) feeds the two feed-forward GEMMs (bf16 operand) and the residual of s2 = x1 + dropout(FFN): with
+    # the residual read from the bf16 copy as well (round 5) the LayerNorm writes 2 instead of 6 bytes per element and the
+    # FFN2 epilogue reads 2 instead of 4 -- the residual stream between LN1 and LN2 is bf16, as the GEMM operands already are
+    x1_f32 = not (nat and BF16_RESIDUAL)
+    # ... and the residual sums s1, s2 themselves leave their GEMM epilogues in bf16: 2 instead of 4 bytes out of the epilogue,
+    # into the LayerNorm forward and into its backward (include/vqcpc.h: vqcpc_layernorm_fwd_xb16)
+    s16 = bool(nat and BF16_RESIDUAL and BF16_SUMS)
+    g16 = s16 and BF16_GRAD_SUMS         # d s2 / d s1 only feed the residual operand of a dgrad epilogue -> bf16 (next to a bf16 sum)
+    # d s1 is bf16 only where the dgrad of the in_proj consumes it here (the all-bf16 attention routes)
+    g16_1 = bool(g16 and own and need_dx and att_bwd in ('b16', 'b16io', 'b16_L'))
+    # round 5: the main-stream gradient in bf16 -- y announces that this layer's backward reads its gradient so (vqcpc_layernorm_bwd_b16io;
+    # the next layer's input-gradient GEMM then writes 2 instead of 4 bytes per element and LN2's backward reads 2), and d x1 enters
+    # LN1's backward so; dx_b16: the sum d x leaves in bf16 only, for a producer of x that announced the same
+    g16_stream = g16 and BF16_GRAD_STREAM
+    # a bf16-only input reaching a layer off the all-bf16 path (or shapes off the 256-tile bf16 kernels) is upcast, and its gradient fp32
+    x_b16_only = bool(x_b16 and s16 and own and hip.get_gemm_mode() == 2)
+    return _LayerRoute(
+        nat=nat, ext_qkv=ext_qkv, need_dx=need_dx, x_b16_only=x_b16_only, att_fwd=att_fwd, att_bwd=att_bwd, tab_b16=tab_b16, s16=s16,
+        x1_f32=x1_f32, sform1=_residual_sum_in_epilogue(Mq, d, d, nat), sform2=_residual_sum_in_epilogue(Mq, d, ffd, nat),
+        gate_bits=not nat and gatebits_worthwhile(Mq, ffd, d),       # relu / dropout gate of the backward as a bit mask (1/32 of the bytes)
+        y_carrier=bool(out_b16_only and s16 and BF16_ACT_STREAM), g16=g16, g16_1=g16_1, g16_stream=g16_stream,
+        dx_b16=bool(g16_1 and BF16_GRAD_STREAM and x_b16_grad and (x_b16_only or not x_b16)))
+
+
+def _attention_fwd(route, qproj, qkv, tok, e1, e2, M, d, L, f, H, p, seed):
+    """The layer's relative attention on the route's kernel.  Returns (context fp32 | None, context bf16 | None, probs)."""
+    nblk, hd, dev = M // L, d // H, qkv.device
+    probs = torch.empty(nblk, H, L // f, L, dtype=torch.float32, device=dev)
+    b16 = route in _ATT_B16_ROUTES
+    att = torch.empty(M // f, d, dtype=torch.bfloat16 if b16 else torch.float32, device=dev)
+    if route == 'b16io':
+        hip.call('vqcpc_relattn16_fwd_b16io', qkv, 3 * d, e1, e2, att, d, probs, nblk, H, hd, p, seed)
+    elif route == 'b16':
+        hip.call('vqcpc_relattn16_fwd_b16', qkv, 3 * d, tok, e1, e2, att, d, probs, nblk, H, hd, p, seed)
+    elif route == 'b16_L':
+        hip.call('vqcpc_relattn_fwd_b16', qkv, 3 * d, e1, e2, att, d, probs, nblk, L, H, hd, p, seed)
+    elif route == 'tab':
+        hip.call('vqcpc_relattn_tab_fwd', qkv, 3 * d, tok, e1, e2, att, d, probs, nblk, L, H, hd, p, seed)
+    elif route == 'f32':
+        hip.call('vqcpc_relattn_fwd', qkv, 3 * d, e1, e2, att, d, probs, nblk, L, H, hd, p, seed)
+    else:
+        hip.call('vqcpc_relattn_sub_fwd_b16' if b16 else 'vqcpc_relattn_sub_fwd', qproj, d, qkv, 2 * d, e1, e2, att, d, probs, nblk, L,
+                 f, H, hd, p, seed)
+    return (None, att, probs) if b16 else (att, None, probs)
+
+
+def _attention_bwd(route, datt, qproj, qkv, tok, probs, e1, e2, M, d, L, f, H, p, seed):
+    """Its backward.  Returns (d q | k | v -- on the sub routes the pair (d q, d k | v) --, d e1, d e2); bf16 on the b16 routes."""
+    nblk, hd, dev = M // L, d // H, qkv.device
+    de1, de2 = torch.empty_like(e1), torch.empty_like(e2)
+    b16 = torch.bfloat16 if route in _ATT_B16_ROUTES else torch.float32
+    if f > 1:
+        nbytes = hip.query('vqcpc_relattn_sub_bwd_workspace', nblk, L, f, H, hd)
+        ws = hip.workspace(nbytes, dev)
+        dq = torch.empty(M // f, d, dtype=torch.float32, device=dev)
+        # bf16 path: d k | v (8 x the bytes of d q) only feeds GEMMs that read bf16 -> written so by the kernel
+        dkv = torch.empty(M, 2 * d, dtype=b16, device=dev)
+        hip.call('vqcpc_relattn_sub_bwd_b16' if route == 'sub_b16' else 'vqcpc_relattn_sub_bwd', datt, d, qproj, d, qkv, 2 * d, probs, e1,
+                 e2, dq, d, dkv, 2 * d, de1, de2, nblk, L, f, H, hd, p, seed, ws, nbytes)
+        return (dq, dkv), de1, de2
+    nbytes = hip.query('vqcpc_relattn_bwd_workspace', nblk, L, H, hd)
+    ws = hip.workspace(nbytes, dev)
+    # b16 routes: d qkv only feeds the in_proj's two GEMMs (or the table's segment sum) -> written as bf16 by the attention backward itself
+    dqkv = torch.empty(M, 3 * d, dtype=b16, device=dev)
+    if route == 'b16io':
+        hip.call('vqcpc_relattn16_bwd_b16io', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, H, hd, p, seed, ws, nbytes)
+    elif route == 'b16':
+        hip.call('vqcpc_relattn16_bwd_b16', datt, d, qkv, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, H, hd, p, seed, ws, nbytes)
+    elif route == 'b16_L':
+        hip.call('vqcpc_relattn_bwd_b16', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, seed, ws, nbytes)
+    elif route == 'tab':
+        hip.call('vqcpc_relattn_tab_bwd', datt, d, qkv, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, seed, ws, nbytes)
+    else:
+        hip.call('vqcpc_relattn_bwd', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, seed, ws, nbytes)
+    return dqkv, de1, de2
+
+
+def _ln_bwd(form, dyv, xin, ldxin, r, gamma, beta, mean, rstd, p, seed, nat, ds_bf16=False):
+    """Backward of y = LN(xin + dropout(r)) in the form the route names: 'add' (fp32 streams), 'xb16' (xin, a residual sum, in bf16) or
+    'b16io' (... and the incoming gradient too, where an input-gradient GEMM of this path produced it, round 5).
+    r None: xin is the residual sum itself (s-form, include/vqcpc.h); the mask of d_r is regenerated from `seed`
+    ds_bf16 (bf16 forms): the gradient of the residual branch leaves in bf16 only (returned in place of ds)"""
+    (Mq, d), dev = dyv.shape, dyv.device
+    ds = None if ds_bf16 else torch.empty(Mq, d, dtype=torch.float32, device=dev)
+    dsb = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev) if ds_bf16 else None
+    # bf16 path: the gradient of the sub-layer output only feeds GEMMs, which read its bf16 copy -> no fp32 d_r stream
+    dr = torch.empty(Mq, d, dtype=torch.float32, device=dev) if (p > 0 and not nat) else None
+    drb = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev) if nat else None    # GEMM-operand copy of dr
+    nbytes = hip.query('vqcpc_add_layernorm_bwd_workspace', Mq, d)
+    ws = hip.workspace(nbytes, dev)
+    if defer_ln_param_grads(ws, Mq, d, gamma, beta, r is not None):     # gamma / beta partial sums: reduced with all the others later
+        dg = db = None
+    else:
+        dg = torch.empty(d, dtype=torch.float32, device=dev)
+        db = torch.empty(d, dtype=torch.float32, device=dev)
+    if form == 'add':
+        assert dyv.dtype == xin.dtype == torch.float32 and not ds_bf16
+        hip.call('vqcpc_add_layernorm_bwd_b16', dyv, xin, ldxin, r, gamma, mean, rstd, ds, dr, drb, dg, db, Mq, d, p, seed, ws, nbytes)
+    else:                                            # the residual sum was written in bf16 (s-form only)
+        assert r is None and xin.dtype == torch.bfloat16 and dyv.dtype == (torch.bfloat16 if form == 'b16io' else torch.float32)
+        hip.call('vqcpc_layernorm_bwd_' + form, dyv, xin, ldxin, gamma, mean, rstd, ds, dsb, dr, drb, dg, db, Mq, d, p, seed, ws, nbytes)
+        if ds_bf16:
+            ds = dsb
+    return ds, (dr if dr is not None else (None if (nat and p > 0) else ds)), dg, db, drb
+
+
 class EncoderLayerFn(torch.autograd.Function):
     """y = LN2(x1 + drop(W2 drop(relu(W1 x1 + b1)) + b2)),  x1 = LN1(x + drop(Wo attn(x) + bo)).
     Parameter order: in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, e1, e2, linear1.weight,
@@ -1341,7 +1483,9 @@ class EncoderLayerFn(torch.autograd.Function):
     qstride = f > 1 (last layer of a stack): only rows 0, f, 2f, ... of the output are produced -- the reference computes
     all rows and keeps `output[::f]` (relative_transformer_downscaler.py:125); everything after the attention is
     per-token, so queries / out-proj / LayerNorms / FFN run on M/f rows while keys and values still cover every token.
-    Identical results, ~60 % fewer FLOPs in that layer."""
+    Identical results, ~60 % fewer FLOPs in that layer.
+
+    Which kernels run and which tensors exist in bf16 only is decided once, by _layer_route in forward (ctx.route)."""
 
     @staticmethod
     def forward(ctx, x, L, H, drop_p, seed, qstride, qkv_in, qkv_tokens, out_b16_only, wqkv, bqkv, wo, bo, e1, e2, w1, b1, w2, b2, g1,
@@ -1351,160 +1495,102 @@ class EncoderLayerFn(torch.autograd.Function):
         # (M,) int64 -- the (vmax * L, 3d) block table, which the attention kernels read through the token indirection
         # out_b16_only: the caller promises that the ONE consumer of y is the next EncoderLayerFn of the stack (an interior layer): on
         # the bf16 path y then exists in bf16 only (_bf16_act_carrier)
-        x_accepts_b16_grad = bool(getattr(x, '_vqcpc_accepts_bf16_grad', False))     # set by the layer that produced x
         xb_in = _bf16_act_of(x)              # x itself in bf16 only (the previous interior layer's output)
-        if xb_in is not None and not (hip.get_gemm_mode() == 2 and BF16_RESIDUAL and BF16_SUMS and qkv_in is None):
+        M, d = x.shape
+        p, f, ffd = float(drop_p), int(qstride), w1.shape[0]
+        r = ctx.route = _layer_route(M, d, H, L, f, ffd, qkv_in is not None, qkv_in.shape[0] // L if qkv_tokens is not None else 0,
+                                     xb_in is not None, bool(getattr(x, '_vqcpc_accepts_bf16_grad', False)),     # set by the layer that produced x
+                                     out_b16_only, ctx.needs_input_grad[0])
+        nat, s16 = r.nat, r.s16
+        if xb_in is not None and not r.x_b16_only:
             x, xb_in = xb_in.float(), None   # a consumer off the all-bf16 path: the values, upcast
-            x_accepts_b16_grad = False
         if xb_in is None:
             x, ldx = _rows(_f32(x))
         else:
-            ldx = x.shape[1]
-        M, d = x.shape
-        hd = d // H
-        nblk = M // L
+            ldx = d
         dev = x.device
-        p = float(drop_p)
-        f = int(qstride)
         s = [int(seed) + 0x1000 * i for i in range(4)]     # attention probs, dropout1, ffn dropout, dropout2
-        ffd = w1.shape[0]
-        Mq_ = M // f
-        # bf16 mode (configs[4]): the layer's GEMMs take bf16 operands from HBM; activations that only feed GEMMs get a bf16
-        # copy from the producing epilogue (FFN hidden) or from a cast pass (x, attention output, LayerNorm output)
-        nat = bf16_native((M, 3 * d if (f == 1 and qkv_in is None) else 2 * d, d), (Mq_, d, d), (Mq_, ffd, d), (Mq_, d, ffd)) and \
-            hip.query('vqcpc_gemm_tn_bf16_supported', Mq_, d, d)
         lin = gemm_nt_bf16 if nat else gemm_nt
-        if xb_in is not None and not nat:               # (shapes off the 256-tile bf16 kernels)
-            x, xb_in = xb_in.float(), None
-            x_accepts_b16_grad = False
-            x, ldx = _rows(x)
-        xb = None                                       # bf16 copies: GEMM operands now, weight-gradient operands later
+        # in-proj
+        xb = xsb = None                                 # bf16 copies: GEMM operands now, weight-gradient operands later
         if nat and (qkv_in is None or f > 1):
             xb = xb_in if xb_in is not None else _bf16_copy_of(x)      # written by the previous layer's LayerNorm kernel
             if xb is None:
                 xb = cast_bf16(x)
-        xsb = None
         if f == 1:
             Mq, xs, ldxs = M, x, ldx
             xsb = xb if xb_in is not None else None
-            probs = torch.empty(nblk, H, L, L, dtype=torch.float32, device=dev)
-            # bf16 path at L = 16: the attention context only feeds the out-proj GEMM, which reads bf16 -> the kernel writes
-            # bf16 directly (no fp32 tensor, no cast pass); where the projection runs here (no block table) q | k | v are
-            # bf16 as well -- the in_proj epilogue writes them so and the attention kernels read half the bytes
-            b16_att = nat and ATT_B16_OUT and bool(hip.query('vqcpc_relattn16_b16_supported', L, H, hd))
-            b16_qkv = b16_att and ATT_B16_IN and qkv_in is None
             if qkv_in is not None:
                 qkv = _f32(qkv_in).contiguous()
-            elif b16_qkv:
+            elif r.att_fwd == 'b16io':
                 qkv = gemm_nt_bf16(xb, wqkv, bias=bqkv, out_f32=False, out_bf16=True)
             else:
                 qkv = lin(xb if nat else x, wqkv, bias=bqkv)
-            attb_direct = None
-            if b16_att:
-                attb_direct = torch.empty(M, d, dtype=torch.bfloat16, device=dev)
-                att = None
-                if b16_qkv:
-                    hip.call('vqcpc_relattn16_fwd_b16io', qkv, 3 * d, e1, e2, attb_direct, d, probs, nblk, H, hd, p, s[0])
-                else:
-                    hip.call('vqcpc_relattn16_fwd_b16', qkv, 3 * d, qkv_tokens, e1, e2, attb_direct, d, probs, nblk, H, hd, p, s[0])
-            elif (nat and ATT_B16_OUT and qkv_tokens is None and hip.query('vqcpc_relattn_b16_supported', L, H, hd)):
-                attb_direct = torch.empty(M, d, dtype=torch.bfloat16, device=dev)      # the other block lengths (L = 4)
-                att = None
-                hip.call('vqcpc_relattn_fwd_b16', qkv, 3 * d, e1, e2, attb_direct, d, probs, nblk, L, H, hd, p, s[0])
-            else:
-                att = torch.empty(M, d, dtype=torch.float32, device=dev)
-                if qkv_tokens is not None:
-                    hip.call('vqcpc_relattn_tab_fwd', qkv, 3 * d, qkv_tokens, e1, e2, att, d, probs, nblk, L, H, hd, p, s[0])
-                else:
-                    hip.call('vqcpc_relattn_fwd', qkv, 3 * d, e1, e2, att, d, probs, nblk, L, H, hd, p, s[0])
             qproj = qkv
         else:
             assert L % f == 0 and qkv_in is None
-            attb_direct = None
             Mq = M // f
             xs, ldxs = _rows(x[::f]) if xb_in is None else (None, 0)       # query / residual rows: a stride, not a copy
             xsb = xb[::f].contiguous() if nat else None
             qkv = lin(xb if nat else x, wqkv[d:], bias=bqkv[d:])           # k | v for every token   (M, 2d)
             qproj = lin(xsb if nat else xs, wqkv[:d], bias=bqkv[:d])       # q for the kept rows     (Mq, d)
-            probs = torch.empty(nblk, H, L // f, L, dtype=torch.float32, device=dev)
-            if nat and ATT_B16_OUT and hip.query('vqcpc_relattn_sub_b16_supported', L, f, H, hd):
-                attb_direct = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev)
-                att = None
-                hip.call('vqcpc_relattn_sub_fwd_b16', qproj, d, qkv, 2 * d, e1, e2, attb_direct, d, probs, nblk, L, f, H, hd, p, s[0])
-            else:
-                att = torch.empty(Mq, d, dtype=torch.float32, device=dev)
-                hip.call('vqcpc_relattn_sub_fwd', qproj, d, qkv, 2 * d, e1, e2, att, d, probs, nblk, L, f, H, hd, p, s[0])
-        attb = (attb_direct if attb_direct is not None else cast_bf16(att)) if nat else None
-        # s1 = x + dropout(att Wo^T + bo): the residual sum is formed by the out-proj epilogue (bias -> dropout -> + x), so the
-        # LayerNorm kernels read ONE input stream and the backward needs neither x nor the projection output again
-        sform1 = _residual_sum_in_epilogue(Mq, d, d, nat)
-        # bf16 path: x1 = LN1(...) feeds the two feed-forward GEMMs (bf16 operand) and the residual of s2 = x1 + dropout(FFN): with
-        # the residual read from the bf16 copy as well (round 5) the LayerNorm writes 2 instead of 6 bytes per element and the
-        # FFN2 epilogue reads 2 instead of 4 -- the residual stream between LN1 and LN2 is bf16, as the GEMM operands already are
-        x1 = None if (nat and BF16_RESIDUAL) else torch.empty(Mq, d, dtype=torch.float32, device=dev)
+        # attention
+        att, attb, probs = _attention_fwd(r.att_fwd, qproj, qkv, qkv_tokens, e1, e2, M, d, L, f, H, p, s[0])
+        if nat and attb is None:
+            attb, att = cast_bf16(att), None            # the fp32 context is not kept for the backward on this path
+        # out-proj + LN1.  s1 = x + dropout(att Wo^T + bo): the residual sum is formed by the out-proj epilogue (bias -> dropout -> + x),
+        # so the LayerNorm kernels read ONE input stream and the backward needs neither x nor the projection output again
+        x1 = torch.empty(Mq, d, dtype=torch.float32, device=dev) if r.x1_f32 else None
         mean1 = torch.empty(Mq, dtype=torch.float32, device=dev)
         rstd1 = torch.empty(Mq, dtype=torch.float32, device=dev)
         x1b = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev) if nat else None
-        # ... and the residual sums s1, s2 themselves leave their GEMM epilogues in bf16: 2 instead of 4 bytes out of the epilogue,
-        # into the LayerNorm forward and into its backward (include/vqcpc.h: vqcpc_layernorm_fwd_xb16)
-        s16 = nat and BF16_RESIDUAL and BF16_SUMS
-        assert xb_in is None or s16
         if s16:
             s1 = (gemm_nt_bf16(attb, wo, bias=bo, drop_p=p, seed=s[1], add_b=xsb, out_f32=False, out_bf16=True) if xb_in is not None
                   else gemm_nt_bf16(attb, wo, bias=bo, drop_p=p, seed=s[1], add=xs, out_f32=False, out_bf16=True))
             hip.call('vqcpc_layernorm_fwd_xb16', s1, d, g1, be1, x1, x1b, mean1, rstd1, Mq, d, 1e-5)
-        elif sform1:
+        elif r.sform1:
             s1 = lin(attb if nat else att, wo, bias=bo, drop_p=p, seed=s[1], add=xs)
             hip.call('vqcpc_add_layernorm_fwd_b16', s1, d, None, g1, be1, x1, x1b, mean1, rstd1, Mq, d, 1e-5, 0.0, 0)
         else:           # s1 holds the projection output a; LayerNorm adds x and the dropout itself
             s1 = lin(att, wo, bias=bo)
             hip.call('vqcpc_add_layernorm_fwd_b16', xs, ldxs, s1, g1, be1, x1, x1b, mean1, rstd1, Mq, d, 1e-5, p, s[1])
-        h2b = None
+        # FFN + LN2
+        h2 = h2b = ctx.gate_mask = None
         if nat:     # the FFN hidden activation exists in bf16 only: FFN2, the backward gate and the weight gradient read it
             h2b = gemm_nt_bf16(x1b, w1, bias=b1, act=1, drop_p=p, seed=s[2], out_f32=False, out_bf16=True)
             s2 = (gemm_nt_bf16(h2b, w2, bias=b2, drop_p=p, seed=s[3], add_b=x1b, out_f32=not s16, out_bf16=s16) if x1 is None else
                   gemm_nt_bf16(h2b, w2, bias=b2, drop_p=p, seed=s[3], add=x1))
-            sform2 = True
-            h2 = att = x1b[:0]                       # placeholders in the saved list (never read on this path)
         else:
-            if gatebits_worthwhile(Mq, ffd, d):       # relu / dropout gate of the backward as a bit mask (1/32 of the bytes)
+            if r.gate_bits:
                 h2, ctx.gate_mask = gemm_nt_relu_mask(x1, w1, b1, drop_p=p, seed=s[2])
             else:
-                h2, ctx.gate_mask = gemm_nt(x1, w1, bias=b1, act=1, drop_p=p, seed=s[2]), None
-            sform2 = _residual_sum_in_epilogue(Mq, d, ffd, nat)
-            if sform2:
+                h2 = gemm_nt(x1, w1, bias=b1, act=1, drop_p=p, seed=s[2])
+            if r.sform2:
                 s2 = gemm_nt(h2, w2, bias=b2, drop_p=p, seed=s[3], add=x1)      # x1 + dropout(FFN(x1))
             else:
                 s2 = gemm_nt(h2, w2, bias=b2)                                   # FFN(x1): LayerNorm adds x1 and the dropout
-        y_carrier = bool(out_b16_only and s16 and BF16_ACT_STREAM)
-        y = None if y_carrier else torch.empty(Mq, d, dtype=torch.float32, device=dev)
+        y = None if r.y_carrier else torch.empty(Mq, d, dtype=torch.float32, device=dev)
         mean2 = torch.empty(Mq, dtype=torch.float32, device=dev)
         rstd2 = torch.empty(Mq, dtype=torch.float32, device=dev)
         yb = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev) if nat else None
         if s16:
             hip.call('vqcpc_layernorm_fwd_xb16', s2, d, g2, be2, y, yb, mean2, rstd2, Mq, d, 1e-5)
-            if y_carrier:
+            if r.y_carrier:
                 y = _bf16_act_carrier(yb)
-        elif sform2:
+        elif r.sform2:
             hip.call('vqcpc_add_layernorm_fwd_b16', s2, d, None, g2, be2, y, yb, mean2, rstd2, Mq, d, 1e-5, 0.0, 0)
         else:
             hip.call('vqcpc_add_layernorm_fwd_b16', x1, d, s2, g2, be2, y, yb, mean2, rstd2, Mq, d, 1e-5, p, s[3])
-        if nat:
-            if not y_carrier:
-                _attach_bf16_copy(y, yb)
-            # round 5: this layer's backward reads the gradient of y as bf16 (vqcpc_layernorm_bwd_b16io) when the consumer hands it
-            # over so -- the next layer's input-gradient GEMM then writes 2 instead of 4 bytes per element and LN2's backward reads 2
-            if s16 and BF16_GRAD_SUMS and BF16_GRAD_STREAM:
-                y._vqcpc_accepts_bf16_grad = True
-        ctx.dx_b16 = bool(nat and x_accepts_b16_grad and BF16_GRAD_SUMS and BF16_GRAD_STREAM)
-        ctx.x_b16_only = xb_in is not None
+        if nat and not r.y_carrier:
+            _attach_bf16_copy(y, yb)
+        if r.g16_stream:
+            y._vqcpc_accepts_bf16_grad = True
         if xb_in is not None:
             x = x[:0]                       # the carrier's values are never read: only its shape (ctx.x_shape)
         ctx.x_shape = (M, d)
         ctx.save_for_backward(x, qkv, qproj, probs, att, s1, x1, mean1, rstd1, h2, s2, mean2, rstd2, wqkv, wo, e1, e2, w1,
                               w2, g1, g2)
-        ctx.meta = (L, H, p, s, f, qkv_in is not None)
-        ctx.sform = (sform1, sform2)
+        ctx.meta = (L, H, p, s, f)
         ctx.bf16 = (xb, xsb, attb, x1b, h2b) if nat else None
         ctx.biases = (bqkv, bo, b1, b2)
         ctx.ln_betas = (be1, be2)
@@ -1520,57 +1606,25 @@ class EncoderLayerFn(torch.autograd.Function):
         if dy is None:
             dy = torch.zeros(s2.shape, dtype=torch.float32, device=s2.device)
         dyb = _bf16_grad_of(dy)              # the consumer's input gradient in bf16 (see _bf16_grad_carrier)
-        L, H, p, s, f, ext_qkv = ctx.meta
+        r = ctx.route
+        nat, need_dx, tok = r.nat, r.need_dx, ctx.qkv_tokens
+        L, H, p, s, f = ctx.meta
         bqkv, bo, b1, b2 = ctx.biases
         be1, be2 = ctx.ln_betas
         M, d = ctx.x_shape
-        if ctx.x_b16_only:                   # x existed in bf16 only (ctx.bf16 holds it): no fp32 rows to address
-            ldx, xs, ldxs = d, None, 0
+        if r.x_b16_only:                     # x existed in bf16 only (ctx.bf16 holds it): no fp32 rows to address
+            xs, ldxs = None, 0
         else:
             x, ldx = _rows(x)
             xs, ldxs = (x, ldx) if f == 1 else _rows(x[::f])
-        hd, nblk, dev = d // H, M // L, x.device
-        Mq = M // f
         dy = dyb if dyb is not None else dy.contiguous()
-
-        nat = ctx.bf16 is not None
-
-        def ln_bwd(dyv, xin, ldxin, r, gamma, beta, mean, rstd, seed, ds_bf16=False):
-            # r None: xin is the residual sum itself (s-form, include/vqcpc.h); the mask of d_r is regenerated from `seed`
-            # ds_bf16 (bf16 path, xin in bf16): the gradient of the residual branch leaves in bf16 only (returned in place of ds)
-            ds_bf16 = ds_bf16 and xin.dtype == torch.bfloat16
-            ds = None if ds_bf16 else torch.empty(Mq, d, dtype=torch.float32, device=dev)
-            dsb = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev) if ds_bf16 else None
-            # bf16 path: the gradient of the sub-layer output only feeds GEMMs, which read its bf16 copy -> no fp32 d_r stream
-            dr = torch.empty(Mq, d, dtype=torch.float32, device=dev) if (p > 0 and not nat) else None
-            drb = torch.empty(Mq, d, dtype=torch.bfloat16, device=dev) if nat else None    # GEMM-operand copy of dr
-            nbytes = hip.query('vqcpc_add_layernorm_bwd_workspace', Mq, d)
-            ws = hip.workspace(nbytes, dev)
-            if defer_ln_param_grads(ws, Mq, d, gamma, beta, r is not None):     # gamma / beta partial sums: reduced with all the others later
-                dg = db = None
-            else:
-                dg = torch.empty(d, dtype=torch.float32, device=dev)
-                db = torch.empty(d, dtype=torch.float32, device=dev)
-            if xin.dtype == torch.bfloat16:              # the residual sum was written in bf16 (s-form only)
-                assert r is None
-                # ... and the incoming gradient too where an input-gradient GEMM of this path produced it (round 5)
-                hip.call('vqcpc_layernorm_bwd_b16io' if dyv.dtype == torch.bfloat16 else 'vqcpc_layernorm_bwd_xb16', dyv, xin, ldxin,
-                         gamma, mean, rstd, ds, dsb, dr, drb, dg, db, Mq, d, p, seed, ws, nbytes)
-                if ds_bf16:
-                    ds = dsb
-            else:
-                assert dyv.dtype == torch.float32
-                hip.call('vqcpc_add_layernorm_bwd_b16', dyv, xin, ldxin, r, gamma, mean, rstd, ds, dr, drb, dg, db, Mq, d, p, seed,
-                         ws, nbytes)
-            return ds, (dr if dr is not None else (None if (nat and p > 0) else ds)), dg, db, drb
-
-        sform1, sform2 = ctx.sform
-        g16 = nat and BF16_GRAD_SUMS            # bf16 path: d s2 / d s1 only feed the residual operand of a dgrad epilogue -> bf16
-        if sform2:
-            ds2, df, dg2, dbe2, dfb = ln_bwd(dy, s2, d, None, g2, be2, mean2, rstd2, s[3], ds_bf16=g16)
-        else:
-            ds2, df, dg2, dbe2, dfb = ln_bwd(dy, x1, d, s2, g2, be2, mean2, rstd2, s[3])
         lin = gemm_nt_bf16 if nat else gemm_nt
+        # FFN + LN2
+        if r.sform2:
+            ds2, df, dg2, dbe2, dfb = _ln_bwd(('b16io' if dyb is not None else 'xb16') if r.s16 else 'add', dy, s2, d, None, g2, be2,
+                                              mean2, rstd2, p, s[3], nat, ds_bf16=r.g16)
+        else:
+            ds2, df, dg2, dbe2, dfb = _ln_bwd('add', dy, x1, d, s2, g2, be2, mean2, rstd2, p, s[3], nat)
         if nat:
             xb, xsb, attb, x1b, h2b = ctx.bf16
             # FFN: da = (df @ W2) * [h2 > 0] / (1 - p), bf16 only (it feeds two GEMMs and nothing else)
@@ -1578,12 +1632,11 @@ class EncoderLayerFn(torch.autograd.Function):
             dw2, db2 = wgrad(dfb, h2b, w2, b2)
             dw1, db1 = wgrad(da, x1b, w1, b1)
             # d x1 -- the gradient that enters LN1's backward -- in bf16 only where that kernel reads the residual sum in bf16 too
-            dx1_b16 = BF16_GRAD_STREAM and sform1 and ds2.dtype == torch.bfloat16 and s1.dtype == torch.bfloat16
-            dx1 = (gemm_nt_bf16(da, transpose(w1), add_b=ds2, out_f32=not dx1_b16, out_bf16=dx1_b16)
-                   if ds2.dtype == torch.bfloat16 else gemm_nt_bf16(da, transpose(w1), add=ds2))
+            dx1 = (gemm_nt_bf16(da, transpose(w1), add_b=ds2, out_f32=not r.g16_stream, out_bf16=r.g16_stream)
+                   if r.g16 else gemm_nt_bf16(da, transpose(w1), add=ds2))
         else:
             # FFN: da = (df @ W2) * [h2 > 0] / (1 - p)   (relu + dropout backward folded into the GEMM epilogue)
-            if ctx.gate_mask is not None:
+            if r.gate_bits:
                 da = gemm_nt_gatebits(df, transpose(w2), ctx.gate_mask, gate_scale=1.0 / (1.0 - p))
             else:
                 da = gemm_nt(df, transpose(w2), gate=h2, gate_scale=1.0 / (1.0 - p))
@@ -1591,94 +1644,24 @@ class EncoderLayerFn(torch.autograd.Function):
             dw1, db1 = wgrad(da, x1, w1, b1)
             dx1 = gemm_nt_residual(da, transpose(w1), ds2, res_may_alias=df)     # ds2 is dead afterwards
         del da, df, ds2
-        # d s1 is bf16 only where the dgrad of the in_proj consumes it here (the all-bf16 attention paths below)
-        g16_1 = (g16 and f == 1 and not ext_qkv and ctx.qkv_tokens is None and ATT_B16_OUT and ctx.needs_input_grad[0]
-                 and bool(hip.query('vqcpc_relattn16_b16_supported', L, H, hd) or hip.query('vqcpc_relattn_b16_supported', L, H, hd)))
-        if sform1:
-            ds1, dA, dg1, dbe1, dAb = ln_bwd(dx1, s1, d, None, g1, be1, mean1, rstd1, s[1], ds_bf16=g16_1)
+        # out-proj + LN1
+        if r.sform1:
+            ds1, dA, dg1, dbe1, dAb = _ln_bwd(('b16io' if r.g16_stream else 'xb16') if r.s16 else 'add', dx1, s1, d, None, g1, be1,
+                                              mean1, rstd1, p, s[1], nat, ds_bf16=r.g16_1)
         else:
-            ds1, dA, dg1, dbe1, dAb = ln_bwd(dx1, xs, ldxs, s1, g1, be1, mean1, rstd1, s[1])
-        b16_io = nat and f == 1 and qkv.dtype == torch.bfloat16       # the all-bf16 attention backward reads d ctx as bf16
+            ds1, dA, dg1, dbe1, dAb = _ln_bwd('add', dx1, xs, ldxs, s1, g1, be1, mean1, rstd1, p, s[1], nat)
+        b16_io = r.att_bwd == 'b16io'        # the all-bf16 attention backward reads d ctx as bf16
         if nat:
             dwo, dbo = wgrad(dAb, attb, wo, bo)
             datt = gemm_nt_bf16(dAb, transpose(wo), out_f32=not b16_io, out_bf16=b16_io)
         else:
             dwo, dbo = wgrad(dA, att, wo, bo)
             datt = gemm_nt(dA, transpose(wo))
-        de1 = torch.empty_like(e1)
-        de2 = torch.empty_like(e2)
-        need_dx = ctx.needs_input_grad[0]
-        if f == 1:
-            nbytes = hip.query('vqcpc_relattn_bwd_workspace', nblk, L, H, hd)
-            ws = hip.workspace(nbytes, dev)
-            tok = ctx.qkv_tokens
-            if (nat and not ext_qkv and tok is None and ATT_B16_OUT
-                    and hip.query('vqcpc_relattn16_b16_supported', L, H, hd)):
-                # bf16 path: d qkv only feeds the two GEMMs below -> written as bf16 by the attention backward itself
-                dqkvb = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dev)
-                if b16_io:
-                    hip.call('vqcpc_relattn16_bwd_b16io', datt, d, qkv, 3 * d, probs, e1, e2, dqkvb, 3 * d, de1, de2, nblk, H,
-                             hd, p, s[0], ws, nbytes)
-                else:
-                    hip.call('vqcpc_relattn16_bwd_b16', datt, d, qkv, 3 * d, None, probs, e1, e2, dqkvb, 3 * d, de1, de2, nblk,
-                             H, hd, p, s[0], ws, nbytes)
-                dwqkv, dbqkv = wgrad(dqkvb, xb, wqkv, bqkv)
-                dx = _dgrad_plus_residual_bf16(dqkvb, transpose(wqkv), ds1, carrier=ctx.dx_b16) if need_dx else None
-                de1, de2, dg1, dbe1, dg2, dbe2 = accumulate_small((e1, e2, g1, be1, g2, be2), (de1, de2, dg1, dbe1, dg2, dbe2))
-                return (dx, None, None, None, None, None, None, None, None, dwqkv, dbqkv, dwo, dbo, de1, de2, dw1, db1, dw2, db2, dg1,
-                        dbe1, dg2, dbe2)
-            if (nat and not ext_qkv and tok is None and ATT_B16_OUT and hip.query('vqcpc_relattn_b16_supported', L, H, hd)):
-                dqkvb = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dev)        # the other block lengths (L = 4)
-                hip.call('vqcpc_relattn_bwd_b16', datt, d, qkv, 3 * d, probs, e1, e2, dqkvb, 3 * d, de1, de2, nblk, L, H, hd, p,
-                         s[0], ws, nbytes)
-                dwqkv, dbqkv = wgrad(dqkvb, xb, wqkv, bqkv)
-                dx = _dgrad_plus_residual_bf16(dqkvb, transpose(wqkv), ds1, carrier=ctx.dx_b16) if need_dx else None
-                de1, de2, dg1, dbe1, dg2, dbe2 = accumulate_small((e1, e2, g1, be1, g2, be2), (de1, de2, dg1, dbe1, dg2, dbe2))
-                return (dx, None, None, None, None, None, None, None, None, dwqkv, dbqkv, dwo, dbo, de1, de2, dw1, db1, dw2, db2, dg1,
-                        dbe1, dg2, dbe2)
-            # bf16 path, block table (first layer): d q | k | v only feeds the segment sum below -> the attention backward writes it as
-            # bf16 (the rounding the in_proj's bf16 input-gradient operand would get anyway), the segment sum reads half the bytes
-            tab_b16 = (nat and tok is not None and ATT_B16_OUT and BF16_TAB_GRAD and L == 16 and qkv.shape[0] // L <= 80
-                       and bool(hip.query('vqcpc_relattn16_b16_supported', L, H, hd)))      # (80 tokens: the bf16 segment sum's LDS table)
-            dqkv = torch.empty(M, 3 * d, dtype=torch.bfloat16 if tab_b16 else torch.float32, device=dev)
-            if tok is not None:
-                if tab_b16:
-                    hip.call('vqcpc_relattn16_bwd_b16', datt, d, qkv, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, H, hd, p,
-                             s[0], ws, nbytes)
-                else:
-                    hip.call('vqcpc_relattn_tab_bwd', datt, d, qkv, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd,
-                             p, s[0], ws, nbytes)
-                vmax = qkv.shape[0] // L                                  # table gradient = segment sum of d qkv
-                d_in = torch.empty_like(qkv)
-                nb2 = hip.query('vqcpc_block_table_segsum_workspace', M, L, vmax, 3 * d)
-                ws2 = hip.workspace(nb2, dev)
-                hip.call('vqcpc_block_table_segsum_b16' if tab_b16 else 'vqcpc_block_table_segsum', dqkv, tok, d_in, M, L, vmax,
-                         3 * d, ws2, nb2)
-            else:
-                hip.call('vqcpc_relattn_bwd', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, s[0],
-                         ws, nbytes)
-                d_in = dqkv
-            if ext_qkv:          # projection lives outside: its gradient leaves through qkv_in, x keeps the residual path
-                de1, de2, dg1, dbe1, dg2, dbe2 = accumulate_small((e1, e2, g1, be1, g2, be2),
-                                                                  (de1, de2, dg1, dbe1, dg2, dbe2))
-                return (ds1 if need_dx else None, None, None, None, None, None, d_in, None, None, None, None, dwo, dbo, de1, de2, dw1,
-                        db1, dw2, db2, dg1, dbe1, dg2, dbe2)
-            if nat:
-                dqkvb = cast_bf16(dqkv)
-                dwqkv, dbqkv = wgrad(dqkvb, xb, wqkv, bqkv)
-                dx = gemm_nt_bf16(dqkvb, transpose(wqkv), add=ds1) if need_dx else None
-            else:
-                dwqkv, dbqkv = wgrad(dqkv, x, wqkv, bqkv)
-                dx = gemm_nt_residual(dqkv, transpose(wqkv), ds1, res_may_alias=dA) if need_dx else None
-        else:
-            nbytes = hip.query('vqcpc_relattn_sub_bwd_workspace', nblk, L, f, H, hd)
-            ws = hip.workspace(nbytes, dev)
-            sub_b16 = nat and ATT_B16_OUT and bool(hip.query('vqcpc_relattn_sub_b16_supported', L, f, H, hd))
-            dq = torch.empty(Mq, d, dtype=torch.float32, device=dev)
-            # bf16 path: d k | v (8 x the bytes of d q) only feeds GEMMs that read bf16 -> written so by the kernel
-            dkv = torch.empty(M, 2 * d, dtype=torch.bfloat16 if sub_b16 else torch.float32, device=dev)
-            hip.call('vqcpc_relattn_sub_bwd_b16' if sub_b16 else 'vqcpc_relattn_sub_bwd', datt, d, qproj, d, qkv, 2 * d, probs, e1,
-                     e2, dq, d, dkv, 2 * d, de1, de2, nblk, L, f, H, hd, p, s[0], ws, nbytes)
+        # attention, in-proj
+        dqkv, de1, de2 = _attention_bwd(r.att_bwd, datt, qproj, qkv, tok, probs, e1, e2, M, d, L, f, H, p, s[0])
+        d_in = dx = dwqkv = dbqkv = None
+        if f > 1:
+            dq, dkv = dqkv
             if nat:
                 dkv = cast_bf16(dkv)                                   # a no-op on a bf16 tensor
                 dwq, dbq = wgrad(cast_bf16(dq), xsb, wqkv, bqkv, rows=slice(0, d))
@@ -1686,18 +1669,34 @@ class EncoderLayerFn(torch.autograd.Function):
             else:
                 dwq, dbq = wgrad(dq, xs, wqkv, bqkv, rows=slice(0, d))
                 dwkv, dbkv = wgrad(dkv, x, wqkv, bqkv, rows=slice(d, 3 * d))
-            if dwq is None:
-                dwqkv = dbqkv = None                                       # accumulated in place into in_proj's gradient
-            else:
+            if dwq is not None:                                        # (None: accumulated in place into in_proj's gradient)
                 dwqkv, dbqkv = torch.cat([dwq, dwkv], dim=0), torch.cat([dbq, dbkv], dim=0)
-            dx = None
             if need_dx:
                 wt = transpose(wqkv)                                       # (d, 3d): columns q | k | v
                 dx = lin(dkv, wt[:, d:])                                   # every row: keys / values path
                 dxs = dx[::f]                                              # kept rows also get the query + residual paths
                 gemm_nt(dq, wt[:, :d], add=ds1, add2=dxs, out=dxs)
+        elif r.ext_qkv:          # projection lives outside: its gradient leaves through qkv_in, x keeps the residual path
+            d_in, dx = dqkv, (ds1 if need_dx else None)
+            if tok is not None:
+                vmax = qkv.shape[0] // L                                  # table gradient = segment sum of d qkv
+                d_in = torch.empty_like(qkv)
+                nb2 = hip.query('vqcpc_block_table_segsum_workspace', M, L, vmax, 3 * d)
+                ws2 = hip.workspace(nb2, d_in.device)
+                hip.call('vqcpc_block_table_segsum_b16' if r.tab_b16 else 'vqcpc_block_table_segsum', dqkv, tok, d_in, M, L, vmax,
+                         3 * d, ws2, nb2)
+        elif r.att_bwd in _ATT_B16_ROUTES:
+            dwqkv, dbqkv = wgrad(dqkv, xb, wqkv, bqkv)
+            dx = _dgrad_plus_residual_bf16(dqkv, transpose(wqkv), ds1, r.g16_1, r.dx_b16) if need_dx else None
+        elif nat:
+            dqkvb = cast_bf16(dqkv)
+            dwqkv, dbqkv = wgrad(dqkvb, xb, wqkv, bqkv)
+            dx = gemm_nt_bf16(dqkvb, transpose(wqkv), add=ds1) if need_dx else None
+        else:
+            dwqkv, dbqkv = wgrad(dqkv, x, wqkv, bqkv)
+            dx = gemm_nt_residual(dqkv, transpose(wqkv), ds1, res_may_alias=dA) if need_dx else None
         de1, de2, dg1, dbe1, dg2, dbe2 = accumulate_small((e1, e2, g1, be1, g2, be2), (de1, de2, dg1, dbe1, dg2, dbe2))
-        return (dx, None, None, None, None, None, None, None, None, dwqkv, dbqkv, dwo, dbo, de1, de2, dw1, db1, dw2, db2, dg1, dbe1,
+        return (dx, None, None, None, None, None, d_in, None, None, dwqkv, dbqkv, dwo, dbo, de1, de2, dw1, db1, dw2, db2, dg1, dbe1,
                 dg2, dbe2)
 
 
