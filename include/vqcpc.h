@@ -728,6 +728,19 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
  *   teacher[b * ldteach + pos].  Writes tokens[b * ldtok + pos], next_in row b = table row token * U + pos % U (the
  *   input of position pos + 1, decoders/decoder.py:_target_rows), optionally the filtered probabilities probs[b][0..V_c),
  *   and finally pos[0] = pos + 1.  Nothing happens once pos >= T.  M <= 64, nc <= 16, V_c <= 256, d <= 4096.
+ * vqcpc_decode_sample_constrained: vqcpc_decode_sample (the same kernel body, a compile-time flag) without teacher, with
+ *   seeds required, and three more things, all addressed at column col = pos (win == NULL) or win[1] * U + pos -- win[1]
+ *   (device int32) is the live window's first code as vqcpc_decode_window leaves it, the rule of vqcpc_decode_source_rows,
+ *   so constraint and logp are in chorale coordinates and one captured step or slide serves every window:
+ *     constraint[b * ldcons + col] (device int64, NULL = nothing forced): >= 0 is the token to emit, clamped to [0, V_c)
+ *       as teacher is; < 0 draws the token exactly as vqcpc_decode_sample does, keyed by (seeds[b], pos) -- forcing some
+ *       positions does not shift the draws of the others.  A forced token ignores exclude / top-k / top-p.
+ *     logp[b * ldlogp + col] (may be NULL) = logits[tok] - logsumexp(logits) over the voice's V_c columns for the emitted
+ *       token, forced or drawn: the model's UNMODIFIED distribution (temperature 1, no filter).  fp32, the maximum
+ *       subtracted, summed in an order that depends on the lane layout only (a row's value does not depend on M).
+ *     win[1] < 0: nothing is forced and no logp is written.  Likewise for a column col >= ldcons (free) / col >= ldlogp
+ *       (not written): the window index is not known to the host, which checks ldcons, ldlogp >= T only.
+ *   probs, next_in, tokens[b * ldtok + pos], pos[0] = pos + 1, the no-op once pos >= T and the limits are unchanged.
  *
  * Sliding-window generation (decoders/decoder.py:729-854): the window moves by one code, the caches of its P prefix rows
  * are rebuilt teacher-forced (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_block_table_gather for the row-wise parts).
@@ -763,6 +776,11 @@ int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_o
                         int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
                         int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,
                         int U, float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream);
+int vqcpc_decode_sample_constrained(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M,
+                                    float temperature, int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds,
+                                    const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
+                                    int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d, int U,
+                                    float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream);
 int vqcpc_decode_prefill_attn(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldk, float* k_cache,
                               float* v_cache, int64_t ldc, const float* e1, const float* e2, float* ctx, int64_t ldo, int64_t M,
                               int P, int Lk, int ratio, int H, int hd, int mask, void* stream);

@@ -14,6 +14,9 @@
 //   * vqcpc_decode_sample: temperature, exclusion mask, top-k, top-p, softmax and one counter-based draw per row; writes the
 //     token, the next step's input row (a row of the target table) and advances `pos`.  ONE workgroup: the position
 //     counter is read by every kernel of the step and written here once, after a barrier.
+//   * vqcpc_decode_sample_constrained: the same kernel body with a compile-time flag: per (row, position) a token to emit or a
+//     draw, and the emitted token's log-probability under the unfiltered row; both addressed in chorale coordinates through
+//     the device window index.
 //
 // Sliding-window generation (reference: decoder.py:729-854) moves the model window by one code at a time; the caches of
 // the new window's prefix are rebuilt by a teacher-forced pass over its P prefix rows (GEMMs + LayerNorm of the training
@@ -486,11 +489,19 @@ __device__ __forceinline__ float wave_incl_scan(float v, int lane) {
     return v;
 }
 
+// CONS (vqcpc_decode_sample_constrained): `teacher` is the constraint -- per (row, column) a token to emit, or < 0 for a draw --
+// and the emitted token's log-probability under the UNFILTERED row (temperature 1) goes to logp.  Both are addressed at column
+// col = pos (win == NULL) or win[1] * U + pos, the chorale coordinate of the live window's position: one captured step serves
+// every window.  A column outside [0, ldteach) / [0, ldlogp) is free / not written.  The log-sum-exp is a lane-serial sum of
+// four and a butterfly over the 64 lanes: its order depends on nothing but the lane layout, so a row's value is the same
+// whatever M.  Without CONS the kernel is what it was before the flag: none of the added code is instantiated.
+template <bool CONS>
 __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
     const float* __restrict__ logits, int64_t ldl, VoiceOffsets vo, int nc, int M, float temperature, int top_k, float top_p,
     const uint32_t* __restrict__ exclude, const int64_t* __restrict__ seeds, const int64_t* __restrict__ teacher,
     int64_t ldteach, int64_t* __restrict__ tokens, int64_t ldtok, int T, const float* __restrict__ table, int64_t table_rows,
-    int d, int U, float* __restrict__ next_in, int64_t ldn, float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp) {
+    int d, int U, float* __restrict__ next_in, int64_t ldn, float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp,
+    float* __restrict__ logp, int64_t ldlogp, const int32_t* __restrict__ win) {
     __shared__ float sl[kSampWaves][kDecMaxVocab];            // a wave's (filtered) logits
     __shared__ float srt[kSampWaves][kDecMaxVocab];           // top-p: probabilities in descending order, then their cumsum
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -499,16 +510,24 @@ __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
     const int c = live_pos ? pos % nc : 0;
     const int V = vo.off[c + 1] - vo.off[c];
     const float ninf = -INFINITY;
+    int64_t col = -1;                                         // CONS: the column of constraint / logp, < 0 = no live window
+    if constexpr (CONS) {
+        const int w0 = win ? win[1] : 0;
+        if (live_pos && w0 >= 0) col = (int64_t)w0 * U + pos;
+    }
     for (int r0 = 0; r0 < M; r0 += kSampWaves) {             // uniform trip count: every wave reaches every barrier
         const int b = r0 + wave;
         const bool act = live_pos && b < M;
         float l[4];
+        float raw[4] = {ninf, ninf, ninf, ninf};              // CONS: the row as the model gave it
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int i = 4 * lane + t;
             float v = ninf;
             if (act && i < V) {
-                v = logits[(int64_t)b * ldl + vo.off[c] + i] / temperature;
+                v = logits[(int64_t)b * ldl + vo.off[c] + i];
+                if constexpr (CONS) raw[t] = v;
+                v = v / temperature;
                 if (exclude && ((exclude[c * 8 + (i >> 5)] >> (i & 31)) & 1u)) v = ninf;
             }
             l[t] = v;
@@ -602,8 +621,12 @@ __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
                     if (4 * lane + t < V) probs[(int64_t)b * ldp + 4 * lane + t] = e[t] * inv;
             }
             int tok;
-            if (teacher) {
-                tok = (int)teacher[(int64_t)b * ldteach + pos];
+            int64_t forced = -1;
+            if constexpr (CONS) {
+                if (teacher && col >= 0 && col < ldteach) forced = teacher[(int64_t)b * ldteach + col];
+            }
+            if (CONS ? forced >= 0 : teacher != nullptr) {
+                tok = CONS ? (int)min(forced, (int64_t)kDecMaxVocab) : (int)teacher[(int64_t)b * ldteach + pos];
             } else {
                 const uint64_t sd = (uint64_t)seeds[b];
                 const uint32_t r = rng_u24_from_x0(rng_x0(sd, (uint32_t)pos), (uint32_t)(sd >> 32));
@@ -630,6 +653,19 @@ __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
             if (lane == 0) tokens[(int64_t)b * ldtok + pos] = tok;
             const int64_t row = min((int64_t)tok * U + pos % U, table_rows - 1);     // _target_rows: input of position pos + 1
             for (int k = lane; k < d; k += 64) next_in[(int64_t)b * ldn + k] = table[row * d + k];
+            if constexpr (CONS) {
+                if (logp && col >= 0 && col < ldlogp) {       // uniform: the shuffles below run in every lane or in none
+                    const float rmx = wave_max(fmaxf(fmaxf(raw[0], raw[1]), fmaxf(raw[2], raw[3])));
+                    float rs = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) rs += raw[t] > ninf ? expf(raw[t] - rmx) : 0.0f;
+                    rs = wave_sum(rs);
+                    const int tt = tok & 3;
+                    const float mine = tt == 0 ? raw[0] : tt == 1 ? raw[1] : tt == 2 ? raw[2] : raw[3];
+                    const float rt = __shfl(mine, tok >> 2, 64);
+                    if (lane == 0) logp[(int64_t)b * ldlogp + col] = (rt - rmx) - logf(rs);
+                }
+            }
         }
         __syncthreads();
     }
@@ -716,10 +752,43 @@ int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_o
     VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!teacher || ldteach >= T) && (!probs || ldp >= vmax),
                "decode_sample: bad leading dimensions");
     VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "decode_sample: the table has too few rows for V_c * U");
-    hipLaunchKernelGGL(decode_sample_kernel, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc, (int)M,
-                       temperature, top_k, top_p, exclude, seeds, teacher, ldteach, tokens, ldtok, T, table, table_rows, d, U,
-                       next_in, ldn, probs, ldp, pos);
+    hipLaunchKernelGGL(decode_sample_kernel<false>, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc,
+                       (int)M, temperature, top_k, top_p, exclude, seeds, teacher, ldteach, tokens, ldtok, T, table, table_rows,
+                       d, U, next_in, ldn, probs, ldp, pos, (float*)nullptr, (int64_t)0, (const int32_t*)nullptr);
     VQ_CHECK_LAUNCH("decode_sample");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_sample_constrained(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M,
+                                    float temperature, int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds,
+                                    const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
+                                    int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d, int U,
+                                    float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream) {
+    VQ_REQUIRE(logits && voice_offsets && seeds && tokens && table && next_in && pos && nc >= 1 && nc <= kDecMaxVoices && M >= 1 &&
+               M <= kDecMaxRows && T >= 1 && d >= 1 && d <= kDecMaxDim && U >= 1 && table_rows >= 1,
+               "decode_sample_constrained: bad arguments (seeds needed, 1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)");
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "decode_sample_constrained: temperature > 0, top_k >= 0");
+    VoiceOffsets vo;
+    vo.off[0] = voice_offsets[0];
+    VQ_REQUIRE(vo.off[0] >= 0, "decode_sample_constrained: negative voice offset");
+    int vmax = 0;
+    for (int c = 0; c < nc; ++c) {
+        const int V = voice_offsets[c + 1] - voice_offsets[c];
+        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "decode_sample_constrained: voice %d has %d tokens (1 <= V_c <= 256)", c, V);
+        vo.off[c + 1] = voice_offsets[c + 1];
+        vmax = std::max(vmax, V);
+    }
+    for (int c = nc + 1; c <= kDecMaxVoices; ++c) vo.off[c] = vo.off[nc];
+    // the window index lives on the device: with win the host can only ask for one window's columns, and the kernel
+    // treats a column at or past the leading dimension as free / does not write it
+    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!constraint || ldcons >= T) && (!logp || ldlogp >= T) &&
+               (!probs || ldp >= vmax), "decode_sample_constrained: bad leading dimensions (ldcons, ldlogp >= T)");
+    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows,
+               "decode_sample_constrained: the table has too few rows for V_c * U");
+    hipLaunchKernelGGL(decode_sample_kernel<true>, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc,
+                       (int)M, temperature, top_k, top_p, exclude, seeds, constraint, ldcons, tokens, ldtok, T, table,
+                       table_rows, d, U, next_in, ldn, probs, ldp, pos, logp, ldlogp, win);
+    VQ_CHECK_LAUNCH("decode_sample_constrained");
     return VQCPC_OK;
 }
 

@@ -311,30 +311,71 @@ class Decoder(FlatTraining, nn.Module):
         """:723-726: an all-zero (1, num_events, num_channels) token tensor on the device."""
         return torch.zeros(1, num_events, self.num_channels, dtype=torch.int64, device=self.sos.device)
 
+    def _keep_voices(self, keep_voices):
+        """keep_voices -> sorted voice indices (ValueError outside [0, channels))."""
+        voices = sorted({int(v) for v in keep_voices})
+        if any(not 0 <= v < self.num_channels for v in voices):
+            raise ValueError(f'keep_voices: voice indices in [0, {self.num_channels}) expected, got {list(keep_voices)}')
+        return voices
+
+    def _constraint_rows(self, constraint, rows, events, first=0, last=None):
+        """A public constraint (rows, events, channels) int64, -1 = free -> (rows, events * channels) int64 on the device,
+        position-major, with the events outside [first, last) freed.  ValueError on a wrong shape or dtype and -- one host
+        check per call -- on a forced token outside its voice's vocabulary."""
+        constraint = torch.as_tensor(constraint)
+        nc = self.num_channels
+        if tuple(constraint.shape) != (rows, events, nc) or constraint.dtype != torch.int64:
+            raise ValueError(f'constraint: ({rows}, {events}, {nc}) int64 expected (-1 = free), got {tuple(constraint.shape)} '
+                             f'{constraint.dtype}')
+        constraint = constraint.to(self.sos.device).clone()
+        constraint[:, :first] = -1
+        if last is not None:
+            constraint[:, last:] = -1
+        vocab = torch.tensor([int(v) for v in self.num_tokens_per_channel], dtype=torch.int64, device=constraint.device)
+        if bool((constraint >= vocab).any()):
+            raise ValueError(f'constraint: a forced token is outside its voice\'s vocabulary {vocab.tolist()}')
+        return constraint.reshape(rows, events * nc)
+
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
-                            use_graph=True):
+                            use_graph=True, constraint=None, return_logp=False):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
         temperature / top-k / top-p rule (utils.py:101-128) on the GPU.
         exclude_tokens: per voice, token ids never drawn (the meta symbols of exclude_meta_symbols); seed: an int (per-row
         seeds derived from it), a per-row int64 tensor, or None (drawn from torch's generator).  use_graph=False runs the
-        steps eagerly (same tokens).  -> int64 tokens (B * num_decodings, events, channels) on the device."""
+        steps eagerly (same tokens).  -> int64 tokens (B * num_decodings, events, channels) on the device.
+        constraint: (B, events, channels) int64, a token >= 0 is emitted at its place (also one listed in exclude_tokens),
+        -1 leaves it to the sampler; rows are repeated with num_decodings like the codes.  The free positions draw what
+        they would draw without the constraint given the same prefix (the draw is keyed by seed and position).
+        return_logp=True -> (tokens, logp): logp float32 of the tokens' shape, every emitted token's log-probability
+        under the model's unfiltered distribution (temperature 1, no top-k / top-p / exclusion)."""
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
         codes = self._source_on_device(codes, 'codes', self.num_tokens_source)
+        T, nc = self.num_tokens_target, self.num_channels
+        if constraint is not None:
+            constraint = self._constraint_rows(constraint, codes.shape[0], T // nc)
         if num_decodings > 1:
             codes = codes.repeat_interleave(num_decodings, dim=0)
-        B, T, nc = codes.shape[0], self.num_tokens_target, self.num_channels
+            if constraint is not None:
+                constraint = constraint.repeat_interleave(num_decodings, dim=0)
+        B = codes.shape[0]
         seeds = row_seeds(seed, B)
+        logp = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logp else None
 
         def chunk(n, rows):
             inc = IncrementalDecoder(self, n)
             inc.prefill(codes[rows])
-            inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens)
-            return inc.run(use_graph=use_graph)
-        return generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
+            inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens,
+                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp)
+            tokens = inc.run(use_graph=use_graph)
+            if return_logp:
+                logp[rows] = inc.logp
+            return tokens
+        tokens = generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
+        return (tokens, logp.view(B, T // nc, nc)) if return_logp else tokens
 
     def _source_on_device(self, source, name, length=None):
         source = torch.as_tensor(source)
@@ -351,17 +392,19 @@ class Decoder(FlatTraining, nn.Module):
         return [[n2i[c][s] for s in syms if s in n2i[c]] for c in range(self.num_channels)]
 
     def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
-                 plot_attentions=False, code_juxtaposition=False, seed=None):
+                 plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None):
         """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
         code_juxtaposition) as the reference writes them.  Returns {'original', 'generation', 'codes', 'recoding'} tensors
         instead of music21 scores (no score writing here).  seed: as generate_from_codes.  A continuous decoder returns
-        the latents as 'codes', 'recoding' None and writes no file (:674-701)."""
+        the latents as 'codes', 'recoding' None and writes no file (:674-701).  keep_voices: voice indices whose tokens
+        are forced to the seed chorale's (`generate_from_codes(constraint=...)`): the other voices are written around them."""
         if plot_attentions:
             raise NotImplementedError('plot_attentions: attention plots need the full forward per token (matplotlib); '
                                       'not available on the incremental path')
         exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
+        voices = None if keep_voices is None else self._keep_voices(keep_voices)
         generator_train, generator_val, _ = self.dataloader_generator.dataloaders(batch_size=1, shuffle_val=True)
         if seed_set == 'val':
             stream = generator_val
@@ -382,8 +425,12 @@ class Decoder(FlatTraining, nn.Module):
         self.eval()
         try:
             codes = self.encode(x_original)
+            constraint = None
+            if voices is not None:
+                constraint = torch.full_like(x_original, -1)
+                constraint[:, :, voices] = x_original[:, :, voices]
             x = self.generate_from_codes(codes, temperature=temperature, top_k=top_k, top_p=top_p, exclude_tokens=exclude,
-                                         seed=seed)
+                                         seed=seed, constraint=constraint)
             recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
             self.train(was_training)
@@ -442,7 +489,7 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate_from_code_long(self, encoding_indices=None, temperature=None, top_k=0, top_p=1., exclude_meta_symbols=False,
                                 num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
-                                use_graph=True):
+                                use_graph=True, constraint=None, return_logp=False):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -455,7 +502,11 @@ class Decoder(FlatTraining, nn.Module):
         token, an all-PAD chorale and an empty first prefill); exclude_meta_symbols=True is honoured as in `generate` (the
         reference ignores it, its code is commented out, :786-793; the default False is its behaviour).  pad / start: see
         `init_generation_chorale`.  seed: as `generate_from_codes`; a row's draw is a function of (row seed, absolute
-        chorale position).  A bare call without codes raises NotImplementedError, as before this method existed."""
+        chorale position).  A bare call without codes raises NotImplementedError, as before this method existed.
+        constraint: (B, nb * events_per_code, channels) int64 over the WHOLE code sequence, in chorale coordinates: a token
+        >= 0 is emitted at its place, -1 is free; events outside [code_index_start, code_index_end) are ignored.  Rows are
+        repeated with num_decodings.  return_logp=True -> (tokens, logp), logp float32 of the tokens' shape (see
+        `generate_from_codes`)."""
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
@@ -474,18 +525,28 @@ class Decoder(FlatTraining, nn.Module):
         epc = self.num_events_per_code
         exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
         chorale = self.init_generation_chorale(num_events=nb * epc, start_index=code_index_start * epc, pad=pad, start=start)
+        if constraint is not None:
+            constraint = self._constraint_rows(constraint, codes.shape[0], nb * epc, code_index_start * epc, code_index_end * epc)
         if num_decodings > 1:
             codes = codes.repeat_interleave(num_decodings, dim=0)
+            if constraint is not None:
+                constraint = constraint.repeat_interleave(num_decodings, dim=0)
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
+        logp = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_logp else None
 
         def chunk(n, rows):
             inc = IncrementalDecoder(self, n)
             inc.start_long(codes[rows], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[rows], temperature=temperature,
-                           top_k=top_k, top_p=top_p, exclude=exclude)
-            return inc.run_long(code_index_start, code_index_end, use_graph=use_graph)
+                           top_k=top_k, top_p=top_p, exclude=exclude,
+                           constraint=None if constraint is None else constraint[rows], want_logp=return_logp)
+            tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph)
+            if return_logp:
+                logp[rows] = inc.logp
+            return tokens
         out = generate_in_chunks(self, B, nb * U, chunk)
-        return out.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
+        cut = lambda t: t.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
+        return (cut(out), cut(logp)) if return_logp else cut(out)
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent
@@ -506,13 +567,18 @@ class Decoder(FlatTraining, nn.Module):
                                             code_index_start=len(start_codes),
                                             code_index_end=len(start_codes) + len(body_codes), **kwargs)
 
-    def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False, **kwargs):
+    def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False,
+                           keep_voices=None, return_logp=False, **kwargs):
         """The body of generate_reharmonisation (:871-941) on a (1, events, channels) token tensor: the chorale is cut into
         model-sized chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD),
         every chunk is encoded, the codes are glued and the chorale's own codes are decoded `num_reharmonisations` times.
         Needs the dataset's START / END / XX symbols.  -> int64 (num_reharmonisations, events', channels), or with
         return_bounds=True (tokens, code_index_start, code_index_end, number of codes).  kwargs go to
-        `generate_from_code_long`."""
+        `generate_from_code_long`.
+        keep_voices: voice indices whose tokens are forced to x's -- harmonising a given melody is keep_voices=(0,).  Event
+        e of x sits at chorale event E + e (after the PAD...START chunk); everything else, the END / PAD completion
+        included, stays free, so events [0, x.shape[1]) of the kept voices come back equal to x.  return_logp=True: `tokens`
+        above is the pair (tokens, logp) of `generate_from_code_long`."""
         n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
         if n2i is None:
             raise ValueError('reharmonise_tokens needs dataset.note2index_dicts with the START / END / XX symbols')
@@ -520,6 +586,14 @@ class Decoder(FlatTraining, nn.Module):
         x = torch.as_tensor(x).long().cpu()
         if x.dim() != 3 or x.shape[0] != 1 or x.shape[2] != nc or x.shape[1] < 1:
             raise ValueError(f'x: (1, events, {nc}) tokens expected, got {tuple(x.shape)}')
+        voices = None if keep_voices is None else self._keep_voices(keep_voices)
+        if voices is not None and kwargs.get('constraint') is not None:
+            raise ValueError('reharmonise_tokens: keep_voices builds the constraint; pass one of the two')
+        kept = None
+        if voices is not None:                           # checked before the encoder embeds x
+            kept = torch.full_like(x, -1)
+            kept[:, :, voices] = x[:, :, voices]
+            self._constraint_rows(kept, 1, x.shape[1])
         PAD, START, END = ([int(n2i[c][sym]) for c in range(nc)] for sym in ('XX', 'START', 'END'))
         row = lambda ids, n: torch.tensor(ids, dtype=torch.int64).view(1, 1, nc).repeat(1, n, 1)
         x_chunks = list(x.split(E, 1))
@@ -542,9 +616,13 @@ class Decoder(FlatTraining, nn.Module):
         U = self.total_upscaling
         code_index_start = start_chunk.size(1) * nc // U
         code_index_end = codes.size(1) - (end_chunk.size(1) + completion_length) * nc // U
+        if voices is not None:
+            constraint = torch.full((1, codes.size(1) * self.num_events_per_code, nc), -1, dtype=torch.int64)
+            constraint[:, E:E + x.shape[1]] = kept
+            kwargs['constraint'] = constraint
         tokens = self.generate_from_code_long(codes, temperature=temperature, top_k=top_k, top_p=top_p,
                                               num_decodings=num_reharmonisations, code_index_start=code_index_start,
-                                              code_index_end=code_index_end, **kwargs)
+                                              code_index_end=code_index_end, return_logp=return_logp, **kwargs)
         return (tokens, code_index_start, code_index_end, codes.size(1)) if return_bounds else tokens
 
     def generate_reharmonisation(self, *a, **k):

@@ -9,7 +9,10 @@ this module adds what the decoder has on top of it:
   one [sum V_c, d] weight.
 
   the step's cross hook (csrc/decode.hip, 11 launches per layer + 2 in all): cross q -> cross-attention on the memory's k | v
-  -> out_proj + residual -> add & LayerNorm;  and vqcpc_decode_sample, which draws the token of position pos.
+  -> out_proj + residual -> add & LayerNorm;  and vqcpc_decode_sample, which draws the token of position pos.  With a
+  constraint or token scores (`start(constraint=..., want_logp=...)`) the sampler is vqcpc_decode_sample_constrained: the same
+  kernel body, which emits the given token where the constraint holds one and writes the emitted token's log-probability; it
+  reads both at the position's CHORALE column through the device window index, so nothing else of the step or slide changes.
 
 Long mode (reference: generate_from_code_long, decoder.py:729-854, one full forward on the moved window per token): a code
 sequence of any length nb >= S is decoded by sliding the window one code at a time.  The chorale (M, nb * U) and the codes
@@ -79,6 +82,7 @@ class IncrementalDecoder(IncrementalStack):
         self.tokens = torch.zeros(M, self.T, dtype=torch.int64, device=dev)
         self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
         self.memkv = None
+        self.constraint, self.logp, self.constrained = None, None, False
         self.continuous = bool(getattr(dec, 'continuous_source', False))
         if self.continuous:
             self.dz = dec.source_dim
@@ -125,10 +129,14 @@ class IncrementalDecoder(IncrementalStack):
         for lay, kv in zip(self.layers, self.memkv):                                    # (M * S, 2d): k | v
             ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:], out=kv)
 
-    def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False):
+    def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
+              constraint=None, want_logp=False):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
-        probabilities of the last step in `probs` (M, max V_c)."""
+        probabilities of the last step in `probs` (M, max V_c).
+        constraint: (M, T) int64, a token >= 0 is emitted at its position, < 0 leaves the draw free; want_logp: keep every
+        emitted token's log-probability under the unfiltered distribution in `logp` (M, T) float32, NaN where no token was
+        emitted yet.  Either one switches the step's sampler to vqcpc_decode_sample_constrained."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
@@ -145,12 +153,33 @@ class IncrementalDecoder(IncrementalStack):
         else:
             self.teacher = None
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
+        self._constrain(constraint, want_logp, self.T, None)
         self.reset()
+
+    def _constrain(self, constraint, want_logp, width, win):
+        """The constrained sampler's buffers, (M, width) each: width = T and win = None for the fixed window, width = nb * U and
+        win = the device window index in long mode (chorale coordinates)."""
+        if (constraint is not None or want_logp) and self.teacher is not None:
+            raise ValueError('constraint / want_logp and teacher exclude each other (an all-forced constraint is teacher forcing)')
+        if constraint is not None:
+            if tuple(constraint.shape) != (self.M, width) or constraint.dtype != torch.int64:
+                raise ValueError(f'constraint: ({self.M}, {width}) int64 expected, got {tuple(constraint.shape)} '
+                                 f'{constraint.dtype}')
+            constraint = constraint.to(self.dev).contiguous()
+        self.constraint = constraint
+        self.logp = torch.full((self.M, width), float('nan'), dtype=torch.float32, device=self.dev) if want_logp else None
+        self.constrained = constraint is not None or want_logp
+        self._cons_width, self._cons_win = width, win
 
     def reset(self):
         self.pos.zero_()
         self.tokens.zero_()
         self.x.copy_(self.table[-1].expand(self.M, self.d))                            # start-of-sentence row
+        self._forget_logp()
+
+    def _forget_logp(self):
+        if self.logp is not None:
+            self.logp.fill_(float('nan'))                                               # what a warm-up step wrote
 
     # ---- one step: the cross hooks and the sampler ----------------------------------------------------------------------
     def _cross_attention(self, li, lay):
@@ -171,6 +200,13 @@ class IncrementalDecoder(IncrementalStack):
 
     def _sample(self):
         T, d = self.T, self.d
+        if self.constrained:
+            w = self._cons_width
+            hip.call('vqcpc_decode_sample_constrained', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M,
+                     self.temperature, self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds,
+                     self.constraint, w, self.logp, w, self._cons_win, self.tokens, T, T, self.table, self.table.shape[0], d,
+                     self.U, self.x, d, self.probs, self.vmax, self.pos)
+            return
         hip.call('vqcpc_decode_sample', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.temperature,
                  self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds, self.teacher, T, self.tokens, T, T,
                  self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
@@ -194,10 +230,12 @@ class IncrementalDecoder(IncrementalStack):
 
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
-    def start_long(self, codes_full, chorale, seeds=None, **sampling):
+    def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
-        tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  sampling: the
-        keywords of `start`."""
+        tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
+        want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
+        live window's chorale column (the device window index), so the captured step and slide serve every window.
+        sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
         if self.continuous:
@@ -220,6 +258,7 @@ class IncrementalDecoder(IncrementalStack):
         if self.continuous:
             self.z_full, self.z_nb = z_full, nb
         self.start(seeds=seeds, **sampling)
+        self._constrain(constraint, want_logp, nb * U, self.win)
         self.row_seeds.copy_(self.seeds)
 
     def _window(self, P, advance):
@@ -287,6 +326,7 @@ class IncrementalDecoder(IncrementalStack):
                 self.slide(tb0, tr_mid)
                 slide_graph = self.capture(lambda: self.slide(None, tr_mid, advance=1))
             self.chorale.copy_(chorale0)          # the warm-up launches drew and committed tokens: start again
+            self._forget_logp()
             self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
         live = None
         for _, tb, _, tr in plan:
