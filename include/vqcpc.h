@@ -721,6 +721,14 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
  *   bias q.e1[h, Lk-1-(pos-j)].  Cross mode (k_new == NULL): the Lk cached memory rows, p = pos / ratio, mask 0 none /
  *   1 causal (j <= p) / 2 anticausal (j >= p), bias of vqcpc_relattn_x_fwd.  q unscaled; ctx [M][ldo].  hd in
  *   {16, 32, 64, 128}, Lk <= 1024, no dropout.
+ * vqcpc_decode_attn_probs: vqcpc_decode_attn (the same kernel body, a compile-time flag; ctx and the cache rows have the same
+ *   bits) which also writes the row of attention probabilities it multiplies V by: probs is [M][H][rows][ldp] float32,
+ *   ldp >= Lk, and a live launch (0 <= pos, p < Lk) writes probs[b][h][r][j] for every j in [0, Lk) at row r = pos (win ==
+ *   NULL) or r = win[1] * win_stride + pos -- the rule of vqcpc_decode_sample_constrained's column, so with win_stride = U the
+ *   rows are chorale positions and one captured step serves every window.  The value is exp(s_j - max) / sum as the kernel
+ *   holds it, +0.0f for a masked key and, in self mode, for j > pos.  Columns [Lk, ldp) and every other row are never
+ *   touched.  With r outside [0, rows), or no live window (win[1] < 0), no probability is written and ctx and the cache rows
+ *   are still produced; a dead launch writes nothing at all.  rows >= 1; win_stride >= 1 when win is given.
  * vqcpc_decode_sample: one step's tail, ONE workgroup.  voice c = pos % nc; voice_offsets (HOST int32 [nc + 1]) give its
  *   logits columns.  Per row b: logits / temperature, tokens whose bit is set in exclude[c][8] (device uint32, NULL =
  *   none) to -inf, top-k (drop logits < the k-th largest; 0 = off), top-p (utils.py:116-126; top_p <= 0 or >= 1 = off),
@@ -772,6 +780,10 @@ int vqcpc_decode_linear(const float* x, int64_t ldx, const int64_t* gather, cons
 int vqcpc_decode_attn(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
                       const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
                       const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, void* stream);
+int vqcpc_decode_attn_probs(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
+                            const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
+                            const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, float* probs, int64_t ldp,
+                            int64_t rows, const int32_t* win, int win_stride, void* stream);
 int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
                         int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
                         int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,

@@ -11,6 +11,9 @@
 //   * vqcpc_decode_attn: one query row per (sequence, head) against the layer's K/V cache (self: the step's k / v row is
 //     stored at row `pos` first; causal) or the memory's K/V (cross: the rectangular rule of vqcpc_relattn_x_fwd).
 //     `pos` is read from device memory, so a captured step is position-independent.
+//   * vqcpc_decode_attn_probs: the same kernel body with a compile-time flag: the normalised attention row -- the very
+//     sc[j] * inv the P.V product multiplies by -- is also written out, one coalesced store of Lk floats per (sequence, head),
+//     at the row of the position's CHORALE coordinate (the device window index, as the constrained sampler's column).
 //   * vqcpc_decode_sample: temperature, exclusion mask, top-k, top-p, softmax and one counter-based draw per row; writes the
 //     token, the next step's input row (a row of the target table) and advances `pos`.  ONE workgroup: the position
 //     counter is read by every kernel of the step and written here once, after a barrier.
@@ -157,14 +160,19 @@ __device__ __forceinline__ void dot_rows(const float* __restrict__ qs, const flo
     s_e = e;
 }
 
-template <int HD>
+// PROBS (vqcpc_decode_attn_probs): the row of probabilities goes to probs[b][h][r][0 .. Lk), r = pos (win == NULL) or
+// win[1] * win_stride + pos; no live window (win[1] < 0) or r outside [0, rows): nothing is written, ctx and the cache rows are
+// produced as usual.  Every thread stores the keys it owns in the score loop (j = tid, tid + 256, ...): it reads back its own
+// sc[j], no barrier is needed.  Without PROBS the kernel is what it was before the flag: none of the added code is instantiated.
+template <int HD, bool PROBS>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const float* __restrict__ q, int64_t ldq, float* __restrict__ kc,
                                                           float* __restrict__ vc, int64_t ldc,
                                                           const float* __restrict__ knew, const float* __restrict__ vnew,
                                                           int64_t ldn, const float* __restrict__ e1,
                                                           const float* __restrict__ e2, float* __restrict__ ctx, int64_t ldo,
                                                           const int32_t* __restrict__ posp, int Lk, int ratio, int H,
-                                                          int mask, float scale) {
+                                                          int mask, float scale, float* __restrict__ probs, int64_t ldp,
+                                                          int64_t rows, const int32_t* __restrict__ win, int win_stride) {
     constexpr int G = 1024 / HD;                             // key groups of the P.V product
     __shared__ __attribute__((aligned(16))) float qs[HD];
     __shared__ float sc[kDecMaxLk];
@@ -211,6 +219,14 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const float* __restric
         sum += e;
     }
     const float inv = 1.0f / block_sum256(sum, red);
+    if constexpr (PROBS) {
+        const int w0 = win ? win[1] : 0;
+        const int64_t r = win ? (int64_t)w0 * win_stride + pos : (int64_t)pos;
+        if (w0 >= 0 && r >= 0 && r < rows) {                 // uniform
+            float* pr = probs + ((b * H + h) * rows + r) * ldp;
+            for (int j = tid; j < Lk; j += 256) pr[j] = sc[j] * inv;     // masked keys and (self) j > pos: 0.0f * inv == +0
+        }
+    }
     // ctx[c] = sum_j p_j v_j[c]: thread (g, c4) owns columns 4c4 .. 4c4 + 3 and keys j = g, g + G, ...  (eight in flight);
     // the G partial sums are added in group order
     const int c4 = tid % (HD / 4), g = tid / (HD / 4);
@@ -698,35 +714,64 @@ int vqcpc_decode_linear(const float* x, int64_t ldx, const int64_t* gather, cons
     return VQCPC_OK;
 }
 
-int vqcpc_decode_attn(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
-                      const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
-                      const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, void* stream) {
+// the two attention entry points share their checks and their launch; `name` is the one the caller's errors carry
+static int decode_attn_launch(const char* name, const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc,
+                              const float* k_new, const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx,
+                              int64_t ldo, const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, bool want_probs,
+                              float* probs, int64_t ldp, int64_t rows, const int32_t* win, int win_stride, void* stream) {
     VQ_REQUIRE(q && k_cache && v_cache && e1 && e2 && ctx && pos && M >= 1 && M <= kDecMaxRows && Lk >= 1 && Lk <= kDecMaxLk &&
                ratio >= 1 && H >= 1 && mask >= 0 && mask <= 2,
-               "decode_attn: bad arguments (1 <= M <= 64, 1 <= Lk <= 1024, mask in {0, 1, 2})");
-    VQ_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "decode_attn: hd must be 16, 32, 64 or 128 (got %d)", hd);
+               "%s: bad arguments (1 <= M <= 64, 1 <= Lk <= 1024, mask in {0, 1, 2})", name);
+    VQ_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "%s: hd must be 16, 32, 64 or 128 (got %d)", name, hd);
     const int64_t d = (int64_t)H * hd;
     VQ_REQUIRE(ldq >= d && ldc >= d && ldo >= d && ldq % 4 == 0 && ldc % 4 == 0 && aligned16(q) && aligned16(k_cache) &&
-               aligned16(e1) && aligned16(e2), "decode_attn: bad leading dimensions or alignment");
-    VQ_REQUIRE((k_new == nullptr) == (v_new == nullptr), "decode_attn: k_new and v_new go together");
+               aligned16(e1) && aligned16(e2), "%s: bad leading dimensions or alignment", name);
+    VQ_REQUIRE((k_new == nullptr) == (v_new == nullptr), "%s: k_new and v_new go together", name);
     if (k_new)
         VQ_REQUIRE(mask == 1 && ratio == 1 && ldn >= d && ldn % 4 == 0 && aligned16(k_new),
-                   "decode_attn: self mode (k_new given) is causal with ratio 1");
+                   "%s: self mode (k_new given) is causal with ratio 1", name);
+    if (want_probs)
+        VQ_REQUIRE(probs && ldp >= Lk && rows >= 1 && (!win || win_stride >= 1),
+                   "%s: probs [M][H][rows][ldp] needs probs != NULL, ldp >= Lk, rows >= 1 (and win_stride >= 1 with win)", name);
     const float scale = 1.0f / sqrtf((float)hd);
     const dim3 grid((unsigned)(M * H)), block(256);
     hipStream_t s = (hipStream_t)stream;
-#define DEC_ATTN(HD)                                                                                                           \
-    hipLaunchKernelGGL(decode_attn_kernel<HD>, grid, block, 0, s, q, ldq, k_cache, v_cache, ldc, k_new, v_new, ldn, e1, e2,   \
-                       ctx, ldo, pos, Lk, ratio, H, mask, scale)
-    switch (hd) {
-        case 16: DEC_ATTN(16); break;
-        case 32: DEC_ATTN(32); break;
-        case 64: DEC_ATTN(64); break;
-        default: DEC_ATTN(128); break;
+#define DEC_ATTN(HD, PROBS)                                                                                                    \
+    hipLaunchKernelGGL((decode_attn_kernel<HD, PROBS>), grid, block, 0, s, q, ldq, k_cache, v_cache, ldc, k_new, v_new, ldn,   \
+                       e1, e2, ctx, ldo, pos, Lk, ratio, H, mask, scale, probs, ldp, rows, win, win_stride)
+    if (want_probs) {
+        switch (hd) {
+            case 16: DEC_ATTN(16, true); break;
+            case 32: DEC_ATTN(32, true); break;
+            case 64: DEC_ATTN(64, true); break;
+            default: DEC_ATTN(128, true); break;
+        }
+    } else {
+        switch (hd) {
+            case 16: DEC_ATTN(16, false); break;
+            case 32: DEC_ATTN(32, false); break;
+            case 64: DEC_ATTN(64, false); break;
+            default: DEC_ATTN(128, false); break;
+        }
     }
 #undef DEC_ATTN
-    VQ_CHECK_LAUNCH("decode_attn");
+    VQ_CHECK_LAUNCH(name);
     return VQCPC_OK;
+}
+
+int vqcpc_decode_attn(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
+                      const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
+                      const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, void* stream) {
+    return decode_attn_launch("decode_attn", q, ldq, k_cache, v_cache, ldc, k_new, v_new, ldn, e1, e2, ctx, ldo, pos, M, Lk, ratio,
+                              H, hd, mask, false, nullptr, 0, 0, nullptr, 0, stream);
+}
+
+int vqcpc_decode_attn_probs(const float* q, int64_t ldq, float* k_cache, float* v_cache, int64_t ldc, const float* k_new,
+                            const float* v_new, int64_t ldn, const float* e1, const float* e2, float* ctx, int64_t ldo,
+                            const int32_t* pos, int64_t M, int Lk, int ratio, int H, int hd, int mask, float* probs, int64_t ldp,
+                            int64_t rows, const int32_t* win, int win_stride, void* stream) {
+    return decode_attn_launch("decode_attn_probs", q, ldq, k_cache, v_cache, ldc, k_new, v_new, ldn, e1, e2, ctx, ldo, pos, M, Lk,
+                              ratio, H, hd, mask, true, probs, ldp, rows, win, win_stride, stream);
 }
 
 int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,

@@ -336,8 +336,50 @@ class Decoder(FlatTraining, nn.Module):
             raise ValueError(f'constraint: a forced token is outside its voice\'s vocabulary {vocab.tolist()}')
         return constraint.reshape(rows, events * nc)
 
+    def _attention_layers(self, return_attentions, default=None):
+        """return_attentions -> None (False), or the sorted tuple of decoder-layer indices to record: True = every layer
+        (`default`, when given), an iterable = those layers.  ValueError on an index outside the stack or an empty choice."""
+        nl = len(self.transformer.decoder.layers)
+        if return_attentions is False or return_attentions is None:
+            return None
+        if return_attentions is True:
+            return tuple(range(nl)) if default is None else tuple(default)
+        try:
+            layers = sorted({int(li) for li in return_attentions})
+        except TypeError:
+            raise ValueError(f'return_attentions: False, True or an iterable of layer indices expected, got {return_attentions!r}')
+        if not layers or layers[0] < 0 or layers[-1] >= nl:
+            raise ValueError(f'return_attentions: layer indices in [0, {nl}) expected, got {list(return_attentions)}')
+        return tuple(layers)
+
+    def _check_attention_bytes(self, B, layers, rows, with_encoder, max_attention_bytes):
+        """The bytes of the requested maps for B sequences and `rows` recorded positions; ValueError above the limit."""
+        H = self.transformer.nhead
+        T, S = self.num_tokens_target, self.num_tokens_source
+        keys = T + (0 if self.cross_attention_type == 'diagonal' else S)
+        nbytes = 4 * B * len(layers) * H * rows * keys
+        if with_encoder:
+            nbytes += 4 * B * len(self.transformer.encoder.layers) * H * S * S
+        if nbytes > max_attention_bytes:
+            raise ValueError(f'return_attentions: the maps of {len(layers)} layer(s) for {B} sequences take {nbytes} bytes '
+                             f'({nbytes / 2 ** 30:.2f} GiB), above max_attention_bytes = {max_attention_bytes}; ask for fewer '
+                             'layers or fewer sequences, or raise max_attention_bytes')
+        return nbytes
+
+    @staticmethod
+    def attention_window_starts(num_blocks, num_blocks_model, tokens_per_block, code_index_start, code_index_end):
+        """(num_blocks * tokens_per_block,) int64 on the host: for every chorale position, the first code of the model window
+        in which `generate_from_code_long` emits it -- `compute_start_end_times` of its code, as `run_long` walks it -- or -1
+        for the positions of codes outside [code_index_start, code_index_end), which are never emitted."""
+        out = torch.full((num_blocks * tokens_per_block,), -1, dtype=torch.int64)
+        for ci in range(code_index_start, code_index_end):
+            out[ci * tokens_per_block:(ci + 1) * tokens_per_block] = Decoder.compute_start_end_times(ci, num_blocks,
+                                                                                                     num_blocks_model)[0]
+        return out
+
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
-                            use_graph=True, constraint=None, return_logp=False):
+                            use_graph=True, constraint=None, return_logp=False, return_attentions=False,
+                            max_attention_bytes=4 << 30):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
@@ -349,10 +391,22 @@ class Decoder(FlatTraining, nn.Module):
         -1 leaves it to the sampler; rows are repeated with num_decodings like the codes.  The free positions draw what
         they would draw without the constraint given the same prefix (the draw is keyed by seed and position).
         return_logp=True -> (tokens, logp): logp float32 of the tokens' shape, every emitted token's log-probability
-        under the model's unfiltered distribution (temperature 1, no top-k / top-p / exclusion)."""
+        under the model's unfiltered distribution (temperature 1, no top-k / top-p / exclusion).
+        return_attentions: True (every decoder layer) or an iterable of decoder-layer indices (ValueError outside the stack)
+        -> `attentions` as the LAST element of the result, (tokens, attentions) or (tokens, logp, attentions): what every
+        emitted token attended to (the reference keeps these rows in its generate loop, :647-667), a dict of
+          'layers'              the recorded decoder layers, a tuple
+          'self_attns_decoder'  (B', layers, H, T, T) float32, row t = the attention of token t over the tokens written so far
+                                (exactly 0 above the diagonal)
+          'attns_cross'         (B', layers, H, T, S) over the codes; None for the diagonal decoder, which has no cross attention
+          'self_attns_encoder'  (B', encoder layers, H, S, S), the source encoder's maps (every layer: they are computed anyway)
+        with B' = B * num_decodings, on the device.  The rows are the ones the step's attention kernel multiplies V by
+        (vqcpc_decode_attn_probs); tokens and logp are bit-identical to a call without the keyword.  The maps' bytes are computed
+        first: ValueError above max_attention_bytes (default 4 GiB)."""
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
+        layers = self._attention_layers(return_attentions)
         codes = self._source_on_device(codes, 'codes', self.num_tokens_source)
         T, nc = self.num_tokens_target, self.num_channels
         if constraint is not None:
@@ -364,18 +418,38 @@ class Decoder(FlatTraining, nn.Module):
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
         logp = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logp else None
+        maps = None
+        if layers is not None:
+            self._check_attention_bytes(B, layers, T, True, max_attention_bytes)
+            maps = {'layers': layers, 'self_attns_decoder': [], 'attns_cross': [], 'self_attns_encoder': []}
 
         def chunk(n, rows):
             inc = IncrementalDecoder(self, n)
             inc.prefill(codes[rows])
             inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens,
-                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp)
+                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp, want_attentions=layers)
             tokens = inc.run(use_graph=use_graph)
             if return_logp:
                 logp[rows] = inc.logp
+            if maps is not None:
+                maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
+                maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
+                maps['self_attns_encoder'].append(torch.stack(inc.enc_probs, dim=1))
             return tokens
         tokens = generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
-        return (tokens, logp.view(B, T // nc, nc)) if return_logp else tokens
+        out = (tokens, logp.view(B, T // nc, nc)) if return_logp else (tokens,)
+        if maps is not None:
+            out += (self._join_attention_chunks(maps),)
+        return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def _join_attention_chunks(maps):
+        """The per-chunk lists of (n, ...) maps -> one (B, ...) tensor each (a single chunk's buffer is returned as it is)."""
+        for key, parts in list(maps.items()):
+            if key in ('layers', 'window_start'):
+                continue
+            maps[key] = None if parts[0] is None else (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)).contiguous()
+        return maps
 
     def _source_on_device(self, source, name, length=None):
         source = torch.as_tensor(source)
@@ -392,17 +466,26 @@ class Decoder(FlatTraining, nn.Module):
         return [[n2i[c][s] for s in syms if s in n2i[c]] for c in range(self.num_channels)]
 
     def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
-                 plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None):
+                 plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None, return_attentions=False,
+                 max_attention_bytes=4 << 30):
         """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
         code_juxtaposition) as the reference writes them.  Returns {'original', 'generation', 'codes', 'recoding'} tensors
         instead of music21 scores (no score writing here).  seed: as generate_from_codes.  A continuous decoder returns
         the latents as 'codes', 'recoding' None and writes no file (:674-701).  keep_voices: voice indices whose tokens
-        are forced to the seed chorale's (`generate_from_codes(constraint=...)`): the other voices are written around them."""
+        are forced to the seed chorale's (`generate_from_codes(constraint=...)`): the other voices are written around them.
+        return_attentions: True records decoder layer min(2, layers - 1) (the reference's plot_attentions block hard-codes layer
+        2, :649), an iterable chooses the layers; the result gains 'attentions', the dict of `generate_from_codes`, and next to
+        the codes file {timestamp}_attentions.npz holds the reference's three stems as arrays (no PDF is drawn): attns_cross
+        (absent for the diagonal decoder), self_attns_decoder and self_attns_encoder, each (batch, H, T, keys) for the FIRST
+        recorded layer (the encoder's layer of that index, or its last), plus `layers`.  Row t of self_attns_encoder is the
+        encoder's row (t // channels * channels) // tokens-per-code, the code of t's event (:650-659)."""
         if plot_attentions:
-            raise NotImplementedError('plot_attentions: attention plots need the full forward per token (matplotlib); '
-                                      'not available on the incremental path')
+            raise NotImplementedError('plot_attentions: no plots are drawn here (no matplotlib); return_attentions=True returns '
+                                      'the attention maps of every emitted token and writes them as arrays')
+        nl = len(self.transformer.decoder.layers)
+        layers = self._attention_layers(return_attentions, default=(min(2, nl - 1),))
         exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
         voices = None if keep_voices is None else self._keep_voices(keep_voices)
         generator_train, generator_val, _ = self.dataloader_generator.dataloaders(batch_size=1, shuffle_val=True)
@@ -430,12 +513,17 @@ class Decoder(FlatTraining, nn.Module):
                 constraint = torch.full_like(x_original, -1)
                 constraint[:, :, voices] = x_original[:, :, voices]
             x = self.generate_from_codes(codes, temperature=temperature, top_k=top_k, top_p=top_p, exclude_tokens=exclude,
-                                         seed=seed, constraint=constraint)
+                                         seed=seed, constraint=constraint, return_attentions=layers or False,
+                                         max_attention_bytes=max_attention_bytes)
+            attentions = None
+            if layers is not None:
+                x, attentions = x
             recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
             self.train(was_training)
+        extra = {} if attentions is None else {'attentions': attentions}
         if recoding is None:
-            return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': None}
+            return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': None, **extra}
         timestamp = datetime.now().strftime('%Y-%m-%d_%H-%M-%S')
         save_dir = f'{self.model_dir}/juxtapositions' if code_juxtaposition else f'{self.model_dir}/generations'
         os.makedirs(save_dir, exist_ok=True)
@@ -443,8 +531,25 @@ class Decoder(FlatTraining, nn.Module):
             for aa in recoding.cpu().numpy():
                 ff.write(' , '.join(map(str, list(aa))))
                 ff.write('\n')
+        if attentions is not None:
+            np.savez(f'{save_dir}/{timestamp}_attentions.npz', **self._attention_arrays(attentions))
         print(f'Saved in {save_dir}/{timestamp}')
-        return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': recoding}
+        return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': recoding, **extra}
+
+    def _attention_arrays(self, attentions):
+        """The three stems of the reference's plot_attentions block (:647-667, :711-720) for the first recorded layer, as
+        host arrays (batch, H, T, keys)."""
+        layer = attentions['layers'][0]
+        enc = attentions['self_attns_encoder']
+        enc = enc[:, min(layer, enc.shape[1] - 1)]                                           # (B, H, S, S)
+        t = torch.arange(self.num_tokens_target, device=enc.device)
+        enc_rows = (t // self.num_channels * self.num_channels) // self.total_upscaling      # the code of t's event
+        arrays = {'layers': np.asarray(attentions['layers'], dtype=np.int64),
+                  'self_attns_decoder': attentions['self_attns_decoder'][:, 0].cpu().numpy(),
+                  'self_attns_encoder': enc[:, :, enc_rows].cpu().numpy()}
+        if attentions['attns_cross'] is not None:
+            arrays['attns_cross'] = attentions['attns_cross'][:, 0].cpu().numpy()
+        return arrays
 
     # ---- long-form generation (:728-1062): sliding-window decoding with KV-cache re-prefill, decoders/generation.py --
     @staticmethod
@@ -489,7 +594,8 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate_from_code_long(self, encoding_indices=None, temperature=None, top_k=0, top_p=1., exclude_meta_symbols=False,
                                 num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
-                                use_graph=True, constraint=None, return_logp=False):
+                                use_graph=True, constraint=None, return_logp=False, return_attentions=False,
+                                max_attention_bytes=4 << 30, graph_slides=None):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -506,13 +612,20 @@ class Decoder(FlatTraining, nn.Module):
         constraint: (B, nb * events_per_code, channels) int64 over the WHOLE code sequence, in chorale coordinates: a token
         >= 0 is emitted at its place, -1 is free; events outside [code_index_start, code_index_end) are ignored.  Rows are
         repeated with num_decodings.  return_logp=True -> (tokens, logp), logp float32 of the tokens' shape (see
-        `generate_from_codes`)."""
+        `generate_from_codes`).
+        return_attentions: as in `generate_from_codes` (the last element of the result), over the WHOLE code sequence in chorale
+        coordinates: 'self_attns_decoder' (B', layers, H, nb * U, T), 'attns_cross' (B', layers, H, nb * U, S; None for the
+        diagonal decoder) and 'window_start' (nb * U,) int64 on the host (`attention_window_starts`): the first code w of the
+        window in which position c was emitted, -1 where none was -- those rows stay NaN.  Key j of row c is chorale token
+        w * U + j (self) / code w + j (cross).  No encoder maps: they change with every window.
+        graph_slides: `IncrementalDecoder.run_long`'s (None: as use_graph)."""
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
+        layers = self._attention_layers(return_attentions)
         codes = self._source_on_device(encoding_indices, 'encoding_indices')
         S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
         nb = codes.shape[1]
@@ -534,19 +647,31 @@ class Decoder(FlatTraining, nn.Module):
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
         logp = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_logp else None
+        maps = None
+        if layers is not None:
+            self._check_attention_bytes(B, layers, nb * U, False, max_attention_bytes)
+            maps = {'layers': layers, 'self_attns_decoder': [], 'attns_cross': [],
+                    'window_start': self.attention_window_starts(nb, S, U, code_index_start, code_index_end)}
 
         def chunk(n, rows):
             inc = IncrementalDecoder(self, n)
             inc.start_long(codes[rows], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[rows], temperature=temperature,
                            top_k=top_k, top_p=top_p, exclude=exclude,
-                           constraint=None if constraint is None else constraint[rows], want_logp=return_logp)
-            tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph)
+                           constraint=None if constraint is None else constraint[rows], want_logp=return_logp,
+                           want_attentions=layers)
+            tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph, graph_slides=graph_slides)
             if return_logp:
                 logp[rows] = inc.logp
+            if maps is not None:
+                maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
+                maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
             return tokens
         out = generate_in_chunks(self, B, nb * U, chunk)
         cut = lambda t: t.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
-        return (cut(out), cut(logp)) if return_logp else cut(out)
+        res = (cut(out), cut(logp)) if return_logp else (cut(out),)
+        if maps is not None:
+            res += (self._join_attention_chunks(maps),)
+        return res if len(res) > 1 else res[0]
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent

@@ -13,6 +13,9 @@ this module adds what the decoder has on top of it:
   constraint or token scores (`start(constraint=..., want_logp=...)`) the sampler is vqcpc_decode_sample_constrained: the same
   kernel body, which emits the given token where the constraint holds one and writes the emitted token's log-probability; it
   reads both at the position's CHORALE column through the device window index, so nothing else of the step or slide changes.
+  Attention maps (`start(want_attentions=layers)`): the listed layers' self- and cross-attention launches are
+  vqcpc_decode_attn_probs, which also stores the row of probabilities of the emitted token into `self_probs` / `cross_probs` at
+  the row of the position's chorale coordinate (the same window index); the encoder's maps of the prefill are kept as `enc_probs`.
 
 Long mode (reference: generate_from_code_long, decoder.py:729-854, one full forward on the moved window per token): a code
 sequence of any length nb >= S is decoded by sliding the window one code at a time.  The chorale (M, nb * U) and the codes
@@ -83,6 +86,7 @@ class IncrementalDecoder(IncrementalStack):
         self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
         self.memkv = None
         self.constraint, self.logp, self.constrained = None, None, False
+        self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
         self.continuous = bool(getattr(dec, 'continuous_source', False))
         if self.continuous:
             self.dz = dec.source_dim
@@ -119,7 +123,9 @@ class IncrementalDecoder(IncrementalStack):
                      lin.bias, src, d, M, self.S, d)
         else:
             src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
-        memory, _ = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
+        memory, att = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
+        # per encoder layer (M, H, S, S); a moved window's maps are not kept (a captured slide would pin its own pool's tensors)
+        self.enc_probs = None if windowed else [a['a_self_encoder'] for a in att]
         if self.diagonal:
             for lay, C in zip(self.layers, self.memkv):
                 l1, l2 = lay.cross_attn[0], lay.cross_attn[2]
@@ -130,13 +136,16 @@ class IncrementalDecoder(IncrementalStack):
             ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:], out=kv)
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
-              constraint=None, want_logp=False):
+              constraint=None, want_logp=False, want_attentions=None):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
         probabilities of the last step in `probs` (M, max V_c).
         constraint: (M, T) int64, a token >= 0 is emitted at its position, < 0 leaves the draw free; want_logp: keep every
         emitted token's log-probability under the unfiltered distribution in `logp` (M, T) float32, NaN where no token was
-        emitted yet.  Either one switches the step's sampler to vqcpc_decode_sample_constrained."""
+        emitted yet.  Either one switches the step's sampler to vqcpc_decode_sample_constrained.
+        want_attentions: None, or a sorted tuple of decoder-layer indices whose attention rows are kept for every emitted token:
+        `self_probs` (layers, M, H, T, T) and `cross_probs` (layers, M, H, T, S; None for the diagonal decoder), float32, NaN
+        where no token was emitted yet.  Those layers' attention launches become vqcpc_decode_attn_probs."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
@@ -154,6 +163,7 @@ class IncrementalDecoder(IncrementalStack):
             self.teacher = None
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
         self._constrain(constraint, want_logp, self.T, None)
+        self._record_attentions(want_attentions, self.T, None, 1)
         self.reset()
 
     def _constrain(self, constraint, want_logp, width, win):
@@ -171,6 +181,26 @@ class IncrementalDecoder(IncrementalStack):
         self.constrained = constraint is not None or want_logp
         self._cons_width, self._cons_win = width, win
 
+    def _record_attentions(self, layers, rows, win, stride):
+        """The attention-map buffers, allocated here once (before any warm-up step: a captured step holds their addresses):
+        rows = T and win = None for the fixed window, rows = nb * U, win = the device window index and stride = U in long mode
+        (chorale coordinates).  layers=None frees them and every launch is the plain one again."""
+        self.self_probs = self.cross_probs = None
+        self._attn_slot, self.attn_layers = {}, None
+        if layers is None:
+            return
+        layers = tuple(int(li) for li in layers)
+        if not layers or list(layers) != sorted(set(layers)) or layers[0] < 0 or layers[-1] >= len(self.layers):
+            raise ValueError(f'want_attentions: a sorted tuple of distinct layer indices in [0, {len(self.layers)}) expected, '
+                             f'got {layers}')
+        nan = dict(fill_value=float('nan'), dtype=torch.float32, device=self.dev)
+        self.self_probs = torch.full((len(layers), self.M, self.H, rows, self.T), **nan)
+        if not self.diagonal:
+            self.cross_probs = torch.full((len(layers), self.M, self.H, rows, self.S), **nan)
+        self.attn_layers = layers
+        self._attn_slot = {li: k for k, li in enumerate(layers)}
+        self._attn_rows, self._attn_win, self._attn_stride = int(rows), win, int(stride)
+
     def reset(self):
         self.pos.zero_()
         self.tokens.zero_()
@@ -180,14 +210,23 @@ class IncrementalDecoder(IncrementalStack):
     def _forget_logp(self):
         if self.logp is not None:
             self.logp.fill_(float('nan'))                                               # what a warm-up step wrote
+        for maps in (self.self_probs, self.cross_probs):
+            if maps is not None:
+                maps.fill_(float('nan'))
 
     # ---- one step: the cross hooks and the sampler ----------------------------------------------------------------------
     def _cross_attention(self, li, lay):
         d, ca, kv = self.d, lay.multihead_attn, self.memkv[li]
         hip.call('vqcpc_decode_linear', self.h1, d, None, ca.in_proj_weight, ca.in_proj_bias, None, 0, self.qc, d, self.M, d, d,
                  0)
-        hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
-                 ca.attn_bias.e2, self.att, d, self.pos, self.M, self.S, self.T // self.S, self.H, self.hd, self.cross_mask)
+        slot = self._attn_slot.get(li)
+        if slot is None:
+            hip.call('vqcpc_decode_attn', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                     ca.attn_bias.e2, self.att, d, self.pos, self.M, self.S, self.T // self.S, self.H, self.hd, self.cross_mask)
+        else:
+            hip.call('vqcpc_decode_attn_probs', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
+                     ca.attn_bias.e2, self.att, d, self.pos, self.M, self.S, self.T // self.S, self.H, self.hd, self.cross_mask,
+                     self.cross_probs[slot], self.S, self._attn_rows, self._attn_win, self._attn_stride)
         self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
         self._ln(self.s, lay.norm2, self.h2)
         return self.h2
@@ -230,11 +269,13 @@ class IncrementalDecoder(IncrementalStack):
 
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
-    def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, **sampling):
+    def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
         tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
         want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
         live window's chorale column (the device window index), so the captured step and slide serve every window.
+        want_attentions: as in `start`, with `self_probs` (layers, M, H, nb * U, T) and `cross_probs` (layers, M, H, nb * U, S):
+        the row is the emitted token's chorale position, its keys are those of the window it was emitted in.
         sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
@@ -259,6 +300,7 @@ class IncrementalDecoder(IncrementalStack):
             self.z_full, self.z_nb = z_full, nb
         self.start(seeds=seeds, **sampling)
         self._constrain(constraint, want_logp, nb * U, self.win)
+        self._record_attentions(want_attentions, nb * U, self.win, U)
         self.row_seeds.copy_(self.seeds)
 
     def _window(self, P, advance):

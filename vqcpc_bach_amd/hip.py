@@ -203,6 +203,8 @@ SIGNATURES = {
                                     c_ptr]),
     'vqcpc_decode_attn': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
                                   c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    'vqcpc_decode_attn_probs': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                                        c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr]),
     'vqcpc_decode_sample': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
                                     c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
     'vqcpc_decode_sample_constrained': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_i64,

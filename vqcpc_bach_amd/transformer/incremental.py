@@ -10,7 +10,8 @@ prior's N codes): position t's output depends on positions < t only (causal self
   the head(s) and the subclass's sampler, which draws the position's token, writes the input row of position pos + 1 and
   advances the device counter `pos`.  7 launches per layer + 2 plus the cross hook's: none (prior, whose stack has no
   cross block), 3 + a LayerNorm (decoder: cross q -> cross-attention -> out_proj + residual), 1 + a LayerNorm (diagonal
-  decoder: vqcpc_decode_aligned_add).
+  decoder: vqcpc_decode_aligned_add).  A layer whose attention maps are recorded (the decoder's `want_attentions`) calls
+  vqcpc_decode_attn_probs where the others call vqcpc_decode_attn: same launch count, same ctx bits.
 
   prefix (`prefill_prefix`): when a window moves, every cache row is stale.  The stack is teacher-forced over the P prefix
   rows of every sequence (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_decode_prefill_attn, the prefix-side cross hook),
@@ -95,6 +96,7 @@ class IncrementalStack:
         self._pmean, self._prstd = torch.empty(M * W, **f32), torch.empty(M * W, **f32)
         self.teacher = None
         self.probs = None
+        self.self_probs, self._attn_slot = None, {}           # attention maps: off (a subclass's `start` may turn them on)
         self._cross, self._prefix_cross = IncrementalStack._no_cross, IncrementalStack._no_prefix_cross
 
     # ---- one step ----------------------------------------------------------------------------------------------------
@@ -120,8 +122,14 @@ class IncrementalStack:
             hout = self.hb[li % 2]
             self._linear(hin, sa.in_proj_weight, sa.in_proj_bias, self.qkv)
             q0 = self.qkv.data_ptr()
-            hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
-                     sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, W, 1, H, hd, ops.MASK_CAUSAL)
+            slot = self._attn_slot.get(li)
+            if slot is None:
+                hip.call('vqcpc_decode_attn', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d, 3 * d,
+                         sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, W, 1, H, hd, ops.MASK_CAUSAL)
+            else:                                         # a recorded layer: the same kernel body, which also stores its row
+                hip.call('vqcpc_decode_attn_probs', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d,
+                         3 * d, sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, W, 1, H, hd, ops.MASK_CAUSAL,
+                         self.self_probs[slot], W, self._attn_rows, self._attn_win, self._attn_stride)
             self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
             self._ln(self.s, lay.norm1, self.h1)
             h = cross(self, li, lay)
