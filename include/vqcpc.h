@@ -819,6 +819,21 @@ int vqcpc_decode_source_rows(const float* z_full, int64_t nb, int dz, const int3
  *   table_rows >= V), optionally the filtered probabilities probs[b][0..V).  The last workgroup to finish (ticket: device
  *   int32, zero before the first call, zero again after every call) writes pos[0] = pos + 1.  Every reduction runs inside
  *   the row's workgroup in an order that depends on V only: a row's codes do not depend on M.
+ * vqcpc_prior_sample_constrained: vqcpc_prior_sample (the same kernel body, a compile-time flag) without teacher, with seeds
+ *   required, and three more things, all addressed at the sequence column col = pos (win == NULL) or win[1] + pos -- win[1]
+ *   (device int32) is the live window's first code as vqcpc_prior_window leaves it, code j of window w being sequence column
+ *   w + j, so constraint and logp are in sequence coordinates and one captured step and one captured move serve every window:
+ *     constraint[b * ldcons + col] (device int64, NULL = nothing forced): >= 0 is the code to emit, clamped to [0, V) as
+ *       teacher is; < 0 draws the code exactly as vqcpc_prior_sample does, keyed by (seeds[b], pos) -- forcing some positions
+ *       does not shift the draws of the others.  A forced code ignores top-k / top-p.
+ *     logp[b * ldlogp + col] (may be NULL) = logits[code] - logsumexp(logits[0..V)) for the emitted code, forced or drawn: the
+ *       model's UNMODIFIED distribution (temperature 1, no filter).  fp32, the maximum subtracted, reduced inside the row's
+ *       workgroup in an order that depends on V only (a row's value does not depend on M).  -inf logits contribute zero; a
+ *       forced code whose logit is -inf gets -inf.
+ *     win[1] < 0: nothing is forced and no logp is written.  Likewise for a column col >= ldcons (free) / col >= ldlogp
+ *       (not written): the window index is not known to the host, which checks ldcons, ldlogp >= N only.
+ *   codes[b * ldc + pos], next_in, probs (the filtered distribution whatever is forced), the ticket that advances pos[0], the
+ *   no-op once pos >= N and the limits are unchanged.
  * vqcpc_prior_window: ONE workgroup; win (device int32 [2]) = {next window's first code, live window's first code or -1}.
  *   First the live window's codes [0, pos) go back into seq[M][ldseq] (code j of window w is column w + j).  Then, unless
  *   win[0] < 0 or win[0] + N > num_tokens (commit only): codes_win[M][N] = seq columns win[0].., prefix_rows[b * P + j] =
@@ -830,6 +845,11 @@ int vqcpc_prior_sample(const float* logits, int64_t ldl, int V, int64_t M, float
                        const int64_t* seeds, const int64_t* teacher, int64_t ldteach, int64_t* codes, int64_t ldc, int N,
                        const float* table, int64_t table_rows, int d, float* next_in, int64_t ldn, float* probs, int64_t ldp,
                        int32_t* pos, int32_t* ticket, void* stream);
+int vqcpc_prior_sample_constrained(const float* logits, int64_t ldl, int V, int64_t M, float temperature, int top_k, float top_p,
+                                   const int64_t* seeds, const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp,
+                                   const int32_t* win, int64_t* codes, int64_t ldc, int N, const float* table,
+                                   int64_t table_rows, int d, float* next_in, int64_t ldn, float* probs, int64_t ldp,
+                                   int32_t* pos, int32_t* ticket, void* stream);
 int vqcpc_prior_window(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t* win, int advance, int64_t* codes_win, int N,
                        int P, int64_t* prefix_rows, const float* table, int64_t table_rows, int d, float* x, int64_t ldx,
                        const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);

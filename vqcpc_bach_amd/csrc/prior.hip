@@ -9,6 +9,8 @@
 //     radix select of the k-th largest logit, top-p by a bitonic sort of (logit, index) keys in LDS and a scan in sorted
 //     order, softmax, one counter-based draw.  The position counter is shared by every kernel of the step: the last
 //     workgroup to finish (a ticket in device memory) advances it.
+//   * vqcpc_prior_sample_constrained: the same kernel body under a compile-time flag.  Per (row, sequence column) a code to
+//     emit or < 0 for the draw, and the emitted code's log-probability under the row as the model gave it.
 //   * vqcpc_prior_window: ONE workgroup.  Commits the live window's codes into the sequence, loads the next window, the
 //     prefix's table-row indices, the input row of position P, the window's seeds and `pos`.
 #include "common.h"
@@ -72,6 +74,14 @@ __device__ __forceinline__ int block_max_int(int v, int* red) {
     __syncthreads();
     return max(max(red[0], red[1]), max(red[2], red[3]));
 }
+// sum over the block: wave butterfly, then the four waves' totals pairwise
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
 // exclusive prefix of the threads' totals in thread order (wave scan, then the previous waves' totals in wave order);
 // `total` receives the sum over the block
 __device__ __forceinline__ float block_excl_scan(float v, float* red, float& total) {
@@ -95,11 +105,19 @@ __device__ __forceinline__ float block_excl_scan(float v, float* red, float& tot
     return base + incl - v;
 }
 
+// CONS (vqcpc_prior_sample_constrained): `teacher` is the constraint -- per (row, column) a code to emit, or < 0 for a draw --
+// and the emitted code's log-probability under the UNFILTERED row (temperature 1) goes to logp.  Both are addressed at the
+// sequence column col = pos (win == NULL) or win[1] + pos, the live window's first code plus the position: one captured step
+// and one captured move serve every window.  A column outside [0, ldteach) / [0, ldlogp) is free / not written.  The
+// log-sum-exp re-reads the row from global memory: thread t sums its 16 codes in ascending order, then `block_sum` -- an order
+// that depends on V only.  Without CONS the kernel is what it was before the flag: none of the added code is instantiated.
+template <bool CONS>
 __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
     const float* __restrict__ logits, int64_t ldl, int V, float temperature, int top_k, float top_p,
     const int64_t* __restrict__ seeds, const int64_t* __restrict__ teacher, int64_t ldteach, int64_t* __restrict__ codes,
     int64_t ldc, int N, const float* __restrict__ table, int d, float* __restrict__ next_in, int64_t ldn,
-    float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp, int32_t* __restrict__ ticket) {
+    float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp, int32_t* __restrict__ ticket,
+    float* __restrict__ logp, int64_t ldlogp, const int32_t* __restrict__ win) {
     __shared__ float sl[kMaxVocab];                           // the row's (filtered) logits
     __shared__ uint64_t keys[kMaxVocab];                      // top-p: (descending logit, index) sort keys
     __shared__ float redf[kWaves];
@@ -110,6 +128,11 @@ __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
     const int pos = *posp;
     if (pos < 0 || pos >= N) return;                         // past the end: nothing happens (uniform over the grid)
     const float ninf = -INFINITY;
+    int64_t col = -1;                                         // CONS: the column of constraint / logp, < 0 = no live window
+    if constexpr (CONS) {
+        const int w0 = win ? win[1] : 0;
+        if (w0 >= 0) col = (int64_t)w0 + pos;
+    }
     for (int i = tid; i < kMaxVocab; i += kThreads) sl[i] = i < V ? logits[b * ldl + i] * temperature : ninf;
     __syncthreads();
     const int i0 = tid * kPer;
@@ -213,8 +236,12 @@ __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
             if (i0 + t < V) probs[b * ldp + i0 + t] = e[t] * inv;
     }
     int tok;
-    if (teacher) {
-        tok = (int)teacher[b * ldteach + pos];
+    int64_t forced = -1;
+    if constexpr (CONS) {
+        if (teacher && col >= 0 && col < ldteach) forced = teacher[b * ldteach + col];
+    }
+    if (CONS ? forced >= 0 : teacher != nullptr) {           // uniform over the workgroup
+        tok = CONS ? (int)min(forced, (int64_t)kMaxVocab) : (int)teacher[b * ldteach + pos];
     } else {
         const uint64_t sd = (uint64_t)seeds[b];
         const uint32_t r = rng_u24_from_x0(rng_x0(sd, (uint32_t)pos), (uint32_t)(sd >> 32));
@@ -234,6 +261,22 @@ __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
     tok = min(max(tok, 0), V - 1);
     if (tid == 0) codes[b * ldc + pos] = tok;
     for (int k = tid; k < d; k += kThreads) next_in[b * ldn + k] = table[(int64_t)tok * d + k];   // input of position pos + 1
+    if constexpr (CONS) {
+        if (logp && col >= 0 && col < ldlogp) {              // uniform: every thread reaches the barriers below or none does
+            float raw[kPer], rmx = ninf;
+#pragma unroll
+            for (int t = 0; t < kPer; ++t) {
+                raw[t] = i0 + t < V ? logits[b * ldl + i0 + t] : ninf;     // the row as the model gave it
+                rmx = fmaxf(rmx, raw[t]);
+            }
+            rmx = block_max(rmx, redf);
+            float rs = 0.0f;
+#pragma unroll
+            for (int t = 0; t < kPer; ++t) rs += raw[t] > ninf ? expf(raw[t] - rmx) : 0.0f;
+            rs = block_sum(rs, redf);
+            if (tid == 0) logp[b * ldlogp + col] = (logits[b * ldl + tok] - rmx) - logf(rs);
+        }
+    }
     // the last workgroup to get here advances the position: every workgroup read it before it took its ticket
     __syncthreads();
     if (tid == 0) {
@@ -311,10 +354,32 @@ int vqcpc_prior_sample(const float* logits, int64_t ldl, int V, int64_t M, float
     VQ_REQUIRE(teacher || seeds, "prior_sample: seeds are needed unless the codes are teacher-forced");
     VQ_REQUIRE(ldl >= V && ldc >= N && ldn >= d && (!teacher || ldteach >= N) && (!probs || ldp >= V) && table_rows >= V,
                "prior_sample: bad leading dimensions, or a table of fewer than V rows");
-    hipLaunchKernelGGL(prior::prior_sample_kernel, dim3((unsigned)M), dim3(prior::kThreads), 0, (hipStream_t)stream, logits, ldl,
-                       V, temperature, top_k, top_p, seeds, teacher, ldteach, codes, ldc, N, table, d, next_in, ldn, probs, ldp,
-                       pos, ticket);
+    hipLaunchKernelGGL(prior::prior_sample_kernel<false>, dim3((unsigned)M), dim3(prior::kThreads), 0, (hipStream_t)stream,
+                       logits, ldl, V, temperature, top_k, top_p, seeds, teacher, ldteach, codes, ldc, N, table, d, next_in, ldn,
+                       probs, ldp, pos, ticket, (float*)nullptr, (int64_t)0, (const int32_t*)nullptr);
     VQ_CHECK_LAUNCH("prior_sample");
+    return VQCPC_OK;
+}
+
+int vqcpc_prior_sample_constrained(const float* logits, int64_t ldl, int V, int64_t M, float temperature, int top_k, float top_p,
+                                   const int64_t* seeds, const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp,
+                                   const int32_t* win, int64_t* codes, int64_t ldc, int N, const float* table,
+                                   int64_t table_rows, int d, float* next_in, int64_t ldn, float* probs, int64_t ldp,
+                                   int32_t* pos, int32_t* ticket, void* stream) {
+    VQ_REQUIRE(V >= 1 && V <= prior::kMaxVocab, "prior_sample_constrained: %d codes (1 <= V <= 4096)", V);
+    VQ_REQUIRE(M >= 1 && M <= prior::kMaxRows, "prior_sample_constrained: %lld rows (1 <= M <= 64)", (long long)M);
+    VQ_REQUIRE(logits && codes && table && next_in && pos && ticket, "prior_sample_constrained: null pointer");
+    VQ_REQUIRE(seeds, "prior_sample_constrained: seeds are needed (a position the constraint leaves free is drawn)");
+    VQ_REQUIRE(N >= 1 && N <= prior::kMaxWindow && d >= 1 && d <= prior::kMaxDim,
+               "prior_sample_constrained: bad arguments (1 <= N <= 1024, 1 <= d <= 4096)");
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "prior_sample_constrained: temperature > 0, top_k >= 0");
+    VQ_REQUIRE(ldl >= V && ldc >= N && ldn >= d && (!constraint || ldcons >= N) && (!logp || ldlogp >= N) &&
+               (!probs || ldp >= V) && table_rows >= V,
+               "prior_sample_constrained: bad leading dimensions (ldcons, ldlogp >= N), or a table of fewer than V rows");
+    hipLaunchKernelGGL(prior::prior_sample_kernel<true>, dim3((unsigned)M), dim3(prior::kThreads), 0, (hipStream_t)stream,
+                       logits, ldl, V, temperature, top_k, top_p, seeds, constraint, ldcons, codes, ldc, N, table, d, next_in,
+                       ldn, probs, ldp, pos, ticket, logp, ldlogp, win);
+    VQ_CHECK_LAUNCH("prior_sample_constrained");
     return VQCPC_OK;
 }
 

@@ -217,6 +217,9 @@ SIGNATURES = {
     'vqcpc_decode_source_rows': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr]),
     'vqcpc_prior_sample': (c_int, [c_ptr, c_i64, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_int,
                                    c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_sample_constrained': (c_int, [c_ptr, c_i64, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
+                                               c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr,
+                                               c_ptr, c_ptr]),
     'vqcpc_prior_window': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr,
                                    c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'vqcpc_aligned_expand': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),

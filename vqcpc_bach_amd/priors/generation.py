@@ -5,7 +5,11 @@ The prior is one causal stack: position e's logits depend on codes < e of the wi
 LayerNorm / FFN, causal self-attention), so an incremental step per code computes the same function.  The step is the
 shared stack's (transformer/incremental.py) with no cross block, i.e. the decoder's without the cross-attention, 7 launches
 per layer + 2; its sampler is vqcpc_prior_sample, which draws the code of position pos, writes the input row of position
-pos + 1 and advances the device counter `pos`.
+pos + 1 and advances the device counter `pos`.  With given codes or code scores (`start(constraint=..., want_logp=...)`) the
+sampler is vqcpc_prior_sample_constrained: the same kernel body, which emits the given code where the constraint holds one
+and writes the emitted code's log-probability under the model's unmodified row (temperature 1, no filter); it addresses both
+at the sequence column win[1] + pos through the device's window index, so the captured step and the captured move below
+serve it unchanged.  The default path launches the plain sampler, exactly as before.
 
 Two regimes, as in the reference (:331-336):
 
@@ -57,8 +61,8 @@ class IncrementalPrior(IncrementalStack):
     """One generation of `batch` <= 64 rows of `prior` (a PriorRelative in eval mode; the caller holds utils.STEP_LOCK).
 
         inc = IncrementalPrior(prior, B)
-        inc.start(num_tokens, seeds, temperature, top_k, top_p)
-        codes = inc.run(use_graph, window_stride)                 # (B, num_tokens) int64
+        inc.start(num_tokens, seeds, temperature, top_k, top_p)   # constraint=, want_logp=: given codes, code scores
+        codes = inc.run(use_graph, window_stride)                 # (B, num_tokens) int64; inc.logp (B, num_tokens) float32
 
     `start` + `slide` + `step` expose the single launches (teacher forcing, the sampler's input `logits` and its optional
     probability output `probs`) for the tests."""
@@ -81,9 +85,14 @@ class IncrementalPrior(IncrementalStack):
         head = pr.pre_softmaxes[0]
         self.head_w, self.head_b = head.weight, head.bias
 
-    def start(self, num_tokens, seeds=None, temperature=1.0, top_k=0, top_p=1.0, teacher=None, want_probs=False):
+    def start(self, num_tokens, seeds=None, temperature=1.0, top_k=0, top_p=1.0, teacher=None, want_probs=False,
+              constraint=None, want_logp=False):
         """A new generation of `num_tokens` >= N codes per row.  teacher: (M, N) codes of the live window to force instead
-        of drawing (single-step use); want_probs: keep the filtered probabilities of the last step in `probs` (M, V)."""
+        of drawing (single-step use); want_probs: keep the filtered probabilities of the last step in `probs` (M, V).
+        constraint: (M, num_tokens) int64 in sequence coordinates, a code >= 0 is emitted at its column, < 0 leaves the draw
+        free; want_logp: keep every emitted code's log-probability under the unfiltered row at temperature 1 in `logp`
+        (M, num_tokens) float32 (NaN where no step has written yet).  Either one switches the sampler to
+        vqcpc_prior_sample_constrained, in both step forms."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         if num_tokens < self.N:
@@ -93,13 +102,26 @@ class IncrementalPrior(IncrementalStack):
         if seeds is not None:
             self.row_seeds.copy_(row_seeds(seeds, self.M))
         self.teacher = None if teacher is None else teacher.to(self.dev, torch.int64).reshape(self.M, self.N).contiguous()
+        if (constraint is not None or want_logp) and self.teacher is not None:
+            raise ValueError('constraint / want_logp and teacher exclude each other (an all-forced constraint is teacher forcing)')
+        if constraint is not None:
+            if tuple(constraint.shape) != (self.M, self.nt) or constraint.dtype != torch.int64:
+                raise ValueError(f'constraint: ({self.M}, {self.nt}) int64 expected, got {tuple(constraint.shape)} '
+                                 f'{constraint.dtype}')
+            constraint = constraint.to(self.dev).contiguous()
+        self.constraint = constraint
+        self.logp = torch.empty(self.M, self.nt, dtype=torch.float32, device=self.dev) if want_logp else None
+        self.constrained = constraint is not None or bool(want_logp)
         self.probs = torch.zeros(self.M, self.V, dtype=torch.float32, device=self.dev) if want_probs else None
         self.seq = torch.zeros(self.M, self.nt, dtype=torch.int64, device=self.dev)
         self.reset()
 
     def reset(self):
-        """Back to the head regime's first position; the sequence is cleared."""
+        """Back to the head regime's first position; the sequence is cleared, and so is every log-probability (NaN: a run
+        writes each column once, so none stays)."""
         self.seq.zero_()
+        if self.logp is not None:
+            self.logp.fill_(float('nan'))
         self.codes_win.zero_()
         self.ticket.zero_()
         self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
@@ -108,6 +130,11 @@ class IncrementalPrior(IncrementalStack):
     # ---- one step: the sampler, and the forward form ---------------------------------------------------------------------
     def _sample(self):
         N = self.N
+        if self.constrained:
+            hip.call('vqcpc_prior_sample_constrained', self.logits, self.V, self.V, self.M, self.temperature, self.top_k,
+                     self.top_p, self.seeds, self.constraint, self.nt, self.logp, self.nt, self.win, self.codes_win, N, N,
+                     self.table, self.table.shape[0], self.d, self.x, self.d, self.probs, self.V, self.pos, self.ticket)
+            return
         hip.call('vqcpc_prior_sample', self.logits, self.V, self.V, self.M, self.temperature, self.top_k, self.top_p,
                  self.seeds, self.teacher, N, self.codes_win, N, N, self.table, self.table.shape[0], self.d, self.x, self.d,
                  self.probs, self.V, self.pos, self.ticket)
@@ -171,7 +198,9 @@ class IncrementalPrior(IncrementalStack):
         """Generates the `num_tokens` codes of `start`: N steps in window 0, then moves of `window_stride` codes.
         method: the form of the steps per regime (module docstring).  use_graph: the cached step is a captured graph (the
         forward form's launches are always eager); graph_slides (default: use_graph): the cached form's full-stride moves are ONE captured graph
-        too.  Returns the sequence (M, num_tokens)."""
+        too.  Returns the sequence (M, num_tokens).  With `start(want_logp=True)` every column of `logp` is written exactly
+        once: columns 0 .. N - 1 in window 0, then `window_stride` columns per move, then the last, shorter move's; what the
+        warm-up launches of a capture wrote is cleared by the `reset` that follows them."""
         N, nt, k = self.N, self.nt, int(window_stride)
         if not 1 <= k < max(N, 2):
             raise ValueError(f'run: 1 <= window_stride < {N} (got {window_stride})')

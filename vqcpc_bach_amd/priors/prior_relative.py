@@ -25,11 +25,18 @@ softmax(temperature * logits): a LARGER temperature gives a MORE peaked distribu
 `logits / temperature` -- and it passes the same number on to the decoder (:356-358).  Both are kept: `temperature` means
 for the prior what the reference makes it mean and goes to the decoder unchanged unless `decoder_temperature` is given.
 `generate` returns (codes, tokens) tensors; music21 scores and XML writing are out of scope, as in the decoder.
+GIVEN CODES AND SCORES: `generate_codes(constraint=..., return_logp=True)` emits the given codes where the constraint holds
+one, draws the others as it would without the constraint given the same prefix (a draw is keyed by seed and position), and
+returns every emitted code's log-probability -- under the model's UNMODIFIED row: temperature 1 and no filter, whatever
+`temperature`, `top_k` and `top_p` are (vqcpc_prior_sample_constrained; the default path launches vqcpc_prior_sample as
+before).  `score_codes` is the everything-forced call; `continue_tokens` encodes the opening of a piece, lets the prior go on
+from its codes and has the decoder write tokens around the given ones.
 
 The reference ships no prior configuration; `configs.make_prior_config()` is this package's own.
 """
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -39,7 +46,7 @@ from ..training import FlatTraining
 from ..transformer.transformer_custom import TransformerEncoderCustom, TransformerEncoderLayerCustom
 from ..utils import STEP_LOCK
 
-MAX_SAMPLED_VOCAB = 4096         # vqcpc_prior_sample: codes per step of `generate_codes`
+MAX_SAMPLED_VOCAB = 4096         # vqcpc_prior_sample / vqcpc_prior_sample_constrained: codes per step of `generate_codes`
 
 
 class PriorRelative(FlatTraining, nn.Module):
@@ -170,8 +177,21 @@ class PriorRelative(FlatTraining, nn.Module):
             return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss', save_best=self.save)     # :292-294
 
     # ---- generation (:308-368): KV-cached sampling on the GPU, priors/generation.py -----------------------------------
+    def _code_constraint(self, constraint, rows, num_tokens):
+        """A public code constraint (rows, num_tokens) or (1, num_tokens) int64, -1 = free -> (rows, num_tokens) int64 on the
+        device."""
+        constraint = torch.as_tensor(constraint)
+        if constraint.dim() != 2 or constraint.shape[0] not in (1, rows) or constraint.shape[1] != num_tokens or \
+                constraint.dtype != torch.int64:
+            raise ValueError(f'constraint: ({rows}, {num_tokens}) or (1, {num_tokens}) int64 expected (-1 = free), got '
+                             f'{tuple(constraint.shape)} {constraint.dtype}')
+        V = self.num_tokens_per_channel[0]
+        if bool((constraint >= V).any()):
+            raise ValueError(f'constraint: a forced code is outside the {V} merged codes')
+        return constraint.to(self.sos.device).expand(rows, num_tokens).contiguous()
+
     def generate_codes(self, num_tokens, temperature=1.0, num_generated_codes=1, top_k=0, top_p=1.0, seed=None, use_graph=True,
-                       window_stride=1, method='auto'):
+                       window_stride=1, method='auto', constraint=None, return_logp=False):
         """Samples `num_generated_codes` sequences of `num_tokens` >= N merged codes (:315-353).  Code e < N comes from the
         first window (one cached step per code); code e >= N from the window that ends at e, as in the reference, when
         `window_stride` = 1.  window_stride = k > 1 (an opt-in of this package, NOT the reference's model context) moves the
@@ -181,7 +201,12 @@ class PriorRelative(FlatTraining, nn.Module):
         seeds derived from it), a per-row int64 tensor, or None (drawn from torch's generator); use_graph=False runs the same
         launches eagerly (same codes).  method: 'auto' picks per regime and batch between the KV-cached step and the
         full-stack step on the window (priors/generation.py: the faster of the two as measured), 'cached' / 'forward' force
-        one; both compute the same logits to rounding.  -> int64 (num_generated_codes, num_tokens) on the device."""
+        one; both compute the same logits to rounding.  -> int64 (num_generated_codes, num_tokens) on the device.
+        constraint: (num_generated_codes, num_tokens) int64, or (1, num_tokens) for every row: a code >= 0 is emitted at its
+        place (whatever top_k / top_p would leave of it), -1 is free; the free codes are what they would be without the
+        constraint given the same codes before them.  return_logp=True -> (codes, logp): logp float32 of the codes' shape,
+        every emitted code's log-probability, forced or drawn, under the model's unmodified distribution at that place --
+        temperature 1, no filter, whatever `temperature` is."""
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalPrior
         V, N = self.num_tokens_per_channel[0], self.num_tokens
@@ -197,26 +222,109 @@ class PriorRelative(FlatTraining, nn.Module):
             raise ValueError(f'generate_codes: 1 <= window_stride < {N} (got {window_stride})')
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
+        if constraint is not None:
+            constraint = self._code_constraint(constraint, B, num_tokens)
         seeds = row_seeds(seed, B)
+        logp = torch.empty(B, num_tokens, dtype=torch.float32, device=self.sos.device) if return_logp else None
 
         def chunk(n, rows):
             inc = IncrementalPrior(self, n)
-            inc.start(num_tokens, seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p)
-            return inc.run(use_graph=use_graph, window_stride=stride, method=method)
-        return generate_in_chunks(self, B, num_tokens, chunk)
+            inc.start(num_tokens, seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p,
+                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp)
+            codes = inc.run(use_graph=use_graph, window_stride=stride, method=method)
+            if return_logp:
+                logp[rows] = inc.logp
+            return codes
+        codes = generate_in_chunks(self, B, num_tokens, chunk)
+        return (codes, logp) if return_logp else codes
+
+    def score_codes(self, codes, use_graph=True, window_stride=1, method='auto'):
+        """log-probability of every code of `codes` (B, L) int64, L >= N, given the codes before it: float32 (B, L).  Column
+        e < N is scored in the first window, column e >= N in the window that ends at e (the reference's window rule, at
+        `window_stride` = 1).  It is `generate_codes` with every code forced, so it is the model's distribution at temperature
+        1 without a filter; use_graph / window_stride / method as there."""
+        codes = self._checked_codes(codes)
+        if bool((codes < 0).any()):
+            raise ValueError('score_codes: negative codes')
+        B, L = codes.shape
+        return self.generate_codes(L, num_generated_codes=B, seed=0, use_graph=use_graph, window_stride=window_stride,
+                                   method=method, constraint=codes, return_logp=True)[1]
 
     def generate(self, num_tokens, decoder, temperature=1.0, num_generated_codes=1, num_decodings_per_generating_code=1,
-                 decoder_temperature=None, seed=None, **decoder_sampling):
+                 decoder_temperature=None, seed=None, code_constraint=None, return_logp=False, **decoder_sampling):
         """:308-368: `generate_codes`, then `decoder.generate_from_code_long` on them.  `temperature` goes to BOTH, as in the
         reference (where it sharpens the prior and flattens the decoder as it grows, module docstring);
         decoder_temperature overrides the decoder's.  decoder_sampling: top_k, top_p, pad, start, ... of
         `generate_from_code_long`.  -> (codes (B, num_tokens), tokens (B * decodings, events, channels)) int64 tensors on the
-        device; score objects and XML files need music21 and are out of scope."""
-        codes = self.generate_codes(num_tokens, temperature=temperature, num_generated_codes=num_generated_codes, seed=seed)
+        device; score objects and XML files need music21 and are out of scope.
+        code_constraint / return_logp: `generate_codes`' constraint / return_logp; with return_logp=True the result is
+        (codes, tokens, code_logp (B, num_tokens) float32)."""
+        out = self.generate_codes(num_tokens, temperature=temperature, num_generated_codes=num_generated_codes, seed=seed,
+                                  constraint=code_constraint, return_logp=return_logp)
+        codes, code_logp = out if return_logp else (out, None)
         tokens = decoder.generate_from_code_long(encoding_indices=codes,
                                                  temperature=temperature if decoder_temperature is None else decoder_temperature,
                                                  num_decodings=num_decodings_per_generating_code, seed=seed, **decoder_sampling)
-        return codes, tokens
+        return (codes, tokens, code_logp) if return_logp else (codes, tokens)
+
+    def continue_tokens(self, x, num_new_codes, decoder, temperature=1.0, decoder_temperature=None, num_continuations=1,
+                        seed=None, return_logp=False, **decoder_sampling):
+        """"Here are the first bars, go on": x (1, events, channels) tokens of a piece's opening, events a multiple of the
+        events per code.  The opening is framed at the front as `Decoder.reharmonise_tokens` frames a chorale (one model-sized
+        PAD ... START chunk, then x; no END completion), encoded by this prior's frozen encoder in model-sized chunks and the
+        codes glued: the L given codes.  The prior then samples `num_continuations` sequences of L + num_new_codes codes whose
+        first L are the given ones (`generate_codes(constraint=...)`), and `decoder.generate_from_code_long` decodes the
+        codes after the framing chunk with x's tokens forced at their chorale events.  temperature / decoder_temperature as
+        in `generate`; decoder_sampling: top_k, top_p, ... of `generate_from_code_long`.
+        -> (codes (num_continuations, L + num_new_codes), tokens (num_continuations, x's events + num_new_codes * events per
+        code, channels)): events [0, x.shape[1]) of every token row equal x.  return_logp=True -> (codes, tokens, code_logp,
+        token_logp), the scores of `generate_codes` and of `generate_from_code_long` (each at temperature 1, unfiltered).
+        Needs the decoder's dataset's START / XX symbols."""
+        if decoder.continuous_source:
+            raise NotImplementedError('a prior over continuous (NoQuantization) codes does not exist')
+        n2i = getattr(getattr(decoder.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
+        if n2i is None:
+            raise ValueError('continue_tokens needs dataset.note2index_dicts with the START / XX symbols')
+        nc, E, epc, U = decoder.num_channels, decoder.data_processor.num_events, decoder.num_events_per_code, decoder.total_upscaling
+        if int(np.prod(self.encoder.downscaler.downscale_factors)) != U:
+            raise ValueError(f"continue_tokens: the prior's encoder makes one code of "
+                             f'{int(np.prod(self.encoder.downscaler.downscale_factors))} tokens, the decoder of {U}')
+        x = torch.as_tensor(x).long().cpu()
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[2] != nc:
+            raise ValueError(f'x: (1, events, {nc}) tokens expected, got {tuple(x.shape)}')
+        if x.shape[1] < epc or x.shape[1] % epc != 0:
+            raise ValueError(f'x: a multiple of {epc} events (the events of one code), at least {epc}, expected; got {x.shape[1]}')
+        num_new_codes = int(num_new_codes)
+        if num_new_codes < 0:
+            raise ValueError('continue_tokens: num_new_codes >= 0')
+        PAD, START = ([int(n2i[c][sym]) for c in range(nc)] for sym in ('XX', 'START'))
+        row = lambda ids, n: torch.tensor(ids, dtype=torch.int64).view(1, 1, nc).repeat(1, n, 1)
+        framed = torch.cat([row(PAD, E - 1), row(START, 1), x], dim=1).to(self.sos.device)
+        was_training = self.training
+        self.eval()
+        try:
+            prefix = torch.cat([self.encode(c) for c in framed.split(E, 1)], dim=1)           # glued: (1, L)
+        finally:
+            self.train(was_training)
+        L = prefix.shape[1]
+        total = L + num_new_codes
+        if total < max(self.num_tokens, decoder.num_tokens_source):
+            raise ValueError(f'continue_tokens: {L} given + {num_new_codes} new codes, fewer than one model window '
+                             f'({max(self.num_tokens, decoder.num_tokens_source)})')
+        constraint = torch.full((1, total), -1, dtype=torch.int64, device=prefix.device)
+        constraint[:, :L] = prefix
+        out = self.generate_codes(total, temperature=temperature, num_generated_codes=num_continuations, seed=seed,
+                                  constraint=constraint, return_logp=return_logp)
+        codes, code_logp = out if return_logp else (out, None)
+        token_constraint = torch.full((int(num_continuations), total * epc, nc), -1, dtype=torch.int64)
+        token_constraint[:, E:E + x.shape[1]] = x
+        res = decoder.generate_from_code_long(encoding_indices=codes,
+                                              temperature=temperature if decoder_temperature is None else decoder_temperature,
+                                              code_index_start=E * nc // U, seed=seed, constraint=token_constraint,
+                                              return_logp=return_logp, **decoder_sampling)
+        if return_logp:
+            return codes, res[0], code_logp, res[1]
+        return codes, res
 
     def plot(self, *a, **k):
         raise NotImplementedError('tensorboard plots (:301-306) are out of scope')
