@@ -492,6 +492,26 @@ int vqcpc_vq_commit_bwd(const float* z, const float* codebooks, const int64_t* i
 int vqcpc_vq_ema_update(const float* stats, float* cluster_size, float* ema_sum, float* codebooks, int ncb, int K, int dsub,
                         float g, float h, float eps, void* stream);
 
+/* Dead-code restarts of the EMA codebooks (opt-in: EMAProductVectorQuantizer(restart_threshold=...)); two launches after
+ * ema_update, which stays as it is.
+ * restart_candidates: cand [ncb][K][dsub], EVERY element written, independent of N.  With
+ *       mix(x): x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31     (mod 2^64)
+ *       key = mix(seed + (count + 1) * 0x9E3779B97F4A7C15) ;  r = mix(key + (c * K + k + 1) * 0x9E3779B97F4A7C15)
+ *   code (c, k) draws row r_glob = r mod (R * world) of the z [R][ncb * dsub] of `world` ranks laid end to end in rank order:
+ *   cand[c][k][:] = z[r_glob % R][c * dsub : (c + 1) * dsub] on the rank r_glob / R, and +0.0f on every other rank (so that
+ *   the sum over the ranks is the row).  count = step_dev[0] when step_dev is non-NULL, else `step`.  step_dev is the
+ *   counter vqcpc_adam_step_dev reads, and this kernel reads the value that Adam launch reads: the counter AFTER
+ *   vqcpc_rng_salt_advance has incremented it for the step, i.e. Adam's t of the step (1 for the first).  The host form
+ *   passes that same t.  Refuses R * world >= 2^31, world < 1 and rank outside [0, world).
+ * ema_restart, in place: for every code with N[c][k] < thr (strict, fp32): e[c][k] = m[c][k] = cand[c][k], N[c][k] = 1 (the
+ *   quantiser's initial-state convention); every other cell keeps its bits.  restarts [ncb] int32 is INCREMENTED by the
+ *   number of codes restarted (wave ballot + popcount, one integer atomic per workgroup: schedule-independent); the host
+ *   zeroes it.  thr = 0 restarts nothing; a negative thr is refused. */
+int vqcpc_vq_restart_candidates(const float* z, int64_t R, int ncb, int K, int dsub, uint64_t seed, uint64_t step,
+                                const uint64_t* step_dev, int rank, int world, float* cand, void* stream);
+int vqcpc_vq_ema_restart(const float* cand, float* cluster_size, float* ema_sum, float* codebooks, int ncb, int K, int dsub,
+                         float thr, int32_t* restarts, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * MlpUpscaler middle: h' = SELU(dropout(h))  (VQCPCB/upscalers/mlp_upscaler.py:21-34); element index = flat index.
  * ------------------------------------------------------------------------------------------------------------------ */

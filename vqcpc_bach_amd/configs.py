@@ -88,6 +88,22 @@ def make_prior_config(dropout=0.2, **over):
     return cfg
 
 
+_QUANTIZER_KEYS = ('ema_restart_threshold', 'ema_restart_seed')
+
+
+def _with_overrides(cfg, over):
+    """A deep copy of cfg with the top-level keys of `over` replaced; the EMA quantiser's restart options
+    (ema_restart_threshold / ema_restart_seed, with quantizer_type='ema') go into quantizer_kwargs, where get_encoder reads them."""
+    cfg = copy.deepcopy(cfg)
+    for k, v in over.items():
+        if k not in _QUANTIZER_KEYS:
+            cfg[k] = v
+    for k in _QUANTIZER_KEYS:
+        if k in over:
+            cfg['quantizer_kwargs'][k] = over[k]
+    return cfg
+
+
 def make_sameseq_config(dropout=0.1, quantizer_type='commitment', **over):
     """VQCPCB/configs/encoder_sameSeq.py:11-86 in this package's schema: the GRU block downscaler ('lstm_downscaler':
     hidden 512, 2 layers, bidirectional, one 16-token block per code), 1 x 32 codes of dim 3, MLP upscaler 32 / 512, context
@@ -121,10 +137,7 @@ def make_sameseq_config(dropout=0.1, quantizer_type='commitment', **over):
         cfg['auxiliary_networks_kwargs']['quantization_weighting'] = 0.5
     elif quantizer_type != 'commitment':
         cfg['quantizer_type'] = quantizer_type
-    cfg = copy.deepcopy(cfg)
-    for k, v in over.items():
-        cfg[k] = v
-    return cfg
+    return _with_overrides(cfg, over)
 
 
 def make_config(name='C1', dropout=0.1, **over):
@@ -159,7 +172,4 @@ def make_config(name='C1', dropout=0.1, **over):
         'lr': 1e-4, 'schedule_lr': False, 'batch_size': B, 'num_batches': 256, 'num_epochs': 1,
         'quantizer_regularization': dict(corrupt_labels=False), 'timestamp': None, 'savename': f'encoder_cpc_{name}',
     }
-    cfg = copy.deepcopy(cfg)
-    for k, v in over.items():
-        cfg[k] = v
-    return cfg
+    return _with_overrides(cfg, over)

@@ -354,6 +354,64 @@ __global__ __launch_bounds__(kVqThreads) void vq_ema_update_kernel(const float* 
     }
 }
 
+// ---- dead-code restarts (opt-in companion of the EMA update) ---------------------------------------------------------------
+// mix of include/vqcpc.h (the splitmix64 finaliser csrc/clusters.hip uses), all arithmetic mod 2^64
+__device__ __forceinline__ uint64_t restart_mix(uint64_t x) {
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// candidates, one lane per element of cand [ncb][K][dsub]: the row r mod (R world) of the ranks' concatenated z, this rank's
+// value when it owns the row and +0.0f otherwise.  The lanes of one code recompute the same hash: ncb K dsub elements in all.
+__global__ __launch_bounds__(kVqThreads) void vq_restart_candidates_kernel(const float* __restrict__ z, int64_t R, int ncb, int K,
+                                                                           int dsub, uint64_t seed, uint64_t step,
+                                                                           const uint64_t* __restrict__ step_dev, int rank,
+                                                                           int world, float* __restrict__ cand) {
+    const int64_t i = (int64_t)blockIdx.x * kVqThreads + threadIdx.x;
+    if (i >= (int64_t)ncb * K * dsub) return;
+    const int64_t code = i / dsub;              // c * K + k
+    const int t = (int)(i - code * dsub);
+    const int c = (int)(code / K);
+    const uint64_t count = step_dev ? step_dev[0] : step;
+    const uint64_t key = restart_mix(seed + (count + 1) * 0x9E3779B97F4A7C15ull);
+    const uint64_t r = restart_mix(key + ((uint64_t)code + 1) * 0x9E3779B97F4A7C15ull);
+    const uint64_t r_glob = r % ((uint64_t)R * (uint64_t)world);
+    const int64_t owner = (int64_t)(r_glob / (uint64_t)R), row = (int64_t)(r_glob % (uint64_t)R);
+    cand[i] = owner == rank ? z[row * ((int64_t)ncb * dsub) + (int64_t)c * dsub + t] : 0.0f;
+}
+
+// restart, one lane per code: N < thr (strict) -> e = m = cand, N = 1; every other cell keeps its bits.  The codes restarted by a
+// workgroup are counted by wave ballot + popcount, summed over its waves in LDS and added to restarts[c] by ONE integer atomic.
+__global__ __launch_bounds__(kVqThreads) void vq_ema_restart_kernel(const float* __restrict__ cand, float* __restrict__ N,
+                                                                    float* __restrict__ m, float* __restrict__ cb, int K, int dsub,
+                                                                    float thr, int* __restrict__ restarts) {
+    __shared__ int wave_count[kVqThreads / kWave];
+    const int c = blockIdx.y;
+    const int k = blockIdx.x * kVqThreads + threadIdx.x;
+    const int64_t code = (int64_t)c * K + k;
+    const bool dead = k < K && N[code] < thr;
+    if (dead) {
+        const float* src = cand + code * dsub;
+        float* mk = m + code * dsub;
+        float* ek = cb + code * dsub;
+        for (int t = 0; t < dsub; ++t) {
+            const float v = src[t];
+            ek[t] = v;
+            mk[t] = v;
+        }
+        N[code] = 1.0f;
+    }
+    const uint64_t bal = __ballot(dead);         // every lane of the wave arrives here
+    if ((threadIdx.x & (kWave - 1)) == 0) wave_count[threadIdx.x / kWave] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < kVqThreads / kWave; ++w) total += wave_count[w];
+        if (total > 0) atomicAdd(restarts + c, total);
+    }
+}
+
 }  // namespace vq
 
 using namespace vq;
@@ -471,6 +529,33 @@ int vqcpc_vq_ema_update(const float* stats, float* cluster_size, float* ema_sum,
     hipLaunchKernelGGL(vq_ema_update_kernel, dim3(ncb), dim3(kVqThreads), lds, (hipStream_t)stream, stats, cluster_size, ema_sum,
                        codebooks, K, dsub, P, g, h, eps);
     VQ_CHECK_LAUNCH("vq_ema_update");
+    return VQCPC_OK;
+}
+
+int vqcpc_vq_restart_candidates(const float* z, int64_t R, int ncb, int K, int dsub, uint64_t seed, uint64_t step,
+                                const uint64_t* step_dev, int rank, int world, float* cand, void* stream) {
+    VQ_REQUIRE(z && cand, "vq_restart_candidates: null pointer");
+    VQ_REQUIRE(R >= 1 && ncb >= 1 && K >= 1 && dsub >= 1, "vq_restart_candidates: bad shape R=%lld ncb=%d K=%d dsub=%d",
+               (long long)R, ncb, K, dsub);
+    VQ_REQUIRE(world >= 1 && rank >= 0 && rank < world, "vq_restart_candidates: rank %d outside [0, world = %d)", rank, world);
+    VQ_REQUIRE(R < ((int64_t)1 << 31) && R * world < ((int64_t)1 << 31),
+               "vq_restart_candidates: %lld rows on %d ranks: 2^31 rows and more are refused", (long long)R, world);
+    const int64_t n = (int64_t)ncb * K * dsub;
+    VQ_REQUIRE(n < ((int64_t)1 << 31) * kVqThreads, "vq_restart_candidates: %lld elements exceed the grid", (long long)n);
+    hipLaunchKernelGGL(vq_restart_candidates_kernel, dim3((unsigned)ceil_div(n, kVqThreads)), dim3(kVqThreads), 0,
+                       (hipStream_t)stream, z, R, ncb, K, dsub, seed, step, step_dev, rank, world, cand);
+    VQ_CHECK_LAUNCH("vq_restart_candidates");
+    return VQCPC_OK;
+}
+
+int vqcpc_vq_ema_restart(const float* cand, float* cluster_size, float* ema_sum, float* codebooks, int ncb, int K, int dsub,
+                         float thr, int32_t* restarts, void* stream) {
+    VQ_REQUIRE(cand && cluster_size && ema_sum && codebooks && restarts, "vq_ema_restart: null pointer");
+    VQ_REQUIRE(ncb >= 1 && ncb <= 65535 && K >= 1 && dsub >= 1, "vq_ema_restart: bad shape ncb=%d K=%d dsub=%d", ncb, K, dsub);
+    VQ_REQUIRE(thr >= 0.0f, "vq_ema_restart: threshold %g is negative (or NaN)", (double)thr);
+    hipLaunchKernelGGL(vq_ema_restart_kernel, dim3((unsigned)ceil_div(K, kVqThreads), (unsigned)ncb), dim3(kVqThreads), 0,
+                       (hipStream_t)stream, cand, cluster_size, ema_sum, codebooks, K, dsub, thr, restarts);
+    VQ_CHECK_LAUNCH("vq_ema_restart");
     return VQCPC_OK;
 }
 

@@ -124,6 +124,9 @@ def get_encoder(model_dir, dataloader_generator, config):
     downscaler_kwargs['num_channels'] = data_processor.num_channels
     downscaler = get_downscaler(config['downscaler_type'], downscaler_kwargs)
     if config['quantizer_type'] == 'commitment':
+        if quantizer_kwargs.get('ema_restart_threshold'):
+            raise ValueError("ema_restart_threshold restarts EMA codebooks: quantizer_type 'commitment' trains its codebooks by "
+                             "Adam and keeps no usage statistic; use quantizer_type 'ema' or drop the key")
         quantizer = ProductVectorQuantizer(codebook_size=quantizer_kwargs['codebook_size'],
                                            num_codebooks=quantizer_kwargs['num_codebooks'],
                                            codebook_dim=quantizer_kwargs['codebook_dim'],
@@ -141,7 +144,9 @@ def get_encoder(model_dir, dataloader_generator, config):
                                               squared_l2_norm=quantizer_kwargs['squared_l2_norm'],
                                               commitment_cost=quantizer_kwargs['commitment_cost'],
                                               decay=quantizer_kwargs.get('ema_decay', 0.99),
-                                              epsilon=quantizer_kwargs.get('ema_epsilon', 1e-5))
+                                              epsilon=quantizer_kwargs.get('ema_epsilon', 1e-5),
+                                              restart_threshold=quantizer_kwargs.get('ema_restart_threshold'),
+                                              restart_seed=quantizer_kwargs.get('ema_restart_seed', 0))
     elif config['quantizer_type'] is None:
         quantizer = NoQuantization(codebook_dim=quantizer_kwargs['codebook_dim'])
     else:

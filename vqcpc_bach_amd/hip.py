@@ -152,6 +152,8 @@ SIGNATURES = {
     'vqcpc_vq_ema_stats': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr]),
     'vqcpc_vq_commit_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr]),
     'vqcpc_vq_ema_update': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_f32, c_f32, c_ptr]),
+    'vqcpc_vq_restart_candidates': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_u64, c_u64, c_ptr, c_int, c_int, c_ptr, c_ptr]),
+    'vqcpc_vq_ema_restart': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_ptr, c_ptr]),
     'vqcpc_dropout_selu_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_f32, c_u64, c_ptr]),
     'vqcpc_dropout_selu_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_u64, c_ptr]),
     'vqcpc_nce_fwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr,

@@ -1927,14 +1927,19 @@ class VQFn(torch.autograd.Function):
         return dz, dcb, None, None, None
 
 
+_M64 = (1 << 64) - 1      # seeds and step counts cross the ABI as uint64
+
+
 class VQEmaFn(torch.autograd.Function):
     """The EMA quantiser's forward / backward (quantizer.vector_quantizer.EMAProductVectorQuantizer): nearest-code search,
     straight-through output and the commitment loss beta * l; the codebooks receive NO gradient (their update is
     vqcpc_vq_ema_update on the statistics).  `stats` (ncb, K, 1 + dsub) is filled with this call's per-code counts and sums when
-    given (training); `stats_idx` is the uncorrupted nearest-code assignment when `given_idx` forces another (label corruption)."""
+    given (training); `stats_idx` is the uncorrupted nearest-code assignment when `given_idx` forces another (label corruption).
+    `restart` = (cand, seed, step, step_dev, rank, world) fills cand (ncb, K, dsub) with the step's restart candidates, rows of
+    this same z chosen by a keyed hash whatever the indices are (include/vqcpc.h: vqcpc_vq_restart_candidates)."""
 
     @staticmethod
-    def forward(ctx, z, codebooks, beta, squared, given_idx=None, stats=None, stats_idx=None):
+    def forward(ctx, z, codebooks, beta, squared, given_idx=None, stats=None, stats_idx=None, restart=None):
         z = _f32(z).contiguous()
         codebooks = _f32(codebooks).contiguous()
         R, D = z.shape
@@ -1953,6 +1958,12 @@ class VQEmaFn(torch.autograd.Function):
             nbytes = hip.query('vqcpc_vq_ema_stats_workspace', R, ncb, K, dsub)
             ws = hip.workspace(nbytes, z.device)
             hip.call('vqcpc_vq_ema_stats', z, sidx, R, ncb, K, dsub, stats, ws, nbytes)
+        if restart is not None:
+            cand, seed, step, step_dev, rank, world = restart
+            assert cand.shape == (ncb, K, dsub) and cand.is_contiguous() and cand.dtype == torch.float32
+            assert step_dev is None or (step_dev.dtype == torch.int64 and step_dev.numel() == 1)
+            hip.call('vqcpc_vq_restart_candidates', z, R, ncb, K, dsub, int(seed) & _M64, int(step) & _M64, step_dev, int(rank),
+                     int(world), cand)
         ctx.save_for_backward(z, codebooks, idx)
         ctx.meta = (float(beta), int(bool(squared)))
         ctx.mark_non_differentiable(idx)
@@ -1969,7 +1980,7 @@ class VQEmaFn(torch.autograd.Function):
         g_loss = g_loss.contiguous() if g_loss is not None else torch.zeros(R, dtype=torch.float32, device=z.device)
         dz = torch.empty_like(z)
         hip.call('vqcpc_vq_commit_bwd', z, codebooks, idx, g_zq, g_loss, R, ncb, K, dsub, beta, squared, dz)
-        return dz, None, None, None, None, None, None
+        return dz, None, None, None, None, None, None, None
 
 
 def vq_ema_update(stats, cluster_size, ema_sum, codebooks, decay, epsilon):
@@ -1980,6 +1991,16 @@ def vq_ema_update(stats, cluster_size, ema_sum, codebooks, decay, epsilon):
     assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (stats, cluster_size, ema_sum, codebooks))
     hip.call('vqcpc_vq_ema_update', stats, cluster_size, ema_sum, codebooks, ncb, K, dsub, float(decay), 1.0 - float(decay),
              float(epsilon))
+
+
+def vq_ema_restart(cand, cluster_size, ema_sum, codebooks, threshold, restarts):
+    """In place: every code with cluster_size < threshold (strict) takes its row of `cand` as codeword and as ema_sum, and
+    cluster_size 1; `restarts` (ncb,) int32 grows by the number of such codes (include/vqcpc.h: vqcpc_vq_ema_restart)."""
+    ncb, K, dsub = codebooks.shape
+    assert cand.shape == (ncb, K, dsub) and cluster_size.shape == (ncb, K) and ema_sum.shape == codebooks.shape
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (cand, cluster_size, ema_sum, codebooks))
+    assert restarts.shape == (ncb,) and restarts.dtype == torch.int32 and restarts.is_contiguous()
+    hip.call('vqcpc_vq_ema_restart', cand, cluster_size, ema_sum, codebooks, ncb, K, dsub, float(threshold), restarts)
 
 
 def vq_assign(z, codebooks):

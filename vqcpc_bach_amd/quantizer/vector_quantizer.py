@@ -97,13 +97,28 @@ class EMAProductVectorQuantizer(VectorQuantizer):
     `ema_cluster_size` (ncb, K), `ema_sum` (ncb, K, dsub) and the per-step `stats` (ncb, K, 1 + dsub) are BUFFERS: they never
     enter the flat parameter / gradient buffers, Adam or the clip norm.  forward() in training mode (with gradients enabled)
     leaves the step's statistics in `stats`; `apply_update()` folds them in (the trainer calls it after Adam, after the
-    statistics were sum-reduced over the ranks)."""
+    statistics were sum-reduced over the ranks).
+
+    Dead-code restarts (`restart_threshold`, default None = off; 0 is off too, a negative value raises ValueError): after the
+    update every code whose N_k is below the threshold (strict, fp32) becomes a row of THIS step's quantiser input -- sub-vector
+    c of the row a keyed hash of (restart_seed, step, c, k) names among the rows of all ranks -- with m_k = e_k and N_k = 1, the
+    initial-state convention above.  N is an average of rows per step: with decay 0.99 a code that receives no row falls from 1
+    to 0.5 in 69 steps (0.99^69 = 0.4998), one that receives a row per step stays near 1, so 0.5 reads "no row for about 70
+    steps" and a restarted code gets the same 70 steps of grace.  A threshold of 1 or more restarts every code that misses a
+    single step right after the initialisation: accepted, and almost never what is wanted.  Two dead codes may draw the same
+    row; the later index then loses every tie, stays dead and draws again on a later step.  The option adds two non-persistent
+    buffers (`restart_rows`, `restarts`: the per-codebook count since it was last zeroed) and two launches per step; the
+    state_dict keys are the same with and without it."""
 
     def __init__(self, codebook_size, codebook_dim, commitment_cost, num_codebooks, initialize, squared_l2_norm, decay=0.99,
-                 epsilon=1e-5):
+                 epsilon=1e-5, restart_threshold=None, restart_seed=0):
         super().__init__()
         assert codebook_dim % num_codebooks == 0
         assert 0.0 < decay < 1.0 and epsilon > 0.0
+        restart_threshold = 0.0 if restart_threshold is None else float(restart_threshold)
+        if not restart_threshold >= 0.0:
+            raise ValueError(f'restart_threshold must be None or >= 0, got {restart_threshold}')
+        self.restart_threshold, self.restart_seed = restart_threshold, int(restart_seed)
         self.num_codebooks = num_codebooks
         self.codebook_dim = codebook_dim
         self.codebook_size = codebook_size
@@ -119,6 +134,17 @@ class EMAProductVectorQuantizer(VectorQuantizer):
         self.squared_l2_norm = squared_l2_norm
         self.use_batch_norm = False
         self.init_broadcast = None
+        # (step, step_dev, rank, world) of the step being enqueued, set by the trainer (its optimiser owns the step count);
+        # without one, a quantiser used on its own counts its own apply_update() calls and is the only rank
+        self.restart_context = None
+        self._updates = 0
+        if self.restarting:
+            self.register_buffer('restart_rows', torch.zeros(num_codebooks, codebook_size, dsub), persistent=False)
+            self.register_buffer('restarts', torch.zeros(num_codebooks, dtype=torch.int32), persistent=False)
+
+    @property
+    def restarting(self):
+        return self.restart_threshold > 0.0
 
     def ema_buffers(self):
         return [self.embeddings, self.ema_cluster_size, self.ema_sum]
@@ -156,8 +182,18 @@ class EMAProductVectorQuantizer(VectorQuantizer):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def apply_update(self):
-        """Enqueues the EMA update on the statistics of the last training forward."""
+        """Enqueues the EMA update on the statistics of the last training forward, then (restart_threshold > 0) the restart of
+        the codes it left below the threshold from the candidates of that same forward."""
         ops.vq_ema_update(self.stats, self.ema_cluster_size, self.ema_sum, self.embeddings, self.decay, self.epsilon)
+        if self.restarting:
+            ops.vq_ema_restart(self.restart_rows, self.ema_cluster_size, self.ema_sum, self.embeddings, self.restart_threshold,
+                               self.restarts)
+            self._updates += 1
+
+    def codebook_perplexity(self):
+        """(ncb,) exp(-sum_k p_k log p_k) with p = N / sum N: the effective number of codes in use per codebook."""
+        p = self.ema_cluster_size / self.ema_cluster_size.sum(-1, keepdim=True)
+        return torch.exp(-(p * torch.log(p.clamp_min(torch.finfo(p.dtype).tiny))).sum(-1))
 
     def forward(self, inputs, corrupt_labels=False, init_rows=None, corrupt_rows=None, **kwargs):
         """As ProductVectorQuantizer.forward; the loss is commitment_cost * l.  In training mode with gradients enabled the
@@ -178,6 +214,10 @@ class EMAProductVectorQuantizer(VectorQuantizer):
                     keep = keep | ~only
                 given = torch.where(keep, nearest, rnd)
         stats = self.stats if (self.training and torch.is_grad_enabled()) else None
+        restart = None
+        if stats is not None and self.restarting:
+            ctx = self.restart_context() if self.restart_context is not None else (self._updates + 1, None, 0, 1)
+            restart = (self.restart_rows, self.restart_seed) + tuple(ctx)
         zq, idx, loss = ops.VQEmaFn.apply(flat, self.embeddings, self._commitment_cost, self.squared_l2_norm, given, stats,
-                                          nearest)
+                                          nearest, restart)
         return zq.view(shape), idx.view(*shape[:-1], self.num_codebooks), loss.view(shape[:-1])

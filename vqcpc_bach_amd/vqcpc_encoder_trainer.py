@@ -57,6 +57,19 @@ class VQCPCEncoderTrainer(EncoderTrainer):
         q = self.encoder.quantizer
         return q if hasattr(q, 'apply_update') else None
 
+    @property
+    def _restarting(self):
+        """True when the EMA quantiser restarts dead codewords (its restart_threshold > 0)."""
+        return self._ema is not None and self._ema.restarting
+
+    def _restart_context(self):
+        """(step, step_dev, rank, world) for the restart candidates of the step being enqueued.  step is Adam's t of this step:
+        the forward runs before optimizer.step() counts it, hence + 1; a captured step reads the device counter instead, which
+        the graph's first node has already incremented to the same t."""
+        opt = self.optimizer
+        capturing = opt._dev is not None and torch.cuda.is_current_stream_capturing()
+        return opt.step_count + 1, (opt._dev[1] if capturing else None), self.dp.rank, self.dp.world_size
+
     # ---- optimiser ---------------------------------------------------------------------------------------------
     def _modules_with_params(self):
         mods = [self.c_module, self.fks_module, self.encoder]
@@ -72,6 +85,8 @@ class VQCPCEncoderTrainer(EncoderTrainer):
         if self._ema is not None:
             for t in self._ema.ema_buffers():
                 self.dp.broadcast_(t, src=0)
+        if self._restarting:
+            self._ema.restart_context = self._restart_context
         self.lr, self.schedule_lr = lr, schedule_lr
         self.optimizer = ops.FlatAdam(self.flat.flat, self.flat.flat_grad, lr=lr, max_norm=5.0)
         self.scheduler = self.lr_lambda if schedule_lr else None
@@ -182,17 +197,20 @@ class VQCPCEncoderTrainer(EncoderTrainer):
         return out
 
     def _step_apply(self, out):
-        """clip + Adam (:313-316), then the EMA codebooks' update."""
+        """clip + Adam (:313-316), then the EMA codebooks' update (and, when asked for, the restart of the dead codewords)."""
         super()._step_apply(out)
         if self._ema is not None:
             self._ema.apply_update()          # EMA codebooks: counts and sums of the step (summed over ranks, not averaged)
         return out
 
     def _all_reduce_gradients(self):
-        """The flat gradient bucket and, with EMA codebooks, the step's per-code counts and sums next to it."""
+        """The flat gradient bucket and, with EMA codebooks, the step's per-code counts and sums next to it; with restarts the
+        candidate rows too: exactly one rank holds a non-zero row per code, so the sum is that row on every rank."""
         super()._all_reduce_gradients()
         if self._ema is not None:
             self.dp.all_reduce_sum_(self._ema.stats)
+            if self._ema.restarting:
+                self.dp.all_reduce_sum_(self._ema.restart_rows)
 
     def train_step(self, tensor_dict, train=True, corrupt_labels=False):
         """One iteration.  Returns device-side metrics.  With `enable_step_graph()` a training step is a HIP-graph replay
@@ -214,12 +232,19 @@ class VQCPCEncoderTrainer(EncoderTrainer):
         k_r = self.dataloader_generator.num_blocks_right
         sums = torch.zeros(5 + k_r, dtype=torch.float32, device=dev)   # loss, quantize, contrastive, ncw, ncw_neg, acc[k]
         dproc = self.encoder.data_processor
+        restarting = train and self._restarting
+        if restarting:
+            self._ema.restarts.zero_()
         n = 0
         for tensor_dict in islice(data_loader, num_batches):
             out = self.train_step(tensor_dict, train=train, corrupt_labels=corrupt_labels)
             sums += out['metrics']
             n += 1
         sums /= max(n, 1) * self.dp.world_size
+        if restarting:
+            # every rank holds the same counts and cluster sizes: divided by the world size they ride in the rank sum below
+            ncb = self._ema.num_codebooks
+            sums = torch.cat([sums, torch.cat([self._ema.restarts.float(), self._ema.codebook_perplexity()]) / self.dp.world_size])
         flag = dproc.bad_token_flag()
         if flag is not None:
             sums = torch.cat([sums, flag.float()])
@@ -229,9 +254,14 @@ class VQCPCEncoderTrainer(EncoderTrainer):
         host = sums.cpu().tolist()                                    # the only host sync of the epoch
         if flag is not None:
             dproc.raise_if_bad_tokens(host.pop())                     # nn.Embedding's IndexError, one epoch late at most
+        if restarting:
+            host, tail = host[:-2 * ncb], host[-2 * ncb:]
         means = dict(loss=host[0], accuracy=host[5:], loss_quantize=host[1], loss_contrastive=host[2],
                      num_codewords=host[3], num_codewords_negative=host[4])
         means['loss_monitor'] = -sum(means['accuracy']) / len(means['accuracy'])
+        if restarting:
+            means['codebook_restarts'] = [int(round(v)) for v in tail[:ncb]]      # total over the epoch, per codebook
+            means['codebook_perplexity'] = tail[ncb:]                             # of N at the end of the epoch, per codebook
         if train:
             self._report_scale_saturation(means)      # training.FlatTraining: means['f16x3_scale_saturations'] + marked steps
         return means
