@@ -128,6 +128,35 @@ int vqcpc_embedding_bwd(const float* g, int64_t ldg, const int64_t* sorted_idx, 
                         int64_t V, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Product codes (this package's extension; the reference has only the merged table).  A merged code of a product quantiser
+ * of ncb codebooks of K codewords is ncb digits, digit j: c_j = (code / K^j) % K (the order of Encoder.merge_codes),
+ * V = K^ncb.  Its embedding is the SUM of one row per codebook, so no tensor of V rows exists.
+ * Limits (refused with VQCPC_EINVAL): 1 <= ncb <= 4, 1 <= K <= 4096, V + n_extra < 2^31; C a multiple of 4.
+ *
+ * vqcpc_product_gather: tables [ncb][K][C], idx [M] int64, 1 <= nj <= ncb leading digits take part.
+ *   idx[m] < V:              out[m][:] = (res ? res[m][:] + : ) tables[0][c_0][:] + tables[1][c_1][:] + ... + tables[nj-1][c_{nj-1}][:]
+ *                            evaluated left to right, every add one separately rounded fp32 add; without res the chain STARTS at
+ *                            the first table row (no `0 +`): nj = 1 without res is a bit-exact row copy.
+ *   V <= idx[m] < V + n_extra: out[m][:] = extra[idx[m] - V][:], extra [n_extra][C] (the start-of-sentence rows).
+ *   res [M][ldr] (ldr >= C) and extra exclude each other; extra != NULL exactly when n_extra > 0.  out [M][ldo], ldo >= C (ldr
+ *   and ldo multiples of 4); columns [C, ldo) are never touched.  A row's bits depend on its own index, its res row and the
+ *   tables only.  Indices are NOT checked, as in vqcpc_block_table_gather: the caller guarantees 0 <= idx[m] < V + n_extra.
+ *
+ * vqcpc_product_gather_bwd: its gradient for the tables and the extra rows (d res = g is the caller's).  The caller forms, for
+ *   j < nj and every m, the key  j * K + c_j(idx[m])  where idx[m] < V,  ncb * K + (idx[m] - V)  for j = 0 where idx[m] >= V, and
+ *   any value >= ncb * K + n_extra (ignored) for j >= 1 where idx[m] >= V; sorted_keys / perm [S], S = nj * M, are the flattened
+ *   [nj][M] key array sorted ascending by a STABLE sort and the permutation that sorts it (perm[s] % M is the row of g).
+ *   d_tables [ncb][K][C] and d_extra [n_extra][C] are overwritten:
+ *     d_tables[j][k][:] = sum of g[m][:] over {m : idx[m] < V, c_j(idx[m]) = k}   (j < nj; codebooks j >= nj become 0)
+ *     d_extra[e][:]     = sum of g[m][:] over {m : idx[m] = V + e}
+ *   in ascending m, starting from 0; rows nobody refers to become 0.  Deterministic, no floating-point atomics.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_product_gather(const float* tables, const int64_t* idx, const float* res, int64_t ldr, const float* extra, int n_extra,
+                         float* out, int64_t ldo, int64_t M, int ncb, int K, int nj, int C, void* stream);
+int vqcpc_product_gather_bwd(const float* g, int64_t ldg, const int64_t* sorted_keys, const int64_t* perm, float* d_tables,
+                             float* d_extra, int64_t M, int64_t S, int ncb, int K, int n_extra, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * fp32 MFMA GEMMs (v_mfma_f32_32x32x2_f32).  Replace every F.linear / nn.Linear on the path:
  * multihead_attention_custom.py:171,346 (in_proj / out_proj), transformer_custom.py:285 (linear1/linear2),
  * relative_transformer_downscaler.py:132 (output_linear), mlp_upscaler.py:21-34 and their autograd backward.
@@ -873,6 +902,48 @@ int vqcpc_prior_sample_constrained(const float* logits, int64_t ldl, int V, int6
 int vqcpc_prior_window(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t* win, int advance, int64_t* codes_win, int N,
                        int P, int64_t* prefix_rows, const float* table, int64_t table_rows, int d, float* x, int64_t ldx,
                        const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The prior over PRODUCT codes (prior_kwargs['code_model'] = 'product'; csrc/product_codes.hip, the kernel bodies of the three
+ * entry points above under a compile-time flag).  A code is predicted digit by digit: a step's tail is, per stage j = 0 ..
+ * ncb - 1, one vqcpc_decode_linear (head j on h_j) and one vqcpc_prior_sample_product.  Notation and limits of the "Product
+ * codes" section: digit j of a code is (code / K^j) % K, V = K^ncb.  Adding them left the ABI version alone.
+ *
+ * vqcpc_prior_sample_product: ONE STAGE.  One workgroup per row b < M <= 64; nothing happens at any stage once pos[0] >= N.
+ *   logits[b][0..K) are the stage's.  Temperature (multiplication, the prior's sense), top-k and top-p filter THIS stage's
+ *   distribution exactly as vqcpc_prior_sample filters a row of K codes; probs[b][0..K) (may be NULL) receives it.
+ *   The digit: digit `stage` of teacher[b * ldteach + pos] (teacher != NULL; negative codes count as 0), else digit `stage` of
+ *   constraint[b * ldcons + col] where that is >= 0 -- a forced code is clamped to [0, V) first --, col = pos (win == NULL) or
+ *   win[1] + pos and the win[1] < 0 / col >= ldcons rules of vqcpc_prior_sample_constrained; else ONE draw from the stage's
+ *   filtered distribution.  A forced digit ignores the filters; a free one is drawn as if nothing were forced.
+ *   Draw keys: stage 0 draws with (seeds[b], pos), the merged sampler's key; stage j >= 1 with (s_j, pos),
+ *     s_j = splitmix64(seeds[b] XOR j * 0xA0761D6478BD642F)   (splitmix64: the finaliser vqcpc_decode_window's seed rule uses).
+ *   No key depends on M.  With ncb = 1 the kernel is vqcpc_prior_sample_constrained bit for bit (and so vqcpc_prior_sample,
+ *   where nothing is forced and logp == NULL): codes, next_in, probs, logp, pos, ticket.
+ *   Stage log-probability (computed when logp != NULL and col is in [0, ldlogp) with win[1] >= 0):
+ *     logits[digit] - logsumexp(logits[0..K)), unfiltered, temperature 1, reduced in an order that depends on K only; stage 0
+ *     STORES it in logp_acc[b], stage j >= 1 ADDS it (logp_acc[b] + own, one fp32 add, ascending j).
+ *   A stage j < ncb - 1 then stores its digit in digits[b * ncb + j] (device int32 scratch [M][ncb]) and writes
+ *     h_next[b][:] = h[b][:] + dtab[j][digit][:]   (one fp32 add per element; dtab [ncb - 1][K][d], the prior's digit-conditioning
+ *     table; h [M][ldh] is what this stage's head read, h_next [M][ldhn] what the next stage's head reads)
+ *   and touches neither codes, next_in, logp, pos nor the ticket.  The LAST stage forms the merged code from digits[b][0 ..
+ *   ncb - 1) and its own digit, writes codes[b * ldc + pos], next_in row b = tables[0][c_0] + tables[1][c_1] + ... (tables
+ *   [ncb][K][d]: the chain of vqcpc_product_gather without res, same order, same bits), logp[b * ldlogp + col] = the accumulated
+ *   sum, and advances pos[0] through the ticket as vqcpc_prior_sample does.
+ * vqcpc_prior_window_product: vqcpc_prior_window (commit, load, seeds rule, pos = P, win update) with the product row rule:
+ *   prefix_rows[b * P + j] = the merged code of input j clamped to [0, V), or V for the start-of-sentence input (j = 0); x row b
+ *   = the vqcpc_product_gather chain over tables [ncb][K][d] of the input of position P, or sos [d] when P = 0.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_prior_sample_product(const float* logits, int64_t ldl, int K, int ncb, int stage, int64_t M, float temperature, int top_k,
+                               float top_p, const int64_t* seeds, const int64_t* teacher, int64_t ldteach,
+                               const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
+                               int32_t* digits, float* logp_acc, const float* h, int64_t ldh, const float* dtab, float* h_next,
+                               int64_t ldhn, int64_t* codes, int64_t ldc, int N, const float* tables, int d, float* next_in,
+                               int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket, void* stream);
+int vqcpc_prior_window_product(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t* win, int advance, int64_t* codes_win,
+                               int N, int P, int64_t* prefix_rows, const float* tables, int ncb, int K, const float* sos, int d,
+                               float* x, int64_t ldx, const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The aligned ("diagonal") cross block of the decoder (TransformerAlignedDecoderLayerCustom,

@@ -21,7 +21,7 @@ OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libvqcpc_hip.so')
 LAB_OBJ = os.path.join(CSRC, '_obj_lab')
 LAB_LIB = os.path.join(HERE, 'libvqcpc_hip_lab.so')
-SOURCES = ['util.hip', 'vq.hip', 'nce.hip', 'embed_ln.hip', 'relattn.hip', 'relattn_sub.hip', 'relattn16.hip', 'relattn_x.hip', 'gemm.hip', 'gemm_bf16.hip', 'gemm_grad.hip', 'student.hip', 'gru.hip', 'decode.hip', 'prior.hip', 'aligned.hip', 'corpus.hip', 'duplicates.hip', 'clusters.hip']
+SOURCES = ['util.hip', 'vq.hip', 'nce.hip', 'embed_ln.hip', 'relattn.hip', 'relattn_sub.hip', 'relattn16.hip', 'relattn_x.hip', 'gemm.hip', 'gemm_bf16.hip', 'gemm_grad.hip', 'student.hip', 'gru.hip', 'decode.hip', 'prior.hip', 'aligned.hip', 'corpus.hip', 'duplicates.hip', 'clusters.hip', 'product_codes.hip']
 LAB_SOURCES = ['gemm_dma.hip', 'gemm_planes.hip', 'gemm_sw.hip']      # measurement-only translation units
 # the VQ argmin and the codeword neighbours must reproduce separately-rounded sub/mul/add: no FMA contraction in those files
 EXTRA = {'vq.hip': ['-ffp-contract=off'], 'clusters.hip': ['-ffp-contract=off']}
@@ -48,7 +48,8 @@ def build(force=False, verbose=True, lab=None):
     OBJ, LIB, SOURCES, FLAGS = _variant(lab)
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(HERE, '..', 'include', 'vqcpc.h')]
+    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'prior_kernels.h'),
+               os.path.join(HERE, '..', 'include', 'vqcpc.h')]
     hdr_m = max(os.path.getmtime(h) for h in headers)
     objs, jobs = [], []
     for src in SOURCES:

@@ -42,7 +42,7 @@ def make_student_config(dropout=0.1, **over):
     return cfg
 
 
-def make_decoder_config(dropout=0.2, **over):
+def make_decoder_config(dropout=0.2, source_embedding=None, **over):
     """VQCPCB/configs/decoder_relative_AC_AC_C_random.py:4-46 (24 beats = 96 ticks = 384
     target tokens, d_model 512, 8 heads, 3 + 3 layers, ff 1024, dropout 0.2, batch 32, scheduled lr) on the frozen
     transformer encoder of VQCPCB/configs/encoder_random_transfo_config.py:26-63 (d_model 512, 8 heads, [2, 2] layers,
@@ -50,7 +50,8 @@ def make_decoder_config(dropout=0.2, **over):
     `make_config('SAMESEQ')` and can be passed as `config_encoder=...` -- the default stays the transformer encoder the DEC
     measurements were taken with.  `decoder_type=` (like every key) is an override: 'transformer_relative_diagonal' is the DEC
     shape of VQCPCB/configs/decoder_relative_AC_D_C_*.py, 'transformer_relative_full' that of decoder_relative_F_F_C_*.py,
-    'transformer_relative_fullCross'; the default 'transformer_relative' is unchanged."""
+    'transformer_relative_fullCross'; the default 'transformer_relative' is unchanged.  `source_embedding='product'` (ours) goes
+    into `decoder_kwargs`: per-codebook source embeddings for a product-quantised `config_encoder` (decoders/decoder.py)."""
     enc = make_config('C1', dropout=0.1)
     enc['downscaler_kwargs'].update(d_model=512, n_head=8, list_of_num_layers=[2, 2], dim_feedforward=2048)
     enc['quantizer_kwargs'].update(num_codebooks=1, codebook_size=32, codebook_dim=3, initialize=False)
@@ -67,10 +68,12 @@ def make_decoder_config(dropout=0.2, **over):
     cfg = copy.deepcopy(cfg)
     for k, v in over.items():
         cfg[k] = v
+    if source_embedding is not None:
+        cfg['decoder_kwargs']['source_embedding'] = source_embedding
     return cfg
 
 
-def make_prior_config(dropout=0.2, **over):
+def make_prior_config(dropout=0.2, code_model=None, **over):
     """The code prior (VQCPCB/priors/prior_relative.py) on the DEC configuration's frozen encoder (1 x 32 codes, 24 codes per
     24-beat window).  The reference ships NO prior configuration: `prior_kwargs` (d_model 512, 8 heads, 6 layers, ff 1024,
     embedding 32, dropout 0.2 -- the decoder's widths with its 3 + 3 layers in one stack) is this package's own choice."""
@@ -85,6 +88,8 @@ def make_prior_config(dropout=0.2, **over):
     cfg = copy.deepcopy(cfg)
     for k, v in over.items():
         cfg[k] = v
+    if code_model is not None:                 # 'product': the code digit by digit, for a product-quantised `config_encoder`
+        cfg['prior_kwargs']['code_model'] = code_model
     return cfg
 
 

@@ -17,6 +17,9 @@ A decoder on continuous latents (a `NoQuantization` encoder without upscaler, de
 `check_duplicate` / `check_duplicate_all_corpus` (:983-1017) report the longest run of tokens a generation shares with another
 sequence or with the training corpus (csrc/duplicates.hip; dataloaders/corpus.py states the definition and where it departs from
 the reference's character-level difflib match).  Plots and the absolute-position variant are out of scope and raise.
+`source_embedding='product'` (ours, `decoder_kwargs['source_embedding']`; default 'merged' = the reference's table of
+K**ncb rows): `source_embeddings` is a `ProductEmbedding` (ncb, K, d_model) and a code's source row the sum of the rows of its
+ncb digits (quantizer/product_embedding.py).  Merged codes stay the interface; only the lookup differs.
 
 Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
   * source: `source_embeddings` lookup of the merged codes (gather + deterministic segment-sum gradient), or, on continuous
@@ -39,6 +42,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..quantizer.product_embedding import ProductEmbedding
 from ..training import FlatTraining
 from ..transformer.transformer_custom import (TransformerAlignedDecoderLayerCustom, TransformerCustom, TransformerDecoderCustom,
                                               TransformerDecoderLayerCustom, TransformerEncoderCustom,
@@ -87,8 +91,10 @@ class Decoder(FlatTraining, nn.Module):
     def __init__(self, model_dir, dataloader_generator, data_processor, encoder, transformer_type, encoder_attention_type,
                  cross_attention_type, d_model, num_encoder_layers, num_decoder_layers, n_head, dim_feedforward,
                  positional_embedding_size, num_channels_encoder, num_events_encoder, num_channels_decoder,
-                 num_events_decoder, dropout):
+                 num_events_decoder, dropout, source_embedding='merged'):
         super().__init__()
+        if source_embedding not in ('merged', 'product'):
+            raise ValueError(f"source_embedding {source_embedding!r}: 'merged' or 'product'")
         if transformer_type != 'relative':
             raise NotImplementedError("transformer_type 'absolute' (learned absolute positions, nn attention without "
                                       'relative bias) is not on the path: SURVEY.md section 8(f) N4 covers the relative decoder')
@@ -135,6 +141,9 @@ class Decoder(FlatTraining, nn.Module):
         self.linear_target = nn.Linear(self.data_processor.embedding_size + positional_embedding_size * 2, self.d_model)
         self.sos = nn.Parameter(torch.randn((1, 1, self.d_model)))
         self.continuous_source = type(self.encoder.quantizer).__name__ == 'NoQuantization'
+        self.source_embedding = source_embedding
+        if self.continuous_source and source_embedding == 'product':
+            raise ValueError("source_embedding 'product' needs a quantised encoder: a NoQuantization encoder has no codes")
         if self.continuous_source:                                                           # :222-229
             if self.encoder.upscaler is not None:
                 raise NotImplementedError('a NoQuantization encoder WITH an upscaler: the decoder reads the latents before the '
@@ -143,6 +152,10 @@ class Decoder(FlatTraining, nn.Module):
             if self.source_dim % 4 != 0 or not 4 <= self.source_dim <= 256:
                 raise NotImplementedError(f'continuous source of dimension {self.source_dim}: a multiple of 4 in [4, 256] is needed')
             self.source_embeddings = nn.Linear(self.source_dim, self.d_model)
+        elif source_embedding == 'product':                  # ours: a code's row is the sum of one row per codebook
+            self.source_dim = None
+            self.source_embeddings = ProductEmbedding(self.encoder.quantizer.num_codebooks, self.encoder.quantizer.codebook_size,
+                                                      self.d_model)
         else:
             self.source_dim = None
             codebook_size = self.encoder.quantizer.codebook_size ** self.encoder.quantizer.num_codebooks
@@ -228,6 +241,13 @@ class Decoder(FlatTraining, nn.Module):
         shifted = torch.cat([torch.full((B, 1), vmax * U, dtype=idx.dtype, device=dev), idx[:, :-1]], dim=1)
         return ops.EmbeddingFn.apply(table, shifted.reshape(-1))
 
+    def source_rows(self, codes):
+        """Merged codes (...) -> (codes.numel(), d_model) source rows: the `source_embeddings` lookup, or, with
+        source_embedding='product', the sum of the per-codebook rows of the code's digits."""
+        if self.source_embedding == 'product':
+            return self.source_embeddings(codes)
+        return ops.EmbeddingFn.apply(self.source_embeddings.weight, codes.reshape(-1))
+
     def _check_source(self, source, name, length=None):
         """The source of this decoder's kind: (B, n) integer merged codes, or (B, n, dz) floating-point latents for a
         continuous decoder; n == length unless length is None.  ValueError otherwise."""
@@ -250,7 +270,7 @@ class Decoder(FlatTraining, nn.Module):
             z = source.detach().to(torch.float32).reshape(-1, self.source_dim)
             src = ops.linear(z, self.source_embeddings.weight, self.source_embeddings.bias)
         else:
-            src = ops.EmbeddingFn.apply(self.source_embeddings.weight, source.reshape(-1))  # (B * S, d)
+            src = self.source_rows(source)                                                  # (B * S, d)
         tgt = self._target_rows(x)
         memory_mask = ops.MASK_NONE if self.cross_attention_type == 'diagonal' else mask_code(self.cross_attention_type)   # :487-488
         out, att_dec, att_enc = self.transformer.forward_rows(

@@ -122,7 +122,7 @@ class IncrementalDecoder(IncrementalStack):
             hip.call('vqcpc_decode_source_rows', self.z_full, self.z_nb, self.dz, self.win if windowed else None, lin.weight,
                      lin.bias, src, d, M, self.S, d)
         else:
-            src = ops.EmbeddingFn.apply(dec.source_embeddings.weight, codes.reshape(-1))
+            src = dec.source_rows(codes)
         memory, att = dec.transformer.encoder.forward_rows_masked(src, M, mask_code(dec.encoder_attention_type))
         # per encoder layer (M, H, S, S); a moved window's maps are not kept (a captured slide would pin its own pool's tensors)
         self.enc_probs = None if windowed else [a['a_self_encoder'] for a in att]

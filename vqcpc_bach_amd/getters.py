@@ -205,7 +205,7 @@ def get_decoder(model_dir, dataloader_generator, data_processor, encoder, decode
                    n_head=k['n_head'], dim_feedforward=k['dim_feedforward'], dropout=k['dropout'],
                    positional_embedding_size=k['positional_embedding_size'], num_channels_encoder=num_channels_encoder,
                    num_events_encoder=num_events_encoder, num_channels_decoder=num_channels_decoder,
-                   num_events_decoder=num_events_decoder)
+                   num_events_decoder=num_events_decoder, source_embedding=k.get('source_embedding', 'merged'))
 
 
 def get_prior(model_dir, dataloader_generator, encoder, prior_type, prior_kwargs):
@@ -227,4 +227,4 @@ def get_prior(model_dir, dataloader_generator, encoder, prior_type, prior_kwargs
     return PriorRelative(model_dir=model_dir, dataloader_generator=dataloader_generator, encoder=encoder,
                          d_model=k['d_model'], num_layers=k['num_layers'], n_head=k['n_head'],
                          dim_feedforward=k['dim_feedforward'], embedding_size=k['embedding_size'], num_channels=num_channels,
-                         num_events=num_events, dropout=k['dropout'])
+                         num_events=num_events, dropout=k['dropout'], code_model=k.get('code_model', 'merged'))

@@ -125,6 +125,9 @@ SIGNATURES = {
                                     c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_f32,
                                     c_u64, c_ptr, c_i64, c_ptr]),
     'vqcpc_embedding_bwd': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr]),
+    'vqcpc_product_gather': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int,
+                                     c_ptr]),
+    'vqcpc_product_gather_bwd': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_ptr]),
     'vqcpc_add_layernorm_fwd': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32,
                                         c_f32, c_u64, c_ptr]),
     'vqcpc_add_layernorm_fwd_b16': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32,
@@ -224,6 +227,11 @@ SIGNATURES = {
                                                c_ptr, c_ptr]),
     'vqcpc_prior_window': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr,
                                    c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'vqcpc_prior_sample_product': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr,
+                                           c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
+                                           c_int, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_window_product': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr,
+                                           c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'vqcpc_aligned_expand': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     'vqcpc_aligned_reduce': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr]),
     'vqcpc_elu_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_ptr]),

@@ -1887,6 +1887,73 @@ class EmbeddingFn(torch.autograd.Function):
         return d_table, None
 
 
+PRODUCT_MAX_CODEBOOKS, PRODUCT_MAX_CODEBOOK_SIZE = 4, 4096
+
+
+def check_product_shape(ncb, K, n_extra=0):
+    """The limits of the product-code kernels (include/vqcpc.h), checked on the host: ValueError outside them.  Returns V."""
+    ncb, K, n_extra = int(ncb), int(K), int(n_extra)
+    if not (1 <= ncb <= PRODUCT_MAX_CODEBOOKS and 1 <= K <= PRODUCT_MAX_CODEBOOK_SIZE and n_extra >= 0):
+        raise ValueError(f'product codes: need 1 <= num_codebooks <= {PRODUCT_MAX_CODEBOOKS} and 1 <= codebook_size <= '
+                         f'{PRODUCT_MAX_CODEBOOK_SIZE}, got {ncb} x {K} (+ {n_extra} extra rows)')
+    if K ** ncb + n_extra >= 2 ** 31:
+        raise ValueError(f'product codes: {K}^{ncb} + {n_extra} merged codes do not fit 31 bits')
+    return K ** ncb
+
+
+class ProductEmbeddingFn(torch.autograd.Function):
+    """out[m] = (res[m] +) tables[0][c_0] + ... + tables[nj-1][c_{nj-1}] for the digits c_j = (idx[m] // K**j) % K of merged
+    codes idx < V = K**ncb, left to right in fp32; out[m] = extra[idx[m] - V] for V <= idx[m] < V + len(extra) (the
+    start-of-sentence rows).  tables (ncb, K, C); extra (n_extra, C) or None; nj (default ncb) leading digits take part; res
+    (M, C) or None, not together with extra.  vqcpc_product_gather; backward = deterministic segment sums over ONE stable sort of
+    the (row, codebook) keys (integer plumbing only) in vqcpc_product_gather_bwd, d res = the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, tables, extra, idx, nj=None, res=None):
+        tables = _f32(tables).contiguous()
+        ncb, K, C = tables.shape
+        n_extra = 0 if extra is None else extra.shape[0]
+        check_product_shape(ncb, K, n_extra)
+        nj = ncb if nj is None else int(nj)
+        if not 1 <= nj <= ncb:
+            raise ValueError(f'ProductEmbeddingFn: nj = {nj} of {ncb} codebooks')
+        if res is not None and extra is not None:
+            raise ValueError('ProductEmbeddingFn: res and extra are not given together')
+        if C % 4 != 0:
+            raise ValueError(f'ProductEmbeddingFn: rows of {C} floats, a multiple of 4 is needed')
+        idx = idx.reshape(-1).to(torch.int64).contiguous()
+        M = idx.numel()
+        ldr = 0
+        if res is not None:
+            res, ldr = _rows(_f32(res))
+            assert res.shape == (M, C), (res.shape, (M, C))
+        if extra is not None:
+            extra = _f32(extra).contiguous()
+            assert extra.shape[1] == C
+        out = torch.empty(M, C, dtype=torch.float32, device=tables.device)
+        hip.call('vqcpc_product_gather', tables, idx, res, ldr, extra, n_extra, out, C, M, ncb, K, nj, C)
+        ctx.save_for_backward(idx)
+        ctx.meta = (ncb, K, C, n_extra, nj, res is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        ncb, K, C, n_extra, nj, has_res = ctx.meta
+        g, ldg = _rows(_f32(g) if g.stride(1) == 1 else _f32(g).contiguous())
+        M = idx.numel()
+        dev = g.device
+        j = torch.arange(nj, device=dev).view(nj, 1)
+        code = idx.view(1, M) < K ** ncb
+        keys = j * K + (idx.view(1, M) // (K ** j)) % K                                    # (nj, M): row j * K + c_j of the tables
+        sos = torch.where(j == 0, ncb * K + idx.view(1, M) - K ** ncb, ncb * K + n_extra)  # extra row for j = 0, nobody's after
+        sorted_keys, perm = torch.sort(torch.where(code, keys, sos).reshape(-1), stable=True)
+        d_tables = torch.empty(ncb, K, C, dtype=torch.float32, device=dev)
+        d_extra = torch.empty(n_extra, C, dtype=torch.float32, device=dev) if n_extra else None
+        hip.call('vqcpc_product_gather_bwd', g, ldg, sorted_keys, perm, d_tables, d_extra, M, nj * M, ncb, K, n_extra, C)
+        return d_tables, d_extra, None, None, (g if has_res else None)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # A9/A10: product vector quantiser
 # ------------------------------------------------------------------------------------------------------------------

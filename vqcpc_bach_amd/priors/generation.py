@@ -76,14 +76,22 @@ class IncrementalPrior(IncrementalStack):
         self.V = pr.num_tokens_per_channel[0]
         layers = list(pr.transformer.layers)
         super().__init__(dev, M, layers, [lay.norm2 for lay in layers], N, pr.d_model)
-        self.logits = torch.empty(M, self.V, dtype=torch.float32, device=dev)
         self.codes_win = torch.zeros(M, N, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self._sos_col = torch.full((M, 1), self.V, dtype=torch.int64, device=dev)    # table row of the start-of-sentence input
+        self._init_model()
+
+    def _init_model(self):
+        """The model-side buffers of the merged code: the input table, the head and its logits."""
+        pr = self.prior
+        self.logits = torch.empty(self.M, self.V, dtype=torch.float32, device=self.dev)
         with torch.no_grad():
             self.table = pr._input_table().contiguous()                    # (V + 1, d)
         head = pr.pre_softmaxes[0]
         self.head_w, self.head_b = head.weight, head.bias
+
+    def _probs_buffer(self):
+        return torch.zeros(self.M, self.V, dtype=torch.float32, device=self.dev)
 
     def start(self, num_tokens, seeds=None, temperature=1.0, top_k=0, top_p=1.0, teacher=None, want_probs=False,
               constraint=None, want_logp=False):
@@ -112,7 +120,7 @@ class IncrementalPrior(IncrementalStack):
         self.constraint = constraint
         self.logp = torch.empty(self.M, self.nt, dtype=torch.float32, device=self.dev) if want_logp else None
         self.constrained = constraint is not None or bool(want_logp)
-        self.probs = torch.zeros(self.M, self.V, dtype=torch.float32, device=self.dev) if want_probs else None
+        self.probs = self._probs_buffer() if want_probs else None
         self.seq = torch.zeros(self.M, self.nt, dtype=torch.int64, device=self.dev)
         self.reset()
 
@@ -146,8 +154,13 @@ class IncrementalPrior(IncrementalStack):
         if not 0 <= p < N:
             raise ValueError(f'step_forward: 0 <= p < {N} (got {p})')
         idx = torch.cat([self._sos_col, self.codes_win[:, :N - 1]], dim=1).reshape(-1)       # the shift by one
-        rows = ops.EmbeddingFn.apply(self.table, idx)                                        # (M * N, d)
+        rows = self._input_rows(idx)                                                         # (M * N, d)
         out, _ = self.prior.transformer.forward_rows_masked(rows, M, ops.MASK_CAUSAL)
+        self._forward_tail(out, p)
+
+    def _forward_tail(self, out, p):
+        """The head on row p of every sequence of `out` (M * N, d), and the sampler."""
+        M, N, d, V = self.M, self.N, self.d, self.V
         hip.call('vqcpc_decode_linear', out.data_ptr() + 4 * p * d, N * d, None, self.head_w, self.head_b, None, 0, self.logits,
                  V, M, V, d, 0)
         self._sample()
@@ -246,3 +259,68 @@ class IncrementalPrior(IncrementalStack):
         torch.cuda.current_stream(self.dev).synchronize()
         del step_graph, slide_graph
         return self.seq
+
+
+class IncrementalProductPrior(IncrementalPrior):
+    """`IncrementalPrior` for a prior with code_model = 'product' (priors/prior_relative.py): the same stack, moves, regimes and
+    forms on merged codes; what differs is where a code enters and leaves the stack.
+
+      inputs: a code's input row is the sum of its digits' rows of the (ncb, K, d) tables (vqcpc_product_gather; the sampler and
+      vqcpc_prior_window_product write the same chain), the start of sentence is row V = K**ncb, `sos`.
+      a step's tail: per stage j, ONE vqcpc_decode_linear (head j on h_j) and ONE vqcpc_prior_sample_product, which draws or
+      forces digit j, adds the stage's log-probability and hands h_{j+1} = h_j + D_j[digit] to the next stage; the last stage
+      emits the merged code, the next input row and advances `pos`.  2 ncb launches in place of 2; `stage_logits` holds the ncb
+      stages' rows (ncb, M, K) (`logits` is stage 0's), `probs` likewise.  temperature / top_k / top_p act on each digit's conditional distribution.
+
+    No buffer of K**ncb rows exists."""
+
+    def _init_model(self):
+        pr, M, dev, d = self.prior, self.M, self.dev, self.d
+        ncb, K = self.ncb, self.K = pr.num_codebooks, pr.codebook_size
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.stage_logits = torch.empty(ncb, M, K, **f32)
+        self.logits = self.stage_logits[0]                                 # what the stack's step fills: stage 0's
+        with torch.no_grad():
+            self.tables = pr._input_tables().contiguous()                  # (ncb, K, d)
+            self.sos = pr.sos.detach().reshape(1, d).contiguous()
+        self.heads = [(h.weight, h.bias) for h in pr.pre_softmaxes]
+        self.head_w, self.head_b = self.heads[0]                           # the stack's step runs head 0 on its output
+        self.dtab = pr.digit_embeddings.weight if ncb > 1 else None
+        self.hs = [torch.empty(M, d, **f32) for _ in range(ncb - 1)]       # h_1 .. h_{ncb-1}
+        self.digits = torch.zeros(M, ncb, dtype=torch.int32, device=dev)
+        self.logp_acc = torch.zeros(M, **f32)
+
+    def _probs_buffer(self):
+        return torch.zeros(self.ncb, self.M, self.K, dtype=torch.float32, device=self.dev)
+
+    def _input_rows(self, idx):
+        return ops.ProductEmbeddingFn.apply(self.tables, self.sos, idx)
+
+    def _stages(self, h0, ldh0):
+        """The ncb stages on h_0 = the stack's output rows (a pointer and its leading dimension); stage 0's logits are there."""
+        M, N, K, ncb, d = self.M, self.N, self.K, self.ncb, self.d
+        for j in range(ncb):
+            h, ldh = (h0, ldh0) if j == 0 else (self.hs[j - 1], d)
+            if j > 0:
+                w, b = self.heads[j]
+                hip.call('vqcpc_decode_linear', h, d, None, w, b, None, 0, self.stage_logits[j], K, M, K, d, 0)
+            last = j == ncb - 1
+            hip.call('vqcpc_prior_sample_product', self.stage_logits[j], K, K, ncb, j, M, self.temperature, self.top_k, self.top_p,
+                     self.seeds, self.teacher, N, self.constraint, self.nt, self.logp, self.nt, self.win, self.digits,
+                     self.logp_acc, None if last else h, ldh, None if last else self.dtab, None if last else self.hs[j], d,
+                     self.codes_win, N, N, self.tables, d, self.x, d, None if self.probs is None else self.probs[j], K, self.pos,
+                     self.ticket)
+
+    def _sample(self):
+        self._stages(self.hb[(len(self.layers) - 1) % 2], self.d)          # the cached step's last LayerNorm wrote h_0 there
+
+    def _forward_tail(self, out, p):
+        M, N, d, K = self.M, self.N, self.d, self.K
+        h0 = out.data_ptr() + 4 * p * d                                     # row p of every sequence
+        hip.call('vqcpc_decode_linear', h0, N * d, None, self.head_w, self.head_b, None, 0, self.logits, K, M, K, d, 0)
+        self._stages(h0, N * d)
+
+    def _window(self, P, advance):
+        hip.call('vqcpc_prior_window_product', self.seq, self.nt, self.nt, self.win, int(advance), self.codes_win, self.N, int(P),
+                 self.prefix_rows, self.tables, self.ncb, self.K, self.sos, self.d, self.x, self.d, self.row_seeds, self.seeds,
+                 self.pos, self.M)

@@ -32,6 +32,17 @@ returns every emitted code's log-probability -- under the model's UNMODIFIED row
 before).  `score_codes` is the everything-forced call; `continue_tokens` encodes the opening of a piece, lets the prior go on
 from its codes and has the decoder write tokens around the given ones.
 
+PRODUCT CODES: `code_model='product'` (ours, `prior_kwargs['code_model']`; default 'merged' = the reference's model, one symbol
+of a vocabulary of V = K**ncb, which `generate_codes` samples up to V = 4096).  A merged code is ncb digits c_j = (code // K**j)
+% K.  `embedding` is a `ProductEmbedding` (ncb, K, embedding_size) and a code's input row linear(sum_j E_j[c_j]), evaluated as
+sum_j T_j[c_j] over per-codebook tables of ncb * K rows (`_input_tables`); `pre_softmaxes` is ncb heads Linear(d_model, K);
+`digit_embeddings` a `ProductEmbedding` (ncb - 1, K, d_model), absent when ncb = 1.  With h_e the stack's output at position e,
+stage j's logits are pre_softmaxes[j](h_e + sum_{i<j} D_i[c_{e,i}]): p(code_e | codes < e) = prod_j softmax(logits_{e,j})[c_{e,j}],
+the loss sum_j mean CE_j, and no tensor of V rows exists anywhere.  Merged int64 codes stay the interface of every method;
+`forward` returns the ncb logit tensors.  In `generate_codes`, `temperature`, `top_k` and `top_p` filter EACH DIGIT'S conditional
+distribution (a filter on the joint distribution over K**ncb codes does not exist), and `logp` is the sum of the ncb stage
+log-probabilities.  With ncb = 1 the model, its kernels' bits and its codes are the merged prior's.
+
 The reference ships no prior configuration; `configs.make_prior_config()` is this package's own.
 """
 import os
@@ -42,6 +53,7 @@ from torch import nn
 
 from .. import ops
 from ..decoders.decoder import HeadsFn
+from ..quantizer.product_embedding import ProductEmbedding
 from ..training import FlatTraining
 from ..transformer.transformer_custom import TransformerEncoderCustom, TransformerEncoderLayerCustom
 from ..utils import STEP_LOCK
@@ -51,8 +63,11 @@ MAX_SAMPLED_VOCAB = 4096         # vqcpc_prior_sample / vqcpc_prior_sample_const
 
 class PriorRelative(FlatTraining, nn.Module):
     def __init__(self, model_dir, dataloader_generator, encoder, d_model, num_layers, n_head, dim_feedforward, embedding_size,
-                 num_channels, num_events, dropout):
+                 num_channels, num_events, dropout, code_model='merged'):
         super().__init__()
+        if code_model not in ('merged', 'product'):
+            raise ValueError(f"code_model {code_model!r}: 'merged' or 'product'")
+        self.code_model = code_model
         self.model_dir = model_dir
         self.encoder = encoder
         self.encoder.eval()                                # frozen (:49-52)
@@ -70,10 +85,23 @@ class PriorRelative(FlatTraining, nn.Module):
                                                       num_channels=num_channels, num_events=num_events,
                                                       dim_feedforward=dim_feedforward, dropout=dropout)
         self.transformer = TransformerEncoderCustom(encoder_layer=encoder_layer, num_layers=num_layers)
-        self.embedding = nn.Embedding(self.num_tokens_per_channel[0], embedding_size)
+        self.num_codebooks, self.codebook_size = int(encoder.quantizer.num_codebooks), int(encoder.quantizer.codebook_size)
+        if code_model == 'product':                        # ours: a code is predicted digit by digit (module docstring)
+            ncb, K = self.num_codebooks, self.codebook_size
+            ops.check_product_shape(ncb, K, 1)
+            if d_model % 4 != 0:
+                raise ValueError(f"code_model 'product': d_model = {d_model}, a multiple of 4 is needed")
+            self.embedding = ProductEmbedding(ncb, K, embedding_size)
+        else:
+            self.embedding = nn.Embedding(self.num_tokens_per_channel[0], embedding_size)
         self.linear = nn.Linear(embedding_size, self.d_model)
         self.sos = nn.Parameter(torch.randn((1, 1, self.d_model)))
-        self.pre_softmaxes = nn.ModuleList([nn.Linear(self.d_model, n) for n in self.num_tokens_per_channel])
+        if code_model == 'product':
+            self.pre_softmaxes = nn.ModuleList([nn.Linear(self.d_model, K) for _ in range(ncb)])
+            if ncb > 1:
+                self.digit_embeddings = ProductEmbedding(ncb - 1, K, self.d_model)
+        else:
+            self.pre_softmaxes = nn.ModuleList([nn.Linear(self.d_model, n) for n in self.num_tokens_per_channel])
         self.lr = 1e-3
 
     def __repr__(self):
@@ -86,7 +114,8 @@ class PriorRelative(FlatTraining, nn.Module):
 
     # ---- the trainable parameters (the frozen encoder is excluded) -------------------------------------------------
     def _trainable(self):
-        return [self.transformer, self.embedding, self.linear, self.sos, self.pre_softmaxes]
+        own = [self.transformer, self.embedding, self.linear, self.sos, self.pre_softmaxes]
+        return own + ([self.digit_embeddings] if hasattr(self, 'digit_embeddings') else [])
 
     def init_optimizers(self, lr=1e-3, dp=None):
         self._init_flat(self._trainable(), self.sos.device, dp)
@@ -121,12 +150,45 @@ class PriorRelative(FlatTraining, nn.Module):
         table = ops.linear(self.embedding.weight, self.linear.weight, self.linear.bias)
         return torch.cat([table, self.sos.view(1, self.d_model)], dim=0)
 
+    def _input_tables(self):
+        """code_model 'product': (ncb, K, d_model) per-codebook input rows, T_0 = linear(E_0) with the bias, T_j = E_j W^T without
+        it for j >= 1, so that a code's input row sum_j T_j[c_j] is linear(sum_j E_j[c_j]): two small GEMMs on ncb * K rows."""
+        E, lin = self.embedding.weight, self.linear
+        first = ops.linear(E[0], lin.weight, lin.bias)
+        if self.num_codebooks == 1:
+            return first.unsqueeze(0)
+        rest = ops.linear(E[1:].reshape(-1, E.shape[2]), lin.weight, None)
+        return torch.cat([first, rest], dim=0).view(self.num_codebooks, self.codebook_size, self.d_model)
+
+    def _compute_loss_product(self, codes):
+        """codes (B, N) -> (loss, [logits_j (B, N, K) for the ncb digits]).  Stage j's head reads the stack's output plus the
+        digit-conditioning rows of the digits i < j of the SAME code: p(code) = prod_j softmax(logits_j)[c_j], and the loss
+        sum_j mean CE_j is minus the mean log-probability per code, the merged prior's scale."""
+        B, N = codes.shape
+        ncb, K, V, d = self.num_codebooks, self.codebook_size, self.num_tokens_per_channel[0], self.d_model
+        shifted = torch.cat([torch.full((B, 1), V, dtype=torch.int64, device=codes.device), codes[:, :-1]], dim=1)
+        rows = ops.ProductEmbeddingFn.apply(self._input_tables(), self.sos.view(1, d), shifted.reshape(-1))   # (B * N, d)
+        out, _ = self.transformer.forward_rows_masked(rows, B, ops.MASK_CAUSAL)
+        flat = codes.reshape(-1)
+        low = flat % (K ** (ncb - 1))                      # the digits the conditioning table knows: all but the last
+        loss, logits = None, []
+        for j, head in enumerate(self.pre_softmaxes):
+            h = out if j == 0 else ops.ProductEmbeddingFn.apply(self.digit_embeddings.weight, None, low, j, out)
+            (lg,) = HeadsFn.apply(h, 1, head.weight, head.bias)                              # (B * N, K)
+            ce = ops.SoftmaxCEFn.apply(lg, (flat // (K ** j)) % K, None).mean()
+            loss = ce if loss is None else loss + ce
+            logits.append(lg.reshape(B, N, K))
+        return loss, logits
+
     def compute_loss(self, codes):
-        """codes (B, N) merged codes, device int64 -> (loss, logits (B, N, V))."""
+        """codes (B, N) merged codes, device int64 -> (loss, logits (B, N, V)) [code_model 'product': the list of the ncb
+        digits' logits (B, N, K)]."""
         B, N = codes.shape
         V = self.num_tokens_per_channel[0]
         if N != self.num_tokens:
             raise ValueError(f'PriorRelative: windows of {self.num_tokens} codes expected, got {N}')
+        if self.code_model == 'product':
+            return self._compute_loss_product(codes)
         table = self._input_table()
         shifted = torch.cat([torch.full((B, 1), V, dtype=torch.int64, device=codes.device), codes[:, :-1]], dim=1)
         rows = ops.EmbeddingFn.apply(table, shifted.reshape(-1))                             # (B * N, d), shifted by one
@@ -145,7 +207,8 @@ class PriorRelative(FlatTraining, nn.Module):
     def forward(self, x):
         """API-compatible `PriorRelative.forward` (:122-181): x (B, N) merged codes."""
         loss, logits = self.compute_loss(self._checked_codes(x))
-        return {'loss': loss, 'weights_per_category': [logits], 'monitored_quantities': {'loss': loss.item()}}
+        return {'loss': loss, 'weights_per_category': logits if self.code_model == 'product' else [logits],
+                'monitored_quantities': {'loss': loss.item()}}
 
     def encode(self, x):
         """:205-208 + the merge the reference forgot: frozen encoder, inference only -> merged codes (B, N)."""
@@ -206,11 +269,16 @@ class PriorRelative(FlatTraining, nn.Module):
         place (whatever top_k / top_p would leave of it), -1 is free; the free codes are what they would be without the
         constraint given the same codes before them.  return_logp=True -> (codes, logp): logp float32 of the codes' shape,
         every emitted code's log-probability, forced or drawn, under the model's unmodified distribution at that place --
-        temperature 1, no filter, whatever `temperature` is."""
+        temperature 1, no filter, whatever `temperature` is.
+        code_model 'product': a code is drawn digit by digit; temperature, top_k and top_p filter EACH DIGIT'S conditional
+        distribution over its K values (not the joint distribution over the K**ncb codes), a forced code forces every digit,
+        and logp is the sum of the ncb digits' log-probabilities.  Any K**ncb < 2**31 is sampled."""
         from ..transformer.incremental import generate_in_chunks, row_seeds
-        from .generation import IncrementalPrior
+        from .generation import IncrementalPrior, IncrementalProductPrior
+        if self.code_model == 'product':
+            IncrementalPrior = IncrementalProductPrior
         V, N = self.num_tokens_per_channel[0], self.num_tokens
-        if V > MAX_SAMPLED_VOCAB:
+        if V > MAX_SAMPLED_VOCAB and self.code_model != 'product':
             raise ValueError(f'generate_codes: {V} merged codes, the sampling kernel (vqcpc_prior_sample) takes at most '
                              f'{MAX_SAMPLED_VOCAB}')
         num_tokens, B, stride = int(num_tokens), int(num_generated_codes), int(window_stride)

@@ -153,13 +153,18 @@ class IncrementalStack:
         FFN reads."""
         return h1
 
+    def _input_rows(self, idx):
+        """The input rows of the table-row indices idx: a lookup in `table` (a subclass whose inputs are not one table overrides
+        it)."""
+        return ops.EmbeddingFn.apply(self.table, idx)
+
     def prefill_prefix(self, P):
         """The stack, teacher-forced over prefix rows [0, P) of every sequence (inputs: table rows `prefix_rows`): fills
         every layer's K/V cache rows [0, P)."""
         if P == 0:
             return
         M, d, W, H, hd = self.M, self.d, self.W, self.H, self.hd
-        h = ops.EmbeddingFn.apply(self.table, self.prefix_rows[:M * P])               # (M * P, d), row b * P + i
+        h = self._input_rows(self.prefix_rows[:M * P])                                # (M * P, d), row b * P + i
         last = len(self.layers) - 1
         for li, lay in enumerate(self.layers):
             sa = lay.self_attn
