@@ -251,7 +251,9 @@ int vqcpc_gemm_nt_f16x3(const float* A, int64_t lda, const float* B, int64_t ldb
  * vqcpc_gemm_nt_g3_pl: vqcpc_gemm_nt_grad | vqcpc_gemm_nt_f16x3 with B (and optionally A) given as P4 images + the device scalar
  *   their planes were scaled with (pl_amax_b required, pl_amax_a NULL for an fp32 A): same loads, same LDS image, same products in
  *   the same order -- bit-identical to the fp32-operand entry points whenever those run under the same amax
- *   (tests/test_kernels_gpu.py::test_p4_*).  scale_state still receives the amax of an fp32 A.
+ *   (tests/test_kernels_gpu.py::test_p4_*).  scale_state still receives the amax of an fp32 A.  A P4 A (pl_amax_a != NULL) goes with
+ *   these forms only: none | + add | add == C in place | bias | bias + add | bias + dropout + add.  With add + add2, add2 == C, the
+ *   gate mask or relu + mask_out the call is refused (VQCPC_EINVAL, nothing is launched): A must be fp32 there.
  * vqcpc_gemm_nt_g3_small: the 64 x 128-tile kernel of vqcpc_gemm_nt_grad_tail as a general entry point -- tail rows of ragged
  *   launches on P4 operands AND whole products too small for 256-tiles (M % 64 == 0, N % 128 == 0, K % 32 == 0: the 3 072 - 12 288-row
  *   products of the student / decoder steps); operands fp32 or P4 (pl_amax_* NULL: fp32); epilogue in the order of vqcpc_gemm_nt:

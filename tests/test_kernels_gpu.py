@@ -2495,7 +2495,7 @@ def test_p4_weight_planes_hold_the_two_plane_split(ops, bf16x6):
             assert bool((err <= 2.0 ** -21 * ref.double().abs() + 2.0 ** -36 * float(amax[i])).all()), (i, float(err.max()))
 
 
-@pytest.mark.parametrize('M,N,K', [(4096, 1024, 256), (2048, 256, 1024), (1024, 768, 256)])
+@pytest.mark.parametrize('M,N,K', [(4096, 1024, 256), (2048, 256, 1024), (1024, 768, 256), (512, 512, 96)])
 def test_p4_products_are_bit_identical_to_the_fp32_operand_kernels(ops, bf16x6, M, N, K):
     """vqcpc_gemm_nt_g3_pl with B (and A) as P4 images == vqcpc_gemm_nt_f16x3 / vqcpc_gemm_nt_grad on the fp32 operands under the same
     amax, bit for bit, for every epilogue form of the training step -- and the scale state still receives the amax of an fp32 A."""
@@ -2555,3 +2555,54 @@ def test_p4_products_are_bit_identical_to_the_fp32_operand_kernels(ops, bf16x6, 
         hip.call('vqcpc_gemm_nt_g3_small', a_[:rows * K], K, wp, K, out, N, rows, N, K, bias, 0, 0.1, 9, 4096, None, 0, 1.0, add[:rows], N,
                  None, 0, state(), am, amax[0:1])
         assert torch.equal(out, ref), am is not None
+
+    # Instantiated forms (csrc/gemm_forms.h) that no launch of the training step selects, into an output whose leading dimension is
+    # greater than N.  The fp32-operand result against fp64 within the bound of test_f16x3_input_gradient_epilogues (3e-6 of the
+    # largest element), the P4 results bit-identical to it.
+    ldc = N + 64
+
+    def wide(src=None):
+        buf = torch.zeros(M, ldc, device='cuda')
+        if src is not None:
+            buf[:, :N] = src
+        return buf
+
+    def grad(a_, b_, out, add_=None, add2_=None, amax_a=None, amax_b=None):
+        """vqcpc_gemm_nt_grad (no P4 operand) or vqcpc_gemm_nt_g3_pl into `out` (leading dimension ldc); residuals may be `out`."""
+        lds = [0 if t is None else t.stride(0) for t in (add_, add2_)]
+        if amax_b is None:
+            hip.call('vqcpc_gemm_nt_grad', a_, K, b_, K, out, ldc, M, N, K, add_, lds[0], add2_, lds[1], None, 1.0, state())
+        else:
+            hip.call('vqcpc_gemm_nt_g3_pl', a_, K, b_, K, out, ldc, M, N, K, None, 0, 0.0, 0, add_, lds[0], add2_, lds[1], None, 1.0, None,
+                     state(), amax_a, amax_b)
+        assert bool((out[:, N:] == 0).all()), 'wrote past column N'
+        return out[:, :N]
+
+    prod = a.double() @ w.double().t()
+    for kw, ref64 in ((dict(), prod), (dict(add_=add), prod + add.double())):
+        ref = grad(a, w, wide(), **kw)
+        assert float((ref.double() - ref64).abs().max() / ref64.abs().max()) < 3e-6, list(kw)
+        assert torch.equal(grad(ap, wp, wide(), amax_a=amax[1:2], amax_b=amax[0:1], **kw), ref), list(kw)      # PL = 3
+    # add2 == C, in place: fp32 operands (PL = 0) and a P4 B (PL = 2) give the bits of the out-of-place two-residual form
+    ref, ref64 = grad(a, w, wide(), add_=add, add2_=add2), prod + add.double() + add2.double()
+    assert float((ref.double() - ref64).abs().max() / ref64.abs().max()) < 3e-6
+    for b_, am_b in ((w, None), (wp, amax[0:1])):
+        acc = wide(add2)
+        assert torch.equal(grad(a, b_, acc, add_=add, add2_=acc, amax_b=am_b), ref), am_b is not None
+
+    # 64 x 128 tiles: 128 x 256 x 64 (the leading block of the operands), row0 != 0, dropout and a gate
+    m, n, k, p, gs = 128, 256, 64, 0.1, 1.25
+    gate = torch.randn(m, n, device='cuda', generator=gen)
+    outs = []
+    for a_, b_, am_a, am_b in ((a, w, None, None), (a, wp, None, amax[0:1]), (ap, wp, amax[1:2], amax[0:1])):
+        out = torch.zeros(m, n + 64, device='cuda')
+        hip.call('vqcpc_gemm_nt_g3_small', a_, K, b_, K, out, n + 64, m, n, k, bias, 0, p, 9, 4096, gate, n, gs, add, N, None, 0,
+                 state(), am_a, am_b)
+        assert bool((out[:, n:] == 0).all()), 'wrote past column n'
+        outs.append(out[:, :n])
+    assert torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0])
+    full = (a[:m, :k].double() @ w[:n, :k].double().t() + bias[:n].double()) * (gs / (1 - p)) + add[:m, :n].double()
+    zeroed = outs[0] == add[:m, :n]                                   # gated off or dropped: the residual alone
+    assert bool(zeroed[gate <= 0].all())
+    assert 0.05 < float(zeroed[gate > 0].float().mean()) < 0.15       # p = 0.1 of ~16 000 elements
+    assert float((outs[0].double() - full)[~zeroed].abs().max() / full.abs().max()) < 3e-6

@@ -48,8 +48,8 @@ def build(force=False, verbose=True, lab=None):
     OBJ, LIB, SOURCES, FLAGS = _variant(lab)
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'prior_kernels.h'),
-               os.path.join(HERE, '..', 'include', 'vqcpc.h')]
+    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'gemm_forms.h'),
+               os.path.join(CSRC, 'prior_kernels.h'), os.path.join(HERE, '..', 'include', 'vqcpc.h')]
     hdr_m = max(os.path.getmtime(h) for h in headers)
     objs, jobs = [], []
     for src in SOURCES:

@@ -2012,23 +2012,12 @@ static int gemm_nt_launch(const float* A, int64_t lda, const float* B, int64_t l
     if (mode == 1 && tiles <= s64_max_tiles && (M % kS64 == 0) && (N % kS64 == 0) && (K % BK == 0) && M >= kS64) {
         const int tn64 = N / kS64;
         const dim3 g64((unsigned)((M / kS64) * tn64));
-#define S64_CASE(EPIV)                                                                                                     \
-    case EPIV:                                                                                                             \
-        hipLaunchKernelGGL((gemm_nt_x6_s64_kernel<EPIV>), g64, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tn64, ep);   \
-        VQ_CHECK_LAUNCH("gemm_nt_x6_s64");                                                                                 \
-        return VQCPC_OK;
-        switch (flags) {
-            S64_CASE(0)
-            S64_CASE(E_BIAS)
-            S64_CASE(E_BIAS | E_RELU)
-            S64_CASE(E_BIAS | E_RELU | E_DROP)
-            S64_CASE(E_GATE)
-            S64_CASE(E_ADD)
-            S64_CASE(E_BIAS | E_ADD)
-            S64_CASE(E_BIAS | E_DROP | E_ADD)
-            default: break;
+        if (dispatch(NtForms64{}, flags, 0, [&](auto f) {
+                hipLaunchKernelGGL((gemm_nt_x6_s64_kernel<decltype(f)::a>), g64, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tn64, ep);
+            })) {
+            VQ_CHECK_LAUNCH("gemm_nt_x6_s64");
+            return VQCPC_OK;
         }
-#undef S64_CASE
     }
     // bf16x6, full 256 x 256 tiles: the high-arithmetic-intensity kernel (one workgroup of 8 waves per CU)
     // the 256-tile kernel runs ONE workgroup per CU: pick it only when its last (partial) round of tiles does not waste
@@ -2083,115 +2072,60 @@ static int gemm_nt_launch(const float* A, int64_t lda, const float* B, int64_t l
         const size_t lds2 = 2 * kT2Buf;
         const size_t lds_pp = 2 * 6 * kT2 * 32;          // ping-pong kernel: unpadded swizzled planes (96 KB)
         const size_t lds_pp2 = 2 * 4 * kT2 * 32;         // its two-plane gradient variant (64 KB)
+        // one of the nine forms (gemm_forms.h) on the 256-tile kernels; any other combination goes on to the 128-tile kernel
+        const char* launched = nullptr;
 #if VQCPC_LAB
-// ablation variants of the ping-pong kernel (tools/ablate_pp_gemm.py, VQCPC_PP_ABL; bias epilogue only): lab builds only
-#define T2_ABL(EPIV)                                                                                                       \
-    {                                                                                                                      \
-        static const int abl = lab_env_int("VQCPC_PP_ABL", 0);                                                             \
-        if (use_pp && abl && (EPIV) == E_BIAS) {                                                                           \
-            if (abl == 1) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 1>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 2) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 2>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 3) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 3>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 8) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 8>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 32) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 32>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 16) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 16>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 64) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 64>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 128) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 128>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 192) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 192>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 192>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 256) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 256>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 1024) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 1024>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 2048) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 2048>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 2048>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 4096) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 4096>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 4096>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 512) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 512>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            if (abl == 4) { (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_BIAS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp); hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_BIAS, 4>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); } \
-            VQ_CHECK_LAUNCH("gemm_nt_x6_pp (ablation)");                                                                   \
-            return VQCPC_OK;                                                                                               \
-        }                                                                                                                  \
-    }
-#else
-#define T2_ABL(EPIV)
+        static const int pp_abl = lab_env_int("VQCPC_PP_ABL", 0);
 #endif
-#define T2_LAUNCH(EPIV)                                                                                                    \
-    {                                                                                                                      \
-        static bool attr_done = false;                                                                                     \
-        if (!attr_done) {                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_x6_256_kernel<EPIV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds2);                                                                          \
-            attr_done = true;                                                                                              \
-        }                                                                                                                  \
-        static bool attr_pp = false;                                                                                       \
-        if (!attr_pp) {                                                                                                    \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<EPIV>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                      (int)lds_pp);                                                                        \
-            attr_pp = true;                                                                                                \
-        }                                                                                                                  \
-        if (use_pp && ((EPIV) == 0 || (EPIV) == E_ADD || (EPIV) == (E_ADD | E_ADD2)) && gradient_products_now() == 3) {    \
-            /* opt-in gradient arithmetic (input-gradient GEMMs inside a gradient scope): two planes, three products */    \
-            constexpr int EG = ((EPIV) == 0 || (EPIV) == E_ADD || (EPIV) == (E_ADD | E_ADD2)) ? (EPIV) : 0;                \
-            static bool attr_g = false;                                                                                    \
-            if (!attr_g) {                                                                                                 \
-                (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<EG, 0, 2>,                                     \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pp2);                       \
-                attr_g = true;                                                                                             \
-            }                                                                                                              \
-            hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<EG, 0, 2>), grid2, block2, lds_pp2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); \
-            VQ_CHECK_LAUNCH("gemm_nt_x6_pp (gradient arithmetic)");                                                        \
-            return VQCPC_OK;                                                                                               \
-        }                                                                                                                  \
-        T2_ABL(EPIV)                                                                                                       \
-        if (use_pp)                                                                                                        \
-            hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<EPIV>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((gemm_nt_x6_256_kernel<EPIV>), grid2, block2, lds2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); \
-        VQ_CHECK_LAUNCH("gemm_nt_x6_256");                                                                                 \
-        return VQCPC_OK;                                                                                                   \
-    }
-        switch (flags) {
-            case 0: T2_LAUNCH(0)
-            case E_BIAS: T2_LAUNCH(E_BIAS)
-            case E_BIAS | E_RELU: T2_LAUNCH(E_BIAS | E_RELU)
-            case E_BIAS | E_RELU | E_DROP: T2_LAUNCH(E_BIAS | E_RELU | E_DROP)
-            case E_GATE: T2_LAUNCH(E_GATE)
-            case E_ADD: T2_LAUNCH(E_ADD)
-            case E_ADD | E_ADD2: T2_LAUNCH(E_ADD | E_ADD2)
-            // s = x + dropout(a W^T + b): the residual sum that LayerNorm normalises (transformer_custom.py:282-283,288-289),
-            // produced by the out-proj / FFN2 epilogue so that the LayerNorm kernels read ONE input stream
-            case E_BIAS | E_ADD: T2_LAUNCH(E_BIAS | E_ADD)
-            case E_BIAS | E_DROP | E_ADD: T2_LAUNCH(E_BIAS | E_DROP | E_ADD)
-            default: break;
+        if (use_pp && gradient_products_now() == 3 && dispatch(NtGradForms{}, flags, 0, [&](auto f) {
+                // opt-in gradient arithmetic (input-gradient GEMMs inside a gradient scope): two planes, three products
+                launch_lds<gemm_nt_x6_pp_kernel<decltype(f)::a, 0, 2>>(grid2, block2, lds_pp2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2,
+                                                                       tiles2, ep);
+            }))
+            launched = "gemm_nt_x6_pp (gradient arithmetic)";
+#if VQCPC_LAB
+        // ablation variants of the ping-pong kernel (tools/ablate_pp_gemm.py, VQCPC_PP_ABL; bias epilogue only): lab builds only
+        else if (use_pp && pp_abl && flags == E_BIAS) {
+            using PpAblForms = Forms<Form<E_BIAS, 1>, Form<E_BIAS, 2>, Form<E_BIAS, 3>, Form<E_BIAS, 4>, Form<E_BIAS, 8>, Form<E_BIAS, 16>,
+                                     Form<E_BIAS, 32>, Form<E_BIAS, 64>, Form<E_BIAS, 128>, Form<E_BIAS, 192>, Form<E_BIAS, 256>,
+                                     Form<E_BIAS, 512>, Form<E_BIAS, 1024>, Form<E_BIAS, 2048>, Form<E_BIAS, 4096>>;
+            VQ_REQUIRE(dispatch(PpAblForms{}, flags, pp_abl, [&](auto f) {
+                           launch_lds<gemm_nt_x6_pp_kernel<E_BIAS, decltype(f)::b>>(grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N,
+                                                                                    K, tn2, tiles2, ep);
+                       }),
+                       "gemm_nt: VQCPC_PP_ABL=%d is not an instantiated ablation", pp_abl);
+            launched = "gemm_nt_x6_pp (ablation)";
         }
-#undef T2_LAUNCH
-#undef T2_ABL
+#endif
+        else if (dispatch(NtForms{}, flags, 0, [&](auto f) {
+                     constexpr int EPI = decltype(f)::a;
+                     if (use_pp)
+                         launch_lds<gemm_nt_x6_pp_kernel<EPI>>(grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep);
+                     else
+                         launch_lds<gemm_nt_x6_256_kernel<EPI>>(grid2, block2, lds2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep);
+                 }))
+            launched = "gemm_nt_x6_256";
+        if (launched) {
+            VQ_CHECK_LAUNCH(launched);
+            return VQCPC_OK;
+        }
     }
-#define NT_LAUNCH(FULLV, EPIV)                                                                                            \
-    if (mode == 1)                                                                                                        \
-        hipLaunchKernelGGL((gemm_nt_kernel<FULLV, EPIV, 1>), grid, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tiles_n, ep); \
-    else if (mode == 2)                                                                                                   \
-        hipLaunchKernelGGL((gemm_nt_kernel<FULLV, EPIV, 2>), grid, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tiles_n, ep); \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((gemm_nt_kernel<FULLV, EPIV, 0>), grid, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tiles_n, ep)
-#define NT_CASE(EPIV)                       \
-    case EPIV:                              \
-        if (full) { NT_LAUNCH(true, EPIV); }  \
-        else { NT_LAUNCH(false, EPIV); }      \
-        break;
-    switch (flags) {
-        NT_CASE(0)
-        NT_CASE(E_BIAS)
-        NT_CASE(E_BIAS | E_RELU)
-        NT_CASE(E_BIAS | E_RELU | E_DROP)
-        NT_CASE(E_GATE)
-        NT_CASE(E_ADD)
-        NT_CASE(E_ADD | E_ADD2)
-        NT_CASE(E_BIAS | E_ADD)
-        NT_CASE(E_BIAS | E_DROP | E_ADD)
-        default:
-            if (full) { NT_LAUNCH(true, E_RUNTIME); }
-            else { NT_LAUNCH(false, E_RUNTIME); }
-            break;
-    }
-#undef NT_CASE
-#undef NT_LAUNCH
+    // 128-tile kernel: the nine forms, and E_RUNTIME for every other combination
+    const auto launch128 = [&](auto f) {
+        constexpr int EPI = decltype(f)::a;
+        const auto launch = [&](auto full_tiles) {
+            constexpr bool FULL = decltype(full_tiles)::value;
+            if (mode == 1)
+                hipLaunchKernelGGL((gemm_nt_kernel<FULL, EPI, 1>), grid, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tiles_n, ep);
+            else if (mode == 2)
+                hipLaunchKernelGGL((gemm_nt_kernel<FULL, EPI, 2>), grid, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tiles_n, ep);
+            else
+                hipLaunchKernelGGL((gemm_nt_kernel<FULL, EPI, 0>), grid, block, 0, st, A, lda, B, ldb, C, ldc, M, N, K, tiles_n, ep);
+        };
+        if (full) launch(std::true_type{});
+        else launch(std::false_type{});
+    };
+    if (!dispatch(NtForms{}, flags, 0, launch128)) launch128(Form<E_RUNTIME>{});
     VQ_CHECK_LAUNCH("gemm_nt");
     return VQCPC_OK;
 }
@@ -2402,27 +2336,10 @@ int vqcpc_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, floa
     hipStream_t s = (hipStream_t)stream;
     const bool full_tn = (N % BM == 0) && (K % BN == 0) && (M % TM == 0);
     if (use256) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            (void)hipFuncSetAttribute((const void*)gemm_tn_x6_256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      2 * kW2Buf);
-            attr_done = true;
-        }
         const int tk2 = K / kT2;
+        const dim3 g_((N / kT2) * tk2, splits), b_(kT2Threads);
         if (pp_enabled()) {
-            static bool attr_pp = false;
             constexpr int kPQBuf3 = 2 * 6 * 4 * (2048 + 64), kPQBuf2 = 2 * 4 * 4 * (2048 + 64);       // gemm_tn_x6_pq_kernel images
-            if (!attr_pp) {
-                (void)hipFuncSetAttribute((const void*)gemm_tn_x6_pp_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          2 * kTPBuf);
-                (void)hipFuncSetAttribute((const void*)gemm_tn_x6_pp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          2 * 4 * kTPPlane);
-                (void)hipFuncSetAttribute((const void*)gemm_tn_x6_pq_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          kPQBuf3);
-                (void)hipFuncSetAttribute((const void*)gemm_tn_x6_pq_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          kPQBuf2);
-                attr_pp = true;
-            }
 #if VQCPC_LAB
             // A/B switch of lab builds: VQCPC_TN_PQ=0 keeps the row-pair LDS image of gemm_tn_x6_pp_kernel (read per launch:
             // the lab test flips it inside one process)
@@ -2431,23 +2348,15 @@ int vqcpc_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, floa
 #else
             constexpr bool use_pq = true;                       // the quad-row LDS image (gemm_tn_x6_pq_kernel)
 #endif
-            const dim3 g_((N / kT2) * tk2, splits), b_(kT2Threads);
             if (gradient_products_now() == 3) {        // opt-in gradient arithmetic, inside a gradient scope only
-                if (use_pq)
-                    hipLaunchKernelGGL(gemm_tn_x6_pq_kernel<2>, g_, b_, kPQBuf2, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split,
-                                       ws, ws_bias);
-                else
-                    hipLaunchKernelGGL(gemm_tn_x6_pp_kernel<2>, g_, b_, 2 * 4 * kTPPlane, s, A, lda, B, ldb, M, N, K, tk2,
-                                       rows_per_split, ws, ws_bias);
+                if (use_pq) launch_lds<gemm_tn_x6_pq_kernel<2>>(g_, b_, kPQBuf2, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
+                else launch_lds<gemm_tn_x6_pp_kernel<2>>(g_, b_, 2 * 4 * kTPPlane, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
             } else if (use_pq)
-                hipLaunchKernelGGL(gemm_tn_x6_pq_kernel<3>, g_, b_, kPQBuf3, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws,
-                                   ws_bias);
+                launch_lds<gemm_tn_x6_pq_kernel<3>>(g_, b_, kPQBuf3, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
             else
-                hipLaunchKernelGGL(gemm_tn_x6_pp_kernel<3>, g_, b_, 2 * kTPBuf, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split,
-                                   ws, ws_bias);
+                launch_lds<gemm_tn_x6_pp_kernel<3>>(g_, b_, 2 * kTPBuf, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
         } else
-        hipLaunchKernelGGL(gemm_tn_x6_256_kernel, dim3((N / kT2) * tk2, splits), dim3(kT2Threads), 2 * kW2Buf, s, A, lda, B,
-                           ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
+            launch_lds<gemm_tn_x6_256_kernel>(g_, b_, 2 * kW2Buf, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
     } else if (gemm_mode() == 1) {
         if (full_tn)
             hipLaunchKernelGGL((gemm_tn_x6_kernel<true, 1>), dim3(tiles, splits), dim3(kGemmThreads), 0, s, A, lda, B, ldb, M, N,
@@ -2634,38 +2543,17 @@ static int gatebits_launch(const float* A, int64_t lda, const float* B, int64_t 
     const dim3 grid2((unsigned)std::min(tiles2, kNumCU)), block2(kT2Threads);
     const size_t lds_pp = 2 * 6 * kT2 * 32;
     if (flags == E_GATEBITS && gradient_products_now() == 3) {      // opt-in gradient arithmetic (see gemm_nt_launch)
-        static bool attr_g = false;
-        if (!attr_g) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<E_GATEBITS, 0, 2>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * kT2 * 32);
-            attr_g = true;
-        }
-        hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<E_GATEBITS, 0, 2>), grid2, block2, 2 * 4 * kT2 * 32, st, A, lda, B, ldb, C, ldc, M,
-                           N, K, tn2, tiles2, ep);
+        launch_lds<gemm_nt_x6_pp_kernel<E_GATEBITS, 0, 2>>(grid2, block2, 2 * 4 * kT2 * 32, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2,
+                                                           ep);
         VQ_CHECK_LAUNCH("gemm_nt_x6_pp (mask, gradient arithmetic)");
         return VQCPC_OK;
     }
-#define GB_LAUNCH(EPIV)                                                                                                   \
-    {                                                                                                                      \
-        static bool attr_pp = false;                                                                                       \
-        if (!attr_pp) {                                                                                                    \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_x6_pp_kernel<EPIV>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                      (int)lds_pp);                                                                        \
-            attr_pp = true;                                                                                                \
-        }                                                                                                                  \
-        hipLaunchKernelGGL((gemm_nt_x6_pp_kernel<EPIV>), grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep); \
-        VQ_CHECK_LAUNCH("gemm_nt_x6_pp (mask)");                                                                           \
-        return VQCPC_OK;                                                                                                   \
-    }
-    switch (flags) {
-        case E_BIAS | E_RELU | E_MASKOUT: GB_LAUNCH(E_BIAS | E_RELU | E_MASKOUT)
-        case E_BIAS | E_RELU | E_DROP | E_MASKOUT: GB_LAUNCH(E_BIAS | E_RELU | E_DROP | E_MASKOUT)
-        case E_GATEBITS: GB_LAUNCH(E_GATEBITS)
-        default: break;
-    }
-#undef GB_LAUNCH
-    set_error("gemm gate-bits: epilogue combination %d not instantiated", flags);
-    return VQCPC_EINVAL;
+    VQ_REQUIRE(dispatch(NtMaskForms{}, flags, 0, [&](auto f) {
+                   launch_lds<gemm_nt_x6_pp_kernel<decltype(f)::a>>(grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep);
+               }),
+               "gemm gate-bits: epilogue combination %d not instantiated", flags);
+    VQ_CHECK_LAUNCH("gemm_nt_x6_pp (mask)");
+    return VQCPC_OK;
 }
 
 int vqcpc_gemm_nt_relu_mask(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N,

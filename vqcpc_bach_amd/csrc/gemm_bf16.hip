@@ -1050,59 +1050,36 @@ int vqcpc_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, f
     const dim3 grid((unsigned)std::min(tiles, kNumCU)), block(kBThreads);
     hipStream_t st = (hipStream_t)stream;
     const bool k64 = bf16_variant() == 1 && K % (2 * kKBK) == 0;
-#define BL(EPIV, OUTV)                                                                                                 \
-    if (flags == (EPIV) && out == (OUTV) && k64) {                                                                     \
-        static bool attr_k64 = false;                                                                                  \
-        if (!attr_k64) {                                                                                               \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_bf16_k64_kernel<EPIV, OUTV>,                                \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kKLds);                              \
-            attr_k64 = true;                                                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL((gemm_nt_bf16_k64_kernel<EPIV, OUTV>), grid, block, kKLds, st, (const bf16_t*)A, lda,       \
-                           (const bf16_t*)B, ldb, o, M, N, K, tn, tiles, ep);                                          \
-        VQ_CHECK_LAUNCH("gemm_nt_bf16_k64");                                                                           \
-        return VQCPC_OK;                                                                                               \
-    }                                                                                                                  \
-    if (flags == (EPIV) && out == (OUTV)) {                                                                            \
-        static bool attr_done = false;                                                                                 \
-        if (!attr_done) {                                                                                              \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel<EPIV, OUTV>,                                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kBLds);                              \
-            attr_done = true;                                                                                          \
-        }                                                                                                              \
-        hipLaunchKernelGGL((gemm_nt_bf16_kernel<EPIV, OUTV>), grid, block, kBLds, st, (const bf16_t*)A, lda,           \
-                           (const bf16_t*)B, ldb, o, M, N, K, tn, tiles, ep);                                          \
-        VQ_CHECK_LAUNCH("gemm_nt_bf16");                                                                               \
-        return VQCPC_OK;                                                                                               \
+    // the instantiated (epilogue, output) forms: the combinations the training step uses
+    using Bf16Forms = Forms<
+        Form<0, B_OUT_F32>, Form<E_BIAS, B_OUT_F32>, Form<E_BIAS, B_OUT_F32 | B_OUT_BF16>, Form<E_BIAS | E_RELU, B_OUT_BF16>,
+        Form<E_BIAS | E_RELU | E_DROP, B_OUT_BF16>, Form<E_BIAS | E_RELU, B_OUT_F32>, Form<E_BIAS | E_RELU, B_OUT_F32 | B_OUT_BF16>,
+        Form<E_BIAS | E_RELU | E_DROP, B_OUT_F32 | B_OUT_BF16>, Form<E_GATE, B_OUT_F32 | B_OUT_BF16 | B_GATE_BF16>,
+        Form<E_BIAS | E_RELU | E_DROP, B_OUT_F32>, Form<E_GATE, B_OUT_F32>, Form<E_GATE, B_OUT_BF16 | B_GATE_BF16>,
+        Form<E_GATE, B_OUT_F32 | B_GATE_BF16>, Form<E_ADD, B_OUT_F32>,
+        Form<E_ADD, B_OUT_F32 | B_ADD_BF16>,               // input gradient + the bf16 gradient of the residual branch (round 5)
+        Form<E_ADD, B_OUT_BF16 | B_ADD_BF16>,              // ... and the sum itself in bf16: the main-stream gradient between sub-layers
+        Form<0, B_OUT_BF16>,
+        Form<E_BIAS, B_OUT_BF16>,                          // in_proj output for the all-bf16 attention kernels
+        Form<E_BIAS | E_ADD, B_OUT_F32>,                   // residual sums for LayerNorm (see gemm.hip)
+        Form<E_BIAS | E_DROP | E_ADD, B_OUT_F32>,
+        Form<E_BIAS | E_ADD, B_OUT_F32 | B_ADD_BF16>,      // the same with the residual read from the LayerNorm's bf16 output (round 5)
+        Form<E_BIAS | E_DROP | E_ADD, B_OUT_F32 | B_ADD_BF16>,
+        Form<E_BIAS | E_ADD, B_OUT_BF16>,                  // ... and the residual sum itself written in bf16 (the LayerNorm kernels read
+        Form<E_BIAS | E_DROP | E_ADD, B_OUT_BF16>,         //     it so: vqcpc_layernorm_fwd_xb16 / _bwd_xb16)
+        Form<E_BIAS | E_ADD, B_OUT_BF16 | B_ADD_BF16>, Form<E_BIAS | E_DROP | E_ADD, B_OUT_BF16 | B_ADD_BF16>>;
+    if (dispatch(Bf16Forms{}, flags, out, [&](auto f) {
+            constexpr int EPI = decltype(f)::a, OUT = decltype(f)::b;
+            if (k64)
+                launch_lds<gemm_nt_bf16_k64_kernel<EPI, OUT>>(grid, block, kKLds, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, o, M, N, K,
+                                                              tn, tiles, ep);
+            else
+                launch_lds<gemm_nt_bf16_kernel<EPI, OUT>>(grid, block, kBLds, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, o, M, N, K, tn,
+                                                          tiles, ep);
+        })) {
+        VQ_CHECK_LAUNCH(k64 ? "gemm_nt_bf16_k64" : "gemm_nt_bf16");
+        return VQCPC_OK;
     }
-    // the combinations the training step uses
-    BL(0, B_OUT_F32)
-    BL(E_BIAS, B_OUT_F32)
-    BL(E_BIAS, B_OUT_F32 | B_OUT_BF16)
-    BL(E_BIAS | E_RELU, B_OUT_BF16)
-    BL(E_BIAS | E_RELU | E_DROP, B_OUT_BF16)
-    BL(E_BIAS | E_RELU, B_OUT_F32)
-    BL(E_BIAS | E_RELU, B_OUT_F32 | B_OUT_BF16)
-    BL(E_BIAS | E_RELU | E_DROP, B_OUT_F32 | B_OUT_BF16)
-    BL(E_GATE, B_OUT_F32 | B_OUT_BF16 | B_GATE_BF16)
-    BL(E_BIAS | E_RELU | E_DROP, B_OUT_F32)
-    BL(E_GATE, B_OUT_F32)
-    BL(E_GATE, B_OUT_BF16 | B_GATE_BF16)
-    BL(E_GATE, B_OUT_F32 | B_GATE_BF16)
-    BL(E_ADD, B_OUT_F32)
-    BL(E_ADD, B_OUT_F32 | B_ADD_BF16)                // input gradient + the bf16 gradient of the residual branch (round 5)
-    BL(E_ADD, B_OUT_BF16 | B_ADD_BF16)               // ... and the sum itself in bf16: the main-stream gradient between sub-layers
-    BL(0, B_OUT_BF16)
-    BL(E_BIAS, B_OUT_BF16)                           // in_proj output for the all-bf16 attention kernels
-    BL(E_BIAS | E_ADD, B_OUT_F32)                    // residual sums for LayerNorm (see gemm.hip)
-    BL(E_BIAS | E_DROP | E_ADD, B_OUT_F32)
-    BL(E_BIAS | E_ADD, B_OUT_F32 | B_ADD_BF16)       // the same with the residual read from the LayerNorm's bf16 output (round 5)
-    BL(E_BIAS | E_DROP | E_ADD, B_OUT_F32 | B_ADD_BF16)
-    BL(E_BIAS | E_ADD, B_OUT_BF16)                   // ... and the residual sum itself written in bf16 (the LayerNorm kernels read
-    BL(E_BIAS | E_DROP | E_ADD, B_OUT_BF16)          //     it so: vqcpc_layernorm_fwd_xb16 / _bwd_xb16)
-    BL(E_BIAS | E_ADD, B_OUT_BF16 | B_ADD_BF16)
-    BL(E_BIAS | E_DROP | E_ADD, B_OUT_BF16 | B_ADD_BF16)
-#undef BL
     set_error("gemm_nt_bf16: unsupported epilogue / output combination (flags %d, out %d)", flags, out);
     return VQCPC_EINVAL;
 }
@@ -1138,27 +1115,17 @@ int vqcpc_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, f
     const int64_t rps = round_up(ceil_div(M, splits), 2 * kTRRows);
     if (bf16_variant() == 1 && lda < (1 << 20) && ldb < (1 << 20) &&
         (rps + 2 * kTRRows) * std::max(lda, ldb) * 2 < ((int64_t)1 << 31)) {
-        static bool attr_tr = false;
-        if (!attr_tr) {
-            (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kTRLds);
-            attr_tr = true;
-        }
         const int tkr = K / kB;
-        hipLaunchKernelGGL(gemm_tn_bf16_tr_kernel, dim3((N / kB) * tkr, splits), dim3(kBThreads), kTRLds, s, (const bf16_t*)A, lda,
-                           (const bf16_t*)B, ldb, M, N, K, tkr, rps, ws, ws_bias);
+        launch_lds<gemm_tn_bf16_tr_kernel>(dim3((N / kB) * tkr, splits), dim3(kBThreads), kTRLds, s, (const bf16_t*)A, lda, (const bf16_t*)B,
+                                           ldb, M, N, K, tkr, rps, ws, ws_bias);
         VQ_CHECK_LAUNCH("gemm_tn_bf16_tr");
         if (accumulate == 2) return VQCPC_OK;       // deferred reduction: see vqcpc_gemm_tn_bf16_deferred_splits
         return launch_reduce_splits2(ws, (int64_t)N * K, splits, dW, (int64_t)N * K, ws_bias, N, db, db ? N : 0, accumulate, s);
     }
     const int64_t rows_per_split = round_up(ceil_div(M, splits), 2 * kTBM);
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kTBBuf);
-        attr_done = true;
-    }
     const int tk2 = K / kB;
-    hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3((N / kB) * tk2, splits), dim3(kBThreads), 2 * kTBBuf, s, (const bf16_t*)A, lda,
-                       (const bf16_t*)B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
+    launch_lds<gemm_tn_bf16_kernel>(dim3((N / kB) * tk2, splits), dim3(kBThreads), 2 * kTBBuf, s, (const bf16_t*)A, lda, (const bf16_t*)B, ldb,
+                                    M, N, K, tk2, rows_per_split, ws, ws_bias);
     VQ_CHECK_LAUNCH("gemm_tn_bf16");
     if (accumulate == 2) return VQCPC_OK;
     return launch_reduce_splits2(ws, (int64_t)N * K, splits, dW, (int64_t)N * K, ws_bias, N, db, db ? N : 0, accumulate, s);

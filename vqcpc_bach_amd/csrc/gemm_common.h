@@ -1,7 +1,8 @@
 // Definitions shared by the GEMM translation units (gemm.hip, gemm_dma.hip): epilogue descriptor, tile constants,
-// the exact 3-way bf16 split.
+// the exact 3-way bf16 split, the launch helper (the tables of instantiated forms: gemm_forms.h).
 #pragma once
 #include "common.h"
+#include "gemm_forms.h"
 
 namespace vq {
 
@@ -37,8 +38,19 @@ struct EpiParams {
     const float* pl_amax_b;
 };
 
-// epilogue feature bits (compile-time); E_RUNTIME = decide everything from EpiParams at run time (rare combinations)
-enum { E_BIAS = 1, E_RELU = 2, E_DROP = 4, E_GATE = 8, E_ADD = 16, E_RUNTIME = 32, E_ADD2 = 64, E_MASKOUT = 128, E_GATEBITS = 256 };
+// Host side of every launch with dynamic LDS.  The first launch of an instantiation raises its
+// hipFuncAttributeMaxDynamicSharedMemorySize to `lds` (a kernel is always launched with one size): once per process and kernel, by a
+// function-local static, so threads that launch on their own streams do not race on it.
+template <auto KERNEL>
+inline void raise_lds_limit_once(size_t lds) {
+    static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)once;
+}
+template <auto KERNEL, class... Args>
+inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    raise_lds_limit_once<KERNEL>(lds);
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+}
 
 // bijective XCD-aware remap: consecutive tiles (which share an A row panel) land on the same XCD / L2
 __device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {

@@ -117,7 +117,7 @@ __device__ __forceinline__ void g3_amax_publish_wg(float amax_a, float amax_b, f
 // G_ACCUM: C += A . B^T by buffer_atomic_add_f32 (no return): the "+ residual" form when the residual already sits in C.  One
 // fp32 add per element at the L2, the same value load-add-store gives, and no operand load for the epilogue to wait for (with
 // E_ADD all eight waves stall on those loads together at every tile boundary: the slowest epilogue of this kernel).
-constexpr int G_ACCUM = 512;
+// The instantiated (EPI, PL) forms and how a call's operands select one: gemm_forms.h.
 // =====================================================================================================================
 // ABL (lab builds, VQCPC_G3_ABL; results are wrong by construction): 1 = no operand requests after the prologue, 2 = no split /
 // LDS stores after the prologue, 4 = no MFMAs, 8 = no output stores, 16 = no fragment reads after the prologue
@@ -1032,6 +1032,112 @@ static int tn_g3_splits(int64_t M, int N, int K) {
 
 using namespace vq;
 
+#if VQCPC_LAB
+// ablation variants gemm_nt_g3_kernel<0, ABL> (VQCPC_G3_ABL; results are wrong by construction)
+using G3AblForms = Forms<Form<0, 1>, Form<0, 2>, Form<0, 4>, Form<0, 8>, Form<0, 16>, Form<0, 19>, Form<0, 32>>;
+#endif
+
+// Every launch of gemm_nt_g3_kernel: the shape and operand checks the entry points share, the operands -> (EPI, PL) mapping
+// (g3_form) and the table of instantiated forms (G3Forms), both in gemm_forms.h.  Absent operands are NULL; a form that is not in the
+// table is refused before anything is launched.  `splits` > 1 (vqcpc_gemm_nt_grad_splitk): K is the slice length, C the partial planes.
+// `lab_hooks`: the measurement switches of vqcpc_gemm_nt_grad (lab builds).
+static int g3_launch(const char* who, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N,
+                     int K, const float* bias, int act, float drop_p, uint64_t seed, const float* add, int64_t ldadd, const float* add2,
+                     int64_t ldadd2, const void* gate_mask, float gate_scale, void* mask_out, float* scale_state,
+                     const float* pl_amax_a, const float* pl_amax_b, void* stream, int splits = 1, bool lab_hooks = false) {
+    VQ_REQUIRE(vqcpc_gemm_nt_grad_supported(M, N, K), "%s: M, N multiples of 256 and K of 32, got M=%lld N=%d K=%d", who, (long long)M, N,
+               K);
+    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
+               "%s: bad leading dimensions / alignment", who);
+    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (act == 0 || act == 1), "%s: bad dropout probability / act", who);
+    VQ_REQUIRE((!gate_mask || aligned16(gate_mask)) && (!mask_out || aligned16(mask_out)), "%s: mask must be 16-byte aligned", who);
+    EpiParams ep{};
+    ep.bias = bias;
+    ep.act = act;
+    ep.thr = drop_threshold(drop_p);
+    ep.inv_keep = 1.0f / (1.0f - drop_p);
+    ep.seed = seed;
+    ep.add = add;
+    ep.ldadd = ldadd;
+    ep.add2 = add2;
+    ep.ldadd2 = ldadd2;
+    ep.mask = gate_mask ? (uint32_t*)const_cast<void*>(gate_mask) : (uint32_t*)mask_out;
+    ep.gate_scale = gate_scale;
+    ep.split_plane = M * (int64_t)N;
+    ep.pl_amax_a = pl_amax_a;
+    ep.pl_amax_b = pl_amax_b;
+    const G3Form f = g3_form({bias != nullptr, act == 1, ep.thr != 0, add != nullptr, add2 != nullptr, add == C && ldadd == ldc,
+                              add2 == C && ldadd2 == ldc, gate_mask != nullptr, mask_out != nullptr, pl_amax_a != nullptr,
+                              pl_amax_b != nullptr});
+    const int tn = N / kG;
+    const int tiles = (int)((M / kG) * tn);
+    const dim3 grid((unsigned)std::min(tiles, kNumCU), (unsigned)splits), block(kGThreads);
+    const size_t lds = (size_t)kGSlots * kGSlot;
+    hipStream_t st = (hipStream_t)stream;
+    bool launched = false;
+#if VQCPC_LAB
+    if (lab_hooks) {
+        static const int stagger = lab_env_int("VQCPC_G3_STAGGER", 0), abl = lab_env_int("VQCPC_G3_ABL", 0);
+        ep.act = stagger;
+        if (abl && f.epi == 0 && f.pl == 0) {
+            launched = dispatch(G3AblForms{}, 0, abl, [&](auto v) {
+                launch_lds<gemm_nt_g3_kernel<0, decltype(v)::b>>(grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles, ep,
+                                                                 scale_state);
+            });
+            VQ_REQUIRE(launched, "%s: VQCPC_G3_ABL=%d is not an instantiated ablation", who, abl);
+        }
+    }
+#endif
+    if (!launched)
+        launched = dispatch(G3Forms{}, f.epi, f.pl, [&](auto v) {
+            launch_lds<gemm_nt_g3_kernel<decltype(v)::a, 0, decltype(v)::b>>(grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn,
+                                                                            tiles, ep, scale_state);
+        });
+    VQ_REQUIRE(launched,
+               "%s: no kernel for epilogue flags %d with operand format %d (bit 0 / 1: A / B pre-split).  Dropout goes with a residual or "
+               "relu; a pre-split A with none / add / add == C / bias / bias + add / bias + dropout + add",
+               who, f.epi, f.pl);
+    VQ_CHECK_LAUNCH(who);
+    return VQCPC_OK;
+}
+
+// Every launch of gemm_nt_g3_tail_kernel (64 x 128 tiles).  The kernel reads its epilogue and operand formats from EpiParams at run
+// time: ONE instantiation, every combination of operands is a form of it.
+static int g3_small_launch(const char* who, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
+                           int N, int K, const float* bias, int act, float drop_p, uint64_t seed, int64_t row0, const float* gate,
+                           int64_t ldgate, float gate_scale, const float* add, int64_t ldadd, const float* add2, int64_t ldadd2,
+                           float* scale_state, const float* pl_amax_a, const float* pl_amax_b, void* stream) {
+    VQ_REQUIRE(A && B && C && scale_state, "%s: null pointer", who);
+    VQ_REQUIRE(vqcpc_gemm_nt_grad_tail_supported(M, N, K), "%s: M a multiple of 64, N of 128, K of 32, got M=%lld N=%d K=%d", who,
+               (long long)M, N, K);
+    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
+               "%s: bad leading dimensions / alignment", who);
+    VQ_REQUIRE(!(add2 && !add) && !(add && ldadd < N) && !(add2 && ldadd2 < N) && !(gate && ldgate < N) && drop_p >= 0.f && drop_p < 1.f &&
+                   (act == 0 || act == 1),
+               "%s: bad epilogue operands", who);
+    EpiParams ep{};
+    ep.bias = bias;
+    ep.act = act;
+    ep.thr = drop_threshold(drop_p);
+    ep.inv_keep = 1.0f / (1.0f - drop_p);
+    ep.seed = seed;
+    ep.row0 = row0;
+    ep.gate = gate;
+    ep.ldgate = ldgate;
+    ep.gate_scale = gate_scale;
+    ep.add = add;
+    ep.ldadd = ldadd;
+    ep.add2 = add2;
+    ep.ldadd2 = ldadd2;
+    ep.pl_amax_a = pl_amax_a;
+    ep.pl_amax_b = pl_amax_b;
+    const int tn = N / kRN;
+    launch_lds<gemm_nt_g3_tail_kernel>(dim3((unsigned)((M / kRM) * tn)), dim3(kGThreads), (size_t)2 * kRSlot, (hipStream_t)stream, A, lda,
+                                       B, ldb, C, ldc, N, K, tn, ep, scale_state);
+    VQ_CHECK_LAUNCH(who);
+    return VQCPC_OK;
+}
+
 extern "C" {
 
 // dgrad shapes the three-product kernel takes: whole 256 x 256 tiles, K a multiple of 32.  (Whether the tiles fill the 256
@@ -1044,67 +1150,9 @@ int vqcpc_gemm_nt_grad(const float* A, int64_t lda, const float* B, int64_t ldb,
                        const float* add, int64_t ldadd, const float* add2, int64_t ldadd2, const void* gate_mask,
                        float gate_scale, float* scale_state, void* stream) {
     VQ_REQUIRE(A && B && C && scale_state, "gemm_nt_grad: null pointer");
-    VQ_REQUIRE(vqcpc_gemm_nt_grad_supported(M, N, K), "gemm_nt_grad: M, N multiples of 256 and K of 32, got M=%lld N=%d K=%d",
-               (long long)M, N, K);
-    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
-               "gemm_nt_grad: bad leading dimensions / alignment");
     VQ_REQUIRE(!(add2 && !add) && !(gate_mask && add), "gemm_nt_grad: epilogue is one of none / add / add + add2 / gate mask");
-    VQ_REQUIRE(!gate_mask || aligned16(gate_mask), "gemm_nt_grad: gate mask must be 16-byte aligned");
-    EpiParams ep{};
-    ep.add = add;
-    ep.ldadd = ldadd;
-    ep.add2 = add2;
-    ep.ldadd2 = ldadd2;
-    ep.mask = (uint32_t*)const_cast<void*>(gate_mask);
-    ep.gate_scale = gate_scale;
-#if VQCPC_LAB
-    {
-        static const int stagger = lab_env_int("VQCPC_G3_STAGGER", 0);
-        ep.act = stagger;
-    }
-#endif
-    const int tn = N / kG;
-    const int tiles = (int)((M / kG) * tn);
-    const dim3 grid((unsigned)std::min(tiles, kNumCU)), block(kGThreads);
-    const size_t lds = (size_t)kGSlots * kGSlot;
-    hipStream_t st = (hipStream_t)stream;
-#define G3_LAUNCH(EPIV)                                                                                                  \
-    {                                                                                                                    \
-        static bool attr = false;                                                                                        \
-        if (!attr) {                                                                                                     \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_g3_kernel<EPIV>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                      (int)lds);                                                                         \
-            attr = true;                                                                                                 \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_nt_g3_kernel<EPIV>), grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles,  \
-                           ep, scale_state);                                                                             \
-    }
-#if VQCPC_LAB
-    {
-        static const int abl = lab_env_int("VQCPC_G3_ABL", 0);
-        if (abl && !gate_mask && !add) {
-#define G3_ABL_CASE(V)                                                                                                   \
-    if (abl == V) {                                                                                                      \
-        (void)hipFuncSetAttribute((const void*)gemm_nt_g3_kernel<0, V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((gemm_nt_g3_kernel<0, V>), grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles, ep, \
-                           scale_state);                                                                                 \
-    }
-            G3_ABL_CASE(1) G3_ABL_CASE(2) G3_ABL_CASE(4) G3_ABL_CASE(8) G3_ABL_CASE(16) G3_ABL_CASE(19) G3_ABL_CASE(32)
-#undef G3_ABL_CASE
-            VQ_CHECK_LAUNCH("gemm_nt_g3 (ablation)");
-            return VQCPC_OK;
-        }
-    }
-#endif
-    if (gate_mask) G3_LAUNCH(E_GATEBITS)
-    else if (add && !add2 && add == C && ldadd == ldc) G3_LAUNCH(G_ACCUM)        // the residual already sits in C: accumulate in place
-    else if (add2 && add2 == C && ldadd2 == ldc) G3_LAUNCH(E_ADD | G_ACCUM)      // C += A . B^T + add: the second residual already sits in C
-    else if (add2) G3_LAUNCH(E_ADD | E_ADD2)
-    else if (add) G3_LAUNCH(E_ADD)
-    else G3_LAUNCH(0)
-#undef G3_LAUNCH
-    VQ_CHECK_LAUNCH("gemm_nt_g3");
-    return VQCPC_OK;
+    return g3_launch("gemm_nt_grad", A, lda, B, ldb, C, ldc, M, N, K, nullptr, 0, 0.0f, 0, add, ldadd, add2, ldadd2, gate_mask,
+                     gate_scale, nullptr, scale_state, nullptr, nullptr, stream, 1, true);
 }
 
 // Few output tiles, long K: the remainder rows of a launch whose 256-tiles do not fill whole rounds (139 264 x 256: 2 rounds + 32
@@ -1133,69 +1181,44 @@ int vqcpc_gemm_nt_grad_splitk(const float* A, int64_t lda, const float* B, int64
         set_error("gemm_nt_grad_splitk: workspace too small");
         return VQCPC_EWORKSPACE;
     }
-    EpiParams ep{};
-    ep.gate_scale = 1.0f;
-    ep.split_plane = M * (int64_t)N;
-    const int tn = N / kG;
-    const int tiles = (int)((M / kG) * tn);
-    const size_t lds = (size_t)kGSlots * kGSlot;
-    hipStream_t st = (hipStream_t)stream;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_g3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    hipLaunchKernelGGL((gemm_nt_g3_kernel<0>), dim3((unsigned)std::min(tiles, kNumCU), (unsigned)splits), dim3(kGThreads), lds, st, A,
-                       lda, B, ldb, (float*)workspace, (int64_t)N, M, N, K / splits, tn, tiles, ep, scale_state);
-    VQ_CHECK_LAUNCH("gemm_nt_g3 (split-K)");
+    // the plain product of every K slice into its plane of the workspace ...
+    const int rc = g3_launch("gemm_nt_grad_splitk", A, lda, B, ldb, (float*)workspace, N, M, N, K / splits, nullptr, 0, 0.0f, 0, nullptr, 0,
+                             nullptr, 0, nullptr, 1.0f, nullptr, scale_state, nullptr, nullptr, stream, splits);
+    if (rc) return rc;
+    // ... and the pass that sums the planes and applies the epilogue
     const int64_t total = M * (N / 4);
-    hipLaunchKernelGGL(g3_splitk_epilogue_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 8 * kNumCU)), dim3(256), 0, st,
-                       (const float*)workspace, ep.split_plane, splits, C, ldc, M, N, bias, drop_threshold(drop_p),
+    hipLaunchKernelGGL(g3_splitk_epilogue_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 8 * kNumCU)), dim3(256), 0,
+                       (hipStream_t)stream, (const float*)workspace, M * (int64_t)N, splits, C, ldc, M, N, bias, drop_threshold(drop_p),
                        1.0f / (1.0f - drop_p), seed, row0, add, ldadd, add2, ldadd2);
     VQ_CHECK_LAUNCH("gemm_nt_g3 split-K epilogue");
     return VQCPC_OK;
 }
 
-// The tail rows of a ragged launch on 64 x 128 tiles (gemm_nt_g3_tail_kernel): every epilogue the ragged launches of a training
-// step use -- none | + add | + add + add2 (add may be C: in place) for the input gradients, + bias | + bias + add | + bias +
-// dropout + add for the forward -- with row0 = global row of the first row of this call (dropout element index).
+// The 64 x 128-tile kernel (gemm_nt_g3_tail_kernel) as a GENERAL entry point (round 6): the tail rows of a ragged launch, and whole
+// products whose 256-tiles would not fill the chip (the 3 072 - 12 288-row products of the student / decoder steps: x 1.1-1.36 the
+// six-product 128-tile / split-K path, tools/bench_small_f16x3.py).  Operands fp32 or P4 (pl_amax_a / pl_amax_b NULL: fp32, split in
+// the kernel).  Epilogue, in the order of vqcpc_gemm_nt: + bias, relu (act == 1), dropout (element index (row0 + row) * N + col, row0 =
+// global row of the first row of this call), * (gate > 0 ? gate_scale : 0), + add (may be C), + add2.
 int vqcpc_gemm_nt_grad_tail_supported(int64_t M, int N, int K) {
     return (M >= kRM && (M % kRM) == 0 && N >= kRN && (N % kRN) == 0 && K >= kRBK && (K % kRBK) == 0 &&
             (M / kRM) * (N / kRN) < (1ll << 30)) ? 1 : 0;
 }
 
+int vqcpc_gemm_nt_g3_small(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int K,
+                           const float* bias, int act, float drop_p, uint64_t seed, int64_t row0, const float* gate, int64_t ldgate,
+                           float gate_scale, const float* add, int64_t ldadd, const float* add2, int64_t ldadd2, float* scale_state,
+                           const float* pl_amax_a, const float* pl_amax_b, void* stream) {
+    return g3_small_launch("gemm_nt_g3_small", A, lda, B, ldb, C, ldc, M, N, K, bias, act, drop_p, seed, row0, gate, ldgate, gate_scale,
+                           add, ldadd, add2, ldadd2, scale_state, pl_amax_a, pl_amax_b, stream);
+}
+
+// The tail rows of a ragged launch: vqcpc_gemm_nt_g3_small on fp32 operands without relu and gate -- none | + add | + add + add2 (add
+// may be C: in place) for the input gradients, + bias | + bias + add | + bias + dropout + add for the forward.
 int vqcpc_gemm_nt_grad_tail(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int K,
                             const float* bias, float drop_p, uint64_t seed, int64_t row0, const float* add, int64_t ldadd,
                             const float* add2, int64_t ldadd2, float* scale_state, void* stream) {
-    VQ_REQUIRE(A && B && C && scale_state, "gemm_nt_grad_tail: null pointer");
-    VQ_REQUIRE(vqcpc_gemm_nt_grad_tail_supported(M, N, K), "gemm_nt_grad_tail: M a multiple of 64, N of 128, K of 32, got M=%lld N=%d K=%d",
-               (long long)M, N, K);
-    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
-               "gemm_nt_grad_tail: bad leading dimensions / alignment");
-    VQ_REQUIRE(!(add2 && !add) && !(add && ldadd < N) && !(add2 && ldadd2 < N) && drop_p >= 0.f && drop_p < 1.f,
-               "gemm_nt_grad_tail: bad epilogue operands");
-    EpiParams ep{};
-    ep.bias = bias;
-    ep.thr = drop_threshold(drop_p);
-    ep.inv_keep = 1.0f / (1.0f - drop_p);
-    ep.seed = seed;
-    ep.row0 = row0;
-    ep.add = add;
-    ep.ldadd = ldadd;
-    ep.add2 = add2;
-    ep.ldadd2 = ldadd2;
-    ep.gate_scale = 1.0f;
-    const int tn = N / kRN;
-    const size_t lds = (size_t)2 * kRSlot;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_g3_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    hipLaunchKernelGGL(gemm_nt_g3_tail_kernel, dim3((unsigned)((M / kRM) * tn)), dim3(kGThreads), lds, (hipStream_t)stream, A, lda, B,
-                       ldb, C, ldc, N, K, tn, ep, scale_state);
-    VQ_CHECK_LAUNCH("gemm_nt_g3 (tail rows)");
-    return VQCPC_OK;
+    return g3_small_launch("gemm_nt_grad_tail", A, lda, B, ldb, C, ldc, M, N, K, bias, 0, drop_p, seed, row0, nullptr, 0, 1.0f, add,
+                           ldadd, add2, ldadd2, scale_state, nullptr, nullptr, stream);
 }
 
 // The forward products of a TRAINING step on the same kernel (round 5): C = epilogue(A . B^T) with the epilogues of vqcpc_gemm_nt that
@@ -1206,182 +1229,31 @@ int vqcpc_gemm_nt_f16x3(const float* A, int64_t lda, const float* B, int64_t ldb
                         const float* bias, int act, float drop_p, uint64_t seed, const float* add, int64_t ldadd, void* mask_out,
                         float* scale_state, void* stream) {
     VQ_REQUIRE(A && B && C && scale_state && bias, "gemm_nt_f16x3: null pointer (a bias is part of every forward form)");
-    VQ_REQUIRE(vqcpc_gemm_nt_grad_supported(M, N, K), "gemm_nt_f16x3: M, N multiples of 256 and K of 32, got M=%lld N=%d K=%d",
-               (long long)M, N, K);
-    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
-               "gemm_nt_f16x3: bad leading dimensions / alignment");
-    VQ_REQUIRE(act == 0 || act == 1, "gemm_nt_f16x3: act must be 0 or 1");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gemm_nt_f16x3: bad dropout probability");
     VQ_REQUIRE((act == 1) == (mask_out != nullptr) && !(act == 1 && add) && !(add && ldadd < N),
                "gemm_nt_f16x3: epilogue is one of bias / bias + add / bias + dropout + add / bias + relu (+ dropout) + mask_out");
-    VQ_REQUIRE(!mask_out || aligned16(mask_out), "gemm_nt_f16x3: mask must be 16-byte aligned");
-    EpiParams ep{};
-    ep.bias = bias;
-    ep.act = act;
-    ep.thr = drop_threshold(drop_p);
-    ep.inv_keep = 1.0f / (1.0f - drop_p);
-    ep.seed = seed;
-    ep.add = add;
-    ep.ldadd = ldadd;
-    ep.mask = (uint32_t*)mask_out;
-    ep.gate_scale = 1.0f;
-    const int tn = N / kG;
-    const int tiles = (int)((M / kG) * tn);
-    const dim3 grid((unsigned)std::min(tiles, kNumCU)), block(kGThreads);
-    const size_t lds = (size_t)kGSlots * kGSlot;
-    hipStream_t st = (hipStream_t)stream;
-#define G3_LAUNCH(EPIV)                                                                                                  \
-    {                                                                                                                    \
-        static bool attr = false;                                                                                        \
-        if (!attr) {                                                                                                     \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_g3_kernel<EPIV>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                      (int)lds);                                                                         \
-            attr = true;                                                                                                 \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_nt_g3_kernel<EPIV>), grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles,  \
-                           ep, scale_state);                                                                             \
-    }
-    const bool drop = ep.thr != 0;
-    if (act == 1) {
-        if (drop) G3_LAUNCH(E_BIAS | E_RELU | E_DROP | E_MASKOUT)
-        else G3_LAUNCH(E_BIAS | E_RELU | E_MASKOUT)
-    } else if (add) {
-        if (drop) G3_LAUNCH(E_BIAS | E_DROP | E_ADD)
-        else G3_LAUNCH(E_BIAS | E_ADD)
-    } else {
-        VQ_REQUIRE(!drop, "gemm_nt_f16x3: dropout without a residual or relu is not a forward form of the step");
-        G3_LAUNCH(E_BIAS)
-    }
-#undef G3_LAUNCH
-    VQ_CHECK_LAUNCH("gemm_nt_g3 (forward)");
-    return VQCPC_OK;
+    return g3_launch("gemm_nt_f16x3", A, lda, B, ldb, C, ldc, M, N, K, bias, act, drop_p, seed, add, ldadd, nullptr, 0, nullptr, 1.0f,
+                     mask_out, scale_state, nullptr, nullptr, stream);
 }
 
 // The same products on PRE-SPLIT operands (round 6; "P4" format, see gemm_nt_g3_kernel): `pl_amax_b` (required) = device scalar, the
 // amax B's planes were scaled with -- B then points at the P4 image of the (N, K) operand, same leading dimension; `pl_amax_a`
 // (optional) likewise for A.  One entry point for every epilogue form of vqcpc_gemm_nt_grad (bias == NULL: none | + add | + add + add2
 // | add == C in place | gate-bit mask) and of vqcpc_gemm_nt_f16x3 (bias != NULL: bias | + add | + dropout + add | relu (+ dropout) +
-// mask_out).  Results are bit-identical to those entry points when their scale state holds the same amax values.
+// mask_out).  Results are bit-identical to those entry points when their scale state holds the same amax values.  A P4 A goes with
+// the forms of G3EpiloguesP4A (gemm_forms.h) only.
 int vqcpc_gemm_nt_g3_pl(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int K,
                         const float* bias, int act, float drop_p, uint64_t seed, const float* add, int64_t ldadd, const float* add2,
                         int64_t ldadd2, const void* gate_mask, float gate_scale, void* mask_out, float* scale_state,
                         const float* pl_amax_a, const float* pl_amax_b, void* stream) {
     VQ_REQUIRE(A && B && C && scale_state && pl_amax_b, "gemm_nt_g3_pl: null pointer (B must be a P4 operand)");
-    VQ_REQUIRE(vqcpc_gemm_nt_grad_supported(M, N, K), "gemm_nt_g3_pl: M, N multiples of 256 and K of 32, got M=%lld N=%d K=%d",
-               (long long)M, N, K);
-    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
-               "gemm_nt_g3_pl: bad leading dimensions / alignment");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (act == 0 || act == 1), "gemm_nt_g3_pl: bad dropout probability / act");
-    EpiParams ep{};
-    ep.bias = bias;
-    ep.act = act;
-    ep.thr = drop_threshold(drop_p);
-    ep.inv_keep = 1.0f / (1.0f - drop_p);
-    ep.seed = seed;
-    ep.add = add;
-    ep.ldadd = ldadd;
-    ep.add2 = add2;
-    ep.ldadd2 = ldadd2;
-    ep.gate_scale = bias ? 1.0f : gate_scale;
-    ep.pl_amax_a = pl_amax_a;
-    ep.pl_amax_b = pl_amax_b;
-    const int tn = N / kG;
-    const int tiles = (int)((M / kG) * tn);
-    const dim3 grid((unsigned)std::min(tiles, kNumCU)), block(kGThreads);
-    const size_t lds = (size_t)kGSlots * kGSlot;
-    hipStream_t st = (hipStream_t)stream;
-    const bool drop = ep.thr != 0;
-#define G3PL_LAUNCH(EPIV, PLV)                                                                                           \
-    {                                                                                                                    \
-        static bool attr = false;                                                                                        \
-        if (!attr) {                                                                                                     \
-            (void)hipFuncSetAttribute((const void*)gemm_nt_g3_kernel<EPIV, 0, PLV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds);                                                                         \
-            attr = true;                                                                                                 \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_nt_g3_kernel<EPIV, 0, PLV>), grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles, \
-                           ep, scale_state);                                                                             \
-    }
-#define G3PL_BOTH(EPIV) { if (pl_amax_a) G3PL_LAUNCH(EPIV, 3) else G3PL_LAUNCH(EPIV, 2) }
-    if (bias) {                                  // the forward forms
+    if (bias)                                    // the forward forms
         VQ_REQUIRE(!gate_mask && !add2 && (act == 1) == (mask_out != nullptr) && !(act == 1 && add) && !(add && ldadd < N),
                    "gemm_nt_g3_pl: forward epilogue is one of bias / bias + add / bias + dropout + add / bias + relu (+ dropout) + mask_out");
-        VQ_REQUIRE(!mask_out || aligned16(mask_out), "gemm_nt_g3_pl: mask must be 16-byte aligned");
-        ep.mask = (uint32_t*)mask_out;
-        if (act == 1) {
-            VQ_REQUIRE(!pl_amax_a, "gemm_nt_g3_pl: the relu + mask form takes an fp32 A operand");
-            if (drop) G3PL_LAUNCH(E_BIAS | E_RELU | E_DROP | E_MASKOUT, 2)
-            else G3PL_LAUNCH(E_BIAS | E_RELU | E_MASKOUT, 2)
-        } else if (add) {
-            if (drop) G3PL_BOTH(E_BIAS | E_DROP | E_ADD)
-            else G3PL_BOTH(E_BIAS | E_ADD)
-        } else {
-            VQ_REQUIRE(!drop, "gemm_nt_g3_pl: dropout without a residual or relu is not a forward form of the step");
-            G3PL_BOTH(E_BIAS)
-        }
-    } else {                                     // the input-gradient forms
-        VQ_REQUIRE(!mask_out && !drop && !(add2 && !add) && !(gate_mask && add), "gemm_nt_g3_pl: gradient epilogue is one of none / add / add + add2 / gate mask");
-        VQ_REQUIRE(!gate_mask || aligned16(gate_mask), "gemm_nt_g3_pl: gate mask must be 16-byte aligned");
-        ep.mask = (uint32_t*)const_cast<void*>(gate_mask);
-        if (gate_mask) {
-            VQ_REQUIRE(!pl_amax_a, "gemm_nt_g3_pl: the gate-mask form takes an fp32 A operand");
-            G3PL_LAUNCH(E_GATEBITS, 2)
-        } else if (add && !add2 && add == C && ldadd == ldc) G3PL_BOTH(G_ACCUM)
-        else if (add2 && add2 == C && ldadd2 == ldc) G3PL_LAUNCH(E_ADD | G_ACCUM, 2)
-        else if (add2) G3PL_LAUNCH(E_ADD | E_ADD2, 2)
-        else if (add) G3PL_BOTH(E_ADD)
-        else G3PL_BOTH(0)
-    }
-#undef G3PL_BOTH
-#undef G3PL_LAUNCH
-    VQ_CHECK_LAUNCH("gemm_nt_g3 (P4 operands)");
-    return VQCPC_OK;
-}
-
-// The 64 x 128-tile kernel as a GENERAL entry point (round 6): the tail rows of a ragged launch on P4 operands, and whole products
-// whose 256-tiles would not fill the chip (the 3 072 - 12 288-row products of the student / decoder steps: x 1.1-1.36 the six-product
-// 128-tile / split-K path, tools/bench_small_f16x3.py).  Operands fp32 or P4 (pl_amax_a / pl_amax_b NULL: fp32, split in the kernel).
-// Epilogue, in the order of vqcpc_gemm_nt: + bias, relu (act == 1), dropout (element index (row0 + row) * N + col), * (gate > 0 ?
-// gate_scale : 0), + add (may be C), + add2.
-int vqcpc_gemm_nt_g3_small(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int K,
-                           const float* bias, int act, float drop_p, uint64_t seed, int64_t row0, const float* gate, int64_t ldgate,
-                           float gate_scale, const float* add, int64_t ldadd, const float* add2, int64_t ldadd2, float* scale_state,
-                           const float* pl_amax_a, const float* pl_amax_b, void* stream) {
-    VQ_REQUIRE(A && B && C && scale_state, "gemm_nt_g3_small: null pointer");
-    VQ_REQUIRE(vqcpc_gemm_nt_grad_tail_supported(M, N, K), "gemm_nt_g3_small: M a multiple of 64, N of 128, K of 32, got M=%lld N=%d K=%d",
-               (long long)M, N, K);
-    VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
-               "gemm_nt_g3_small: bad leading dimensions / alignment");
-    VQ_REQUIRE(!(add2 && !add) && !(add && ldadd < N) && !(add2 && ldadd2 < N) && !(gate && ldgate < N) && drop_p >= 0.f && drop_p < 1.f &&
-                   (act == 0 || act == 1),
-               "gemm_nt_g3_small: bad epilogue operands");
-    EpiParams ep{};
-    ep.bias = bias;
-    ep.act = act;
-    ep.thr = drop_threshold(drop_p);
-    ep.inv_keep = 1.0f / (1.0f - drop_p);
-    ep.seed = seed;
-    ep.row0 = row0;
-    ep.gate = gate;
-    ep.ldgate = ldgate;
-    ep.gate_scale = gate_scale;
-    ep.add = add;
-    ep.ldadd = ldadd;
-    ep.add2 = add2;
-    ep.ldadd2 = ldadd2;
-    ep.pl_amax_a = pl_amax_a;
-    ep.pl_amax_b = pl_amax_b;
-    const int tn = N / kRN;
-    const size_t lds = (size_t)2 * kRSlot;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_g3_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    hipLaunchKernelGGL(gemm_nt_g3_tail_kernel, dim3((unsigned)((M / kRM) * tn)), dim3(kGThreads), lds, (hipStream_t)stream, A, lda, B,
-                       ldb, C, ldc, N, K, tn, ep, scale_state);
-    VQ_CHECK_LAUNCH("gemm_nt_g3 (64 x 128 tiles)");
-    return VQCPC_OK;
+    else                                         // the input-gradient forms
+        VQ_REQUIRE(!mask_out && !(add2 && !add) && !(gate_mask && add),
+                   "gemm_nt_g3_pl: gradient epilogue is one of none / add / add + add2 / gate mask");
+    return g3_launch("gemm_nt_g3_pl", A, lda, B, ldb, C, ldc, M, N, K, bias, act, drop_p, seed, add, ldadd, add2, ldadd2, gate_mask,
+                     gate_scale, mask_out, scale_state, pl_amax_a, pl_amax_b, stream);
 }
 
 // wgrad shapes: whole 256 x 256 output tiles, M a multiple of 32 (an even number of 16-row steps per split)
@@ -1408,15 +1280,9 @@ int vqcpc_gemm_tn_grad(const float* A, int64_t lda, const float* B, int64_t ldb,
     float* ws = (float*)workspace;
     float* ws_bias = db ? ws + (int64_t)splits * N * K : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    const size_t lds = (size_t)kGSlots * kQSlot;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_g3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
     const int tk = K / kG;
-    hipLaunchKernelGGL(gemm_tn_g3_kernel, dim3((N / kG) * tk, splits), dim3(kGThreads), lds, s, A, lda, B, ldb, M, N, K, tk,
-                       rows_per_split, ws, ws_bias, scale_state);
+    launch_lds<gemm_tn_g3_kernel>(dim3((N / kG) * tk, splits), dim3(kGThreads), (size_t)kGSlots * kQSlot, s, A, lda, B, ldb, M, N, K, tk,
+                                  rows_per_split, ws, ws_bias, scale_state);
     VQ_CHECK_LAUNCH("gemm_tn_g3");
     return launch_reduce_splits2(ws, (int64_t)N * K, splits, dW, (int64_t)N * K, ws_bias, N, db, db ? N : 0, accumulate, s);
 }
