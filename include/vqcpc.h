@@ -800,6 +800,22 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
  *     win[1] < 0: nothing is forced and no logp is written.  Likewise for a column col >= ldcons (free) / col >= ldlogp
  *       (not written): the window index is not known to the host, which checks ldcons, ldlogp >= T only.
  *   probs, next_in, tokens[b * ldtok + pos], pos[0] = pos + 1, the no-op once pos >= T and the limits are unchanged.
+ * vqcpc_decode_sample_masked: vqcpc_decode_sample_constrained (the same kernel body, one more compile-time flag) with two more
+ *   things at the same column col:
+ *     allowed[(b * ldallow + col) * 8 + w] (device uint32, [M][ldallow][8]; NULL = no restriction): bit i & 31 of word i >> 5
+ *       set means token i may be drawn at (row b, column col).  A token outside the set becomes -inf where exclude is applied
+ *       (after / temperature, before top-k and top-p), so the filters and probs act on the allowed set; the draw is still
+ *       keyed by (seeds[b], pos).  Only bits [0, V_c) count; a set with none of them restricts nothing (the caller is expected
+ *       to refuse such a set).  A forced token (constraint >= 0) wins over the set as it wins over exclude.  col >= ldallow or
+ *       win[1] < 0: no restriction.
+ *     logmass[b * ldmass + col] (may be NULL; column rule of logp) = (m_a - m) + log(s_a) - log(s): m, s the maximum and the
+ *       exp-sum of the unmodified row as logp forms them, m_a, s_a the same over the allowed tokens, summed in the same lane
+ *       order -- the log of the probability the model itself gives to the allowed set (temperature 1, no filter, exclude not
+ *       counted).  Exactly 0.0f for the full set and for a row that is not restricted, -inf when every allowed logit is -inf;
+ *       written at forced positions too; a row's value does not depend on M.  logp is unchanged: the emitted token under the
+ *       unmodified row.
+ *   ldallow >= T with allowed, ldmass >= T with logmass.  With allowed == NULL and logmass == NULL every output has the bits of
+ *   vqcpc_decode_sample_constrained.
  *
  * Sliding-window generation (decoders/decoder.py:729-854): the window moves by one code, the caches of its P prefix rows
  * are rebuilt teacher-forced (vqcpc_gemm_nt, vqcpc_add_layernorm_fwd, vqcpc_block_table_gather for the row-wise parts).
@@ -844,6 +860,12 @@ int vqcpc_decode_sample_constrained(const float* logits, int64_t ldl, const int3
                                     const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
                                     int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d, int U,
                                     float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream);
+int vqcpc_decode_sample_masked(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
+                               int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* constraint,
+                               int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win, const uint32_t* allowed,
+                               int64_t ldallow, float* logmass, int64_t ldmass, int64_t* tokens, int64_t ldtok, int T,
+                               const float* table, int64_t table_rows, int d, int U, float* next_in, int64_t ldn, float* probs,
+                               int64_t ldp, int32_t* pos, void* stream);
 int vqcpc_decode_prefill_attn(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldk, float* k_cache,
                               float* v_cache, int64_t ldc, const float* e1, const float* e2, float* ctx, int64_t ldo, int64_t M,
                               int P, int Lk, int ratio, int H, int hd, int mask, void* stream);

@@ -20,6 +20,8 @@
 //   * vqcpc_decode_sample_constrained: the same kernel body with a compile-time flag: per (row, position) a token to emit or a
 //     draw, and the emitted token's log-probability under the unfiltered row; both addressed in chorale coordinates through
 //     the device window index.
+//   * vqcpc_decode_sample_masked: one more compile-time flag on top of that: per (row, position) a 256-bit set of the tokens that
+//     may be drawn, applied where the exclusion is, and the log of the probability mass the set leaves open; same addressing.
 //
 // Sliding-window generation (reference: decoder.py:729-854) moves the model window by one code at a time; the caches of
 // the new window's prefix are rebuilt by a teacher-forced pass over its P prefix rows (GEMMs + LayerNorm of the training
@@ -511,13 +513,22 @@ __device__ __forceinline__ float wave_incl_scan(float v, int lane) {
 // every window.  A column outside [0, ldteach) / [0, ldlogp) is free / not written.  The log-sum-exp is a lane-serial sum of
 // four and a butterfly over the 64 lanes: its order depends on nothing but the lane layout, so a row's value is the same
 // whatever M.  Without CONS the kernel is what it was before the flag: none of the added code is instantiated.
-template <bool CONS>
+// MASK (vqcpc_decode_sample_masked, on top of CONS): `allowed` [M][ldallow][8] holds per (row, column) a 256-bit set of the tokens
+// that may be drawn, read at the same column as the constraint; lane l's four tokens are bits 4 (l & 7) .. + 3 of word l >> 3.
+// A token outside the set becomes -inf where `exclude` is applied, so top-k, top-p and probs act on the set; a forced token
+// ignores it.  Only bits [0, V) count and a set without any is no restriction.  logmass gets, at logp's column rule, the log
+// of the share of the UNFILTERED row's probability that the set leaves open: (m_a - m) + log(s_a) - log(s) with the maximum
+// and exp-sum of the row (the logp code's) and of its allowed tokens, both summed in the same lane order -- the full set gives
+// exactly 0.  Without MASK none of this is instantiated.
+template <bool CONS, bool MASK = false>
 __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
     const float* __restrict__ logits, int64_t ldl, VoiceOffsets vo, int nc, int M, float temperature, int top_k, float top_p,
     const uint32_t* __restrict__ exclude, const int64_t* __restrict__ seeds, const int64_t* __restrict__ teacher,
     int64_t ldteach, int64_t* __restrict__ tokens, int64_t ldtok, int T, const float* __restrict__ table, int64_t table_rows,
     int d, int U, float* __restrict__ next_in, int64_t ldn, float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp,
-    float* __restrict__ logp, int64_t ldlogp, const int32_t* __restrict__ win) {
+    float* __restrict__ logp, int64_t ldlogp, const int32_t* __restrict__ win, const uint32_t* __restrict__ allowed,
+    int64_t ldallow, float* __restrict__ logmass, int64_t ldmass) {
+    static_assert(CONS || !MASK, "the mask is addressed at the constraint's column");
     __shared__ float sl[kSampWaves][kDecMaxVocab];            // a wave's (filtered) logits
     __shared__ float srt[kSampWaves][kDecMaxVocab];           // top-p: probabilities in descending order, then their cumsum
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -536,6 +547,15 @@ __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
         const bool act = live_pos && b < M;
         float l[4];
         float raw[4] = {ninf, ninf, ninf, ninf};              // CONS: the row as the model gave it
+        uint32_t ok = 0xFu;                                   // MASK: bit t = token 4 * lane + t may be drawn
+        if constexpr (MASK) {
+            if (act && allowed && col >= 0 && col < ldallow) {        // uniform over the wave: the ballot runs in every lane
+                const uint32_t word = allowed[((int64_t)b * ldallow + col) * 8 + (lane >> 3)];
+                const int mine = V - 4 * lane;                         // this lane's tokens below V
+                const uint32_t bits = (word >> ((lane & 7) * 4)) & (mine >= 4 ? 0xFu : mine > 0 ? (1u << mine) - 1u : 0u);
+                if (__ballot(bits != 0u) != 0ull) ok = bits;           // an empty set restricts nothing
+            }
+        }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int i = 4 * lane + t;
@@ -545,6 +565,9 @@ __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
                 if constexpr (CONS) raw[t] = v;
                 v = v / temperature;
                 if (exclude && ((exclude[c * 8 + (i >> 5)] >> (i & 31)) & 1u)) v = ninf;
+                if constexpr (MASK) {
+                    if (!((ok >> t) & 1u)) v = ninf;
+                }
             }
             l[t] = v;
             sl[wave][i] = v;
@@ -669,7 +692,33 @@ __global__ __launch_bounds__(64 * kSampWaves) void decode_sample_kernel(
             if (lane == 0) tokens[(int64_t)b * ldtok + pos] = tok;
             const int64_t row = min((int64_t)tok * U + pos % U, table_rows - 1);     // _target_rows: input of position pos + 1
             for (int k = lane; k < d; k += 64) next_in[(int64_t)b * ldn + k] = table[row * d + k];
-            if constexpr (CONS) {
+            if constexpr (MASK) {
+                const bool wl = logp && col >= 0 && col < ldlogp, wm = logmass && col >= 0 && col < ldmass;
+                if (wl || wm) {                               // uniform, as below; rmx, rs and logp are formed as below
+                    const float rmx = wave_max(fmaxf(fmaxf(raw[0], raw[1]), fmaxf(raw[2], raw[3])));
+                    float rs = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) rs += raw[t] > ninf ? expf(raw[t] - rmx) : 0.0f;
+                    rs = wave_sum(rs);
+                    if (wl) {
+                        const int tt = tok & 3;
+                        const float mine = tt == 0 ? raw[0] : tt == 1 ? raw[1] : tt == 2 ? raw[2] : raw[3];
+                        const float rt = __shfl(mine, tok >> 2, 64);
+                        if (lane == 0) logp[(int64_t)b * ldlogp + col] = (rt - rmx) - logf(rs);
+                    }
+                    if (wm) {
+                        float ar[4];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) ar[t] = (ok >> t) & 1u ? raw[t] : ninf;
+                        const float amx = wave_max(fmaxf(fmaxf(ar[0], ar[1]), fmaxf(ar[2], ar[3])));
+                        float as = 0.0f;
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) as += ar[t] > ninf ? expf(ar[t] - amx) : 0.0f;
+                        as = wave_sum(as);
+                        if (lane == 0) logmass[(int64_t)b * ldmass + col] = (amx - rmx) + logf(as) - logf(rs);
+                    }
+                }
+            } else if constexpr (CONS) {
                 if (logp && col >= 0 && col < ldlogp) {       // uniform: the shuffles below run in every lane or in none
                     const float rmx = wave_max(fmaxf(fmaxf(raw[0], raw[1]), fmaxf(raw[2], raw[3])));
                     float rs = 0.0f;
@@ -799,7 +848,8 @@ int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_o
     VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "decode_sample: the table has too few rows for V_c * U");
     hipLaunchKernelGGL(decode_sample_kernel<false>, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc,
                        (int)M, temperature, top_k, top_p, exclude, seeds, teacher, ldteach, tokens, ldtok, T, table, table_rows,
-                       d, U, next_in, ldn, probs, ldp, pos, (float*)nullptr, (int64_t)0, (const int32_t*)nullptr);
+                       d, U, next_in, ldn, probs, ldp, pos, (float*)nullptr, (int64_t)0, (const int32_t*)nullptr,
+                       (const uint32_t*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0);
     VQ_CHECK_LAUNCH("decode_sample");
     return VQCPC_OK;
 }
@@ -832,8 +882,43 @@ int vqcpc_decode_sample_constrained(const float* logits, int64_t ldl, const int3
                "decode_sample_constrained: the table has too few rows for V_c * U");
     hipLaunchKernelGGL(decode_sample_kernel<true>, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc,
                        (int)M, temperature, top_k, top_p, exclude, seeds, constraint, ldcons, tokens, ldtok, T, table,
-                       table_rows, d, U, next_in, ldn, probs, ldp, pos, logp, ldlogp, win);
+                       table_rows, d, U, next_in, ldn, probs, ldp, pos, logp, ldlogp, win, (const uint32_t*)nullptr, (int64_t)0,
+                       (float*)nullptr, (int64_t)0);
     VQ_CHECK_LAUNCH("decode_sample_constrained");
+    return VQCPC_OK;
+}
+
+int vqcpc_decode_sample_masked(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
+                               int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* constraint,
+                               int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win, const uint32_t* allowed,
+                               int64_t ldallow, float* logmass, int64_t ldmass, int64_t* tokens, int64_t ldtok, int T,
+                               const float* table, int64_t table_rows, int d, int U, float* next_in, int64_t ldn, float* probs,
+                               int64_t ldp, int32_t* pos, void* stream) {
+    VQ_REQUIRE(logits && voice_offsets && seeds && tokens && table && next_in && pos && nc >= 1 && nc <= kDecMaxVoices && M >= 1 &&
+               M <= kDecMaxRows && T >= 1 && d >= 1 && d <= kDecMaxDim && U >= 1 && table_rows >= 1,
+               "decode_sample_masked: bad arguments (seeds needed, 1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)");
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "decode_sample_masked: temperature > 0, top_k >= 0");
+    VoiceOffsets vo;
+    vo.off[0] = voice_offsets[0];
+    VQ_REQUIRE(vo.off[0] >= 0, "decode_sample_masked: negative voice offset");
+    int vmax = 0;
+    for (int c = 0; c < nc; ++c) {
+        const int V = voice_offsets[c + 1] - voice_offsets[c];
+        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "decode_sample_masked: voice %d has %d tokens (1 <= V_c <= 256)", c, V);
+        vo.off[c + 1] = voice_offsets[c + 1];
+        vmax = std::max(vmax, V);
+    }
+    for (int c = nc + 1; c <= kDecMaxVoices; ++c) vo.off[c] = vo.off[nc];
+    // as in the constrained entry point, the host can only ask for one window's columns
+    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!constraint || ldcons >= T) && (!logp || ldlogp >= T) &&
+               (!probs || ldp >= vmax), "decode_sample_masked: bad leading dimensions (ldcons, ldlogp >= T)");
+    VQ_REQUIRE((!allowed || ldallow >= T) && (!logmass || ldmass >= T),
+               "decode_sample_masked: bad leading dimensions (ldallow, ldmass >= T)");
+    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "decode_sample_masked: the table has too few rows for V_c * U");
+    hipLaunchKernelGGL((decode_sample_kernel<true, true>), dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo,
+                       nc, (int)M, temperature, top_k, top_p, exclude, seeds, constraint, ldcons, tokens, ldtok, T, table,
+                       table_rows, d, U, next_in, ldn, probs, ldp, pos, logp, ldlogp, win, allowed, ldallow, logmass, ldmass);
+    VQ_CHECK_LAUNCH("decode_sample_masked");
     return VQCPC_OK;
 }
 

@@ -356,6 +356,62 @@ class Decoder(FlatTraining, nn.Module):
             raise ValueError(f'constraint: a forced token is outside its voice\'s vocabulary {vocab.tolist()}')
         return constraint.reshape(rows, events * nc)
 
+    def _allowed_words(self, allowed, rows, events, first=0, last=None, exclude=None, constraint=None):
+        """A public mask `allowed`, bool (rows, events, channels, vmax) or (events, channels, vmax) shared by all rows ->
+        the sampler's packed sets (rows or 1, events * channels, 8) int32 on the device: bit i & 31 of word i >> 5 = token i may
+        be drawn.  Entries past a voice's vocabulary are ignored (packed as given: the kernel ignores them too) and so are the
+        events outside [first, last).  exclude: the per-voice excluded token ids of the call; constraint: its (rows, events *
+        channels) constraint as `_constraint_rows` returns it.  ValueError on a wrong shape or dtype and -- one host check per
+        call -- on a generated (row, event, voice) that has no allowed token in its vocabulary, none left after `exclude`, or
+        a forced token outside its set; the message names the first one."""
+        allowed = torch.as_tensor(allowed)
+        nc, dev = self.num_channels, self.sos.device
+        sizes = [int(v) for v in self.num_tokens_per_channel]
+        shape = tuple(allowed.shape)
+        if allowed.dtype != torch.bool or allowed.dim() not in (3, 4) or shape[-3:-1] != (events, nc) or \
+                (allowed.dim() == 4 and shape[0] != rows):
+            raise ValueError(f'allowed: bool ({rows}, {events}, {nc}, vmax) or ({events}, {nc}, vmax) expected, got {shape} '
+                             f'{allowed.dtype}')
+        vmax = shape[-1]
+        if vmax > 256:
+            raise ValueError(f'allowed: vmax = {vmax} > 256, the sampler\'s largest vocabulary')
+        if vmax < max(sizes):
+            raise ValueError(f'allowed: vmax = {vmax} is smaller than the largest voice vocabulary {max(sizes)}')
+        allowed = allowed.to(dev).reshape(-1, events, nc, vmax)                                  # (R, ...), R = rows or 1
+        last = events if last is None else last
+        ids = torch.arange(vmax, device=dev)
+        live = allowed & (ids < torch.tensor(sizes, device=dev).unsqueeze(1))                   # inside the voice's vocabulary
+        banned = torch.zeros(nc, vmax, dtype=torch.bool, device=dev)
+        for c, toks in enumerate(exclude or []):
+            for t in toks:
+                if 0 <= int(t) < vmax:
+                    banned[c, int(t)] = True
+        generated = ((torch.arange(events, device=dev) >= first) & (torch.arange(events, device=dev) < last)).view(1, -1, 1)
+        empty = ~live.any(-1) & generated
+        drained = ~(live & ~banned).any(-1) & generated
+        if constraint is not None:
+            forced = constraint.view(rows, events, nc)
+            picked = live.expand(rows, -1, -1, -1).gather(3, forced.clamp(min=0).unsqueeze(3)).squeeze(3)
+            refused = (forced >= 0) & ~picked & generated
+        else:
+            refused = torch.zeros_like(empty)
+        R = max(empty.shape[0], refused.shape[0])
+        kinds = torch.stack([k.expand(R, -1, -1).reshape(-1) for k in (empty, drained, refused)])
+        bad = kinds.any(0)
+        at = bad.to(torch.int32).argmax()
+        found, at, e_, d_, r_ = torch.stack([bad.any().long(), at.long(), *kinds[:, at].long()]).tolist()   # the one host check
+        if found:
+            b, rest = divmod(at, events * nc)
+            e, c = divmod(rest, nc)
+            what = 'has no allowed token inside its vocabulary' if e_ else \
+                'has no allowed token left after exclude_tokens' if d_ else \
+                f'is forced to token {int(constraint.view(rows, events, nc)[b, e, c])}, which its allowed set forbids'
+            raise ValueError(f'allowed: (row {b}, event {e}, voice {c}) {what}')
+        bits = torch.zeros(allowed.shape[0], events * nc, 256, dtype=torch.int32, device=dev)
+        bits[:, :, :vmax] = allowed.reshape(-1, events * nc, vmax)
+        weights = torch.tensor([1 << k for k in range(31)] + [-(1 << 31)], dtype=torch.int32, device=dev)
+        return (bits.view(-1, events * nc, 8, 32) * weights).sum(-1, dtype=torch.int32)
+
     def _attention_layers(self, return_attentions, default=None):
         """return_attentions -> None (False), or the sorted tuple of decoder-layer indices to record: True = every layer
         (`default`, when given), an iterable = those layers.  ValueError on an index outside the stack or an empty choice."""
@@ -399,7 +455,7 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
                             use_graph=True, constraint=None, return_logp=False, return_attentions=False,
-                            max_attention_bytes=4 << 30):
+                            max_attention_bytes=4 << 30, allowed=None, return_allowed_mass=False):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
@@ -422,7 +478,17 @@ class Decoder(FlatTraining, nn.Module):
           'self_attns_encoder'  (B', encoder layers, H, S, S), the source encoder's maps (every layer: they are computed anyway)
         with B' = B * num_decodings, on the device.  The rows are the ones the step's attention kernel multiplies V by
         (vqcpc_decode_attn_probs); tokens and logp are bit-identical to a call without the keyword.  The maps' bytes are computed
-        first: ValueError above max_attention_bytes (default 4 GiB)."""
+        first: ValueError above max_attention_bytes (default 4 GiB).
+        allowed: bool (B, events, channels, vmax) or (events, channels, vmax) shared by all rows, max V_c <= vmax <= 256: at
+        (row, event, voice) only the tokens whose entry is True may be drawn (entries past the voice's vocabulary are
+        ignored); rows are repeated with num_decodings.  The set acts where exclude_tokens does -- before top-k / top-p, which
+        then choose among the allowed tokens -- and a token forced by `constraint` must be in its set.  ValueError, from one
+        host check per call, naming the first (row, event, voice) whose set has no token of its vocabulary, none left after
+        exclude_tokens, or forbids its forced token (`templates.py` builds such masks from a corpus's token names).
+        return_allowed_mass=True -> `allowed_mass` after tokens and logp, float32 of the tokens' shape: the log of the
+        probability the model's unfiltered distribution gives to the position's allowed set (0 where nothing is restricted).
+        Results come in the order (tokens[, logp][, allowed_mass][, attentions]).  Either keyword switches the step's sampler
+        to vqcpc_decode_sample_masked; without them every launch is what it was."""
         from ..transformer.incremental import generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
@@ -431,13 +497,18 @@ class Decoder(FlatTraining, nn.Module):
         T, nc = self.num_tokens_target, self.num_channels
         if constraint is not None:
             constraint = self._constraint_rows(constraint, codes.shape[0], T // nc)
+        if allowed is not None:
+            allowed = self._allowed_words(allowed, codes.shape[0], T // nc, exclude=exclude_tokens, constraint=constraint)
         if num_decodings > 1:
             codes = codes.repeat_interleave(num_decodings, dim=0)
             if constraint is not None:
                 constraint = constraint.repeat_interleave(num_decodings, dim=0)
+            if allowed is not None and allowed.shape[0] > 1:
+                allowed = allowed.repeat_interleave(num_decodings, dim=0)
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
         logp = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logp else None
+        mass = torch.empty(B, T, dtype=torch.float32, device=dev) if return_allowed_mass else None
         maps = None
         if layers is not None:
             self._check_attention_bytes(B, layers, T, True, max_attention_bytes)
@@ -447,10 +518,13 @@ class Decoder(FlatTraining, nn.Module):
             inc = IncrementalDecoder(self, n)
             inc.prefill(codes[rows])
             inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens,
-                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp, want_attentions=layers)
+                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp, want_attentions=layers,
+                      allowed=self._allowed_rows(allowed, n, rows), want_allowed_mass=return_allowed_mass)
             tokens = inc.run(use_graph=use_graph)
             if return_logp:
                 logp[rows] = inc.logp
+            if return_allowed_mass:
+                mass[rows] = inc.logmass
             if maps is not None:
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
@@ -458,9 +532,18 @@ class Decoder(FlatTraining, nn.Module):
             return tokens
         tokens = generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
         out = (tokens, logp.view(B, T // nc, nc)) if return_logp else (tokens,)
+        if return_allowed_mass:
+            out += (mass.view(B, T // nc, nc),)
         if maps is not None:
             out += (self._join_attention_chunks(maps),)
         return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def _allowed_rows(words, n, rows):
+        """The packed sets of a chunk's n rows (a shared mask has one row: a broadcast view, copied by the stack)."""
+        if words is None:
+            return None
+        return words.expand(n, -1, -1) if words.shape[0] == 1 else words[rows]
 
     @staticmethod
     def _join_attention_chunks(maps):
@@ -615,7 +698,7 @@ class Decoder(FlatTraining, nn.Module):
     def generate_from_code_long(self, encoding_indices=None, temperature=None, top_k=0, top_p=1., exclude_meta_symbols=False,
                                 num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
                                 use_graph=True, constraint=None, return_logp=False, return_attentions=False,
-                                max_attention_bytes=4 << 30, graph_slides=None):
+                                max_attention_bytes=4 << 30, graph_slides=None, allowed=None, return_allowed_mass=False):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -638,7 +721,11 @@ class Decoder(FlatTraining, nn.Module):
         diagonal decoder) and 'window_start' (nb * U,) int64 on the host (`attention_window_starts`): the first code w of the
         window in which position c was emitted, -1 where none was -- those rows stay NaN.  Key j of row c is chorale token
         w * U + j (self) / code w + j (cross).  No encoder maps: they change with every window.
-        graph_slides: `IncrementalDecoder.run_long`'s (None: as use_graph)."""
+        graph_slides: `IncrementalDecoder.run_long`'s (None: as use_graph).
+        allowed, return_allowed_mass: as in `generate_from_codes`, with allowed (B, nb * events_per_code, channels, vmax) or
+        (nb * events_per_code, channels, vmax) over the WHOLE code sequence in chorale coordinates, like the constraint: the sets
+        hold whichever window a position is emitted in, events outside [code_index_start, code_index_end) are ignored.
+        allowed_mass has the tokens' shape.  Results: (tokens[, logp][, allowed_mass][, attentions])."""
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
@@ -660,13 +747,19 @@ class Decoder(FlatTraining, nn.Module):
         chorale = self.init_generation_chorale(num_events=nb * epc, start_index=code_index_start * epc, pad=pad, start=start)
         if constraint is not None:
             constraint = self._constraint_rows(constraint, codes.shape[0], nb * epc, code_index_start * epc, code_index_end * epc)
+        if allowed is not None:
+            allowed = self._allowed_words(allowed, codes.shape[0], nb * epc, code_index_start * epc, code_index_end * epc,
+                                          exclude=exclude, constraint=constraint)
         if num_decodings > 1:
             codes = codes.repeat_interleave(num_decodings, dim=0)
             if constraint is not None:
                 constraint = constraint.repeat_interleave(num_decodings, dim=0)
+            if allowed is not None and allowed.shape[0] > 1:
+                allowed = allowed.repeat_interleave(num_decodings, dim=0)
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
         logp = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_logp else None
+        mass = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_allowed_mass else None
         maps = None
         if layers is not None:
             self._check_attention_bytes(B, layers, nb * U, False, max_attention_bytes)
@@ -678,10 +771,13 @@ class Decoder(FlatTraining, nn.Module):
             inc.start_long(codes[rows], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[rows], temperature=temperature,
                            top_k=top_k, top_p=top_p, exclude=exclude,
                            constraint=None if constraint is None else constraint[rows], want_logp=return_logp,
-                           want_attentions=layers)
+                           want_attentions=layers, allowed=self._allowed_rows(allowed, n, rows),
+                           want_allowed_mass=return_allowed_mass)
             tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph, graph_slides=graph_slides)
             if return_logp:
                 logp[rows] = inc.logp
+            if return_allowed_mass:
+                mass[rows] = inc.logmass
             if maps is not None:
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
@@ -689,6 +785,8 @@ class Decoder(FlatTraining, nn.Module):
         out = generate_in_chunks(self, B, nb * U, chunk)
         cut = lambda t: t.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
         res = (cut(out), cut(logp)) if return_logp else (cut(out),)
+        if return_allowed_mass:
+            res += (cut(mass),)
         if maps is not None:
             res += (self._join_attention_chunks(maps),)
         return res if len(res) > 1 else res[0]
@@ -696,7 +794,8 @@ class Decoder(FlatTraining, nn.Module):
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent
         tensors, concatenated along time) decoded as one sequence, the body's events returned: int64 (num_decodings, events,
-        channels).  kwargs go to `generate_from_code_long`."""
+        channels).  kwargs go to `generate_from_code_long` -- `allowed` and `return_allowed_mass` among them, in the coordinates
+        of the whole start + body + end sequence."""
         if start_codes is None or end_codes is None or body_codes is None or temperature is None:
             raise NotImplementedError('generate_alla_mano(start_codes, end_codes, body_codes, temperature): generation '
                                       'without codes is not implemented')
@@ -713,7 +812,7 @@ class Decoder(FlatTraining, nn.Module):
                                             code_index_end=len(start_codes) + len(body_codes), **kwargs)
 
     def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False,
-                           keep_voices=None, return_logp=False, **kwargs):
+                           keep_voices=None, return_logp=False, allowed=None, return_allowed_mass=False, **kwargs):
         """The body of generate_reharmonisation (:871-941) on a (1, events, channels) token tensor: the chorale is cut into
         model-sized chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD),
         every chunk is encoded, the codes are glued and the chorale's own codes are decoded `num_reharmonisations` times.
@@ -723,7 +822,11 @@ class Decoder(FlatTraining, nn.Module):
         keep_voices: voice indices whose tokens are forced to x's -- harmonising a given melody is keep_voices=(0,).  Event
         e of x sits at chorale event E + e (after the PAD...START chunk); everything else, the END / PAD completion
         included, stays free, so events [0, x.shape[1]) of the kept voices come back equal to x.  return_logp=True: `tokens`
-        above is the pair (tokens, logp) of `generate_from_code_long`."""
+        above is the pair (tokens, logp) of `generate_from_code_long`.
+        allowed: bool (x.shape[1], channels, vmax) or (1, x.shape[1], channels, vmax), the token sets of `generate_from_codes` in
+        x's OWN event coordinates (what `templates.rhythm_mask(x, kinds)` returns): event e of x restricts chorale event E + e,
+        every other event stays unrestricted.  return_allowed_mass=True: `tokens` above is the tuple of
+        `generate_from_code_long`, (tokens[, logp], allowed_mass)."""
         n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
         if n2i is None:
             raise ValueError('reharmonise_tokens needs dataset.note2index_dicts with the START / END / XX symbols')
@@ -765,6 +868,17 @@ class Decoder(FlatTraining, nn.Module):
             constraint = torch.full((1, codes.size(1) * self.num_events_per_code, nc), -1, dtype=torch.int64)
             constraint[:, E:E + x.shape[1]] = kept
             kwargs['constraint'] = constraint
+        if allowed is not None:
+            allowed = torch.as_tensor(allowed)
+            if allowed.dtype != torch.bool or allowed.dim() not in (3, 4) or allowed.shape[-3:-1] != (x.shape[1], nc) or \
+                    (allowed.dim() == 4 and allowed.shape[0] != 1):
+                raise ValueError(f'allowed: bool ({x.shape[1]}, {nc}, vmax) in x\'s event coordinates expected, got '
+                                 f'{tuple(allowed.shape)} {allowed.dtype}')
+            whole = torch.ones(codes.size(1) * self.num_events_per_code, nc, allowed.shape[-1], dtype=torch.bool,
+                               device=allowed.device)
+            whole[E:E + x.shape[1]] = allowed.reshape(x.shape[1], nc, -1)
+            kwargs['allowed'] = whole
+        kwargs['return_allowed_mass'] = return_allowed_mass
         tokens = self.generate_from_code_long(codes, temperature=temperature, top_k=top_k, top_p=top_p,
                                               num_decodings=num_reharmonisations, code_index_start=code_index_start,
                                               code_index_end=code_index_end, return_logp=return_logp, **kwargs)

@@ -13,6 +13,9 @@ this module adds what the decoder has on top of it:
   constraint or token scores (`start(constraint=..., want_logp=...)`) the sampler is vqcpc_decode_sample_constrained: the same
   kernel body, which emits the given token where the constraint holds one and writes the emitted token's log-probability; it
   reads both at the position's CHORALE column through the device window index, so nothing else of the step or slide changes.
+  With a per-position token set or its mass (`start(allowed=..., want_allowed_mass=...)`) the sampler is
+  vqcpc_decode_sample_masked, one more flag on the same body: the packed sets (M, width, 8) and the mass (M, width) live in
+  the stack's own buffers and are read / written at that same column, so again nothing else changes.
   Attention maps (`start(want_attentions=layers)`): the listed layers' self- and cross-attention launches are
   vqcpc_decode_attn_probs, which also stores the row of probabilities of the emitted token into `self_probs` / `cross_probs` at
   the row of the position's chorale coordinate (the same window index); the encoder's maps of the prefill are kept as `enc_probs`.
@@ -86,6 +89,7 @@ class IncrementalDecoder(IncrementalStack):
         self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
         self.memkv = None
         self.constraint, self.logp, self.constrained = None, None, False
+        self.allowed, self.logmass, self.masked = None, None, False
         self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
         self.continuous = bool(getattr(dec, 'continuous_source', False))
         if self.continuous:
@@ -136,7 +140,7 @@ class IncrementalDecoder(IncrementalStack):
             ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:], out=kv)
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
-              constraint=None, want_logp=False, want_attentions=None):
+              constraint=None, want_logp=False, want_attentions=None, allowed=None, want_allowed_mass=False):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
         probabilities of the last step in `probs` (M, max V_c).
@@ -145,7 +149,11 @@ class IncrementalDecoder(IncrementalStack):
         emitted yet.  Either one switches the step's sampler to vqcpc_decode_sample_constrained.
         want_attentions: None, or a sorted tuple of decoder-layer indices whose attention rows are kept for every emitted token:
         `self_probs` (layers, M, H, T, T) and `cross_probs` (layers, M, H, T, S; None for the diagonal decoder), float32, NaN
-        where no token was emitted yet.  Those layers' attention launches become vqcpc_decode_attn_probs."""
+        where no token was emitted yet.  Those layers' attention launches become vqcpc_decode_attn_probs.
+        allowed: (M, T, 8) int32, per (row, position) the 256-bit set of the tokens that may be drawn (bit i & 31 of word i >> 5;
+        the caller has checked that every set has a token of its voice); want_allowed_mass: keep in `logmass` (M, T) float32
+        the log of the probability the unfiltered distribution gives to the position's set, NaN where no token was emitted yet.
+        Either one switches the step's sampler to vqcpc_decode_sample_masked."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
@@ -163,6 +171,7 @@ class IncrementalDecoder(IncrementalStack):
             self.teacher = None
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
         self._constrain(constraint, want_logp, self.T, None)
+        self._mask(allowed, want_allowed_mass, self.T)
         self._record_attentions(want_attentions, self.T, None, 1)
         self.reset()
 
@@ -180,6 +189,21 @@ class IncrementalDecoder(IncrementalStack):
         self.logp = torch.full((self.M, width), float('nan'), dtype=torch.float32, device=self.dev) if want_logp else None
         self.constrained = constraint is not None or want_logp
         self._cons_width, self._cons_win = width, win
+
+    def _mask(self, allowed, want_mass, width):
+        """The masked sampler's buffers, addressed like the constrained sampler's: the packed sets are COPIED into a buffer of
+        this stack, (M, width, 8) int32, so a captured step or slide reads every window's sets through the window index."""
+        if (allowed is not None or want_mass) and self.teacher is not None:
+            raise ValueError('allowed / want_allowed_mass and teacher exclude each other')
+        self.allowed = None
+        if allowed is not None:
+            if tuple(allowed.shape) != (self.M, width, 8) or allowed.dtype != torch.int32:
+                raise ValueError(f'allowed: packed sets ({self.M}, {width}, 8) int32 expected, got {tuple(allowed.shape)} '
+                                 f'{allowed.dtype}')
+            self.allowed = torch.empty(self.M, width, 8, dtype=torch.int32, device=self.dev)
+            self.allowed.copy_(allowed)
+        self.logmass = torch.full((self.M, width), float('nan'), dtype=torch.float32, device=self.dev) if want_mass else None
+        self.masked = allowed is not None or bool(want_mass)
 
     def _record_attentions(self, layers, rows, win, stride):
         """The attention-map buffers, allocated here once (before any warm-up step: a captured step holds their addresses):
@@ -210,6 +234,8 @@ class IncrementalDecoder(IncrementalStack):
     def _forget_logp(self):
         if self.logp is not None:
             self.logp.fill_(float('nan'))                                               # what a warm-up step wrote
+        if self.logmass is not None:
+            self.logmass.fill_(float('nan'))
         for maps in (self.self_probs, self.cross_probs):
             if maps is not None:
                 maps.fill_(float('nan'))
@@ -239,6 +265,13 @@ class IncrementalDecoder(IncrementalStack):
 
     def _sample(self):
         T, d = self.T, self.d
+        if self.masked:
+            w = self._cons_width
+            hip.call('vqcpc_decode_sample_masked', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M,
+                     self.temperature, self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds,
+                     self.constraint, w, self.logp, w, self._cons_win, self.allowed, w, self.logmass, w, self.tokens, T, T,
+                     self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
+            return
         if self.constrained:
             w = self._cons_width
             hip.call('vqcpc_decode_sample_constrained', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M,
@@ -269,13 +302,16 @@ class IncrementalDecoder(IncrementalStack):
 
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
-    def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, **sampling):
+    def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, allowed=None,
+                   want_allowed_mass=False, **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
         tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
         want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
         live window's chorale column (the device window index), so the captured step and slide serve every window.
         want_attentions: as in `start`, with `self_probs` (layers, M, H, nb * U, T) and `cross_probs` (layers, M, H, nb * U, S):
         the row is the emitted token's chorale position, its keys are those of the window it was emitted in.
+        allowed, want_allowed_mass: as in `start`, but (M, nb * U, 8) / `logmass` (M, nb * U), in chorale coordinates like the
+        constraint.
         sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
@@ -300,6 +336,7 @@ class IncrementalDecoder(IncrementalStack):
             self.z_full, self.z_nb = z_full, nb
         self.start(seeds=seeds, **sampling)
         self._constrain(constraint, want_logp, nb * U, self.win)
+        self._mask(allowed, want_allowed_mass, nb * U)
         self._record_attentions(want_attentions, nb * U, self.win, U)
         self.row_seeds.copy_(self.seeds)
 

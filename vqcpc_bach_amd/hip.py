@@ -215,6 +215,9 @@ SIGNATURES = {
     'vqcpc_decode_sample_constrained': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_i64,
                                                 c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64,
                                                 c_ptr, c_i64, c_ptr, c_ptr]),
+    'vqcpc_decode_sample_masked': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_i64,
+                                           c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64,
+                                           c_int, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
     'vqcpc_decode_prefill_attn': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64,
                                           c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     'vqcpc_decode_window': (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_ptr,
