@@ -385,6 +385,7 @@ int vqcpc_relattn_tab_bwd(const float* d_ctx, int64_t ldo, const float* table, i
  *   q [n_seq*Lq][ldq], k [n_seq*Lk][ldk], v [n_seq*Lk][ldv] (head h = columns [h*hd, (h+1)*hd), q UNSCALED),
  *   e1, e2 [H*Lk][hd], ctx [n_seq*Lq][ldo], probs [n_seq][H][Lq][Lk] = softmax BEFORE dropout,
  *   dropout element index = ((seq*H + h)*Lq + i)*Lk + j.   Lk <= 1024, hd in {16, 32, 64, 128}.
+ * q, k, v, d_ctx, e1 and e2 are 16-byte aligned and ldq, ldk, ldv, ldo multiples of 4 (rows are loaded as float4).
  * Key tiles a strip of queries cannot see under the mask are skipped (half of the causal self-attention).
  * bwd: same mask as fwd; d_q / d_k / d_v written in full (same layouts, own leading dimensions), d_e1 / d_e2 overwritten. */
 int vqcpc_relattn_x_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,

@@ -291,9 +291,23 @@ __global__ __launch_bounds__(64 * NW) void relattn_x_bwd_dq_kernel(
         const int j = 32 * jt + l31;
         float vb[KH];
         xload_row<KH>(vb, vbase + (int64_t)min(j, Lk - 1) * ldv + g * KH, j < Lk, 1.0f);
+        // HD >= 64: two accumulators (even / odd steps), added at the end.  dS = P (dP - rowsum) cancels, so the rounding of dP is
+        // what the relative error of a dS entry -- and of every dq / dk / dE element made of one or two of them -- consists of:
+        // no chain longer than 32 steps, and two independent MFMA chains instead of one dependent one.  (No more registers, same
+        // occupancy at HD = 64 / 128; at HD = 16 / 32 the chain is 8 / 16 steps and a second accumulator would cost a wave.)
         floatx16 acc = {0};
+        if constexpr (KH > 16) {
+            floatx16 acc1 = {0};
 #pragma unroll
-        for (int s = 0; s < KH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(doa[s], vb[s], acc, 0, 0, 0);
+            for (int s = 0; s < KH; s += 2) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(doa[s], vb[s], acc, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(doa[s + 1], vb[s + 1], acc1, 0, 0, 0);
+            }
+            acc += acc1;
+        } else {
+#pragma unroll
+            for (int s = 0; s < KH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(doa[s], vb[s], acc, 0, 0, 0);
+        }
         // P of the tile: 16 loads issued back to back (clamped addresses; `* okf` instead of a select keeps the compiler
         // from sinking each load behind its own branch, which serialises load -> wait -> use per element)
         float pl[16];
@@ -658,6 +672,8 @@ int vqcpc_relattn_x_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk
     VQ_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldq >= H * hd && ldk >= H * hd &&
                    ldv >= H * hd && ldo >= H * hd && n_seq >= 0 && aligned16(q) && aligned16(k) && aligned16(v),
                "relattn_x_fwd: bad strides / alignment");
+    // the band GEMM loads rows of e1 / e2 as float4 (xload_row on xerel_row; hd % 4 == 0 keeps every row aligned with its table)
+    VQ_REQUIRE(aligned16(e1) && aligned16(e2), "relattn_x_fwd: e1 / e2 must be 16-byte aligned");
     VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn_x_fwd: bad dropout probability");
     hipStream_t s = (hipStream_t)stream;
 #define CALL(DD) x_fwd_t<DD>(q, ldq, k, ldk, v, ldv, e1, e2, ctx, ldo, probs, n_seq, Lq, Lk, H, mask, drop_p, seed, s)
@@ -688,6 +704,8 @@ int vqcpc_relattn_x_bwd(const float* d_ctx, int64_t ldo, const float* q, int64_t
                    ldv >= H * hd && ldo >= H * hd && ldgq >= H * hd && ldgk >= H * hd && ldgv >= H * hd && n_seq >= 1 &&
                    aligned16(d_ctx) && aligned16(k) && aligned16(v),
                "relattn_x_bwd: bad strides / alignment");
+    // the backward kernels read e1 / e2 element by element; the requirement is the forward's, on the same tables
+    VQ_REQUIRE(aligned16(e1) && aligned16(e2), "relattn_x_bwd: e1 / e2 must be 16-byte aligned");
     VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn_x_bwd: bad dropout probability");
     if (workspace_bytes < vqcpc_relattn_x_bwd_workspace(n_seq, Lq, Lk, H, hd)) {
         set_error("relattn_x_bwd: workspace too small");
