@@ -981,6 +981,36 @@ def test_relattn_table_indirection_is_bit_identical_to_gathered_qkv(ops, n, L, H
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize('hd', [16, 32])
+def test_relattn16_b16_table_indirection_is_bit_identical_to_gathered_qkv(ops, hd):
+    """The same with bf16 outputs: vqcpc_relattn16_fwd_b16 / _bwd_b16 with `tokens` == the same calls on the gathered q | k | v, all
+    five outputs bit for bit.  5 blocks x 2 heads = 10 problems over waves of 4: a ragged last group."""
+    from vqcpc_bach_amd import hip
+    n, L, H, p, vmax, seed = 5, 16, 2, 0.1, 7, 99
+    gen = torch.Generator().manual_seed(n + hd)
+    d = H * hd
+    table = torch.randn(vmax * L, 3 * d, generator=gen).cuda()
+    tokens = torch.randint(0, vmax, (n * L,), generator=gen).cuda()
+    e1, e2 = torch.randn(H * L, hd, generator=gen).cuda(), torch.randn(H * L, hd, generator=gen).cuda()
+    dctx = torch.randn(n * L, d, generator=gen).cuda()
+    qkv = ops.BlockTableGatherFn.apply(table, tokens, L)
+    nbytes = hip.query('vqcpc_relattn_bwd_workspace', n, L, H, hd)
+    outs = []
+    for src, tok in ((qkv, None), (table, tokens)):
+        ctx = torch.empty(n * L, d, dtype=torch.bfloat16, device='cuda')
+        probs = torch.empty(n, H, L, L, device='cuda')
+        dqkv = torch.empty(n * L, 3 * d, dtype=torch.bfloat16, device='cuda')
+        de1, de2 = torch.empty_like(e1), torch.empty_like(e2)
+        ws = hip.workspace(nbytes, 'cuda')
+        hip.call('vqcpc_relattn16_fwd_b16', src, 3 * d, tok, e1, e2, ctx, d, probs, n, H, hd, p, seed)
+        hip.call('vqcpc_relattn16_bwd_b16', dctx, d, src, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, n, H, hd, p, seed, ws,
+                 nbytes)
+        outs.append((ctx, probs, dqkv, de1, de2))
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+    assert float(outs[0][0].float().abs().max()) > 0 and float(outs[0][2].float().abs().max()) > 0
+
+
 def _relattn_case(ops, n, L, H, hd, p):
     from vqcpc_bach_amd import hip
     gen = torch.Generator().manual_seed(n + L + H)

@@ -49,7 +49,8 @@ def build(force=False, verbose=True, lab=None):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'gemm_forms.h'),
-               os.path.join(CSRC, 'prior_kernels.h'), os.path.join(HERE, '..', 'include', 'vqcpc.h')]
+               os.path.join(CSRC, 'relattn_forms.h'), os.path.join(CSRC, 'prior_kernels.h'),
+               os.path.join(HERE, '..', 'include', 'vqcpc.h')]
     hdr_m = max(os.path.getmtime(h) for h in headers)
     objs, jobs = [], []
     for src in SOURCES:

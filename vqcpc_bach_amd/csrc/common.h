@@ -148,23 +148,13 @@ __device__ __forceinline__ void store1_out(float* __restrict__ base, int64_t off
 }
 #endif
 
-// L = 16 attention on the fp32 matrix cores (relattn16.hip); tokens != nullptr = block-table indirection
-bool relattn16_supported(int H, int hd);
+// L = 16 attention on the matrix cores (relattn16.hip); tokens != nullptr = block-table indirection; io = the IN16 / OUT16 bits of
+// relattn_forms.h: which of the untyped buffers hold bf16 elements
 int64_t relattn16_bwd_workspace(int64_t n_blocks, int H, int hd);
-int relattn16_fwd(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, float* ctx,
-                  int64_t ldo, float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s);
-int relattn16_bwd(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const int64_t* tokens, const float* probs,
-                  const float* e1, const float* e2, float* d_qkv, int64_t ldg, float* ws, int64_t n_blocks, int H, int hd,
-                  float drop_p, uint64_t seed, hipStream_t s, int* nsplit);
-int relattn16_fwd_b16(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, void* ctx_b16,
-                      int64_t ldo, float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s);
-int relattn16_bwd_b16(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const int64_t* tokens, const float* probs,
-                      const float* e1, const float* e2, void* d_qkv_b16, int64_t ldg, float* ws, int64_t n_blocks, int H, int hd,
-                      float drop_p, uint64_t seed, hipStream_t s, int* nsplit);
-int relattn16_fwd_b16io(const void* qkv_b16, int64_t ldq, const float* e1, const float* e2, void* ctx_b16, int64_t ldo,
-                        float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s);
-int relattn16_bwd_b16io(const void* d_ctx_b16, int64_t ldo, const void* qkv_b16, int64_t ldq, const float* probs,
-                        const float* e1, const float* e2, void* d_qkv_b16, int64_t ldg, float* ws, int64_t n_blocks, int H,
-                        int hd, float drop_p, uint64_t seed, hipStream_t s, int* nsplit);
+int relattn16_fwd(const void* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, void* ctx, int64_t ldo,
+                  float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s, int io);
+int relattn16_bwd(const void* d_ctx, int64_t ldo, const void* qkv, int64_t ldq, const int64_t* tokens, const float* probs,
+                  const float* e1, const float* e2, void* d_qkv, int64_t ldg, float* ws, int64_t n_blocks, int H, int hd,
+                  float drop_p, uint64_t seed, hipStream_t s, int* nsplit, int io);
 
 }  // namespace vq

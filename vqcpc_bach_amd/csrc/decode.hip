@@ -823,35 +823,52 @@ int vqcpc_decode_attn_probs(const float* q, int64_t ldq, float* k_cache, float* 
                               ratio, H, hd, mask, true, probs, ldp, rows, win, win_stride, stream);
 }
 
-int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
-                        int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
-                        int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,
-                        int U, float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream) {
+// the three sampler entry points share their checks and their launch in the same way.  cons: the constrained forms -- `fixed` is the
+// constraint (the plain form's teacher tokens otherwise) and seeds are required; mask: allowed / logmass on top of that
+static int decode_sample_launch(const char* name, bool cons, bool mask, const float* logits, int64_t ldl, const int32_t* voice_offsets,
+                                int nc, int64_t M, float temperature, int top_k, float top_p, const uint32_t* exclude,
+                                const int64_t* seeds, const int64_t* fixed, int64_t ldfixed, float* logp, int64_t ldlogp,
+                                const int32_t* win, const uint32_t* allowed, int64_t ldallow, float* logmass, int64_t ldmass,
+                                int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d, int U,
+                                float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream) {
     VQ_REQUIRE(logits && voice_offsets && tokens && table && next_in && pos && nc >= 1 && nc <= kDecMaxVoices && M >= 1 &&
                M <= kDecMaxRows && T >= 1 && d >= 1 && d <= kDecMaxDim && U >= 1 && table_rows >= 1,
-               "decode_sample: bad arguments (1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)");
-    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "decode_sample: temperature > 0, top_k >= 0");
-    VQ_REQUIRE(teacher || seeds, "decode_sample: seeds are needed unless the tokens are teacher-forced");
+               "%s: bad arguments (1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)", name);
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "%s: temperature > 0, top_k >= 0", name);
+    VQ_REQUIRE(seeds || (!cons && fixed), "%s: seeds are needed%s", name, cons ? "" : " unless the tokens are teacher-forced");
     VoiceOffsets vo;
     vo.off[0] = voice_offsets[0];
-    VQ_REQUIRE(vo.off[0] >= 0, "decode_sample: negative voice offset");
+    VQ_REQUIRE(vo.off[0] >= 0, "%s: negative voice offset", name);
     int vmax = 0;
     for (int c = 0; c < nc; ++c) {
         const int V = voice_offsets[c + 1] - voice_offsets[c];
-        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "decode_sample: voice %d has %d tokens (1 <= V_c <= 256)", c, V);
+        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "%s: voice %d has %d tokens (1 <= V_c <= 256)", name, c, V);
         vo.off[c + 1] = voice_offsets[c + 1];
         vmax = std::max(vmax, V);
     }
     for (int c = nc + 1; c <= kDecMaxVoices; ++c) vo.off[c] = vo.off[nc];
-    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!teacher || ldteach >= T) && (!probs || ldp >= vmax),
-               "decode_sample: bad leading dimensions");
-    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "decode_sample: the table has too few rows for V_c * U");
-    hipLaunchKernelGGL(decode_sample_kernel<false>, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc,
-                       (int)M, temperature, top_k, top_p, exclude, seeds, teacher, ldteach, tokens, ldtok, T, table, table_rows,
-                       d, U, next_in, ldn, probs, ldp, pos, (float*)nullptr, (int64_t)0, (const int32_t*)nullptr,
-                       (const uint32_t*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0);
-    VQ_CHECK_LAUNCH("decode_sample");
+    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!probs || ldp >= vmax), "%s: bad leading dimensions", name);
+    // the window index lives on the device: with win the host can only ask for one window's columns, and the kernel
+    // treats a column at or past the leading dimension as free / does not write it
+    VQ_REQUIRE((!fixed || ldfixed >= T) && (!logp || ldlogp >= T), "%s: bad leading dimensions (%s >= T)", name,
+               cons ? "ldcons, ldlogp" : "ldteach");
+    VQ_REQUIRE((!allowed || ldallow >= T) && (!logmass || ldmass >= T), "%s: bad leading dimensions (ldallow, ldmass >= T)", name);
+    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "%s: the table has too few rows for V_c * U", name);
+    const auto kern = mask ? decode_sample_kernel<true, true> : cons ? decode_sample_kernel<true> : decode_sample_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc, (int)M, temperature, top_k,
+                       top_p, exclude, seeds, fixed, ldfixed, tokens, ldtok, T, table, table_rows, d, U, next_in, ldn, probs, ldp, pos,
+                       logp, ldlogp, win, allowed, ldallow, logmass, ldmass);
+    VQ_CHECK_LAUNCH(name);
     return VQCPC_OK;
+}
+
+int vqcpc_decode_sample(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
+                        int top_k, float top_p, const uint32_t* exclude, const int64_t* seeds, const int64_t* teacher,
+                        int64_t ldteach, int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d,
+                        int U, float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream) {
+    return decode_sample_launch("decode_sample", false, false, logits, ldl, voice_offsets, nc, M, temperature, top_k, top_p, exclude,
+                                seeds, teacher, ldteach, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, tokens, ldtok, T, table,
+                                table_rows, d, U, next_in, ldn, probs, ldp, pos, stream);
 }
 
 int vqcpc_decode_sample_constrained(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M,
@@ -859,33 +876,9 @@ int vqcpc_decode_sample_constrained(const float* logits, int64_t ldl, const int3
                                     const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
                                     int64_t* tokens, int64_t ldtok, int T, const float* table, int64_t table_rows, int d, int U,
                                     float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, void* stream) {
-    VQ_REQUIRE(logits && voice_offsets && seeds && tokens && table && next_in && pos && nc >= 1 && nc <= kDecMaxVoices && M >= 1 &&
-               M <= kDecMaxRows && T >= 1 && d >= 1 && d <= kDecMaxDim && U >= 1 && table_rows >= 1,
-               "decode_sample_constrained: bad arguments (seeds needed, 1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)");
-    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "decode_sample_constrained: temperature > 0, top_k >= 0");
-    VoiceOffsets vo;
-    vo.off[0] = voice_offsets[0];
-    VQ_REQUIRE(vo.off[0] >= 0, "decode_sample_constrained: negative voice offset");
-    int vmax = 0;
-    for (int c = 0; c < nc; ++c) {
-        const int V = voice_offsets[c + 1] - voice_offsets[c];
-        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "decode_sample_constrained: voice %d has %d tokens (1 <= V_c <= 256)", c, V);
-        vo.off[c + 1] = voice_offsets[c + 1];
-        vmax = std::max(vmax, V);
-    }
-    for (int c = nc + 1; c <= kDecMaxVoices; ++c) vo.off[c] = vo.off[nc];
-    // the window index lives on the device: with win the host can only ask for one window's columns, and the kernel
-    // treats a column at or past the leading dimension as free / does not write it
-    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!constraint || ldcons >= T) && (!logp || ldlogp >= T) &&
-               (!probs || ldp >= vmax), "decode_sample_constrained: bad leading dimensions (ldcons, ldlogp >= T)");
-    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows,
-               "decode_sample_constrained: the table has too few rows for V_c * U");
-    hipLaunchKernelGGL(decode_sample_kernel<true>, dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo, nc,
-                       (int)M, temperature, top_k, top_p, exclude, seeds, constraint, ldcons, tokens, ldtok, T, table,
-                       table_rows, d, U, next_in, ldn, probs, ldp, pos, logp, ldlogp, win, (const uint32_t*)nullptr, (int64_t)0,
-                       (float*)nullptr, (int64_t)0);
-    VQ_CHECK_LAUNCH("decode_sample_constrained");
-    return VQCPC_OK;
+    return decode_sample_launch("decode_sample_constrained", true, false, logits, ldl, voice_offsets, nc, M, temperature, top_k, top_p,
+                                exclude, seeds, constraint, ldcons, logp, ldlogp, win, nullptr, 0, nullptr, 0, tokens, ldtok, T, table,
+                                table_rows, d, U, next_in, ldn, probs, ldp, pos, stream);
 }
 
 int vqcpc_decode_sample_masked(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, float temperature,
@@ -894,32 +887,9 @@ int vqcpc_decode_sample_masked(const float* logits, int64_t ldl, const int32_t* 
                                int64_t ldallow, float* logmass, int64_t ldmass, int64_t* tokens, int64_t ldtok, int T,
                                const float* table, int64_t table_rows, int d, int U, float* next_in, int64_t ldn, float* probs,
                                int64_t ldp, int32_t* pos, void* stream) {
-    VQ_REQUIRE(logits && voice_offsets && seeds && tokens && table && next_in && pos && nc >= 1 && nc <= kDecMaxVoices && M >= 1 &&
-               M <= kDecMaxRows && T >= 1 && d >= 1 && d <= kDecMaxDim && U >= 1 && table_rows >= 1,
-               "decode_sample_masked: bad arguments (seeds needed, 1 <= M <= 64, 1 <= nc <= 16, 1 <= d <= 4096)");
-    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "decode_sample_masked: temperature > 0, top_k >= 0");
-    VoiceOffsets vo;
-    vo.off[0] = voice_offsets[0];
-    VQ_REQUIRE(vo.off[0] >= 0, "decode_sample_masked: negative voice offset");
-    int vmax = 0;
-    for (int c = 0; c < nc; ++c) {
-        const int V = voice_offsets[c + 1] - voice_offsets[c];
-        VQ_REQUIRE(V >= 1 && V <= kDecMaxVocab, "decode_sample_masked: voice %d has %d tokens (1 <= V_c <= 256)", c, V);
-        vo.off[c + 1] = voice_offsets[c + 1];
-        vmax = std::max(vmax, V);
-    }
-    for (int c = nc + 1; c <= kDecMaxVoices; ++c) vo.off[c] = vo.off[nc];
-    // as in the constrained entry point, the host can only ask for one window's columns
-    VQ_REQUIRE(ldl >= vo.off[nc] && ldtok >= T && ldn >= d && (!constraint || ldcons >= T) && (!logp || ldlogp >= T) &&
-               (!probs || ldp >= vmax), "decode_sample_masked: bad leading dimensions (ldcons, ldlogp >= T)");
-    VQ_REQUIRE((!allowed || ldallow >= T) && (!logmass || ldmass >= T),
-               "decode_sample_masked: bad leading dimensions (ldallow, ldmass >= T)");
-    VQ_REQUIRE((int64_t)(vmax - 1) * U + (U - 1) < table_rows, "decode_sample_masked: the table has too few rows for V_c * U");
-    hipLaunchKernelGGL((decode_sample_kernel<true, true>), dim3(1), dim3(64 * kSampWaves), 0, (hipStream_t)stream, logits, ldl, vo,
-                       nc, (int)M, temperature, top_k, top_p, exclude, seeds, constraint, ldcons, tokens, ldtok, T, table,
-                       table_rows, d, U, next_in, ldn, probs, ldp, pos, logp, ldlogp, win, allowed, ldallow, logmass, ldmass);
-    VQ_CHECK_LAUNCH("decode_sample_masked");
-    return VQCPC_OK;
+    return decode_sample_launch("decode_sample_masked", true, true, logits, ldl, voice_offsets, nc, M, temperature, top_k, top_p,
+                                exclude, seeds, constraint, ldcons, logp, ldlogp, win, allowed, ldallow, logmass, ldmass, tokens,
+                                ldtok, T, table, table_rows, d, U, next_in, ldn, probs, ldp, pos, stream);
 }
 
 int vqcpc_decode_prefill_attn(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldk, float* k_cache,

@@ -9,6 +9,7 @@
 // f32 MFMA runs at the f32 VALU rate on gfx950, and the tile is 16x16x32, so this kernel is plain VALU + LDS and is
 // bound by HBM traffic (q, k, v in; ctx, probs out).
 #include "common.h"
+#include "relattn_forms.h"
 #include <stdlib.h>
 
 namespace vq {
@@ -421,7 +422,7 @@ static int att_blocks_per_wg(int64_t n_blocks, int slots, int H) {
 template <int L, int HD>
 static int launch_fwd(const float* qkv, int64_t ldq, const float* e1, const float* e2, float* ctx, int64_t ldo,
                       float* probs, int64_t n_blocks, int H, float drop_p, uint64_t seed, hipStream_t s,
-                      const int64_t* tokens = nullptr, int o16 = 0) {
+                      const int64_t* tokens, int o16) {
     using C = AttCfg<L, HD>;
     const size_t lds = (size_t)C::SLOTS * C::FWD_FLOATS * sizeof(float);
     auto kern = relattn_fwd_kernel<L, HD>;
@@ -441,7 +442,7 @@ static int launch_fwd(const float* qkv, int64_t ldq, const float* e1, const floa
 template <int L, int HD>
 static int launch_bwd(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const float* probs, const float* e1,
                       const float* e2, float* d_qkv, int64_t ldg, float* d_e1, float* d_e2, int64_t n_blocks, int H,
-                      float drop_p, uint64_t seed, float* ws, hipStream_t s, const int64_t* tokens = nullptr, int g16 = 0) {
+                      float drop_p, uint64_t seed, float* ws, hipStream_t s, const int64_t* tokens, int g16) {
     using C = AttCfg<L, HD>;
     const size_t lds = (size_t)C::SLOTS * C::BWD_FLOATS * sizeof(float);
     auto kern = relattn_bwd_kernel<L, HD>;
@@ -464,19 +465,12 @@ static int launch_bwd(const float* d_ctx, int64_t ldo, const float* qkv, int64_t
 
 static int g_force_general = 0;   // tests: route L = 16 / 4 through the general-L kernels too
 // L = 16 runs on the matrix cores (relattn16.hip); VQCPC_RELATTN16_LDS=1 keeps the LDS-tiled VALU kernels (A/B, tests)
-static bool use_mfma16(int L, int H, int hd) {
-    static const bool lds_only = lab_env_int("VQCPC_RELATTN16_LDS", 0) != 0;
-    return L == 16 && !lds_only && relattn16_supported(H, hd);
+static bool lds_only() {
+    static const bool on = lab_env_int("VQCPC_RELATTN16_LDS", 0) != 0;
+    return on;
 }
-static int finish_de16(float* ws, int nsplit, int H, int hd, float* d_e1, float* d_e2, hipStream_t s);
-
-static bool att_supported(int L, int H, int hd) {
-    if (g_force_general) return false;
-    if (!(L == 16 || L == 4)) return false;
-    if (!(hd == 16 || hd == 32 || hd == 64)) return false;
-    const int slots = 4 * (64 / (4 * L));
-    return H >= 1 && ((slots % H) == 0 || (H % slots) == 0);
-}
+static bool use_mfma16(int L, int H, int hd) { return att_mfma16_ok(L, H, hd, lds_only()); }
+static bool att_supported(int L, int H, int hd) { return !g_force_general && att_lds_ok(L, H, hd); }
 
 static int finish_de16(float* ws, int nsplit, int H, int hd, float* d_e1, float* d_e2, hipStream_t s) {
     const int total = H * 31 * hd;
@@ -488,21 +482,88 @@ static int finish_de16(float* ws, int nsplit, int H, int hd, float* d_e1, float*
     return VQCPC_OK;
 }
 
+static AttRoute route_of(const AttEntry& e, int L, int H, int hd, const int64_t* tokens, const void* qkv, const void* e1,
+                         const void* e2, const void* out, const void* d_ctx = nullptr, const void* ws = nullptr) {
+    const unsigned aligned = (aligned16(qkv) ? P_QKV : 0) | (aligned16(e1) ? P_E1 : 0) | (aligned16(e2) ? P_E2 : 0) |
+                             (aligned16(out) ? P_OUT : 0) | (aligned16(d_ctx) ? P_DCTX : 0) | (aligned16(ws) ? P_WS : 0);
+    return att_route(e, L, H, hd, g_force_general != 0, lds_only(), aligned, tokens != nullptr);
+}
+
+// The forward of every self-attention entry point (`family`: ATT_F32 .. ATT_TAB of relattn_forms.h): each check once, the kernel
+// from att_route().  Untyped buffers hold what the entry's io bits say; `tokens` is NULL where the entry takes none, L 16 likewise.
+static int self_fwd(int family, const void* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, void* ctx,
+                    int64_t ldo, float* probs, int64_t n_blocks, int L, int H, int hd, float drop_p, uint64_t seed, void* stream) {
+    const AttEntry& e = kAttEntries[2 * family];
+    if (n_blocks == 0) return VQCPC_OK;
+    VQ_REQUIRE(qkv && e1 && e2 && ctx && probs, "%s: null pointer", e.name);
+    VQ_REQUIRE(ldq % (e.io & IN16 ? 8 : 4) == 0 && ldo % 4 == 0 && ldq >= 3 * H * hd && ldo >= H * hd && n_blocks >= 0,
+               "%s: bad strides", e.name);
+    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: bad dropout probability", e.name);
+    const AttRoute r = route_of(e, L, H, hd, tokens, qkv, e1, e2, ctx);
+    VQ_REQUIRE(r.kernel != ATT_REFUSED, "%s: %s L=%d H=%d hd=%d", e.name, r.why, L, H, hd);
+    hipStream_t s = (hipStream_t)stream;
+    if (r.kernel == ATT_STRIP) {
+        // any other L: the strip kernels of relattn_x.hip with Lq = Lk, no mask, q | k | v = column blocks of qkv
+        VQ_REQUIRE(n_blocks * H * (int64_t)((L + 31) / 32) < (1ll << 31), "%s: too many strips", e.name);
+        const float* q = (const float*)qkv;
+        const int d = H * hd;
+        return vqcpc_relattn_x_fwd(q, ldq, q + d, ldq, q + 2 * d, ldq, e1, e2, (float*)ctx, ldo, probs, n_blocks, L, L, H, hd, 0,
+                                   drop_p, seed, stream);
+    }
+    if (r.kernel == ATT_MFMA16) return relattn16_fwd(qkv, ldq, tokens, e1, e2, ctx, ldo, probs, n_blocks, H, hd, drop_p, seed, s, e.io);
+    int rc = VQCPC_EINVAL;
+    dispatch(AttLdsForms{}, L, hd, [&](auto f) {
+        rc = launch_fwd<decltype(f)::a, decltype(f)::b>((const float*)qkv, ldq, e1, e2, (float*)ctx, ldo, probs, n_blocks, H, drop_p,
+                                                        seed, s, tokens, (e.io & OUT16) ? 1 : 0);
+    });
+    return rc;
+}
+
+// ... and the backward.  No check of drop_p here: no backward entry point ever had one (relattn_forms.h).
+static int self_bwd(int family, const void* d_ctx, int64_t ldo, const void* qkv, int64_t ldq, const int64_t* tokens,
+                    const float* probs, const float* e1, const float* e2, void* d_qkv, int64_t ldg, float* d_e1, float* d_e2,
+                    int64_t n_blocks, int L, int H, int hd, float drop_p, uint64_t seed, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+    const AttEntry& e = kAttEntries[2 * family + 1];
+    const int in = e.io & IN16 ? 8 : 4;
+    VQ_REQUIRE(d_ctx && qkv && probs && e1 && e2 && d_qkv && d_e1 && d_e2 && workspace, "%s: null pointer", e.name);
+    VQ_REQUIRE(ldq % in == 0 && ldo % in == 0 && ldg % 4 == 0 && ldq >= 3 * H * hd && ldg >= 3 * H * hd && ldo >= H * hd &&
+                   n_blocks >= 1,
+               "%s: bad strides", e.name);
+    const AttRoute r = route_of(e, L, H, hd, tokens, qkv, e1, e2, d_qkv, d_ctx, workspace);
+    VQ_REQUIRE(r.kernel != ATT_REFUSED, "%s: %s L=%d H=%d hd=%d", e.name, r.why, L, H, hd);
+    if (workspace_bytes < vqcpc_relattn_bwd_workspace(n_blocks, L, H, hd)) {
+        set_error("%s: workspace too small", e.name);
+        return VQCPC_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    if (r.kernel == ATT_STRIP) {
+        const float* q = (const float*)qkv;
+        float* g = (float*)d_qkv;
+        const int d = H * hd;
+        return vqcpc_relattn_x_bwd((const float*)d_ctx, ldo, q, ldq, q + d, ldq, q + 2 * d, ldq, probs, e1, e2, g, ldg, g + d, ldg,
+                                   g + 2 * d, ldg, d_e1, d_e2, n_blocks, L, L, H, hd, 0, drop_p, seed, workspace, workspace_bytes,
+                                   stream);
+    }
+    if (r.kernel == ATT_MFMA16) {
+        int nsplit = 0;
+        int rc = relattn16_bwd(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, d_qkv, ldg, ws, n_blocks, H, hd, drop_p, seed, s, &nsplit,
+                               e.io);
+        return rc ? rc : finish_de16(ws, nsplit, H, hd, d_e1, d_e2, s);
+    }
+    int rc = VQCPC_EINVAL;
+    dispatch(AttLdsForms{}, L, hd, [&](auto f) {
+        rc = launch_bwd<decltype(f)::a, decltype(f)::b>((const float*)d_ctx, ldo, (const float*)qkv, ldq, probs, e1, e2, (float*)d_qkv,
+                                                        ldg, d_e1, d_e2, n_blocks, H, drop_p, seed, ws, s, tokens,
+                                                        (e.io & OUT16) ? 1 : 0);
+    });
+    return rc;
+}
+
 }  // namespace vq
 
 using namespace vq;
-
-#define VQ_ATT_DISPATCH(CALL)                                              \
-    if (L == 16 && hd == 16) return CALL(16, 16);                          \
-    if (L == 16 && hd == 32) return CALL(16, 32);                          \
-    if (L == 16 && hd == 64) return CALL(16, 64);                          \
-    if (L == 4 && hd == 16) return CALL(4, 16);                            \
-    if (L == 4 && hd == 32) return CALL(4, 32);                            \
-    if (L == 4 && hd == 64) return CALL(4, 64);
-
-static bool strip_supported(int L, int H, int hd) {
-    return L >= 1 && L <= 1024 && H >= 1 && (hd == 16 || hd == 32 || hd == 64 || hd == 128);
-}
 
 extern "C" {
 
@@ -513,28 +574,7 @@ int vqcpc_relattn_force_general(int on) {
 
 int vqcpc_relattn_fwd(const float* qkv, int64_t ldq, const float* e1, const float* e2, float* ctx, int64_t ldo,
                       float* probs, int64_t n_blocks, int L, int H, int hd, float drop_p, uint64_t seed, void* stream) {
-    if (n_blocks == 0) return VQCPC_OK;
-    VQ_REQUIRE(qkv && e1 && e2 && ctx && probs, "relattn_fwd: null pointer");
-    const bool small = att_supported(L, H, hd);
-    VQ_REQUIRE(small || strip_supported(L, H, hd), "relattn_fwd: unsupported L=%d H=%d hd=%d (L <= 1024, hd in {16,32,64,128})",
-               L, H, hd);
-    VQ_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ldq >= 3 * H * hd && ldo >= H * hd && n_blocks >= 0, "relattn_fwd: bad strides");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn_fwd: bad dropout probability");
-    hipStream_t s = (hipStream_t)stream;
-    if (!small) {
-        // any other L: the strip kernels of relattn_x.hip with Lq = Lk, no mask, q | k | v = column blocks of qkv
-        VQ_REQUIRE(aligned16(qkv) && aligned16(e1) && aligned16(e2), "relattn_fwd: qkv / e1 / e2 must be 16-byte aligned");
-        VQ_REQUIRE(n_blocks * H * (int64_t)((L + 31) / 32) < (1ll << 31), "relattn_fwd: too many strips");
-        const int d = H * hd;
-        return vqcpc_relattn_x_fwd(qkv, ldq, qkv + d, ldq, qkv + 2 * d, ldq, e1, e2, ctx, ldo, probs, n_blocks, L, L, H, hd, 0,
-                                   drop_p, seed, stream);
-    }
-    if (use_mfma16(L, H, hd) && aligned16(qkv) && aligned16(e1) && aligned16(e2) && aligned16(ctx))
-        return relattn16_fwd(qkv, ldq, nullptr, e1, e2, ctx, ldo, probs, n_blocks, H, hd, drop_p, seed, s);
-#define CALL(LL, DD) launch_fwd<LL, DD>(qkv, ldq, e1, e2, ctx, ldo, probs, n_blocks, H, drop_p, seed, s)
-    VQ_ATT_DISPATCH(CALL)
-#undef CALL
-    return VQCPC_EINVAL;
+    return self_fwd(ATT_F32, qkv, ldq, nullptr, e1, e2, ctx, ldo, probs, n_blocks, L, H, hd, drop_p, seed, stream);
 }
 
 int64_t vqcpc_relattn_bwd_workspace(int64_t n_blocks, int L, int H, int hd) {
@@ -550,35 +590,8 @@ int64_t vqcpc_relattn_bwd_workspace(int64_t n_blocks, int L, int H, int hd) {
 int vqcpc_relattn_bwd(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const float* probs, const float* e1,
                       const float* e2, float* d_qkv, int64_t ldg, float* d_e1, float* d_e2, int64_t n_blocks, int L, int H,
                       int hd, float drop_p, uint64_t seed, void* workspace, int64_t workspace_bytes, void* stream) {
-    VQ_REQUIRE(d_ctx && qkv && probs && e1 && e2 && d_qkv && d_e1 && d_e2 && workspace, "relattn_bwd: null pointer");
-    const bool small = att_supported(L, H, hd);
-    VQ_REQUIRE(small || strip_supported(L, H, hd), "relattn_bwd: unsupported L=%d H=%d hd=%d", L, H, hd);
-    VQ_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0 && ldq >= 3 * H * hd && ldg >= 3 * H * hd && ldo >= H * hd &&
-                   n_blocks >= 1,
-               "relattn_bwd: bad strides");
-    if (workspace_bytes < vqcpc_relattn_bwd_workspace(n_blocks, L, H, hd)) {
-        set_error("relattn_bwd: workspace too small");
-        return VQCPC_EWORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (!small) {
-        VQ_REQUIRE(aligned16(qkv) && aligned16(d_ctx) && aligned16(workspace), "relattn_bwd: buffers must be 16-byte aligned");
-        const int d = H * hd;
-        return vqcpc_relattn_x_bwd(d_ctx, ldo, qkv, ldq, qkv + d, ldq, qkv + 2 * d, ldq, probs, e1, e2, d_qkv, ldg, d_qkv + d, ldg,
-                                   d_qkv + 2 * d, ldg, d_e1, d_e2, n_blocks, L, L, H, hd, 0, drop_p, seed, workspace,
-                                   workspace_bytes, stream);
-    }
-    if (use_mfma16(L, H, hd) && aligned16(qkv) && aligned16(d_ctx) && aligned16(e1) && aligned16(e2) && aligned16(d_qkv)) {
-        int nsplit = 0;
-        int rc = relattn16_bwd(d_ctx, ldo, qkv, ldq, nullptr, probs, e1, e2, d_qkv, ldg, (float*)workspace, n_blocks, H, hd,
-                               drop_p, seed, s, &nsplit);
-        return rc ? rc : finish_de16((float*)workspace, nsplit, H, hd, d_e1, d_e2, s);
-    }
-#define CALL(LL, DD) \
-    launch_bwd<LL, DD>(d_ctx, ldo, qkv, ldq, probs, e1, e2, d_qkv, ldg, d_e1, d_e2, n_blocks, H, drop_p, seed, (float*)workspace, s)
-    VQ_ATT_DISPATCH(CALL)
-#undef CALL
-    return VQCPC_EINVAL;
+    return self_bwd(ATT_F32, d_ctx, ldo, qkv, ldq, nullptr, probs, e1, e2, d_qkv, ldg, d_e1, d_e2, n_blocks, L, H, hd, drop_p, seed,
+                    workspace, workspace_bytes, stream);
 }
 
 /* bf16-output forms of the L = 16 matrix-core attention (the bf16 training path, BASELINE configs[4]): ctx / d_qkv are bf16
@@ -587,165 +600,59 @@ int vqcpc_relattn16_b16_supported(int L, int H, int hd) { return (!g_force_gener
 
 int vqcpc_relattn16_fwd_b16(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, void* ctx_b16,
                             int64_t ldo, float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, void* stream) {
-    if (n_blocks == 0) return VQCPC_OK;
-    VQ_REQUIRE(qkv && e1 && e2 && ctx_b16 && probs, "relattn16_fwd_b16: null pointer");
-    VQ_REQUIRE(vqcpc_relattn16_b16_supported(16, H, hd), "relattn16_fwd_b16: unsupported H=%d hd=%d", H, hd);
-    VQ_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ldq >= 3 * H * hd && ldo >= H * hd && n_blocks >= 0 && aligned16(qkv) &&
-                   aligned16(e1) && aligned16(e2) && aligned16(ctx_b16),
-               "relattn16_fwd_b16: bad strides / alignment");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn16_fwd_b16: bad dropout probability");
-    return relattn16_fwd_b16(qkv, ldq, tokens, e1, e2, ctx_b16, ldo, probs, n_blocks, H, hd, drop_p, seed, (hipStream_t)stream);
+    return self_fwd(ATT16_B16, qkv, ldq, tokens, e1, e2, ctx_b16, ldo, probs, n_blocks, 16, H, hd, drop_p, seed, stream);
 }
 
 int vqcpc_relattn16_bwd_b16(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const int64_t* tokens,
                             const float* probs, const float* e1, const float* e2, void* d_qkv_b16, int64_t ldg, float* d_e1,
                             float* d_e2, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, void* workspace,
                             int64_t workspace_bytes, void* stream) {
-    VQ_REQUIRE(d_ctx && qkv && probs && e1 && e2 && d_qkv_b16 && d_e1 && d_e2 && workspace, "relattn16_bwd_b16: null pointer");
-    VQ_REQUIRE(vqcpc_relattn16_b16_supported(16, H, hd), "relattn16_bwd_b16: unsupported H=%d hd=%d", H, hd);
-    VQ_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0 && ldq >= 3 * H * hd && ldg >= 3 * H * hd && ldo >= H * hd &&
-                   n_blocks >= 1 && aligned16(qkv) && aligned16(d_ctx) && aligned16(e1) && aligned16(e2) && aligned16(d_qkv_b16),
-               "relattn16_bwd_b16: bad strides / alignment");
-    if (workspace_bytes < vqcpc_relattn_bwd_workspace(n_blocks, 16, H, hd)) {
-        set_error("relattn16_bwd_b16: workspace too small");
-        return VQCPC_EWORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int nsplit = 0;
-    int rc = relattn16_bwd_b16(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, d_qkv_b16, ldg, (float*)workspace, n_blocks, H, hd,
-                               drop_p, seed, s, &nsplit);
-    return rc ? rc : finish_de16((float*)workspace, nsplit, H, hd, d_e1, d_e2, s);
+    return self_bwd(ATT16_B16, d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, d_qkv_b16, ldg, d_e1, d_e2, n_blocks, 16, H, hd, drop_p,
+                    seed, workspace, workspace_bytes, stream);
 }
 
 /* bf16-output forms for the other block lengths of the encoder stacks (L = 4; L = 16 is forwarded to the matrix-core kernels). */
-int vqcpc_relattn_b16_supported(int L, int H, int hd) { return (!g_force_general && att_supported(L, H, hd)) ? 1 : 0; }
+int vqcpc_relattn_b16_supported(int L, int H, int hd) { return att_supported(L, H, hd) ? 1 : 0; }
 
 int vqcpc_relattn_fwd_b16(const float* qkv, int64_t ldq, const float* e1, const float* e2, void* ctx_b16, int64_t ldo,
                           float* probs, int64_t n_blocks, int L, int H, int hd, float drop_p, uint64_t seed, void* stream) {
-    if (n_blocks == 0) return VQCPC_OK;
-    VQ_REQUIRE(qkv && e1 && e2 && ctx_b16 && probs, "relattn_fwd_b16: null pointer");
-    VQ_REQUIRE(!g_force_general && att_supported(L, H, hd), "relattn_fwd_b16: unsupported L=%d H=%d hd=%d (L in {16,4})", L, H, hd);
-    VQ_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ldq >= 3 * H * hd && ldo >= H * hd && aligned16(qkv) && aligned16(ctx_b16),
-               "relattn_fwd_b16: bad strides / alignment");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn_fwd_b16: bad dropout probability");
-    hipStream_t s = (hipStream_t)stream;
-    if (use_mfma16(L, H, hd) && aligned16(e1) && aligned16(e2))
-        return relattn16_fwd_b16(qkv, ldq, nullptr, e1, e2, ctx_b16, ldo, probs, n_blocks, H, hd, drop_p, seed, s);
-    float* ctx = reinterpret_cast<float*>(ctx_b16);
-#define CALL(LL, DD) launch_fwd<LL, DD>(qkv, ldq, e1, e2, ctx, ldo, probs, n_blocks, H, drop_p, seed, s, nullptr, 1)
-    VQ_ATT_DISPATCH(CALL)
-#undef CALL
-    return VQCPC_EINVAL;
+    return self_fwd(ATT_B16, qkv, ldq, nullptr, e1, e2, ctx_b16, ldo, probs, n_blocks, L, H, hd, drop_p, seed, stream);
 }
 
 int vqcpc_relattn_bwd_b16(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const float* probs, const float* e1,
                           const float* e2, void* d_qkv_b16, int64_t ldg, float* d_e1, float* d_e2, int64_t n_blocks, int L,
                           int H, int hd, float drop_p, uint64_t seed, void* workspace, int64_t workspace_bytes, void* stream) {
-    VQ_REQUIRE(d_ctx && qkv && probs && e1 && e2 && d_qkv_b16 && d_e1 && d_e2 && workspace, "relattn_bwd_b16: null pointer");
-    VQ_REQUIRE(!g_force_general && att_supported(L, H, hd), "relattn_bwd_b16: unsupported L=%d H=%d hd=%d (L in {16,4})", L, H, hd);
-    VQ_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0 && ldq >= 3 * H * hd && ldg >= 3 * H * hd && ldo >= H * hd &&
-                   n_blocks >= 1 && aligned16(qkv) && aligned16(d_ctx) && aligned16(d_qkv_b16),
-               "relattn_bwd_b16: bad strides / alignment");
-    if (workspace_bytes < vqcpc_relattn_bwd_workspace(n_blocks, L, H, hd)) {
-        set_error("relattn_bwd_b16: workspace too small");
-        return VQCPC_EWORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (use_mfma16(L, H, hd) && aligned16(e1) && aligned16(e2)) {
-        int nsplit = 0;
-        int rc = relattn16_bwd_b16(d_ctx, ldo, qkv, ldq, nullptr, probs, e1, e2, d_qkv_b16, ldg, (float*)workspace, n_blocks, H,
-                                   hd, drop_p, seed, s, &nsplit);
-        return rc ? rc : finish_de16((float*)workspace, nsplit, H, hd, d_e1, d_e2, s);
-    }
-    float* d_qkv = reinterpret_cast<float*>(d_qkv_b16);
-#define CALL(LL, DD)                                                                                                   \
-    launch_bwd<LL, DD>(d_ctx, ldo, qkv, ldq, probs, e1, e2, d_qkv, ldg, d_e1, d_e2, n_blocks, H, drop_p, seed, (float*)workspace, s, \
-                       nullptr, 1)
-    VQ_ATT_DISPATCH(CALL)
-#undef CALL
-    return VQCPC_EINVAL;
+    return self_bwd(ATT_B16, d_ctx, ldo, qkv, ldq, nullptr, probs, e1, e2, d_qkv_b16, ldg, d_e1, d_e2, n_blocks, L, H, hd, drop_p,
+                    seed, workspace, workspace_bytes, stream);
 }
 
 /* all-bf16 forms: q | k | v (written as bf16 by the in_proj GEMM epilogue) and, in the backward, d ctx (out-proj dgrad epilogue)
  * are bf16 too -- half the bytes of the two kernels' dominant streams.  Leading dimensions in elements, multiples of 8. */
 int vqcpc_relattn16_fwd_b16io(const void* qkv_b16, int64_t ldq, const float* e1, const float* e2, void* ctx_b16, int64_t ldo,
                               float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, void* stream) {
-    if (n_blocks == 0) return VQCPC_OK;
-    VQ_REQUIRE(qkv_b16 && e1 && e2 && ctx_b16 && probs, "relattn16_fwd_b16io: null pointer");
-    VQ_REQUIRE(vqcpc_relattn16_b16_supported(16, H, hd), "relattn16_fwd_b16io: unsupported H=%d hd=%d", H, hd);
-    VQ_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldq >= 3 * H * hd && ldo >= H * hd && n_blocks >= 0 && aligned16(qkv_b16) &&
-                   aligned16(e1) && aligned16(e2) && aligned16(ctx_b16),
-               "relattn16_fwd_b16io: bad strides / alignment");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn16_fwd_b16io: bad dropout probability");
-    return relattn16_fwd_b16io(qkv_b16, ldq, e1, e2, ctx_b16, ldo, probs, n_blocks, H, hd, drop_p, seed, (hipStream_t)stream);
+    return self_fwd(ATT16_B16IO, qkv_b16, ldq, nullptr, e1, e2, ctx_b16, ldo, probs, n_blocks, 16, H, hd, drop_p, seed, stream);
 }
 
 int vqcpc_relattn16_bwd_b16io(const void* d_ctx_b16, int64_t ldo, const void* qkv_b16, int64_t ldq, const float* probs,
                               const float* e1, const float* e2, void* d_qkv_b16, int64_t ldg, float* d_e1, float* d_e2,
                               int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, void* workspace,
                               int64_t workspace_bytes, void* stream) {
-    VQ_REQUIRE(d_ctx_b16 && qkv_b16 && probs && e1 && e2 && d_qkv_b16 && d_e1 && d_e2 && workspace,
-               "relattn16_bwd_b16io: null pointer");
-    VQ_REQUIRE(vqcpc_relattn16_b16_supported(16, H, hd), "relattn16_bwd_b16io: unsupported H=%d hd=%d", H, hd);
-    VQ_REQUIRE(ldq % 8 == 0 && ldo % 8 == 0 && ldg % 4 == 0 && ldq >= 3 * H * hd && ldg >= 3 * H * hd && ldo >= H * hd &&
-                   n_blocks >= 1 && aligned16(qkv_b16) && aligned16(d_ctx_b16) && aligned16(e1) && aligned16(e2) &&
-                   aligned16(d_qkv_b16),
-               "relattn16_bwd_b16io: bad strides / alignment");
-    if (workspace_bytes < vqcpc_relattn_bwd_workspace(n_blocks, 16, H, hd)) {
-        set_error("relattn16_bwd_b16io: workspace too small");
-        return VQCPC_EWORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int nsplit = 0;
-    int rc = relattn16_bwd_b16io(d_ctx_b16, ldo, qkv_b16, ldq, probs, e1, e2, d_qkv_b16, ldg, (float*)workspace, n_blocks, H, hd,
-                                 drop_p, seed, s, &nsplit);
-    return rc ? rc : finish_de16((float*)workspace, nsplit, H, hd, d_e1, d_e2, s);
+    return self_bwd(ATT16_B16IO, d_ctx_b16, ldo, qkv_b16, ldq, nullptr, probs, e1, e2, d_qkv_b16, ldg, d_e1, d_e2, n_blocks, 16, H, hd,
+                    drop_p, seed, workspace, workspace_bytes, stream);
 }
 
 int vqcpc_relattn_tab_fwd(const float* table, int64_t ldt, const int64_t* tokens, const float* e1, const float* e2, float* ctx,
                           int64_t ldo, float* probs, int64_t n_blocks, int L, int H, int hd, float drop_p, uint64_t seed,
                           void* stream) {
-    if (n_blocks == 0) return VQCPC_OK;
-    VQ_REQUIRE(table && tokens && e1 && e2 && ctx && probs, "relattn_tab_fwd: null pointer");
-    VQ_REQUIRE(!g_force_general && att_supported(L, H, hd), "relattn_tab_fwd: unsupported L=%d H=%d hd=%d (L in {16,4})", L, H, hd);
-    VQ_REQUIRE(ldt % 4 == 0 && ldo % 4 == 0 && ldt >= 3 * H * hd && ldo >= H * hd, "relattn_tab_fwd: bad strides");
-    VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "relattn_tab_fwd: bad dropout probability");
-    hipStream_t s = (hipStream_t)stream;
-    if (use_mfma16(L, H, hd) && aligned16(table) && aligned16(e1) && aligned16(e2) && aligned16(ctx))
-        return relattn16_fwd(table, ldt, tokens, e1, e2, ctx, ldo, probs, n_blocks, H, hd, drop_p, seed, s);
-#define CALL(LL, DD) launch_fwd<LL, DD>(table, ldt, e1, e2, ctx, ldo, probs, n_blocks, H, drop_p, seed, s, tokens)
-    VQ_ATT_DISPATCH(CALL)
-#undef CALL
-    return VQCPC_EINVAL;
+    return self_fwd(ATT_TAB, table, ldt, tokens, e1, e2, ctx, ldo, probs, n_blocks, L, H, hd, drop_p, seed, stream);
 }
 
 int vqcpc_relattn_tab_bwd(const float* d_ctx, int64_t ldo, const float* table, int64_t ldt, const int64_t* tokens,
                           const float* probs, const float* e1, const float* e2, float* d_qkv, int64_t ldg, float* d_e1,
                           float* d_e2, int64_t n_blocks, int L, int H, int hd, float drop_p, uint64_t seed, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-    VQ_REQUIRE(d_ctx && table && tokens && probs && e1 && e2 && d_qkv && d_e1 && d_e2 && workspace,
-               "relattn_tab_bwd: null pointer");
-    VQ_REQUIRE(!g_force_general && att_supported(L, H, hd), "relattn_tab_bwd: unsupported L=%d H=%d hd=%d", L, H, hd);
-    VQ_REQUIRE(ldt % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0 && ldt >= 3 * H * hd && ldg >= 3 * H * hd && ldo >= H * hd &&
-                   n_blocks >= 1,
-               "relattn_tab_bwd: bad strides");
-    if (workspace_bytes < vqcpc_relattn_bwd_workspace(n_blocks, L, H, hd)) {
-        set_error("relattn_tab_bwd: workspace too small");
-        return VQCPC_EWORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (use_mfma16(L, H, hd) && aligned16(table) && aligned16(d_ctx) && aligned16(e1) && aligned16(e2) && aligned16(d_qkv)) {
-        int nsplit = 0;
-        int rc = relattn16_bwd(d_ctx, ldo, table, ldt, tokens, probs, e1, e2, d_qkv, ldg, (float*)workspace, n_blocks, H, hd,
-                               drop_p, seed, s, &nsplit);
-        return rc ? rc : finish_de16((float*)workspace, nsplit, H, hd, d_e1, d_e2, s);
-    }
-#define CALL(LL, DD)                                                                                                   \
-    launch_bwd<LL, DD>(d_ctx, ldo, table, ldt, probs, e1, e2, d_qkv, ldg, d_e1, d_e2, n_blocks, H, drop_p, seed,       \
-                       (float*)workspace, s, tokens)
-    VQ_ATT_DISPATCH(CALL)
-#undef CALL
-    return VQCPC_EINVAL;
+    return self_bwd(ATT_TAB, d_ctx, ldo, table, ldt, tokens, probs, e1, e2, d_qkv, ldg, d_e1, d_e2, n_blocks, L, H, hd, drop_p, seed,
+                    workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 // S[i][j] = qs_i.k_j + qs_i.Erel[j - i + 15], Erel[r] = e1[h][r] (r < 16) | e2[h][r - 15] (r >= 16)), optional token
 // indirection into the first layer's block table.
 #include "gemm_common.h"
+#include "relattn_forms.h"
 
 namespace vq {
 
@@ -701,36 +702,28 @@ static int a16_blocks_per_chunk(int64_t n_blocks, int H) {
     return (int)ceil_div(n_blocks, chunks);
 }
 
-bool relattn16_supported(int H, int hd) { return H >= 1 && (hd == 16 || hd == 32 || hd == 64); }
-
 int64_t relattn16_bwd_workspace(int64_t n_blocks, int H, int hd) {
     const int bpc = a16_blocks_per_chunk(n_blocks, H);
     const int64_t chunks = ceil_div(n_blocks, bpc);
     return (chunks * kA16Waves + 1) * H * 31 * hd * (int64_t)sizeof(float);
 }
 
-template <int HD, bool B16 = false, bool IN16 = false>
+template <int HD, bool B16, bool IN16>
 static int a16_fwd_t(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, float* ctx,
                      int64_t ldo, float* probs, int64_t n_blocks, int H, float drop_p, uint64_t seed, hipStream_t s) {
     const int64_t total = n_blocks * H;
     static const int x6 = lab_env_int("VQCPC_RELATTN16_X6", 1);      // lab builds: =0 keeps the fp32-MFMA contractions (A/B)
     // GEMM mode 0 is documented as the exact fp32-MFMA arithmetic (include/vqcpc.h): there the contractions over head_dim
     // stay on v_mfma_f32_16x16x4_f32 too; the six-product bf16 form belongs to the bf16x6 / bf16 modes
-    if ((HD == 32 || HD == 64) && x6 && vqcpc_gemm_get_mode() != 0) {
-        hipLaunchKernelGGL((relattn16_fwd_kernel<HD, B16, IN16, (HD == 32 || HD == 64)>), dim3((unsigned)ceil_div(total, kA16Waves)), dim3(kA16Waves * 64),
-                           0, s, qkv, ldq, tokens, e1, e2, ctx, ldo, probs, total, H, 1.0f / sqrtf((float)HD), drop_threshold(drop_p),
-                           1.0f / (1.0f - drop_p), seed);
-        VQ_CHECK_LAUNCH("relattn16_fwd (x6)");
-        return VQCPC_OK;
-    }
-    hipLaunchKernelGGL((relattn16_fwd_kernel<HD, B16, IN16>), dim3((unsigned)ceil_div(total, kA16Waves)), dim3(kA16Waves * 64), 0, s, qkv,
-                       ldq, tokens, e1, e2, ctx, ldo, probs, total, H, 1.0f / sqrtf((float)HD), drop_threshold(drop_p),
-                       1.0f / (1.0f - drop_p), seed);
-    VQ_CHECK_LAUNCH("relattn16_fwd");
+    const bool six = (HD == 32 || HD == 64) && x6 && vqcpc_gemm_get_mode() != 0;
+    const auto kern = six ? relattn16_fwd_kernel<HD, B16, IN16, (HD == 32 || HD == 64)> : relattn16_fwd_kernel<HD, B16, IN16>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(total, kA16Waves)), dim3(kA16Waves * 64), 0, s, qkv, ldq, tokens, e1, e2, ctx, ldo,
+                       probs, total, H, 1.0f / sqrtf((float)HD), drop_threshold(drop_p), 1.0f / (1.0f - drop_p), seed);
+    VQ_CHECK_LAUNCH(six ? "relattn16_fwd (x6)" : "relattn16_fwd");
     return VQCPC_OK;
 }
 
-template <int HD, bool B16 = false, bool IN16 = false>
+template <int HD, bool B16, bool IN16>
 static int a16_bwd_t(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const int64_t* tokens,
                      const float* probs, const float* e1, const float* e2, float* d_qkv, int64_t ldg, float* ws,
                      int64_t n_blocks, int H, float drop_p, uint64_t seed, hipStream_t s, int* nsplit) {
@@ -757,65 +750,31 @@ static int a16_bwd_t(const float* d_ctx, int64_t ldo, const float* qkv, int64_t 
     return VQCPC_OK;
 }
 
-int relattn16_fwd(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, float* ctx,
-                  int64_t ldo, float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s) {
-    if (hd == 16) return a16_fwd_t<16>(qkv, ldq, tokens, e1, e2, ctx, ldo, probs, n_blocks, H, drop_p, seed, s);
-    if (hd == 32) return a16_fwd_t<32>(qkv, ldq, tokens, e1, e2, ctx, ldo, probs, n_blocks, H, drop_p, seed, s);
-    return a16_fwd_t<64>(qkv, ldq, tokens, e1, e2, ctx, ldo, probs, n_blocks, H, drop_p, seed, s);
+// io: the IN16 / OUT16 bits of relattn_forms.h (qkv / d_ctx and ctx / d_qkv hold bf16 elements, leading dimensions in elements)
+int relattn16_fwd(const void* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, void* ctx, int64_t ldo,
+                  float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s, int io) {
+    int rc = VQCPC_EINVAL;
+    if (!dispatch(Att16Forms{}, hd, io, [&](auto f) {
+            constexpr int HD = decltype(f)::a, IO = decltype(f)::b;
+            rc = a16_fwd_t<HD, (IO & OUT16) != 0, (IO & IN16) != 0>((const float*)qkv, ldq, tokens, e1, e2, (float*)ctx, ldo, probs,
+                                                                    n_blocks, H, drop_p, seed, s);
+        }))
+        set_error("relattn16_fwd: no kernel for hd=%d io=%d", hd, io);
+    return rc;
 }
 
 // writes per-wave partials to ws and returns their count; the caller reduces them (tail of ws) and splits into e1 / e2
-int relattn16_bwd(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const int64_t* tokens, const float* probs,
-                  const float* e1, const float* e2, float* d_qkv, int64_t ldg, float* ws, int64_t n_blocks, int H, int hd,
-                  float drop_p, uint64_t seed, hipStream_t s, int* nsplit) {
-    if (hd == 16)
-        return a16_bwd_t<16>(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, d_qkv, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-    if (hd == 32)
-        return a16_bwd_t<32>(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, d_qkv, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-    return a16_bwd_t<64>(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, d_qkv, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-}
-
-// bf16-output forms (ctx / d_qkv are bf16 buffers; leading dimensions in elements)
-int relattn16_fwd_b16(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, void* ctx_b16,
-                      int64_t ldo, float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s) {
-    float* c = reinterpret_cast<float*>(ctx_b16);
-    if (hd == 16) return a16_fwd_t<16, true>(qkv, ldq, tokens, e1, e2, c, ldo, probs, n_blocks, H, drop_p, seed, s);
-    if (hd == 32) return a16_fwd_t<32, true>(qkv, ldq, tokens, e1, e2, c, ldo, probs, n_blocks, H, drop_p, seed, s);
-    return a16_fwd_t<64, true>(qkv, ldq, tokens, e1, e2, c, ldo, probs, n_blocks, H, drop_p, seed, s);
-}
-
-int relattn16_bwd_b16(const float* d_ctx, int64_t ldo, const float* qkv, int64_t ldq, const int64_t* tokens, const float* probs,
-                      const float* e1, const float* e2, void* d_qkv_b16, int64_t ldg, float* ws, int64_t n_blocks, int H, int hd,
-                      float drop_p, uint64_t seed, hipStream_t s, int* nsplit) {
-    float* g = reinterpret_cast<float*>(d_qkv_b16);
-    if (hd == 16)
-        return a16_bwd_t<16, true>(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, g, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-    if (hd == 32)
-        return a16_bwd_t<32, true>(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, g, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-    return a16_bwd_t<64, true>(d_ctx, ldo, qkv, ldq, tokens, probs, e1, e2, g, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-}
-
-// all-bf16 forms: q | k | v (and d ctx in the backward) are bf16 as well; no token indirection (the first layer's table is fp32)
-int relattn16_fwd_b16io(const void* qkv_b16, int64_t ldq, const float* e1, const float* e2, void* ctx_b16, int64_t ldo,
-                        float* probs, int64_t n_blocks, int H, int hd, float drop_p, uint64_t seed, hipStream_t s) {
-    const float* q = reinterpret_cast<const float*>(qkv_b16);
-    float* c = reinterpret_cast<float*>(ctx_b16);
-    if (hd == 16) return a16_fwd_t<16, true, true>(q, ldq, nullptr, e1, e2, c, ldo, probs, n_blocks, H, drop_p, seed, s);
-    if (hd == 32) return a16_fwd_t<32, true, true>(q, ldq, nullptr, e1, e2, c, ldo, probs, n_blocks, H, drop_p, seed, s);
-    return a16_fwd_t<64, true, true>(q, ldq, nullptr, e1, e2, c, ldo, probs, n_blocks, H, drop_p, seed, s);
-}
-
-int relattn16_bwd_b16io(const void* d_ctx_b16, int64_t ldo, const void* qkv_b16, int64_t ldq, const float* probs,
-                        const float* e1, const float* e2, void* d_qkv_b16, int64_t ldg, float* ws, int64_t n_blocks, int H,
-                        int hd, float drop_p, uint64_t seed, hipStream_t s, int* nsplit) {
-    const float* dc = reinterpret_cast<const float*>(d_ctx_b16);
-    const float* q = reinterpret_cast<const float*>(qkv_b16);
-    float* g = reinterpret_cast<float*>(d_qkv_b16);
-    if (hd == 16)
-        return a16_bwd_t<16, true, true>(dc, ldo, q, ldq, nullptr, probs, e1, e2, g, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-    if (hd == 32)
-        return a16_bwd_t<32, true, true>(dc, ldo, q, ldq, nullptr, probs, e1, e2, g, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
-    return a16_bwd_t<64, true, true>(dc, ldo, q, ldq, nullptr, probs, e1, e2, g, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
+int relattn16_bwd(const void* d_ctx, int64_t ldo, const void* qkv, int64_t ldq, const int64_t* tokens, const float* probs,
+                  const float* e1, const float* e2, void* d_qkv, int64_t ldg, float* ws, int64_t n_blocks, int H, int hd,
+                  float drop_p, uint64_t seed, hipStream_t s, int* nsplit, int io) {
+    int rc = VQCPC_EINVAL;
+    if (!dispatch(Att16Forms{}, hd, io, [&](auto f) {
+            constexpr int HD = decltype(f)::a, IO = decltype(f)::b;
+            rc = a16_bwd_t<HD, (IO & OUT16) != 0, (IO & IN16) != 0>((const float*)d_ctx, ldo, (const float*)qkv, ldq, tokens, probs, e1,
+                                                                    e2, (float*)d_qkv, ldg, ws, n_blocks, H, drop_p, seed, s, nsplit);
+        }))
+        set_error("relattn16_bwd: no kernel for hd=%d io=%d", hd, io);
+    return rc;
 }
 
 }  // namespace vq

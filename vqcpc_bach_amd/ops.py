@@ -1393,22 +1393,26 @@ def _layer_route(M, d, H, L, f, ffd, ext_qkv, tab_tokens, x_b16, x_b16_grad, out
         dx_b16=bool(g16_1 and BF16_GRAD_STREAM and x_b16_grad and (x_b16_only or not x_b16)))
 
 
+# self-attention routes (f == 1) -> (forward entry point, backward entry point, takes the tokens, takes L)
+_SELF_ATT = {
+    'f32': ('vqcpc_relattn_fwd', 'vqcpc_relattn_bwd', False, True),
+    'tab': ('vqcpc_relattn_tab_fwd', 'vqcpc_relattn_tab_bwd', True, True),
+    'b16_L': ('vqcpc_relattn_fwd_b16', 'vqcpc_relattn_bwd_b16', False, True),
+    'b16': ('vqcpc_relattn16_fwd_b16', 'vqcpc_relattn16_bwd_b16', True, False),
+    'b16io': ('vqcpc_relattn16_fwd_b16io', 'vqcpc_relattn16_bwd_b16io', False, False),
+}
+
+
 def _attention_fwd(route, qproj, qkv, tok, e1, e2, M, d, L, f, H, p, seed):
     """The layer's relative attention on the route's kernel.  Returns (context fp32 | None, context bf16 | None, probs)."""
     nblk, hd, dev = M // L, d // H, qkv.device
     probs = torch.empty(nblk, H, L // f, L, dtype=torch.float32, device=dev)
     b16 = route in _ATT_B16_ROUTES
     att = torch.empty(M // f, d, dtype=torch.bfloat16 if b16 else torch.float32, device=dev)
-    if route == 'b16io':
-        hip.call('vqcpc_relattn16_fwd_b16io', qkv, 3 * d, e1, e2, att, d, probs, nblk, H, hd, p, seed)
-    elif route == 'b16':
-        hip.call('vqcpc_relattn16_fwd_b16', qkv, 3 * d, tok, e1, e2, att, d, probs, nblk, H, hd, p, seed)
-    elif route == 'b16_L':
-        hip.call('vqcpc_relattn_fwd_b16', qkv, 3 * d, e1, e2, att, d, probs, nblk, L, H, hd, p, seed)
-    elif route == 'tab':
-        hip.call('vqcpc_relattn_tab_fwd', qkv, 3 * d, tok, e1, e2, att, d, probs, nblk, L, H, hd, p, seed)
-    elif route == 'f32':
-        hip.call('vqcpc_relattn_fwd', qkv, 3 * d, e1, e2, att, d, probs, nblk, L, H, hd, p, seed)
+    if route in _SELF_ATT:
+        name, _, toks, takes_L = _SELF_ATT[route]
+        hip.call(name, qkv, 3 * d, *((tok,) if toks else ()), e1, e2, att, d, probs, nblk, *((L,) if takes_L else ()), H, hd, p,
+                 seed)
     else:
         hip.call('vqcpc_relattn_sub_fwd_b16' if b16 else 'vqcpc_relattn_sub_fwd', qproj, d, qkv, 2 * d, e1, e2, att, d, probs, nblk, L,
                  f, H, hd, p, seed)
@@ -1433,16 +1437,9 @@ def _attention_bwd(route, datt, qproj, qkv, tok, probs, e1, e2, M, d, L, f, H, p
     ws = hip.workspace(nbytes, dev)
     # b16 routes: d qkv only feeds the in_proj's two GEMMs (or the table's segment sum) -> written as bf16 by the attention backward itself
     dqkv = torch.empty(M, 3 * d, dtype=b16, device=dev)
-    if route == 'b16io':
-        hip.call('vqcpc_relattn16_bwd_b16io', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, H, hd, p, seed, ws, nbytes)
-    elif route == 'b16':
-        hip.call('vqcpc_relattn16_bwd_b16', datt, d, qkv, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, H, hd, p, seed, ws, nbytes)
-    elif route == 'b16_L':
-        hip.call('vqcpc_relattn_bwd_b16', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, seed, ws, nbytes)
-    elif route == 'tab':
-        hip.call('vqcpc_relattn_tab_bwd', datt, d, qkv, 3 * d, tok, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, seed, ws, nbytes)
-    else:
-        hip.call('vqcpc_relattn_bwd', datt, d, qkv, 3 * d, probs, e1, e2, dqkv, 3 * d, de1, de2, nblk, L, H, hd, p, seed, ws, nbytes)
+    _, name, toks, takes_L = _SELF_ATT[route]
+    hip.call(name, datt, d, qkv, 3 * d, *((tok,) if toks else ()), probs, e1, e2, dqkv, 3 * d, de1, de2, nblk,
+             *((L,) if takes_L else ()), H, hd, p, seed, ws, nbytes)
     return dqkv, de1, de2
 
 
