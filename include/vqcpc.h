@@ -494,9 +494,14 @@ int vqcpc_reduce_grouped(int n, const void* const* ws, const int64_t* stride, co
  * bwd: d_z = g_zq + g_loss * d(loss)/dz ; d_codebooks [ncb][K][dsub] = segment-sum of g_loss * d(loss)/dq
  * (the reference trains codebooks by Adam through this gradient; the EMA codebook update the north_star names is the
  * opt-in second quantiser below: vqcpc_vq_ema_stats / vqcpc_vq_commit_bwd / vqcpc_vq_ema_update).
- * ------------------------------------------------------------------------------------------------------------------  * zq_sg == loss == NULL (with assign = 1): index-only mode for inference consumers (decoders/decoder.py:327-336,
+ * Limits (refused with VQCPC_EINVAL): fwd stages one codebook in the LDS, K * dsub <= 36 864 floats (144 KiB); bwd keeps the
+ * K x dsub accumulator next to 256 staged rows, (K + 256) * dsub + 256 floats <= 160 KiB, so dsub <= 158 at most (K = 1).
+ * zq_sg == loss == NULL (with assign = 1): index-only mode for inference consumers (decoders/decoder.py:327-336,
  * encoder.py:137-159 only read encoding_indices).
- */
+ * Ids are NOT checked: vqcpc_vq_fwd with assign == 0, vqcpc_vq_bwd, vqcpc_embed_pos_fwd / _bwd, vqcpc_block_table_gather /
+ * _segsum / _segsum_b16 and vqcpc_embedding_bwd dereference by the indices and tokens they are given, so the caller guarantees
+ * that every one is in range (0 <= idx < K, 0 <= token < vmax, 0 <= sorted_idx < V, perm a permutation of [0, M)).
+ * ------------------------------------------------------------------------------------------------------------------ */
 int vqcpc_vq_fwd(const float* z, const float* codebooks, int64_t R, int ncb, int K, int dsub, float beta, int squared,
                  int assign, int64_t* idx, float* zq_sg, float* loss, void* stream);
 int64_t vqcpc_vq_bwd_workspace(int64_t R, int ncb, int K, int dsub);

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kVqThreads) void vq_bwd_kernel(const float* __restr
         }
         __syncthreads();
         // owner of cell (k, t): lane ((k % kgroups) * dsub + t)
-        const int kgroups = kVqThreads / dsub;      // dsub <= 256 checked on the host
+        const int kgroups = kVqThreads / dsub;      // >= 1: the host's LDS check admits dsub <= 158 at most
         const int my_t = threadIdx.x % dsub, my_g = threadIdx.x / dsub;
         if (my_g < kgroups) {
             // k % kgroups per row is a scalar division (8 600 scalar instructions per wave at 256 rows x 2 codebooks:
@@ -457,9 +457,11 @@ int vqcpc_vq_bwd(const float* z, const float* codebooks, const int64_t* idx, con
                  int64_t R, int ncb, int K, int dsub, float beta, int squared, float* d_z, float* d_codebooks,
                  void* workspace, int64_t workspace_bytes, void* stream) {
     VQ_REQUIRE(z && codebooks && idx && g_zq && g_loss && d_z && d_codebooks && workspace, "vq_bwd: null pointer");
-    VQ_REQUIRE(R >= 1 && ncb >= 1 && K >= 1 && dsub >= 1 && dsub <= kVqThreads, "vq_bwd: bad shape");
+    VQ_REQUIRE(R >= 1 && ncb >= 1 && K >= 1 && dsub >= 1, "vq_bwd: bad shape");
+    // accumulator [K][dsub] + staged rows [256][dsub] + their codes: dsub <= 158 at K = 1, so a lane group (kgroups = 256 / dsub
+    // >= 1) always exists; larger dsub is refused here with the numbers that do not fit
     const size_t lds = ((size_t)K * dsub + (size_t)kVqThreads * dsub + kVqThreads) * sizeof(float);
-    VQ_REQUIRE(lds <= 160 * 1024, "vq_bwd: codebook does not fit the LDS");
+    VQ_REQUIRE(lds <= 160 * 1024, "vq_bwd: %d codes + %d staged rows of %d floats do not fit the LDS", K, kVqThreads, dsub);
     if (workspace_bytes < vqcpc_vq_bwd_workspace(R, ncb, K, dsub)) {
         set_error("vq_bwd: workspace too small");
         return VQCPC_EWORKSPACE;
