@@ -765,6 +765,19 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
                         float eps, const uint64_t* step_dev, float grad_scale, float max_norm, const double* sumsq,
                         void* stream);
 
+/* Weight averaging (opt-in: FlatTraining.enable_weight_averaging): an exponential moving average of the flat parameters, one
+ * launch after Adam's, in place on avg [n]:
+ *       d_u = min(decay, float(1 + u) / float(10 + u)) ;  w = 1 - d_u ;  avg[i] = avg[i] + w * (p[i] - avg[i])
+ *   all fp32, every operation rounded on its own (no FMA): a numpy float32 restatement gives the same bits.
+ *   u = the number of averaging updates so far, counting this one.  Host form: step_dev NULL, u >= 1 an argument.  Device
+ *   form (a captured step): u = step_dev[0] - t0, step_dev the counter vqcpc_adam_step_dev reads as Adam's t and t0 Adam's
+ *   step count when averaging was enabled; step_dev[0] <= t0 leaves avg untouched.
+ *   avg and p need only be 4-byte aligned (float4 accesses are used where both permit them); no element at an index >= n
+ *   is read or written.  Refused before any HIP call: null avg or p, n < 0, decay outside [0, 1), the host form with
+ *   u < 1.  n == 0 launches nothing. */
+int vqcpc_weight_average(float* avg, const float* p, int64_t n, float decay, uint64_t u, const uint64_t* step_dev, uint64_t t0,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Autoregressive generation (VQCPCB/decoders/decoder.py:552-723, utils.py:101-128): the kernels of one KV-cached
  * decoder step for M <= 64 sequences (vqcpc_bach_amd/decoders/generation.py).  Adding them left the ABI version alone.

@@ -456,6 +456,55 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Weight averaging: avg += w * (p - avg), w = 1 - min(decay, (1 + u) / (10 + u)), u = number of updates so far counting this
+// one (host argument, or step_dev[0] - t0 inside a captured step).  Every operation is rounded on its own (this file is
+// compiled with FMA contraction allowed, hence the pragma): a numpy float32 restatement reproduces the bits.
+constexpr int kWeightAverageBlocks = 2048;      // x 256 threads x 4 elements = 2^21 elements per pass of the grid-stride loop
+
+// (plain operators under the pragma, not __fmul_rn / __fadd_rn: those are inline functions of a header, compiled under this
+// file's contraction setting, and the compiler fuses them into one FMA)
+__device__ __forceinline__ float weight_average_one(float a, float p, float w) {
+#pragma clang fp contract(off)
+    const float diff = p - a;
+    const float step = w * diff;
+    return a + step;
+}
+
+// Elements [head, head + 4 * n4) are visited as float4 (the launcher makes n4 > 0 only when avg + head and p + head are both
+// 16-byte aligned), the other n - 4 * n4 one by one: no element at an index >= n is touched.
+__global__ __launch_bounds__(256) void weight_average_kernel(float* __restrict__ avg, const float* __restrict__ p, int64_t n,
+                                                             int64_t head, int64_t n4, float decay, uint64_t u,
+                                                             const uint64_t* __restrict__ step_dev, uint64_t t0) {
+#pragma clang fp contract(off)
+    if (step_dev != nullptr) {
+        const uint64_t t = step_dev[0];
+        if (t <= t0) return;                    // averaging enabled at a later step than this one: nothing to do
+        u = t - t0;
+    }
+    const float ratio = (float)(1 + u) / (float)(10 + u);      // IEEE division (hipcc's default for fp32 '/')
+    const float d = fminf(decay, ratio);
+    const float w = 1.0f - d;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float4* a4 = reinterpret_cast<float4*>(avg + head);
+    const float4* p4 = reinterpret_cast<const float4*>(p + head);
+    for (int64_t i = first; i < n4; i += stride) {
+        float4 a = a4[i];
+        const float4 q = p4[i];
+        a.x = weight_average_one(a.x, q.x, w);
+        a.y = weight_average_one(a.y, q.y, w);
+        a.z = weight_average_one(a.z, q.z, w);
+        a.w = weight_average_one(a.w, q.w, w);
+        a4[i] = a;
+    }
+    const int64_t rest = n - 4 * n4;            // the elements before and after the float4 range
+    for (int64_t j = first; j < rest; j += stride) {
+        const int64_t i = j < head ? j : j + 4 * n4;
+        avg[i] = weight_average_one(avg[i], p[i], w);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Token range check.  nn.Embedding raises on an id outside its table; the kernels of this library index tables (and an LDS
 // accumulator in the embedding backward) directly, so every token tensor passes through here once: the copy that the
 // kernels consume is clamped into [0, limit[voice]) and `flag` records that a clamp happened (the host raises on it at
@@ -668,6 +717,30 @@ int vqcpc_adam_step_dev(float* p, float* g, float* m, float* v, int64_t n, const
     hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_dev, beta1, beta2,
                        eps, step_dev, grad_scale, max_norm, sumsq);
     VQ_CHECK_LAUNCH("adam_step_dev");
+    return VQCPC_OK;
+}
+
+int vqcpc_weight_average(float* avg, const float* p, int64_t n, float decay, uint64_t u, const uint64_t* step_dev, uint64_t t0,
+                         void* stream) {
+    VQ_REQUIRE(avg != nullptr && p != nullptr, "weight_average: null avg or p");
+    VQ_REQUIRE(n >= 0, "weight_average: n < 0");
+    VQ_REQUIRE(decay >= 0.0f && decay < 1.0f, "weight_average: decay must be in [0, 1)");
+    VQ_REQUIRE(step_dev != nullptr || u >= 1, "weight_average: the host form counts updates from u = 1");
+    const uintptr_t aa = reinterpret_cast<uintptr_t>(avg), pa = reinterpret_cast<uintptr_t>(p);
+    VQ_REQUIRE(((aa | pa) & 3u) == 0, "weight_average: avg and p must be 4-byte aligned");
+    if (n == 0) return VQCPC_OK;
+    // float4 only where BOTH pointers reach a 16-byte boundary after the same number of elements (optimiser slices
+    // flat[a:b] are 4-byte aligned in general)
+    int64_t head = n, n4 = 0;
+    if (((aa ^ pa) & 15u) == 0) {
+        head = std::min<int64_t>(n, (int64_t)(((16u - (aa & 15u)) & 15u) >> 2));
+        n4 = (n - head) >> 2;
+    }
+    const int64_t work = std::max<int64_t>(n4, n - 4 * n4);
+    int blocks = (int)std::min<int64_t>(ceil_div(work, 256), kWeightAverageBlocks);
+    hipLaunchKernelGGL(weight_average_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, avg, p, n, head, n4, decay, u,
+                       step_dev, t0);
+    VQ_CHECK_LAUNCH("weight_average");
     return VQCPC_OK;
 }
 

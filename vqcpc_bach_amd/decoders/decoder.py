@@ -319,9 +319,12 @@ class Decoder(FlatTraining, nn.Module):
         assert self.optimizer is not None, 'call init_optimizers(lr, schedule_lr) first'
         return self._scalar_loss_epoch(data_loader, train, num_batches, [self.data_processor, self.encoder.data_processor])
 
-    def train_model(self, batch_size, num_batches, num_epochs, lr, schedule_lr, plot=False, num_workers=0, **kwargs):
+    def train_model(self, batch_size, num_batches, num_epochs, lr, schedule_lr, plot=False, num_workers=0, weight_average=None,
+                    **kwargs):
         with self._training_defaults():
             self.init_optimizers(lr=lr, schedule_lr=schedule_lr)
+            if weight_average is not None:
+                self.enable_weight_averaging(weight_average)
             return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss',
                                       save_best=lambda: self.save(early_stopped=True),
                                       save_every=lambda: self.save(early_stopped=False))

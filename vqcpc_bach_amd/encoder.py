@@ -206,8 +206,11 @@ class EncoderTrainer(FlatTraining, nn.Module):
     def eval(self):
         return self.train(False)
 
+    def _checkpoint_owners(self):
+        return [self, self.encoder]             # `save` writes the encoder's files through encoder.save
+
     def train_model(self, batch_size, num_batches, num_epochs, lr, corrupt_labels, schedule_lr, plot=False, num_workers=0,
-                    **kwargs):
+                    weight_average=None, **kwargs):
         if plot:
             try:
                 from torch.utils.tensorboard import SummaryWriter
@@ -216,6 +219,8 @@ class EncoderTrainer(FlatTraining, nn.Module):
                 self.writer = None
         with self._training_defaults():
             self.init_optimizers(lr=lr, schedule_lr=schedule_lr)
+            if weight_average is not None:
+                self.enable_weight_averaging(weight_average)
             return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss_monitor',
                                       save_best=lambda: self.save(early_stopped=True),
                                       save_every=lambda: self.save(early_stopped=False),

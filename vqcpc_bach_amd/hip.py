@@ -173,6 +173,7 @@ SIGNATURES = {
     'vqcpc_rng_salt_from_counter': (c_int, [c_ptr, c_u64, c_ptr]),
     'vqcpc_adam_step_dev': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_f32, c_f32, c_f32, c_ptr, c_f32, c_f32, c_ptr,
                                     c_ptr]),
+    'vqcpc_weight_average': (c_int, [c_ptr, c_ptr, c_i64, c_f32, c_u64, c_ptr, c_u64, c_ptr]),
     'vqcpc_gru_cell_fwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_u64, c_u64, c_ptr]),
     'vqcpc_gru_cell_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_u64, c_u64,
                                    c_ptr]),

@@ -2430,9 +2430,27 @@ class FlatAdam:
         self._ws_bytes = hip.query('vqcpc_sumsq_workspace', flat_param.numel())
         self._ws = hip.workspace(self._ws_bytes, flat_param.device)
         self._dev = None            # (lr_dev, step_dev) while a StepGraph owns the per-step scalars (graphs.py)
+        self.avg = None             # the weight average of self.p while enable_average() is in force
+        self.avg_decay, self.avg_t0 = None, None
 
     def use_device_scalars(self, lr_dev, step_dev):
         self._dev = (lr_dev, step_dev) if lr_dev is not None else None
+
+    def enable_average(self, decay, avg=None, t0=None):
+        """From the next step() on, one vqcpc_weight_average launch after Adam's keeps `avg` (default: a clone of the
+        parameters as they are now) an exponential moving average of self.p; t0 (default: the current step_count) is Adam's
+        step count before the first averaged step.  The parameters themselves never read the average."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f'weight-average decay must be in [0, 1), got {decay}')
+        if avg is None:
+            avg = self.p.clone()
+        assert avg.shape == self.p.shape and avg.dtype == self.p.dtype and avg.device == self.p.device
+        self.avg, self.avg_decay = avg, decay
+        self.avg_t0 = self.step_count if t0 is None else int(t0)
+
+    def disable_average(self):
+        self.avg, self.avg_decay, self.avg_t0 = None, None, None
 
     def step(self, lr=None, grad_scale=1.0):
         global _PARAM_STEPS
@@ -2444,10 +2462,14 @@ class FlatAdam:
             # being recorded into a step graph: learning rate and step count are read from device memory at replay time
             hip.call('vqcpc_adam_step_dev', self.p, self.g, self.m, self.v, n, self._dev[0], float(self.betas[0]),
                      float(self.betas[1]), float(self.eps), self._dev[1], float(grad_scale), float(self.max_norm), self.sumsq)
+            if self.avg is not None:
+                hip.call('vqcpc_weight_average', self.avg, self.p, n, self.avg_decay, 0, self._dev[1], self.avg_t0)
             return
         hip.call('vqcpc_adam_step', self.p, self.g, self.m, self.v, n, float(self.lr if lr is None else lr),
                  float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_count, float(grad_scale),
                  float(self.max_norm), self.sumsq)
+        if self.avg is not None:
+            hip.call('vqcpc_weight_average', self.avg, self.p, n, self.avg_decay, self.step_count - self.avg_t0, None, 0)
 
     def grad_norm(self):
         return float(self.sumsq.sqrt().item())

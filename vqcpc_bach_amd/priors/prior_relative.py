@@ -234,9 +234,12 @@ class PriorRelative(FlatTraining, nn.Module):
         assert self.optimizer is not None, 'call init_optimizers(lr) first'
         return self._scalar_loss_epoch(data_loader, train, num_batches, [self.encoder.data_processor])
 
-    def train_model(self, batch_size, num_batches=None, num_epochs=10, lr=1e-3, plot=False, num_workers=0, **kwargs):
+    def train_model(self, batch_size, num_batches=None, num_epochs=10, lr=1e-3, plot=False, num_workers=0, weight_average=None,
+                    **kwargs):
         with self._training_defaults():
             self.init_optimizers(lr=lr)
+            if weight_average is not None:
+                self.enable_weight_averaging(weight_average)
             return self._train_epochs(batch_size, num_batches, num_epochs, num_workers, monitor='loss', save_best=self.save)     # :292-294
 
     # ---- generation (:308-368): KV-cached sampling on the GPU, priors/generation.py -----------------------------------

@@ -29,6 +29,10 @@ class FlatTraining(GraphedTraining):
     global_step = 0
     is_main = True
     _resume_state = None    # what `load` found next to the checkpoint, until init_optimizers applies it
+    _avg = None             # weight averaging (opt-in): dict(decay, buf = the average of the whole flat buffer) while it is on
+    _avg_resume = None      # the checkpoint's average, until enable_weight_averaging continues it
+    _avg_inside = False     # inside averaged_weights(): the flat buffer holds the average
+    _avg_saving = False     # inside save_averaged(): weights only
 
     @staticmethod
     def lr_lambda(step):
@@ -53,6 +57,7 @@ class FlatTraining(GraphedTraining):
         SEEDS.set_rank(self.dp.rank)            # per-rank dropout masks, whatever the launcher seeded
         self.flat = FlatParameters(owners)
         self.dp.broadcast_(self.flat.flat, src=0)                       # identical replicas
+        self._avg = self._avg_resume = None     # an average of an earlier flat buffer is not an average of this one
 
     # ---- optimiser state: an extension over the reference, which restarts Adam and the LR schedule on every resume
     # (SURVEY.md section 5).  `save` writes it, `load` stashes it, init_optimizers applies it once the flat buffers exist ----
@@ -64,9 +69,14 @@ class FlatTraining(GraphedTraining):
         opts = self._graph_optimizers()
         if opts[0] is None:                     # before init_optimizers: nothing to save
             return
+        if self._avg_saving:                    # averaged/ holds weights only
+            return
         cat = (lambda ts: ts[0]) if len(opts) == 1 else torch.cat
-        torch.save(dict(m=cat([o.m for o in opts]), v=cat([o.v for o in opts]), step=opts[0].step_count,
-                        global_step=self.global_step, dropout_stream=self.dropout_stream_state()), path)
+        state = dict(m=cat([o.m for o in opts]), v=cat([o.v for o in opts]), step=opts[0].step_count,
+                     global_step=self.global_step, dropout_stream=self.dropout_stream_state())
+        if self._avg is not None:
+            state.update(avg=self._avg['buf'], avg_decay=self._avg['decay'], avg_t0=opts[0].avg_t0)
+        torch.save(state, path)
 
     def _load_optimizer_state(self, path, map_location):
         self._resume_state = torch.load(path, map_location=map_location) if os.path.exists(path) else None
@@ -76,6 +86,8 @@ class FlatTraining(GraphedTraining):
         if st is None:
             return
         opts = self._graph_optimizers()
+        if 'avg' in st:
+            self._avg_resume = {k: st[k] for k in ('avg', 'avg_decay', 'avg_t0')}
         if st['m'].numel() != sum(o.m.numel() for o in opts):
             print('optimizer state ignored: parameter count differs from the checkpoint')
             return
@@ -88,6 +100,107 @@ class FlatTraining(GraphedTraining):
             a = b
         self.global_step = int(st['global_step'])
         self.restore_dropout_stream(st.get('dropout_stream'))
+
+    # ---- weight averaging (opt-in; no counterpart in the reference): an exponential moving average of the flat parameters,
+    # one launch after each optimiser's Adam launch (ops.FlatAdam.enable_average); the training trajectory never reads it ----
+    def enable_weight_averaging(self, decay=0.999):
+        """Call after init_optimizers.  From the next training step on self.weight_average() follows the parameters with
+        d_u = min(decay, (1 + u) / (10 + u)) at its u-th update; after a `load` whose optimiser state holds an average, that
+        average is continued.  Buffers outside the flat parameters (EMA codebooks: averages already) are not covered."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f'weight_average: decay must be in [0, 1), got {decay}')
+        opts = self._graph_optimizers()
+        assert self.flat is not None and opts[0] is not None, 'call init_optimizers first'
+        if self._avg_inside:
+            raise RuntimeError('enable_weight_averaging inside averaged_weights()')
+        flat = self.flat.flat
+        buf, t0 = flat.clone(), None
+        st, self._avg_resume = self._avg_resume, None
+        if st is not None:
+            if st['avg'].numel() != flat.numel():
+                print('weight average ignored: parameter count differs from the checkpoint')
+            else:
+                buf.copy_(st['avg'])
+                t0 = int(st['avg_t0'])
+        for o in opts:                          # every optimiser averages its own slice of the one buffer
+            a = (o.p.data_ptr() - flat.data_ptr()) // 4
+            o.enable_average(decay, avg=buf[a:a + o.p.numel()], t0=t0)
+        self._avg = dict(decay=decay, buf=buf)
+        self._release_step_graph()
+        return self
+
+    def disable_weight_averaging(self):
+        if self._avg_inside:
+            raise RuntimeError('disable_weight_averaging inside averaged_weights()')
+        for o in self._graph_optimizers():
+            if o is not None:
+                o.disable_average()
+        self._avg = None
+        self._release_step_graph()
+        return self
+
+    def _release_step_graph(self):
+        """A captured step holds the launches of the configuration it was captured in: the next replayable step captures anew,
+        after the eager warm-up steps of a first capture (a capture taken right after a replay of the released graph gave the
+        decoder and the prior a wrong gradient from its second replay on; after two eager steps it replays the eager steps bit
+        for bit)."""
+        if self._graph is not None:
+            self._graph.release()
+            self._graph = None
+            self._graph_eager_steps = 0
+
+    def weight_average(self):
+        """The average of the flat parameter buffer (the live tensor, flat order), or None when averaging is off."""
+        return None if self._avg is None else self._avg['buf']
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside, the flat parameter buffer HOLDS the average (copied in place: every parameter view and every captured
+        generation graph keeps its address) and the raw weights wait in a scratch buffer; on exit they are back bit for bit.
+        Both copies bump ops._PARAM_STEPS, as an optimiser step does: no f16x3 plane image made from one set of weights is
+        paired with the other.  A training step inside, or a nested context, raises RuntimeError."""
+        if self._avg is None:
+            raise RuntimeError('averaged_weights(): weight averaging is not enabled')
+        if self._avg_inside:
+            raise RuntimeError('averaged_weights() does not nest')
+        flat = self.flat.flat
+        parked = flat.clone()
+        flat.copy_(self._avg['buf'])
+        ops._PARAM_STEPS += 1
+        self._avg_inside = True
+        try:
+            yield self
+        finally:
+            flat.copy_(parked)
+            ops._PARAM_STEPS += 1
+            self._avg_inside = False
+
+    def _checkpoint_owners(self):
+        """The objects whose `model_dir` the trainer's `save` writes under."""
+        return [self]
+
+    def _save_averaged_with(self, save):
+        owners = self._checkpoint_owners()
+        dirs = [o.model_dir for o in owners]
+        with contextlib.ExitStack() as stack:
+            if not self._avg_inside:
+                stack.enter_context(self.averaged_weights())
+            self._avg_saving = True
+            try:
+                for o, d in zip(owners, dirs):
+                    o.model_dir = f'{d}/averaged'
+                save()
+            finally:
+                for o, d in zip(owners, dirs):
+                    o.model_dir = d
+                self._avg_saving = False
+
+    def save_averaged(self, *args, **kwargs):
+        """The trainer's own `save(*args, **kwargs)` under the averaged weights, into `{model_dir}/averaged/`: the same relative
+        layout and file names, weights only (no optimiser state).  A model built with model_dir=.../averaged loads them with
+        `load` as always."""
+        self._save_averaged_with(lambda: self.save(*args, **kwargs))
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward_backward(self, forward, tag=None, zero_grad=True):
@@ -165,6 +278,8 @@ class FlatTraining(GraphedTraining):
     def _train_step(self, batch, *args, eager=False):
         """The training half of `train_step`: a replay of the captured step (graphs.py) once the first eager steps have done
         the lazy initialisations, unless this step must be `eager`; *args go to the eager `_train_step_body`."""
+        if self._avg_inside:
+            raise RuntimeError('training step inside averaged_weights(): the flat buffer holds the average, not the weights')
         out = None
         with SEEDS.stream_of(self):            # this trainer's own dropout-seed stream (utils.DropoutSeeds.stream_of)
             if not eager:
@@ -244,8 +359,10 @@ class FlatTraining(GraphedTraining):
             gen_train, gen_val, _ = self.dataloader_generator.dataloaders(batch_size=batch_size, num_workers=num_workers)
             train = self.epoch(data_loader=gen_train, train=True, num_batches=num_batches, **epoch_kwargs)
             del gen_train
-            val = self.epoch(data_loader=gen_val, train=False,
-                             num_batches=num_batches // 2 if num_batches is not None else None, **epoch_kwargs)
+            # with weight averaging on, the best epoch is chosen by the weights a user would ship
+            with self.averaged_weights() if self._avg is not None else contextlib.nullcontext():
+                val = self.epoch(data_loader=gen_val, train=False,
+                                 num_batches=num_batches // 2 if num_batches is not None else None, **epoch_kwargs)
             del gen_val
             if self.is_main:
                 print(f'======= Epoch {epoch_id} =======')
@@ -257,8 +374,12 @@ class FlatTraining(GraphedTraining):
                 print('\n')
                 if save_every is not None:
                     save_every()
+                    if self._avg is not None:
+                        self._save_averaged_with(save_every)
                 if val[monitor] < best_val:
                     save_best()
+                    if self._avg is not None:
+                        self._save_averaged_with(save_best)
                     best_val = val[monitor]
                 if after_epoch is not None:
                     after_epoch(epoch_id, train, val)
