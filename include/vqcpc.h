@@ -1098,6 +1098,43 @@ int vqcpc_cluster_select(const int64_t* codes, int64_t ld, int64_t n, int ncb, i
                          uint64_t key, int E, uint64_t* slots, int32_t* flag, void* stream);
 int vqcpc_codebook_knn(const float* e, int ncb, int K, int d, int k, int32_t* nn, float* dist2, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Particle resampling for constrained generation (csrc/particles.hip, decoders/generation.py; the rule is restated in numpy in
+ * tests/particles_reference.py).  The M <= 64 rows of an incremental stack are G = M / P groups of P consecutive rows, 2 <= P <= 64.
+ * vqcpc_particle_resample: ONE launch for all groups, after the U steps of a code.  c = w0 + pos[0] / U - 1 is the code's
+ *   chorale index (w0 = win ? win[1] : 0, both read from device memory as the samplers read them); c < 0 (no live window,
+ *   pos[0] < U): ancestors = the identity, flag = 0, nothing else is written.  Otherwise, per row b, in ascending q over the
+ *   code's columns [c * U, (c + 1) * U):  lw[b] = lw[b] + logp[b * ldlogp + q] where constraint[b * ldcons + q] >= 0, else
+ *   + logmass[b * ldmass + q] where logmass != NULL (one fp32 add each; NULL buffers and columns past a leading dimension add
+ *   nothing).  NaN counts as -inf.  Per group, members ascending, every operation rounded on its own (no FMA contraction):
+ *     mx = max lw, w = exp(lw - mx), s = sum w, wn = w / s, ess = 1 / sum wn^2, inc = (mx + log s) - log P;
+ *   every member -inf: wn = 1 / P, inc = -inf, evidence[g] = -inf and the group is never resampled.
+ *   A group resamples when force != 0 or ess < threshold * P:  u = (splitmix64(seeds[first row] ^ (c + 1) *
+ *   0x8CB92BA72F3D8DD7) >> 40) * 2^-24; the ancestor of slot k is the first member j whose running fp32 sum of wn (ascending,
+ *   sequential adds) exceeds (u + k) / P, else the last member; evidence[g] += inc and the group's lw become 0.  Otherwise
+ *   the ancestors are the identity and lw keeps the sums.  Outputs: lw, evidence (G), pending (G) = inc, ancestors (M, int32,
+ *   row indices of the stack), wn (M), ess (G), flag[0] = 1 if any ancestor differs from its own row else 0, and row c of the
+ *   histories hist_ancestors (hist_rows, M), hist_wn (hist_rows, M), hist_ess (hist_rows, G) where given and c < hist_rows.
+ * vqcpc_particle_permute_{i64,f32,cache}: row k <- row ancestors[k] of a buffer of M rows, IN PLACE, for every group; returns at
+ *   once when flag[0] == 0.  A workgroup owns a column tile across all rows of a group, loads it into LDS and stores after
+ *   the barrier, so cycles and fan-outs of the map are safe; an ancestor outside the row's group leaves the row alone.
+ *   _i64 / _f32: buf [M][ld], columns [0, width) move, or [0, clamp(pos[0], 0, width)) when pos != NULL.  _cache: cache
+ *   [layers][M][W][d] fp32 (a K or V cache of the stack), positions [0, clamp(pos[0], 0, W)) of every layer move; d % 4 == 0,
+ *   16-byte aligned.  Rows at and beyond the bound, other groups and everything outside the buffer keep their bits.
+ * No allocation or synchronisation in the launch functions.  Adding them left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_particle_resample(float* lw, float* evidence, float* pending, const int64_t* seeds, const int64_t* constraint,
+                            int64_t ldcons, const float* logp, int64_t ldlogp, const float* logmass, int64_t ldmass,
+                            const int32_t* pos, const int32_t* win, int U, float threshold, int force, int32_t* ancestors,
+                            float* wn, float* ess, int32_t* flag, int32_t* hist_ancestors, float* hist_wn, float* hist_ess,
+                            int64_t hist_rows, int64_t M, int P, void* stream);
+int vqcpc_particle_permute_i64(int64_t* buf, int64_t ld, int64_t width, const int32_t* pos, const int32_t* ancestors,
+                               const int32_t* flag, int64_t M, int P, void* stream);
+int vqcpc_particle_permute_f32(float* buf, int64_t ld, int64_t width, const int32_t* pos, const int32_t* ancestors,
+                               const int32_t* flag, int64_t M, int P, void* stream);
+int vqcpc_particle_permute_cache(float* cache, int layers, int64_t W, int d, const int32_t* pos, const int32_t* ancestors,
+                                 const int32_t* flag, int64_t M, int P, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

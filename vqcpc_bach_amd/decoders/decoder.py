@@ -458,7 +458,8 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
                             use_graph=True, constraint=None, return_logp=False, return_attentions=False,
-                            max_attention_bytes=4 << 30, allowed=None, return_allowed_mass=False):
+                            max_attention_bytes=4 << 30, allowed=None, return_allowed_mass=False, particles=None,
+                            resample_threshold=0.5, return_particles=False):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
@@ -491,25 +492,43 @@ class Decoder(FlatTraining, nn.Module):
         return_allowed_mass=True -> `allowed_mass` after tokens and logp, float32 of the tokens' shape: the log of the
         probability the model's unfiltered distribution gives to the position's allowed set (0 where nothing is restricted).
         Results come in the order (tokens[, logp][, allowed_mass][, attentions]).  Either keyword switches the step's sampler
-        to vqcpc_decode_sample_masked; without them every launch is what it was."""
-        from ..transformer.incremental import generate_in_chunks, row_seeds
+        to vqcpc_decode_sample_masked; without them every launch is what it was.
+        particles: None, or P in [2, 64]: a particle filter over the forced tokens and the sets.  Every row (after
+        num_decodings) becomes a group of P consecutive rows with their own seeds; after every code a row's weight grows by
+        the log-probability of its forced tokens and the allowed mass of its restricted ones, and a group whose effective
+        sample size fell below resample_threshold * P (0: never, 1: whenever the weights differ) is resampled systematically:
+        whole rows -- tokens, scores, K/V caches -- are copied onto others (vqcpc_particle_resample, vqcpc_particle_permute_*),
+        so the free choices that the later forced tokens make unlikely die out.  After the last code one forced resampling
+        makes the first row of every group a draw from the final weights, and that row is returned: the result shapes are
+        those of a call without particles.  return_particles=True skips it and returns all B' * P rows (tokens[, logp]
+        [, allowed_mass]) followed by a dict: 'weights' (B', P) the final normalised weights, 'log_evidence' (B',) the log of
+        the estimated probability of the constraints, and per code 'ancestors' (codes, B' * P) int32 row indices (-1: no code
+        finished there), 'wn' (codes, B' * P) and 'ess' (codes, B').  The filter is exact -- a properly weighted sample and
+        an unbiased evidence estimate -- for temperature=1, top_k=0, top_p=1; with a filtered proposal it is the heuristic
+        that logp itself is, which always scores the unfiltered distribution.  ValueError with return_attentions.  Without
+        `particles` every launch, buffer and result is what it was."""
+        from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
         layers = self._attention_layers(return_attentions)
+        P = self._particle_count(particles, resample_threshold, return_particles, layers)
         codes = self._source_on_device(codes, 'codes', self.num_tokens_source)
         T, nc = self.num_tokens_target, self.num_channels
         if constraint is not None:
             constraint = self._constraint_rows(constraint, codes.shape[0], T // nc)
         if allowed is not None:
             allowed = self._allowed_words(allowed, codes.shape[0], T // nc, exclude=exclude_tokens, constraint=constraint)
-        if num_decodings > 1:
-            codes = codes.repeat_interleave(num_decodings, dim=0)
+        if num_decodings * P > 1:
+            codes = codes.repeat_interleave(num_decodings * P, dim=0)
             if constraint is not None:
-                constraint = constraint.repeat_interleave(num_decodings, dim=0)
+                constraint = constraint.repeat_interleave(num_decodings * P, dim=0)
             if allowed is not None and allowed.shape[0] > 1:
-                allowed = allowed.repeat_interleave(num_decodings, dim=0)
+                allowed = allowed.repeat_interleave(num_decodings * P, dim=0)
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
+        filt = {} if particles is not None else None
+        pkw = {} if particles is None else dict(particles=P, resample_threshold=resample_threshold,
+                                                final_resample=not return_particles)
         logp = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logp else None
         mass = torch.empty(B, T, dtype=torch.float32, device=dev) if return_allowed_mass else None
         maps = None
@@ -522,7 +541,7 @@ class Decoder(FlatTraining, nn.Module):
             inc.prefill(codes[rows])
             inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens,
                       constraint=None if constraint is None else constraint[rows], want_logp=return_logp, want_attentions=layers,
-                      allowed=self._allowed_rows(allowed, n, rows), want_allowed_mass=return_allowed_mass)
+                      allowed=self._allowed_rows(allowed, n, rows), want_allowed_mass=return_allowed_mass, **pkw)
             tokens = inc.run(use_graph=use_graph)
             if return_logp:
                 logp[rows] = inc.logp
@@ -532,14 +551,50 @@ class Decoder(FlatTraining, nn.Module):
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
                 maps['self_attns_encoder'].append(torch.stack(inc.enc_probs, dim=1))
+            if filt is not None:
+                self._keep_particle_results(filt, inc.particle_results(), rows.start)
             return tokens
-        tokens = generate_in_chunks(self, B, T, chunk).view(B, T // nc, nc)
-        out = (tokens, logp.view(B, T // nc, nc)) if return_logp else (tokens,)
+        tokens = generate_in_chunks(self, B, T, chunk, MAX_ROWS // P * P)            # whole groups (P = 1: MAX_ROWS, as before)
+        keep = slice(None) if particles is None or return_particles else slice(0, B, P)      # a group's first row
+        nk = len(range(B)[keep])
+        out = (tokens[keep].view(nk, T // nc, nc),)
+        if return_logp:
+            out += (logp[keep].view(nk, T // nc, nc),)
         if return_allowed_mass:
-            out += (mass.view(B, T // nc, nc),)
+            out += (mass[keep].view(nk, T // nc, nc),)
         if maps is not None:
             out += (self._join_attention_chunks(maps),)
+        if return_particles and filt is not None:
+            out += (self._join_particle_results(filt),)
         return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def _particle_count(particles, resample_threshold, return_particles, attention_layers):
+        """The checks of the particle keywords, once per call -> the group size (1 without particles)."""
+        if particles is None:
+            if return_particles:
+                raise ValueError('return_particles=True needs particles=P')
+            return 1
+        if isinstance(particles, bool) or int(particles) != particles or not 2 <= int(particles) <= 64:
+            raise ValueError(f'particles: None or an integer in [2, 64] expected, got {particles!r}')
+        if not 0.0 <= float(resample_threshold) <= 1.0:
+            raise ValueError(f'resample_threshold: a share of the particles in [0, 1] expected, got {resample_threshold!r}')
+        if attention_layers is not None:
+            raise ValueError('return_attentions with particles: the maps of a row are not moved when the row is resampled')
+        return int(particles)
+
+    @staticmethod
+    def _keep_particle_results(filt, res, row0):
+        """A chunk's filter results; its ancestors become row indices of the whole call (the chunk starts at row `row0`)."""
+        anc = res['ancestors']
+        res = dict(res, ancestors=torch.where(anc >= 0, anc + row0, anc))
+        for key, val in res.items():
+            filt.setdefault(key, []).append(val)
+
+    @staticmethod
+    def _join_particle_results(filt):
+        return {key: torch.cat(parts, dim=0 if key in ('weights', 'log_evidence') else 1).contiguous()
+                for key, parts in filt.items()}
 
     @staticmethod
     def _allowed_rows(words, n, rows):
@@ -573,7 +628,7 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
                  plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None, return_attentions=False,
-                 max_attention_bytes=4 << 30):
+                 max_attention_bytes=4 << 30, particles=None, resample_threshold=0.5):
         """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
@@ -586,7 +641,9 @@ class Decoder(FlatTraining, nn.Module):
         the codes file {timestamp}_attentions.npz holds the reference's three stems as arrays (no PDF is drawn): attns_cross
         (absent for the diagonal decoder), self_attns_decoder and self_attns_encoder, each (batch, H, T, keys) for the FIRST
         recorded layer (the encoder's layer of that index, or its last), plus `layers`.  Row t of self_attns_encoder is the
-        encoder's row (t // channels * channels) // tokens-per-code, the code of t's event (:650-659)."""
+        encoder's row (t // channels * channels) // tokens-per-code, the code of t's event (:650-659).
+        particles, resample_threshold: `generate_from_codes`'s particle filter over the kept voices (each of the `batch_size`
+        generations is the survivor of its own group of `particles` rows)."""
         if plot_attentions:
             raise NotImplementedError('plot_attentions: no plots are drawn here (no matplotlib); return_attentions=True returns '
                                       'the attention maps of every emitted token and writes them as arrays')
@@ -620,7 +677,9 @@ class Decoder(FlatTraining, nn.Module):
                 constraint[:, :, voices] = x_original[:, :, voices]
             x = self.generate_from_codes(codes, temperature=temperature, top_k=top_k, top_p=top_p, exclude_tokens=exclude,
                                          seed=seed, constraint=constraint, return_attentions=layers or False,
-                                         max_attention_bytes=max_attention_bytes)
+                                         max_attention_bytes=max_attention_bytes,
+                                         **({} if particles is None else dict(particles=particles,
+                                                                              resample_threshold=resample_threshold)))
             attentions = None
             if layers is not None:
                 x, attentions = x
@@ -701,7 +760,8 @@ class Decoder(FlatTraining, nn.Module):
     def generate_from_code_long(self, encoding_indices=None, temperature=None, top_k=0, top_p=1., exclude_meta_symbols=False,
                                 num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
                                 use_graph=True, constraint=None, return_logp=False, return_attentions=False,
-                                max_attention_bytes=4 << 30, graph_slides=None, allowed=None, return_allowed_mass=False):
+                                max_attention_bytes=4 << 30, graph_slides=None, allowed=None, return_allowed_mass=False,
+                                particles=None, resample_threshold=0.5, return_particles=False):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -728,14 +788,18 @@ class Decoder(FlatTraining, nn.Module):
         allowed, return_allowed_mass: as in `generate_from_codes`, with allowed (B, nb * events_per_code, channels, vmax) or
         (nb * events_per_code, channels, vmax) over the WHOLE code sequence in chorale coordinates, like the constraint: the sets
         hold whichever window a position is emitted in, events outside [code_index_start, code_index_end) are ignored.
-        allowed_mass has the tokens' shape.  Results: (tokens[, logp][, allowed_mass][, attentions])."""
+        allowed_mass has the tokens' shape.  Results: (tokens[, logp][, allowed_mass][, attentions]).
+        particles, resample_threshold, return_particles: as in `generate_from_codes`; the groups are resampled after every
+        generated code, the K/V caches move where the next code is generated in the same window (a slide recomputes them from
+        the moved tokens), and the histories of the returned dict have one row per code of the WHOLE sequence."""
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
-        from ..transformer.incremental import generate_in_chunks, row_seeds
+        from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
         layers = self._attention_layers(return_attentions)
+        P = self._particle_count(particles, resample_threshold, return_particles, layers)
         codes = self._source_on_device(encoding_indices, 'encoding_indices')
         S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
         nb = codes.shape[1]
@@ -753,14 +817,17 @@ class Decoder(FlatTraining, nn.Module):
         if allowed is not None:
             allowed = self._allowed_words(allowed, codes.shape[0], nb * epc, code_index_start * epc, code_index_end * epc,
                                           exclude=exclude, constraint=constraint)
-        if num_decodings > 1:
-            codes = codes.repeat_interleave(num_decodings, dim=0)
+        if num_decodings * P > 1:
+            codes = codes.repeat_interleave(num_decodings * P, dim=0)
             if constraint is not None:
-                constraint = constraint.repeat_interleave(num_decodings, dim=0)
+                constraint = constraint.repeat_interleave(num_decodings * P, dim=0)
             if allowed is not None and allowed.shape[0] > 1:
-                allowed = allowed.repeat_interleave(num_decodings, dim=0)
+                allowed = allowed.repeat_interleave(num_decodings * P, dim=0)
         B = codes.shape[0]
         seeds = row_seeds(seed, B)
+        filt = {} if particles is not None else None
+        pkw = {} if particles is None else dict(particles=P, resample_threshold=resample_threshold,
+                                                final_resample=not return_particles)
         logp = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_logp else None
         mass = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_allowed_mass else None
         maps = None
@@ -775,7 +842,7 @@ class Decoder(FlatTraining, nn.Module):
                            top_k=top_k, top_p=top_p, exclude=exclude,
                            constraint=None if constraint is None else constraint[rows], want_logp=return_logp,
                            want_attentions=layers, allowed=self._allowed_rows(allowed, n, rows),
-                           want_allowed_mass=return_allowed_mass)
+                           want_allowed_mass=return_allowed_mass, **pkw)
             tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph, graph_slides=graph_slides)
             if return_logp:
                 logp[rows] = inc.logp
@@ -784,14 +851,20 @@ class Decoder(FlatTraining, nn.Module):
             if maps is not None:
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
+            if filt is not None:
+                self._keep_particle_results(filt, inc.particle_results(), rows.start)
             return tokens
-        out = generate_in_chunks(self, B, nb * U, chunk)
-        cut = lambda t: t.view(B, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
+        out = generate_in_chunks(self, B, nb * U, chunk, MAX_ROWS // P * P)           # whole groups (P = 1: MAX_ROWS, as before)
+        keep = slice(None) if particles is None or return_particles else slice(0, B, P)      # a group's first row
+        nk = len(range(B)[keep])
+        cut = lambda t: t[keep].view(nk, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
         res = (cut(out), cut(logp)) if return_logp else (cut(out),)
         if return_allowed_mass:
             res += (cut(mass),)
         if maps is not None:
             res += (self._join_attention_chunks(maps),)
+        if return_particles and filt is not None:
+            res += (self._join_particle_results(filt),)
         return res if len(res) > 1 else res[0]
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):

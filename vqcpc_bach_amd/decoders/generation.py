@@ -42,7 +42,13 @@ Continuous decoder (`Decoder.continuous_source`, a NoQuantization encoder): the 
 `source_embeddings` a linear layer.  The first launch of `_encode_memory` is then vqcpc_decode_source_rows instead of the
 embedding gather: it reads the live window's S latents of every sequence from `z_full` through the device window index `win`
 (NULL in the fixed-window prefill), so the captured slide still serves every middle window; vqcpc_decode_window gets a dummy
-all-zero code tensor and keeps its token / seed / position bookkeeping.  Everything after `src` is shared."""
+all-zero code tensor and keeps its token / seed / position bookkeeping.  Everything after `src` is shared.
+
+Particles (`start(particles=P)`, csrc/particles.hip): the rows are groups of P consecutive rows with their own seeds.  After the U
+steps of a code, vqcpc_particle_resample adds the code's forced logp / free logmass to every row's log-weight and, where a
+group's effective sample size fell below the threshold, draws its ancestors; vqcpc_particle_permute_* then moves the ancestors'
+state -- live tokens, chorale row, logp / logmass rows, next input row, K/V cache rows [0, pos) -- onto the rows in place.  Both
+read `pos` and `win` from device memory and sit BETWEEN the replays: the captured step and slide are what they were."""
 import ctypes
 
 import torch
@@ -91,6 +97,7 @@ class IncrementalDecoder(IncrementalStack):
         self.constraint, self.logp, self.constrained = None, None, False
         self.allowed, self.logmass, self.masked = None, None, False
         self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
+        self.particles = None                                                     # group size P, or None: plain rows
         self.continuous = bool(getattr(dec, 'continuous_source', False))
         if self.continuous:
             self.dz = dec.source_dim
@@ -140,7 +147,8 @@ class IncrementalDecoder(IncrementalStack):
             ops.gemm_nt(memory, lay.multihead_attn.in_proj_weight[d:], bias=lay.multihead_attn.in_proj_bias[d:], out=kv)
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
-              constraint=None, want_logp=False, want_attentions=None, allowed=None, want_allowed_mass=False):
+              constraint=None, want_logp=False, want_attentions=None, allowed=None, want_allowed_mass=False, particles=None,
+              resample_threshold=0.5, final_resample=True):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
         probabilities of the last step in `probs` (M, max V_c).
@@ -153,7 +161,11 @@ class IncrementalDecoder(IncrementalStack):
         allowed: (M, T, 8) int32, per (row, position) the 256-bit set of the tokens that may be drawn (bit i & 31 of word i >> 5;
         the caller has checked that every set has a token of its voice); want_allowed_mass: keep in `logmass` (M, T) float32
         the log of the probability the unfiltered distribution gives to the position's set, NaN where no token was emitted yet.
-        Either one switches the step's sampler to vqcpc_decode_sample_masked."""
+        Either one switches the step's sampler to vqcpc_decode_sample_masked.
+        particles: None, or P in [2, 64] dividing M: the rows are M / P groups of P particles, resampled after every code
+        (`_resample`); logp / logmass are then kept whenever a constraint / sets are given.  resample_threshold: a group
+        resamples when its effective sample size falls below resample_threshold * P; final_resample: after the last code one
+        forced resampling makes the first row of every group an unweighted draw from the final weights."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
@@ -170,10 +182,93 @@ class IncrementalDecoder(IncrementalStack):
         else:
             self.teacher = None
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
-        self._constrain(constraint, want_logp, self.T, None)
-        self._mask(allowed, want_allowed_mass, self.T)
+        self._particles(particles, resample_threshold, final_resample, self.S, self.seeds, want_attentions)
+        self._constrain(constraint, want_logp or (particles is not None and constraint is not None), self.T, None)
+        self._mask(allowed, want_allowed_mass or (particles is not None and allowed is not None), self.T)
         self._record_attentions(want_attentions, self.T, None, 1)
         self.reset()
+
+    def _particles(self, P, threshold, final, codes, seeds, want_attentions=None):
+        """The particle filter's state: per row the running log-weight `p_lw`, the last normalised weights `p_wn` and
+        ancestors `p_anc`; per group the log-evidence `p_evidence`, the last code's increment `p_pending` and effective sample
+        size `p_ess`; the device flag `p_flag`; and per chorale code (`codes` rows) the histories `p_hist_anc` (int32, -1 where
+        no code was finished), `p_hist_wn`, `p_hist_ess` (NaN there).  seeds: the per-row seeds that never move (the resampling
+        uniform is keyed by the group's first one and the code's chorale index)."""
+        self.particles = None
+        if P is None:
+            return
+        P = int(P)
+        if not 2 <= P <= MAX_ROWS or self.M % P:
+            raise ValueError(f'particles: 2 <= particles <= {MAX_ROWS} dividing the stack\'s {self.M} rows expected, got {P}')
+        if not 0.0 <= float(threshold) <= 1.0:
+            raise ValueError(f'resample_threshold: a share of the particles in [0, 1] expected, got {threshold}')
+        if want_attentions is not None:
+            raise ValueError('particles: attention maps are not moved with a resampled row; want_attentions must be None')
+        if self.teacher is not None:
+            raise ValueError('particles and teacher exclude each other')
+        M, G, dev = self.M, self.M // P, self.dev
+        self.particles, self.p_threshold, self.p_final, self.p_seeds = P, float(threshold), bool(final), seeds
+        self.p_lw = torch.zeros(M, dtype=torch.float32, device=dev)
+        self.p_wn = torch.full((M,), 1.0 / P, dtype=torch.float32, device=dev)
+        self.p_anc = torch.arange(M, dtype=torch.int32, device=dev)
+        self.p_evidence, self.p_pending = (torch.zeros(G, dtype=torch.float32, device=dev) for _ in range(2))
+        self.p_ess = torch.full((G,), float(P), dtype=torch.float32, device=dev)
+        self.p_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.p_hist_anc = torch.full((codes, M), -1, dtype=torch.int32, device=dev)
+        self.p_hist_wn = torch.full((codes, M), float('nan'), dtype=torch.float32, device=dev)
+        self.p_hist_ess = torch.full((codes, G), float('nan'), dtype=torch.float32, device=dev)
+
+    def _forget_particles(self):
+        if self.particles is None:
+            return
+        self.p_lw.zero_()
+        self.p_wn.fill_(1.0 / self.particles)
+        self.p_anc.copy_(torch.arange(self.M, dtype=torch.int32))
+        self.p_evidence.zero_()
+        self.p_pending.zero_()
+        self.p_ess.fill_(float(self.particles))
+        self.p_flag.zero_()
+        self.p_hist_anc.fill_(-1)
+        self.p_hist_wn.fill_(float('nan'))
+        self.p_hist_ess.fill_(float('nan'))
+
+    def _resample(self, last, move_cache, chorale=None):
+        """After the U steps of a code: the weight update and the resampling decision (vqcpc_particle_resample), then the
+        group's generation state follows the ancestors in place (vqcpc_particle_permute_*): the live window's tokens [0, pos),
+        the chorale row (long mode), the logp / logmass rows, the next input row and, with move_cache -- no slide follows, which
+        would recompute them from the tokens --, every layer's K and V cache rows [0, pos).  The permute launches return at once
+        on the device flag when no row moved.  The launches are issued eagerly between the step replays of a graphed run: replaying
+        them from a captured graph of their own measured slower (profiles/generate_particles_perf_log.md).  last: the code is the generation's last one -- a forced resampling
+        (`final_resample`), or the weight update alone (threshold 0, nothing moves, no permute launch)."""
+        P, M, w = self.particles, self.M, self._cons_width
+        force = bool(last and self.p_final)
+        threshold = 0.0 if last and not self.p_final else self.p_threshold
+        hip.call('vqcpc_particle_resample', self.p_lw, self.p_evidence, self.p_pending, self.p_seeds, self.constraint, w,
+                 self.logp if self.constraint is not None else None, w, self.logmass if self.allowed is not None else None, w,
+                 self.pos, self._cons_win, self.U, threshold, int(force), self.p_anc, self.p_wn, self.p_ess, self.p_flag,
+                 self.p_hist_anc, self.p_hist_wn, self.p_hist_ess, self.p_hist_anc.shape[0], M, P)
+        if threshold == 0.0 and not force:
+            return
+        anc, flag = self.p_anc, self.p_flag
+        hip.call('vqcpc_particle_permute_i64', self.tokens, self.T, self.T, self.pos, anc, flag, M, P)
+        if chorale is not None:
+            hip.call('vqcpc_particle_permute_i64', chorale, chorale.shape[1], chorale.shape[1], None, anc, flag, M, P)
+        for rows in (self.logp, self.logmass):
+            if rows is not None:
+                hip.call('vqcpc_particle_permute_f32', rows, w, w, None, anc, flag, M, P)
+        if not last:
+            hip.call('vqcpc_particle_permute_f32', self.x, self.d, self.d, None, anc, flag, M, P)
+            if move_cache:
+                for cache in (self.kcache, self.vcache):
+                    hip.call('vqcpc_particle_permute_cache', cache, len(self.layers), self.W, self.d, self.pos, anc, flag, M, P)
+
+    def particle_results(self):
+        """After a run: the final normalised weights (G, P), the log-evidence (G,) -- the resampled codes' increments plus the
+        last weights' mx + log(s / P), which a final forced resampling has added already --, and the per-code histories."""
+        G, P = self.M // self.particles, self.particles
+        evidence = self.p_evidence if self.p_final else self.p_evidence + self.p_pending
+        return {'weights': self.p_wn.view(G, P).clone(), 'log_evidence': evidence.clone(), 'ancestors': self.p_hist_anc,
+                'wn': self.p_hist_wn, 'ess': self.p_hist_ess}
 
     def _constrain(self, constraint, want_logp, width, win):
         """The constrained sampler's buffers, (M, width) each: width = T and win = None for the fixed window, width = nb * U and
@@ -239,6 +334,7 @@ class IncrementalDecoder(IncrementalStack):
         for maps in (self.self_probs, self.cross_probs):
             if maps is not None:
                 maps.fill_(float('nan'))
+        self._forget_particles()
 
     # ---- one step: the cross hooks and the sampler ----------------------------------------------------------------------
     def _cross_attention(self, li, lay):
@@ -291,19 +387,26 @@ class IncrementalDecoder(IncrementalStack):
             self.step()                       # first launches outside the capture
             graph = self.capture(self.step)
             self.reset()
-            for _ in range(self.T):
+            for t in range(self.T):
                 graph.replay()
+                self._code_done(t + 1)
             torch.cuda.current_stream(self.dev).synchronize()
             del graph
         else:
-            for _ in range(self.T):
+            for t in range(self.T):
                 self.step()
+                self._code_done(t + 1)
         return self.tokens
+
+    def _code_done(self, steps):
+        """Fixed window, after `steps` steps: resamples when they complete a code (the caches always move, nothing slides)."""
+        if self.particles is not None and steps % self.U == 0:
+            self._resample(steps == self.T, True)
 
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
     def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, allowed=None,
-                   want_allowed_mass=False, **sampling):
+                   want_allowed_mass=False, particles=None, resample_threshold=0.5, final_resample=True, **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
         tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
         want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
@@ -312,6 +415,7 @@ class IncrementalDecoder(IncrementalStack):
         the row is the emitted token's chorale position, its keys are those of the window it was emitted in.
         allowed, want_allowed_mass: as in `start`, but (M, nb * U, 8) / `logmass` (M, nb * U), in chorale coordinates like the
         constraint.
+        particles, resample_threshold, final_resample: as in `start`; the histories have one row per code of the chorale.
         sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
@@ -335,8 +439,9 @@ class IncrementalDecoder(IncrementalStack):
         if self.continuous:
             self.z_full, self.z_nb = z_full, nb
         self.start(seeds=seeds, **sampling)
-        self._constrain(constraint, want_logp, nb * U, self.win)
-        self._mask(allowed, want_allowed_mass, nb * U)
+        self._particles(particles, resample_threshold, final_resample, nb, self.row_seeds, want_attentions)
+        self._constrain(constraint, want_logp or (particles is not None and constraint is not None), nb * U, self.win)
+        self._mask(allowed, want_allowed_mass or (particles is not None and allowed is not None), nb * U)
         self._record_attentions(want_attentions, nb * U, self.win, U)
         self.row_seeds.copy_(self.seeds)
 
@@ -408,7 +513,7 @@ class IncrementalDecoder(IncrementalStack):
             self._forget_logp()
             self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
         live = None
-        for _, tb, _, tr in plan:
+        for k, (_, tb, _, tr) in enumerate(plan):
             if tb != live:
                 if slide_graph is not None and live is not None and tb == live + 1 and tr == tr_mid:
                     slide_graph.replay()          # the device's window index is live + 1 already
@@ -417,6 +522,9 @@ class IncrementalDecoder(IncrementalStack):
                 live = tb
             for _ in range(U):
                 step_graph.replay() if step_graph is not None else self.step()
+            if self.particles is not None:                # the caches move only where the next code is generated without a slide
+                last = k + 1 == len(plan)
+                self._resample(last, not last and plan[k + 1][1] == tb, self.chorale)
         self.commit()
         torch.cuda.current_stream(self.dev).synchronize()
         del step_graph, slide_graph

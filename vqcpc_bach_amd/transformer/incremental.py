@@ -49,17 +49,20 @@ def row_seeds(seed, n):
     return torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
 
 
-def generate_in_chunks(model, B, width, chunk):
+def generate_in_chunks(model, B, width, chunk, chunk_rows=MAX_ROWS):
     """The public generation methods' loop: `chunk(n, rows)` -> (n, width) int64 tokens of the rows `rows` (a slice of
-    n <= MAX_ROWS of the B rows), from an incremental stack that lives for that chunk only.  Runs under STEP_LOCK (never
-    interleaved with a training step of another thread), without gradients and with `model` in eval mode.  -> (B, width)."""
+    n <= chunk_rows <= MAX_ROWS of the B rows), from an incremental stack that lives for that chunk only.  Runs under STEP_LOCK
+    (never interleaved with a training step of another thread), without gradients and with `model` in eval mode.  -> (B, width).
+    chunk_rows: a multiple of the group size when the rows come in groups that must share a stack (particles)."""
+    if not 1 <= chunk_rows <= MAX_ROWS:
+        raise ValueError(f'generate_in_chunks: 1 <= chunk_rows <= {MAX_ROWS} (got {chunk_rows})')
     out = torch.empty(B, width, dtype=torch.int64, device=model.sos.device)
     with STEP_LOCK, torch.no_grad():
         was_training = model.training
         model.eval()
         try:
-            for b0 in range(0, B, MAX_ROWS):
-                n = min(MAX_ROWS, B - b0)
+            for b0 in range(0, B, chunk_rows):
+                n = min(chunk_rows, B - b0)
                 out[b0:b0 + n] = chunk(n, slice(b0, b0 + n))
         finally:
             model.train(was_training)
