@@ -1135,6 +1135,37 @@ int vqcpc_particle_permute_f32(float* buf, int64_t ld, int64_t width, const int3
 int vqcpc_particle_permute_cache(float* cache, int layers, int64_t W, int d, const int32_t* pos, const int32_t* ancestors,
                                  const int32_t* flag, int64_t M, int P, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Voice-leading rules as context-dependent token sets (csrc/rules.hip, decoders/generation.py `rules=`; the rule is restated in
+ * numpy in tests/rules_reference.py).  Exact integer logic.  rules: a mask of CROSSING 1 | LEAP 2 | PARALLEL 4.  kinds [nc][ldk]
+ * int32: per (voice, token) a MIDI pitch >= 0, HOLD -1, or REST / META below; max_leap [nc] int32 (< 0: off for that voice).
+ * Voice 0 is the top voice.  Position: column col, tick e = col / nc, voice v = col % nc.
+ * vqcpc_decode_rules: ONE launch, a wavefront per row, M <= 64, issued before vqcpc_decode_sample_masked inside the step.
+ *   col = pos[0] (win == NULL) or win[1] * U + pos[0]; pos[0] outside [0, T) or win[1] < 0: nothing happens.  History = every
+ *   column < col: tokens[b][c - win[1] * U] for c >= win[1] * U, else chorale[b][c].  pitch_at(u, e') walks back from tick e'
+ *   while voice u holds (no bound but column 0).  prev_u = pitch_at(u, e - 1); the known voices are u < v (emitted) and u > v
+ *   with constraint[b][e * nc + u] >= 0; now_u = the token's pitch, prev_u if it holds.  Candidate k of voice v with pitch p
+ *   (prev_v if it holds) breaks CROSSING when p lies above a known upper or below a known lower voice, LEAP when it is a
+ *   pitch further than max_leap[v] from prev_v, PARALLEL when v and a known u both move in the same direction from an
+ *   interval of 0 or 7 (mod 12) to the same interval.
+ *   Free position: E = static set (all of [0, V_v) without one) minus exclude[v]; while E has no candidate that breaks no
+ *   remaining rule, PARALLEL, then LEAP, then CROSSING is dropped.  sets[b][col][0..8) = static & survivors, bits >= V_v zero
+ *   (never empty inside the vocabulary: then the whole vocabulary is written); report[b][col] = the dropped enabled rules.
+ *   Forced position: sets = the static set unchanged (the whole vocabulary without one); report = the enabled rules the forced
+ *   token breaks, << 4.  Every write is a pure overwrite; a column at or past a leading dimension is not read / written.
+ * vqcpc_rules_audit: x [rows][ld], width columns (a multiple of nc): every token is taken as forced and all history comes
+ *   from x; report[b][c] = the enabled rules token c breaks, << 4 (0 where x < 0).  Grid of (column range, row).
+ * The launch functions refuse, before any HIP call: NULL required pointers, M outside [1, 64], nc > 16, V_c > 256 or > ldk,
+ * leading dimensions smaller than the widths.  No allocation or synchronisation.  Adding them left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_decode_rules(const int64_t* tokens, int64_t ldtok, int T, const int64_t* chorale, int64_t ldch, const int64_t* constraint,
+                       int64_t ldcons, const int32_t* kinds, int ldk, const int32_t* voice_offsets, int nc, const int32_t* max_leap,
+                       int rules, const uint32_t* exclude, const uint32_t* static_sets, int64_t ldstatic, uint32_t* sets,
+                       int64_t ldsets, int32_t* report, int64_t ldreport, const int32_t* pos, const int32_t* win, int U, int64_t M,
+                       void* stream);
+int vqcpc_rules_audit(const int64_t* x, int64_t ld, int64_t width, const int32_t* kinds, int ldk, const int32_t* voice_offsets, int nc,
+                      const int32_t* max_leap, int rules, int32_t* report, int64_t ldreport, int64_t rows, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

@@ -34,6 +34,7 @@ Hot path (`compute_loss`), all numerics in libvqcpc_hip.so:
 Reference defect fixed: `epoch` (:327-344) passes the quantizer's (B, S, num_codebooks) indices to `forward`, which
 raises; the codes are merged with `Encoder.merge_codes` first, as `generate` (:600) does.
 """
+import ctypes
 import os
 from datetime import datetime
 
@@ -459,7 +460,7 @@ class Decoder(FlatTraining, nn.Module):
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
                             use_graph=True, constraint=None, return_logp=False, return_attentions=False,
                             max_attention_bytes=4 << 30, allowed=None, return_allowed_mass=False, particles=None,
-                            resample_threshold=0.5, return_particles=False):
+                            resample_threshold=0.5, return_particles=False, rules=None, return_rule_report=False):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
@@ -506,12 +507,23 @@ class Decoder(FlatTraining, nn.Module):
         finished there), 'wn' (codes, B' * P) and 'ess' (codes, B').  The filter is exact -- a properly weighted sample and
         an unbiased evidence estimate -- for temperature=1, top_k=0, top_p=1; with a filtered proposal it is the heuristic
         that logp itself is, which always scores the unfiltered distribution.  ValueError with return_attentions.  Without
-        `particles` every launch, buffer and result is what it was."""
+        `particles` every launch, buffer and result is what it was.
+        rules: None, or a `templates.VoiceLeadingRules` (no crossing, bounded leaps, no parallel fifths / octaves): before every
+        draw vqcpc_decode_rules narrows the position's set -- `allowed`'s, or the whole vocabulary -- to the tokens that break
+        no rule against the voices already drawn at the tick and those `constraint` forces, relaxing the rules where none is
+        left.  It switches the step to the masked sampler as `allowed` does and combines with `allowed`, `constraint`,
+        `exclude_tokens` and `particles`; `allowed_mass` is then the mass of the narrowed set, so the particle weights see the
+        rules and rows that paint themselves into a corner die out.  return_rule_report=True -> `rule_report` after
+        allowed_mass and before attentions, int32 of the tokens' shape: at a drawn position the rules that had to be dropped
+        (bit 0 crossing, 1 leap, 2 parallel), at a forced one the rules its token breaks << 4.  Results:
+        (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles]).  Without the keywords every launch, buffer
+        and result is what it was."""
         from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev = self.sos.device
         layers = self._attention_layers(return_attentions)
         P = self._particle_count(particles, resample_threshold, return_particles, layers)
+        self._check_rules(rules, return_rule_report)
         codes = self._source_on_device(codes, 'codes', self.num_tokens_source)
         T, nc = self.num_tokens_target, self.num_channels
         if constraint is not None:
@@ -529,8 +541,10 @@ class Decoder(FlatTraining, nn.Module):
         filt = {} if particles is not None else None
         pkw = {} if particles is None else dict(particles=P, resample_threshold=resample_threshold,
                                                 final_resample=not return_particles)
+        rkw = {} if rules is None else dict(rules=rules)
         logp = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logp else None
         mass = torch.empty(B, T, dtype=torch.float32, device=dev) if return_allowed_mass else None
+        report = torch.empty(B, T, dtype=torch.int32, device=dev) if return_rule_report else None
         maps = None
         if layers is not None:
             self._check_attention_bytes(B, layers, T, True, max_attention_bytes)
@@ -541,12 +555,14 @@ class Decoder(FlatTraining, nn.Module):
             inc.prefill(codes[rows])
             inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens,
                       constraint=None if constraint is None else constraint[rows], want_logp=return_logp, want_attentions=layers,
-                      allowed=self._allowed_rows(allowed, n, rows), want_allowed_mass=return_allowed_mass, **pkw)
+                      allowed=self._allowed_rows(allowed, n, rows), want_allowed_mass=return_allowed_mass, **pkw, **rkw)
             tokens = inc.run(use_graph=use_graph)
             if return_logp:
                 logp[rows] = inc.logp
             if return_allowed_mass:
                 mass[rows] = inc.logmass
+            if return_rule_report:
+                report[rows] = inc.rule_report
             if maps is not None:
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
@@ -562,11 +578,53 @@ class Decoder(FlatTraining, nn.Module):
             out += (logp[keep].view(nk, T // nc, nc),)
         if return_allowed_mass:
             out += (mass[keep].view(nk, T // nc, nc),)
+        if return_rule_report:
+            out += (report[keep].view(nk, T // nc, nc),)
         if maps is not None:
             out += (self._join_attention_chunks(maps),)
         if return_particles and filt is not None:
             out += (self._join_particle_results(filt),)
         return out if len(out) > 1 else out[0]
+
+    def _check_rules(self, rules, return_rule_report):
+        """The checks of the rule keywords, once per call."""
+        from ..templates import VoiceLeadingRules
+        if rules is None:
+            if return_rule_report:
+                raise ValueError('return_rule_report=True needs rules=templates.VoiceLeadingRules(...)')
+            return
+        sizes = [int(v) for v in self.num_tokens_per_channel]
+        if not isinstance(rules, VoiceLeadingRules):
+            raise ValueError(f'rules: None or a templates.VoiceLeadingRules expected, got {type(rules).__name__}')
+        if rules.kinds.shape[0] != self.num_channels or rules.kinds.shape[1] < max(sizes):
+            raise ValueError(f'rules: a kinds table ({self.num_channels}, >= {max(sizes)}) expected for this decoder, got '
+                             f'{tuple(rules.kinds.shape)}')
+
+    def audit_voice_leading(self, x, rules):
+        """x: (rows, events, channels) tokens, rules: a `templates.VoiceLeadingRules` -> int32 of x's shape: the enabled rules
+        every token breaks against the other voices of its tick and the pitches held before it, << 4 (bit 4 crossing, 5 leap,
+        6 parallel) -- the forced half of `rule_report`, for a whole piece and without running the model (vqcpc_rules_audit).
+        Every token is taken as given, so a pair of voices that breaks a rule is reported at both."""
+        from .. import hip
+        self._check_rules(rules, False)
+        if rules is None:
+            raise ValueError('audit_voice_leading: rules=templates.VoiceLeadingRules(...) is needed')
+        x = torch.as_tensor(x)
+        nc, dev = self.num_channels, self.sos.device
+        if x.dim() != 3 or x.shape[2] != nc or x.shape[0] < 1 or x.shape[1] < 1 or x.dtype != torch.int64:
+            raise ValueError(f'x: (rows, events, {nc}) int64 tokens expected, got {tuple(x.shape)} {x.dtype}')
+        rows, events = x.shape[0], x.shape[1]
+        flat = x.to(dev).reshape(rows, events * nc).contiguous()
+        offsets = [0]
+        for v in self.num_tokens_per_channel:
+            offsets.append(offsets[-1] + int(v))
+        report = torch.empty(rows, events * nc, dtype=torch.int32, device=dev)
+        kinds, leap = rules.kinds.to(dev).contiguous(), rules.max_leap.to(dev).contiguous()
+        for r0 in range(0, rows, 65535):
+            n = min(65535, rows - r0)
+            hip.call('vqcpc_rules_audit', flat[r0:r0 + n], events * nc, events * nc, kinds, kinds.shape[1],
+                     (ctypes.c_int32 * (nc + 1))(*offsets), nc, leap, rules.mask, report[r0:r0 + n], events * nc, n)
+        return report.view(rows, events, nc)
 
     @staticmethod
     def _particle_count(particles, resample_threshold, return_particles, attention_layers):
@@ -628,7 +686,7 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
                  plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None, return_attentions=False,
-                 max_attention_bytes=4 << 30, particles=None, resample_threshold=0.5):
+                 max_attention_bytes=4 << 30, particles=None, resample_threshold=0.5, rules=None, return_rule_report=False):
         """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
@@ -643,7 +701,8 @@ class Decoder(FlatTraining, nn.Module):
         recorded layer (the encoder's layer of that index, or its last), plus `layers`.  Row t of self_attns_encoder is the
         encoder's row (t // channels * channels) // tokens-per-code, the code of t's event (:650-659).
         particles, resample_threshold: `generate_from_codes`'s particle filter over the kept voices (each of the `batch_size`
-        generations is the survivor of its own group of `particles` rows)."""
+        generations is the survivor of its own group of `particles` rows).
+        rules, return_rule_report: `generate_from_codes`'s voice-leading rules; the result gains 'rule_report'."""
         if plot_attentions:
             raise NotImplementedError('plot_attentions: no plots are drawn here (no matplotlib); return_attentions=True returns '
                                       'the attention maps of every emitted token and writes them as arrays')
@@ -679,14 +738,18 @@ class Decoder(FlatTraining, nn.Module):
                                          seed=seed, constraint=constraint, return_attentions=layers or False,
                                          max_attention_bytes=max_attention_bytes,
                                          **({} if particles is None else dict(particles=particles,
-                                                                              resample_threshold=resample_threshold)))
-            attentions = None
-            if layers is not None:
-                x, attentions = x
+                                                                              resample_threshold=resample_threshold)),
+                                         rules=rules, return_rule_report=return_rule_report)
+            res = x if isinstance(x, tuple) else (x,)                    # (tokens[, rule_report][, attentions])
+            x = res[0]
+            rule_report = res[1] if return_rule_report else None
+            attentions = res[-1] if layers is not None else None
             recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
             self.train(was_training)
         extra = {} if attentions is None else {'attentions': attentions}
+        if rule_report is not None:
+            extra['rule_report'] = rule_report
         if recoding is None:
             return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': None, **extra}
         timestamp = datetime.now().strftime('%Y-%m-%d_%H-%M-%S')
@@ -761,7 +824,8 @@ class Decoder(FlatTraining, nn.Module):
                                 num_decodings=1, code_index_start=None, code_index_end=None, seed=None, pad=None, start=None,
                                 use_graph=True, constraint=None, return_logp=False, return_attentions=False,
                                 max_attention_bytes=4 << 30, graph_slides=None, allowed=None, return_allowed_mass=False,
-                                particles=None, resample_threshold=0.5, return_particles=False):
+                                particles=None, resample_threshold=0.5, return_particles=False, rules=None,
+                                return_rule_report=False):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -791,7 +855,10 @@ class Decoder(FlatTraining, nn.Module):
         allowed_mass has the tokens' shape.  Results: (tokens[, logp][, allowed_mass][, attentions]).
         particles, resample_threshold, return_particles: as in `generate_from_codes`; the groups are resampled after every
         generated code, the K/V caches move where the next code is generated in the same window (a slide recomputes them from
-        the moved tokens), and the histories of the returned dict have one row per code of the WHOLE sequence."""
+        the moved tokens), and the histories of the returned dict have one row per code of the WHOLE sequence.
+        rules, return_rule_report: as in `generate_from_codes`.  A held pitch is followed back through the chorale however far
+        it reaches, also past the model window and before code_index_start (the PAD / START frame has no pitch).  rule_report
+        has the tokens' shape, after allowed_mass and before attentions."""
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
@@ -800,6 +867,7 @@ class Decoder(FlatTraining, nn.Module):
         dev = self.sos.device
         layers = self._attention_layers(return_attentions)
         P = self._particle_count(particles, resample_threshold, return_particles, layers)
+        self._check_rules(rules, return_rule_report)
         codes = self._source_on_device(encoding_indices, 'encoding_indices')
         S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
         nb = codes.shape[1]
@@ -828,8 +896,10 @@ class Decoder(FlatTraining, nn.Module):
         filt = {} if particles is not None else None
         pkw = {} if particles is None else dict(particles=P, resample_threshold=resample_threshold,
                                                 final_resample=not return_particles)
+        rkw = {} if rules is None else dict(rules=rules)
         logp = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_logp else None
         mass = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_allowed_mass else None
+        report = torch.empty(B, nb * U, dtype=torch.int32, device=dev) if return_rule_report else None
         maps = None
         if layers is not None:
             self._check_attention_bytes(B, layers, nb * U, False, max_attention_bytes)
@@ -842,12 +912,14 @@ class Decoder(FlatTraining, nn.Module):
                            top_k=top_k, top_p=top_p, exclude=exclude,
                            constraint=None if constraint is None else constraint[rows], want_logp=return_logp,
                            want_attentions=layers, allowed=self._allowed_rows(allowed, n, rows),
-                           want_allowed_mass=return_allowed_mass, **pkw)
+                           want_allowed_mass=return_allowed_mass, **pkw, **rkw)
             tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph, graph_slides=graph_slides)
             if return_logp:
                 logp[rows] = inc.logp
             if return_allowed_mass:
                 mass[rows] = inc.logmass
+            if return_rule_report:
+                report[rows] = inc.rule_report
             if maps is not None:
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
@@ -861,6 +933,8 @@ class Decoder(FlatTraining, nn.Module):
         res = (cut(out), cut(logp)) if return_logp else (cut(out),)
         if return_allowed_mass:
             res += (cut(mass),)
+        if return_rule_report:
+            res += (cut(report),)
         if maps is not None:
             res += (self._join_attention_chunks(maps),)
         if return_particles and filt is not None:
@@ -871,7 +945,7 @@ class Decoder(FlatTraining, nn.Module):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent
         tensors, concatenated along time) decoded as one sequence, the body's events returned: int64 (num_decodings, events,
         channels).  kwargs go to `generate_from_code_long` -- `allowed` and `return_allowed_mass` among them, in the coordinates
-        of the whole start + body + end sequence."""
+        of the whole start + body + end sequence, and `rules` / `return_rule_report`, which need no coordinates."""
         if start_codes is None or end_codes is None or body_codes is None or temperature is None:
             raise NotImplementedError('generate_alla_mano(start_codes, end_codes, body_codes, temperature): generation '
                                       'without codes is not implemented')
@@ -888,7 +962,8 @@ class Decoder(FlatTraining, nn.Module):
                                             code_index_end=len(start_codes) + len(body_codes), **kwargs)
 
     def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False,
-                           keep_voices=None, return_logp=False, allowed=None, return_allowed_mass=False, **kwargs):
+                           keep_voices=None, return_logp=False, allowed=None, return_allowed_mass=False, rules=None,
+                           return_rule_report=False, **kwargs):
         """The body of generate_reharmonisation (:871-941) on a (1, events, channels) token tensor: the chorale is cut into
         model-sized chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD),
         every chunk is encoded, the codes are glued and the chorale's own codes are decoded `num_reharmonisations` times.
@@ -902,7 +977,9 @@ class Decoder(FlatTraining, nn.Module):
         allowed: bool (x.shape[1], channels, vmax) or (1, x.shape[1], channels, vmax), the token sets of `generate_from_codes` in
         x's OWN event coordinates (what `templates.rhythm_mask(x, kinds)` returns): event e of x restricts chorale event E + e,
         every other event stays unrestricted.  return_allowed_mass=True: `tokens` above is the tuple of
-        `generate_from_code_long`, (tokens[, logp], allowed_mass)."""
+        `generate_from_code_long`, (tokens[, logp], allowed_mass).
+        rules, return_rule_report: `generate_from_code_long`'s; the rules compare the voices of a tick, so they need no
+        coordinates, and rule_report comes back with the tokens, in the same events."""
         n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
         if n2i is None:
             raise ValueError('reharmonise_tokens needs dataset.note2index_dicts with the START / END / XX symbols')
@@ -957,7 +1034,8 @@ class Decoder(FlatTraining, nn.Module):
         kwargs['return_allowed_mass'] = return_allowed_mass
         tokens = self.generate_from_code_long(codes, temperature=temperature, top_k=top_k, top_p=top_p,
                                               num_decodings=num_reharmonisations, code_index_start=code_index_start,
-                                              code_index_end=code_index_end, return_logp=return_logp, **kwargs)
+                                              code_index_end=code_index_end, return_logp=return_logp, rules=rules,
+                                              return_rule_report=return_rule_report, **kwargs)
         return (tokens, code_index_start, code_index_end, codes.size(1)) if return_bounds else tokens
 
     def generate_reharmonisation(self, *a, **k):

@@ -48,7 +48,12 @@ Particles (`start(particles=P)`, csrc/particles.hip): the rows are groups of P c
 steps of a code, vqcpc_particle_resample adds the code's forced logp / free logmass to every row's log-weight and, where a
 group's effective sample size fell below the threshold, draws its ancestors; vqcpc_particle_permute_* then moves the ancestors'
 state -- live tokens, chorale row, logp / logmass rows, next input row, K/V cache rows [0, pos) -- onto the rows in place.  Both
-read `pos` and `win` from device memory and sit BETWEEN the replays: the captured step and slide are what they were."""
+read `pos` and `win` from device memory and sit BETWEEN the replays: the captured step and slide are what they were.
+
+Voice-leading rules (`start(rules=...)`, csrc/rules.hip): the caller's static sets move to `rule_static` and `allowed` becomes the
+rule kernel's output; vqcpc_decode_rules runs immediately before vqcpc_decode_sample_masked, INSIDE the captured step, and
+overwrites the live column's set from the tokens emitted so far (the live window's, and the chorale's before it) and the
+column of `rule_report`.  The sampler, the mass and the particle weights read that set unchanged."""
 import ctypes
 
 import torch
@@ -96,6 +101,7 @@ class IncrementalDecoder(IncrementalStack):
         self.memkv = None
         self.constraint, self.logp, self.constrained = None, None, False
         self.allowed, self.logmass, self.masked = None, None, False
+        self.rules, self.rule_static, self.rule_report = None, None, None
         self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
         self.particles = None                                                     # group size P, or None: plain rows
         self.continuous = bool(getattr(dec, 'continuous_source', False))
@@ -148,7 +154,7 @@ class IncrementalDecoder(IncrementalStack):
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
               constraint=None, want_logp=False, want_attentions=None, allowed=None, want_allowed_mass=False, particles=None,
-              resample_threshold=0.5, final_resample=True):
+              resample_threshold=0.5, final_resample=True, rules=None):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
         probabilities of the last step in `probs` (M, max V_c).
@@ -165,7 +171,10 @@ class IncrementalDecoder(IncrementalStack):
         particles: None, or P in [2, 64] dividing M: the rows are M / P groups of P particles, resampled after every code
         (`_resample`); logp / logmass are then kept whenever a constraint / sets are given.  resample_threshold: a group
         resamples when its effective sample size falls below resample_threshold * P; final_resample: after the last code one
-        forced resampling makes the first row of every group an unweighted draw from the final weights."""
+        forced resampling makes the first row of every group an unweighted draw from the final weights.
+        rules: None, or a `templates.VoiceLeadingRules`: vqcpc_decode_rules writes every position's set before the masked
+        sampler reads it (`_rule_sets`); `rule_report` (M, T) int32 keeps what was relaxed or broken, -1 where no token was
+        emitted yet."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
@@ -184,7 +193,8 @@ class IncrementalDecoder(IncrementalStack):
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
         self._particles(particles, resample_threshold, final_resample, self.S, self.seeds, want_attentions)
         self._constrain(constraint, want_logp or (particles is not None and constraint is not None), self.T, None)
-        self._mask(allowed, want_allowed_mass or (particles is not None and allowed is not None), self.T)
+        self._mask(allowed, want_allowed_mass or (particles is not None and (allowed is not None or rules is not None)), self.T)
+        self._rule_sets(rules, self.T)
         self._record_attentions(want_attentions, self.T, None, 1)
         self.reset()
 
@@ -253,7 +263,7 @@ class IncrementalDecoder(IncrementalStack):
         hip.call('vqcpc_particle_permute_i64', self.tokens, self.T, self.T, self.pos, anc, flag, M, P)
         if chorale is not None:
             hip.call('vqcpc_particle_permute_i64', chorale, chorale.shape[1], chorale.shape[1], None, anc, flag, M, P)
-        for rows in (self.logp, self.logmass):
+        for rows in (self.logp, self.logmass, self.rule_report):     # the report's int32 rows move as 4-byte words
             if rows is not None:
                 hip.call('vqcpc_particle_permute_f32', rows, w, w, None, anc, flag, M, P)
         if not last:
@@ -300,6 +310,26 @@ class IncrementalDecoder(IncrementalStack):
         self.logmass = torch.full((self.M, width), float('nan'), dtype=torch.float32, device=self.dev) if want_mass else None
         self.masked = allowed is not None or bool(want_mass)
 
+    def _rule_sets(self, rules, width):
+        """The rule kernel's buffers (after `_mask`): `kinds` and `max_leap` are uploaded once; the caller's sets stay in
+        `rule_static` (None: none) and `allowed`, the buffer the sampler reads, becomes the kernel's output, which overwrites the
+        live column at every step; `rule_report` (M, width) int32 -- a dtype vqcpc_particle_permute_f32 moves -- starts at -1."""
+        self.rules = self.rule_static = self.rule_report = None
+        if rules is None:
+            return
+        if self.teacher is not None:
+            raise ValueError('rules and teacher exclude each other')
+        kinds = rules.kinds
+        if kinds.shape[0] != self.nc or kinds.shape[1] < self.vmax:
+            raise ValueError(f'rules: a kinds table ({self.nc}, >= {self.vmax}) expected, got {tuple(kinds.shape)}')
+        self.rules = rules
+        self.rule_kinds = kinds.to(self.dev, torch.int32).contiguous()
+        self.rule_leap = rules.max_leap.to(self.dev, torch.int32).contiguous()
+        self.rule_static = self.allowed
+        self.allowed = torch.zeros(self.M, width, 8, dtype=torch.int32, device=self.dev)
+        self.rule_report = torch.full((self.M, width), -1, dtype=torch.int32, device=self.dev)
+        self.masked = True
+
     def _record_attentions(self, layers, rows, win, stride):
         """The attention-map buffers, allocated here once (before any warm-up step: a captured step holds their addresses):
         rows = T and win = None for the fixed window, rows = nb * U, win = the device window index and stride = U in long mode
@@ -331,6 +361,8 @@ class IncrementalDecoder(IncrementalStack):
             self.logp.fill_(float('nan'))                                               # what a warm-up step wrote
         if self.logmass is not None:
             self.logmass.fill_(float('nan'))
+        if self.rule_report is not None:
+            self.rule_report.fill_(-1)
         for maps in (self.self_probs, self.cross_probs):
             if maps is not None:
                 maps.fill_(float('nan'))
@@ -363,6 +395,12 @@ class IncrementalDecoder(IncrementalStack):
         T, d = self.T, self.d
         if self.masked:
             w = self._cons_width
+            if self.rules is not None:                        # the live column's set, from the tokens emitted so far
+                windowed = self._cons_win is not None         # long mode: the history before the live window is the chorale's
+                hip.call('vqcpc_decode_rules', self.tokens, T, T, self.chorale if windowed else None, w if windowed else 0,
+                         self.constraint, w, self.rule_kinds, self.rule_kinds.shape[1], self._offsets_c, self.nc, self.rule_leap,
+                         self.rules.mask, self.exclude if self.excluding else None, self.rule_static, w, self.allowed, w,
+                         self.rule_report, w, self.pos, self._cons_win, self.U, self.M)
             hip.call('vqcpc_decode_sample_masked', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M,
                      self.temperature, self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds,
                      self.constraint, w, self.logp, w, self._cons_win, self.allowed, w, self.logmass, w, self.tokens, T, T,
@@ -406,7 +444,7 @@ class IncrementalDecoder(IncrementalStack):
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
     def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, allowed=None,
-                   want_allowed_mass=False, particles=None, resample_threshold=0.5, final_resample=True, **sampling):
+                   want_allowed_mass=False, particles=None, resample_threshold=0.5, final_resample=True, rules=None, **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
         tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
         want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
@@ -416,6 +454,8 @@ class IncrementalDecoder(IncrementalStack):
         allowed, want_allowed_mass: as in `start`, but (M, nb * U, 8) / `logmass` (M, nb * U), in chorale coordinates like the
         constraint.
         particles, resample_threshold, final_resample: as in `start`; the histories have one row per code of the chorale.
+        rules: as in `start`, with `rule_report` (M, nb * U) in chorale coordinates; the history of a position reaches back through
+        the chorale, wherever the model window lies.
         sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
@@ -441,7 +481,8 @@ class IncrementalDecoder(IncrementalStack):
         self.start(seeds=seeds, **sampling)
         self._particles(particles, resample_threshold, final_resample, nb, self.row_seeds, want_attentions)
         self._constrain(constraint, want_logp or (particles is not None and constraint is not None), nb * U, self.win)
-        self._mask(allowed, want_allowed_mass or (particles is not None and allowed is not None), nb * U)
+        self._mask(allowed, want_allowed_mass or (particles is not None and (allowed is not None or rules is not None)), nb * U)
+        self._rule_sets(rules, nb * U)
         self._record_attentions(want_attentions, nb * U, self.win, U)
         self.row_seeds.copy_(self.seeds)
 

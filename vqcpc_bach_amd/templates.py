@@ -8,7 +8,8 @@ reference's dataset) into bool masks (..., events, voices, vmax).  No kernel her
     allowed = rhythm_mask(chorale, kinds) & pitch_class_mask(kinds, g_major) & range_mask(kinds, low, high)
 
 Masks combine with `&`; a combination that leaves some (event, voice) without a token is refused by the generation call,
-which names the place."""
+which names the place.  Rules BETWEEN the voices -- no crossing, bounded leaps, no parallel fifths or octaves -- are not masks:
+`VoiceLeadingRules` (`rules=`) is applied on the device during the generation (csrc/rules.hip)."""
 import re
 
 import numpy as np
@@ -53,6 +54,58 @@ def _kinds(kinds):
     if kinds.dim() != 2 or kinds.is_floating_point():
         raise ValueError(f'kinds: the (voices, vmax) integer table of token_kinds expected, got {tuple(kinds.shape)}')
     return kinds.cpu().long()
+
+
+class VoiceLeadingRules:
+    """Relational rules between the voices, for `generate_from_codes(rules=...)` and the long forms.  Unlike the masks above
+    they cannot be decided before the generation: whether a token breaks one depends on what the other voices drew at this
+    tick and on the pitch every voice still holds, so a kernel (csrc/rules.hip) narrows every position's token set on the
+    device, between two steps, from the tokens emitted so far.
+
+        rules = VoiceLeadingRules(kinds, no_crossing=True, max_leap=12, no_parallels=True)
+
+    kinds: the (voices, vmax) table of `token_kinds`.  The voices are ordered top to bottom by index -- soprano = 0, as in the
+    Bach corpus; another order is not supported.
+    no_crossing: a voice never sounds above a voice of lower index or below one of higher index.
+    max_leap: None (off), one int >= 0 for every voice, or one entry per voice (None or negative: off for that voice): the
+    largest step in semitones from the pitch the voice sounded last (through holds; a rest forgets it).
+    no_parallels: no parallel fifths or octaves (unisons included) between two voices that move in the same direction.
+    A voice is compared with the voices already drawn at its tick and with those a `constraint` forces.  Where the rules leave
+    no token of the position's set, they are relaxed for that position -- parallels first, then the leap, then the crossing --
+    and `return_rule_report=True` says where: bit 0 CROSSING, bit 1 LEAP, bit 2 PARALLEL were dropped; a forced token reports
+    the rules it breaks in bits 4..6.  ValueError on a wrong table, a negative max_leap, or when no rule is enabled."""
+    CROSSING, LEAP, PARALLEL = 1, 2, 4
+
+    def __init__(self, kinds, no_crossing=True, max_leap=None, no_parallels=False):
+        kinds = torch.as_tensor(kinds)
+        if kinds.dim() != 2 or kinds.is_floating_point() or kinds.is_complex() or kinds.dtype == torch.bool or \
+                not 1 <= kinds.shape[0] <= 16 or not 1 <= kinds.shape[1] <= 256:
+            raise ValueError(f'VoiceLeadingRules: the (voices <= 16, vmax <= 256) integer table of token_kinds expected, got '
+                             f'{tuple(kinds.shape)} {kinds.dtype}')
+        kinds = kinds.cpu().to(torch.int64)
+        if bool((kinds < META).any()) or bool((kinds > 127).any()):
+            raise ValueError('VoiceLeadingRules: kinds holds MIDI pitches in [0, 127], HOLD, REST or META')
+        voices = kinds.shape[0]
+        if max_leap is None:
+            leaps = [-1] * voices
+        elif isinstance(max_leap, (int, np.integer)) and not isinstance(max_leap, bool):
+            if max_leap < 0:
+                raise ValueError(f'VoiceLeadingRules: max_leap >= 0 expected, got {max_leap}')
+            leaps = [int(max_leap)] * voices
+        else:
+            try:
+                leaps = [-1 if m is None or int(m) < 0 else int(m) for m in max_leap]
+            except TypeError:
+                raise ValueError(f'VoiceLeadingRules: max_leap is None, an int or one entry per voice, got {max_leap!r}')
+            if len(leaps) != voices:
+                raise ValueError(f'VoiceLeadingRules: one max_leap per voice ({voices}) expected, got {len(leaps)}')
+        self.kinds = kinds.to(torch.int32).contiguous()
+        self.max_leap = torch.tensor(leaps, dtype=torch.int32)
+        self.no_crossing, self.no_parallels = bool(no_crossing), bool(no_parallels)
+        self.mask = (self.CROSSING if self.no_crossing else 0) | (self.LEAP if any(m >= 0 for m in leaps) else 0) | \
+            (self.PARALLEL if self.no_parallels else 0)
+        if self.mask == 0:
+            raise ValueError('VoiceLeadingRules: no rule is enabled')
 
 
 def rhythm_mask(template_tokens, kinds):
