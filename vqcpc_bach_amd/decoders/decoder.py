@@ -518,72 +518,101 @@ class Decoder(FlatTraining, nn.Module):
         (bit 0 crossing, 1 leap, 2 parallel), at a forced one the rules its token breaks << 4.  Results:
         (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles]).  Without the keywords every launch, buffer
         and result is what it was."""
+        return self._result_tuple(self._window_results(
+            codes, exclude_tokens, use_graph, temperature=temperature, top_k=top_k, top_p=top_p, num_decodings=num_decodings,
+            seed=seed, constraint=constraint, return_logp=return_logp, return_attentions=return_attentions,
+            max_attention_bytes=max_attention_bytes, allowed=allowed, return_allowed_mass=return_allowed_mass, particles=particles,
+            resample_threshold=resample_threshold, return_particles=return_particles, rules=rules,
+            return_rule_report=return_rule_report))
+
+    def _window_results(self, codes, exclude_tokens, use_graph, **options):
+        """`generate_from_codes` with its results by name (`_generate_rows`)."""
+        def drive(inc, codes, settings):
+            inc.prefill(codes)
+            inc.start(**settings)
+            return inc.run(use_graph=use_graph)
+        form = lambda codes: dict(events=self.num_tokens_target // self.num_channels, first=0, last=None, exclude=exclude_tokens,
+                                  drive=drive, maps=lambda: {'self_attns_encoder': []})
+        return self._generate_rows(codes, 'codes', self.num_tokens_source, form, **options)
+
+    def _generate_rows(self, source, name, length, form, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, seed=None,
+                       constraint=None, return_logp=False, return_attentions=False, max_attention_bytes=4 << 30, allowed=None,
+                       return_allowed_mass=False, particles=None, resample_threshold=0.5, return_particles=False, rules=None,
+                       return_rule_report=False):
+        """The body the public generators share: the option checks, then the source (`_source_on_device(source, name, length)`),
+        then `form(codes)`, what the fixed window and the chorale differ in -- a dict of
+          events, first, last   the events of a row, and the range [first, last) of them that is generated
+          exclude               the per-voice excluded token ids
+          drive                 drive(stack, the chunk's codes, the keywords of its `start`) -> the chunk's (n, events * channels) tokens
+          maps                  maps() -> the attention maps kept next to the decoder's: 'self_attns_encoder': [] (the stack's
+                                `enc_probs` of every chunk) or 'window_start': a tensor
+        -- then packing, repetition by num_decodings * particles, seeds, the chunks on their own stacks and their records.
+        -> a dict in the documented order of the results, every row (a group's first one with particles, unless they are returned)
+        as (rows, events, channels): 'tokens', 'logp', 'allowed_mass', 'rule_report', then 'attentions' and 'particles'; what was
+        not asked for is None."""
         from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
-        dev = self.sos.device
+        dev, nc = self.sos.device, self.num_channels
         layers = self._attention_layers(return_attentions)
         P = self._particle_count(particles, resample_threshold, return_particles, layers)
         self._check_rules(rules, return_rule_report)
-        codes = self._source_on_device(codes, 'codes', self.num_tokens_source)
-        T, nc = self.num_tokens_target, self.num_channels
+        codes = self._source_on_device(source, name, length)
+        form = form(codes)
+        events, first, last, exclude = form['events'], form['first'], form['last'], form['exclude']
         if constraint is not None:
-            constraint = self._constraint_rows(constraint, codes.shape[0], T // nc)
+            constraint = self._constraint_rows(constraint, codes.shape[0], events, first, last)
         if allowed is not None:
-            allowed = self._allowed_words(allowed, codes.shape[0], T // nc, exclude=exclude_tokens, constraint=constraint)
+            allowed = self._allowed_words(allowed, codes.shape[0], events, first, last, exclude=exclude, constraint=constraint)
         if num_decodings * P > 1:
             codes = codes.repeat_interleave(num_decodings * P, dim=0)
             if constraint is not None:
                 constraint = constraint.repeat_interleave(num_decodings * P, dim=0)
             if allowed is not None and allowed.shape[0] > 1:
                 allowed = allowed.repeat_interleave(num_decodings * P, dim=0)
-        B = codes.shape[0]
+        B, width = codes.shape[0], events * nc
         seeds = row_seeds(seed, B)
-        filt = {} if particles is not None else None
-        pkw = {} if particles is None else dict(particles=P, resample_threshold=resample_threshold,
-                                                final_resample=not return_particles)
-        rkw = {} if rules is None else dict(rules=rules)
-        logp = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logp else None
-        mass = torch.empty(B, T, dtype=torch.float32, device=dev) if return_allowed_mass else None
-        report = torch.empty(B, T, dtype=torch.int32, device=dev) if return_rule_report else None
-        maps = None
+        settings = dict(temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude, want_logp=return_logp,
+                        want_attentions=layers, want_allowed_mass=return_allowed_mass, particles=None if particles is None else P,
+                        resample_threshold=resample_threshold, final_resample=not return_particles, rules=rules)
+        kept = {'logp': ('logp', torch.float32, return_logp), 'allowed_mass': ('logmass', torch.float32, return_allowed_mass),
+                'rule_report': ('rule_report', torch.int32, return_rule_report)}          # result: the stack's buffer, ...
+        records = {key: torch.empty(B, width, dtype=dtype, device=dev) for key, (_, dtype, wanted) in kept.items() if wanted}
+        maps = filt = None
         if layers is not None:
-            self._check_attention_bytes(B, layers, T, True, max_attention_bytes)
-            maps = {'layers': layers, 'self_attns_decoder': [], 'attns_cross': [], 'self_attns_encoder': []}
+            maps = {'layers': layers, 'self_attns_decoder': [], 'attns_cross': [], **form['maps']()}
+            self._check_attention_bytes(B, layers, width, 'self_attns_encoder' in maps, max_attention_bytes)
+        if particles is not None:
+            filt = {}
 
         def chunk(n, rows):
             inc = IncrementalDecoder(self, n)
-            inc.prefill(codes[rows])
-            inc.start(seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude_tokens,
-                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp, want_attentions=layers,
-                      allowed=self._allowed_rows(allowed, n, rows), want_allowed_mass=return_allowed_mass, **pkw, **rkw)
-            tokens = inc.run(use_graph=use_graph)
-            if return_logp:
-                logp[rows] = inc.logp
-            if return_allowed_mass:
-                mass[rows] = inc.logmass
-            if return_rule_report:
-                report[rows] = inc.rule_report
+            tokens = form['drive'](inc, codes[rows], dict(settings, seeds=seeds[rows],
+                                                          constraint=None if constraint is None else constraint[rows],
+                                                          allowed=self._allowed_rows(allowed, n, rows)))
+            for key, buf in records.items():
+                buf[rows] = getattr(inc, kept[key][0])
             if maps is not None:
                 maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
                 maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
-                maps['self_attns_encoder'].append(torch.stack(inc.enc_probs, dim=1))
+                if 'self_attns_encoder' in maps:
+                    maps['self_attns_encoder'].append(torch.stack(inc.enc_probs, dim=1))
             if filt is not None:
                 self._keep_particle_results(filt, inc.particle_results(), rows.start)
             return tokens
-        tokens = generate_in_chunks(self, B, T, chunk, MAX_ROWS // P * P)            # whole groups (P = 1: MAX_ROWS, as before)
+        tokens = generate_in_chunks(self, B, width, chunk, MAX_ROWS // P * P)        # whole groups (P = 1: MAX_ROWS, as before)
         keep = slice(None) if particles is None or return_particles else slice(0, B, P)      # a group's first row
         nk = len(range(B)[keep])
-        out = (tokens[keep].view(nk, T // nc, nc),)
-        if return_logp:
-            out += (logp[keep].view(nk, T // nc, nc),)
-        if return_allowed_mass:
-            out += (mass[keep].view(nk, T // nc, nc),)
-        if return_rule_report:
-            out += (report[keep].view(nk, T // nc, nc),)
-        if maps is not None:
-            out += (self._join_attention_chunks(maps),)
-        if return_particles and filt is not None:
-            out += (self._join_particle_results(filt),)
+        res = {'tokens': tokens, **{key: records.get(key) for key in kept}}
+        res = {key: None if t is None else t[keep].view(nk, events, nc) for key, t in res.items()}
+        res['attentions'] = None if maps is None else self._join_attention_chunks(maps)
+        res['particles'] = self._join_particle_results(filt) if return_particles and filt is not None else None
+        return res
+
+    @staticmethod
+    def _result_tuple(res, cut=lambda t: t):
+        """`_generate_rows`'s results -> the documented (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles]),
+        `tokens` alone when nothing else was asked for; cut: applied to the per-token tensors."""
+        out = tuple(cut(v) if torch.is_tensor(v) else v for v in res.values() if v is not None)
         return out if len(out) > 1 else out[0]
 
     def _check_rules(self, rules, return_rule_report):
@@ -734,16 +763,11 @@ class Decoder(FlatTraining, nn.Module):
             if voices is not None:
                 constraint = torch.full_like(x_original, -1)
                 constraint[:, :, voices] = x_original[:, :, voices]
-            x = self.generate_from_codes(codes, temperature=temperature, top_k=top_k, top_p=top_p, exclude_tokens=exclude,
-                                         seed=seed, constraint=constraint, return_attentions=layers or False,
-                                         max_attention_bytes=max_attention_bytes,
-                                         **({} if particles is None else dict(particles=particles,
-                                                                              resample_threshold=resample_threshold)),
-                                         rules=rules, return_rule_report=return_rule_report)
-            res = x if isinstance(x, tuple) else (x,)                    # (tokens[, rule_report][, attentions])
-            x = res[0]
-            rule_report = res[1] if return_rule_report else None
-            attentions = res[-1] if layers is not None else None
+            res = self._window_results(codes, exclude, True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                       constraint=constraint, return_attentions=layers or False,
+                                       max_attention_bytes=max_attention_bytes, particles=particles,
+                                       resample_threshold=resample_threshold, rules=rules, return_rule_report=return_rule_report)
+            x, rule_report, attentions = res['tokens'], res['rule_report'], res['attentions']
             recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
             self.train(was_training)
@@ -862,84 +886,32 @@ class Decoder(FlatTraining, nn.Module):
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
-        from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
-        from .generation import IncrementalDecoder
-        dev = self.sos.device
-        layers = self._attention_layers(return_attentions)
-        P = self._particle_count(particles, resample_threshold, return_particles, layers)
-        self._check_rules(rules, return_rule_report)
-        codes = self._source_on_device(encoding_indices, 'encoding_indices')
-        S, U, nc = self.num_tokens_source, self.total_upscaling, self.num_channels
-        nb = codes.shape[1]
-        if nb < S:
-            raise ValueError(f'encoding_indices: at least {S} codes (one model window) are needed, got {nb}')
-        code_index_start = 0 if code_index_start is None else int(code_index_start)
-        code_index_end = nb if code_index_end is None else int(code_index_end)
-        if not 0 <= code_index_start <= code_index_end <= nb:
-            raise ValueError(f'0 <= code_index_start <= code_index_end <= {nb} expected, got {code_index_start}, {code_index_end}')
-        epc = self.num_events_per_code
-        exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
-        chorale = self.init_generation_chorale(num_events=nb * epc, start_index=code_index_start * epc, pad=pad, start=start)
-        if constraint is not None:
-            constraint = self._constraint_rows(constraint, codes.shape[0], nb * epc, code_index_start * epc, code_index_end * epc)
-        if allowed is not None:
-            allowed = self._allowed_words(allowed, codes.shape[0], nb * epc, code_index_start * epc, code_index_end * epc,
-                                          exclude=exclude, constraint=constraint)
-        if num_decodings * P > 1:
-            codes = codes.repeat_interleave(num_decodings * P, dim=0)
-            if constraint is not None:
-                constraint = constraint.repeat_interleave(num_decodings * P, dim=0)
-            if allowed is not None and allowed.shape[0] > 1:
-                allowed = allowed.repeat_interleave(num_decodings * P, dim=0)
-        B = codes.shape[0]
-        seeds = row_seeds(seed, B)
-        filt = {} if particles is not None else None
-        pkw = {} if particles is None else dict(particles=P, resample_threshold=resample_threshold,
-                                                final_resample=not return_particles)
-        rkw = {} if rules is None else dict(rules=rules)
-        logp = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_logp else None
-        mass = torch.empty(B, nb * U, dtype=torch.float32, device=dev) if return_allowed_mass else None
-        report = torch.empty(B, nb * U, dtype=torch.int32, device=dev) if return_rule_report else None
-        maps = None
-        if layers is not None:
-            self._check_attention_bytes(B, layers, nb * U, False, max_attention_bytes)
-            maps = {'layers': layers, 'self_attns_decoder': [], 'attns_cross': [],
-                    'window_start': self.attention_window_starts(nb, S, U, code_index_start, code_index_end)}
+        S, U, epc = self.num_tokens_source, self.total_upscaling, self.num_events_per_code
 
-        def chunk(n, rows):
-            inc = IncrementalDecoder(self, n)
-            inc.start_long(codes[rows], chorale.reshape(1, -1).expand(n, -1), seeds=seeds[rows], temperature=temperature,
-                           top_k=top_k, top_p=top_p, exclude=exclude,
-                           constraint=None if constraint is None else constraint[rows], want_logp=return_logp,
-                           want_attentions=layers, allowed=self._allowed_rows(allowed, n, rows),
-                           want_allowed_mass=return_allowed_mass, **pkw, **rkw)
-            tokens = inc.run_long(code_index_start, code_index_end, use_graph=use_graph, graph_slides=graph_slides)
-            if return_logp:
-                logp[rows] = inc.logp
-            if return_allowed_mass:
-                mass[rows] = inc.logmass
-            if return_rule_report:
-                report[rows] = inc.rule_report
-            if maps is not None:
-                maps['self_attns_decoder'].append(inc.self_probs.transpose(0, 1))
-                maps['attns_cross'].append(None if inc.cross_probs is None else inc.cross_probs.transpose(0, 1))
-            if filt is not None:
-                self._keep_particle_results(filt, inc.particle_results(), rows.start)
-            return tokens
-        out = generate_in_chunks(self, B, nb * U, chunk, MAX_ROWS // P * P)           # whole groups (P = 1: MAX_ROWS, as before)
-        keep = slice(None) if particles is None or return_particles else slice(0, B, P)      # a group's first row
-        nk = len(range(B)[keep])
-        cut = lambda t: t[keep].view(nk, nb * epc, nc)[:, code_index_start * epc:code_index_end * epc].contiguous()
-        res = (cut(out), cut(logp)) if return_logp else (cut(out),)
-        if return_allowed_mass:
-            res += (cut(mass),)
-        if return_rule_report:
-            res += (cut(report),)
-        if maps is not None:
-            res += (self._join_attention_chunks(maps),)
-        if return_particles and filt is not None:
-            res += (self._join_particle_results(filt),)
-        return res if len(res) > 1 else res[0]
+        def form(codes):
+            nonlocal code_index_start, code_index_end
+            nb = codes.shape[1]
+            if nb < S:
+                raise ValueError(f'encoding_indices: at least {S} codes (one model window) are needed, got {nb}')
+            code_index_start = 0 if code_index_start is None else int(code_index_start)
+            code_index_end = nb if code_index_end is None else int(code_index_end)
+            if not 0 <= code_index_start <= code_index_end <= nb:
+                raise ValueError(f'0 <= code_index_start <= code_index_end <= {nb} expected, got {code_index_start}, {code_index_end}')
+            exclude = self._meta_symbol_ids() if exclude_meta_symbols else None
+            chorale = self.init_generation_chorale(num_events=nb * epc, start_index=code_index_start * epc, pad=pad, start=start)
+
+            def drive(inc, codes, settings):
+                inc.start_long(codes, chorale.reshape(1, -1).expand(codes.shape[0], -1), **settings)
+                return inc.run_long(code_index_start, code_index_end, use_graph=use_graph, graph_slides=graph_slides)
+            return dict(events=nb * epc, first=code_index_start * epc, last=code_index_end * epc, exclude=exclude, drive=drive,
+                        maps=lambda: {'window_start': self.attention_window_starts(nb, S, U, code_index_start, code_index_end)})
+        res = self._generate_rows(
+            encoding_indices, 'encoding_indices', None, form, temperature=temperature, top_k=top_k, top_p=top_p,
+            num_decodings=num_decodings, seed=seed, constraint=constraint, return_logp=return_logp,
+            return_attentions=return_attentions, max_attention_bytes=max_attention_bytes, allowed=allowed,
+            return_allowed_mass=return_allowed_mass, particles=particles, resample_threshold=resample_threshold,
+            return_particles=return_particles, rules=rules, return_rule_report=return_rule_report)
+        return self._result_tuple(res, lambda t: t[:, code_index_start * epc:code_index_end * epc].contiguous())
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent

@@ -53,13 +53,21 @@ read `pos` and `win` from device memory and sit BETWEEN the replays: the capture
 Voice-leading rules (`start(rules=...)`, csrc/rules.hip): the caller's static sets move to `rule_static` and `allowed` becomes the
 rule kernel's output; vqcpc_decode_rules runs immediately before vqcpc_decode_sample_masked, INSIDE the captured step, and
 overwrites the live column's set from the tokens emitted so far (the live window's, and the chorale's before it) and the
-column of `rule_report`.  The sampler, the mass and the particle weights read that set unchanged."""
+column of `rule_report`.  The sampler, the mass and the particle weights read that set unchanged.
+
+Where the options are set up: `start` and `start_long` take the sampling settings (`_sampling`) and then make ONE call of
+`_configure` with the generation's coordinate frame (`Frame`, transformer/incremental.py): (T, None, 1, S, seeds) for the fixed
+window, (nb * U, win, U, nb, row_seeds) for a chorale.  Every option buffer above has `frame.width` columns and is addressed
+through `frame.win`; the step, the cross hook, the sampler and the resampling read the frame and nothing else about the
+coordinates.  `_configure` sets every option at every call, so a second `start` leaves the earlier call's options off.  The
+record buffers (`logp`, `logmass`, `rule_report`, `self_probs`, `cross_probs`, the `p_*` state) are allocated there and get their
+initial values in one place, `_clear_records`, which `reset` and the post-warm-up path of `run_long` call."""
 import ctypes
 
 import torch
 
 from .. import hip, ops
-from ..transformer.incremental import MAX_ROWS, IncrementalStack, _splitmix64, row_seeds       # noqa: F401 (re-exported)
+from ..transformer.incremental import MAX_ROWS, Frame, IncrementalStack, _splitmix64, row_seeds    # noqa: F401 (re-exported)
 from ..transformer.transformer_custom import mask_code
 
 
@@ -99,7 +107,6 @@ class IncrementalDecoder(IncrementalStack):
         self.tokens = torch.zeros(M, self.T, dtype=torch.int64, device=dev)
         self.exclude = torch.zeros(self.nc, 8, dtype=torch.int32, device=dev)     # uint32 bits
         self.memkv = None
-        self.constraint, self.logp, self.constrained = None, None, False
         self.allowed, self.logmass, self.masked = None, None, False
         self.rules, self.rule_static, self.rule_report = None, None, None
         self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
@@ -175,6 +182,12 @@ class IncrementalDecoder(IncrementalStack):
         rules: None, or a `templates.VoiceLeadingRules`: vqcpc_decode_rules writes every position's set before the masked
         sampler reads it (`_rule_sets`); `rule_report` (M, T) int32 keeps what was relaxed or broken, -1 where no token was
         emitted yet."""
+        self._sampling(seeds, temperature, top_k, top_p, exclude, teacher, want_probs)
+        self._configure(Frame(self.T, None, 1, self.S, self.seeds), constraint, want_logp, allowed, want_allowed_mass, particles,
+                        resample_threshold, final_resample, rules, want_attentions)
+
+    def _sampling(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False):
+        """The sampling settings of `start`: what the sampler takes whatever options are on."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
@@ -191,19 +204,28 @@ class IncrementalDecoder(IncrementalStack):
         else:
             self.teacher = None
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
-        self._particles(particles, resample_threshold, final_resample, self.S, self.seeds, want_attentions)
-        self._constrain(constraint, want_logp or (particles is not None and constraint is not None), self.T, None)
-        self._mask(allowed, want_allowed_mass or (particles is not None and (allowed is not None or rules is not None)), self.T)
-        self._rule_sets(rules, self.T)
-        self._record_attentions(want_attentions, self.T, None, 1)
+
+    def _configure(self, frame, constraint, want_logp, allowed, want_allowed_mass, particles, resample_threshold, final_resample,
+                   rules, want_attentions):
+        """The options of one generation, all of them at every call (what is not asked for is switched off), in the coordinates
+        of `frame`: `Frame(T, None, 1, S, seeds)` for the fixed window, `Frame(nb * U, win, U, nb, row_seeds)` for a chorale,
+        whose buffers are addressed through the device window index.  The record buffers are allocated here, once and before any
+        warm-up step (a captured step or slide holds their addresses), and get their values from `reset`, which ends the call."""
+        self.frame = frame
+        self._particles(particles, resample_threshold, final_resample, want_attentions)
+        scored = particles is not None                        # the weights are the forced tokens' logp and the sets' mass
+        self._constrain(constraint, want_logp or (scored and constraint is not None), frame.width)
+        self._mask(allowed, want_allowed_mass or (scored and (allowed is not None or rules is not None)))
+        self._rule_sets(rules)
+        self._record_attentions(want_attentions)
         self.reset()
 
-    def _particles(self, P, threshold, final, codes, seeds, want_attentions=None):
+    def _particles(self, P, threshold, final, want_attentions):
         """The particle filter's state: per row the running log-weight `p_lw`, the last normalised weights `p_wn` and
         ancestors `p_anc`; per group the log-evidence `p_evidence`, the last code's increment `p_pending` and effective sample
-        size `p_ess`; the device flag `p_flag`; and per chorale code (`codes` rows) the histories `p_hist_anc` (int32, -1 where
-        no code was finished), `p_hist_wn`, `p_hist_ess` (NaN there).  seeds: the per-row seeds that never move (the resampling
-        uniform is keyed by the group's first one and the code's chorale index)."""
+        size `p_ess`; the device flag `p_flag`; and per code of the frame the histories `p_hist_anc` (int32, -1 where no code
+        was finished), `p_hist_wn`, `p_hist_ess` (NaN there).  `p_seeds`: the frame's seeds (the resampling uniform is keyed by
+        the group's first one and the code's chorale index)."""
         self.particles = None
         if P is None:
             return
@@ -216,31 +238,14 @@ class IncrementalDecoder(IncrementalStack):
             raise ValueError('particles: attention maps are not moved with a resampled row; want_attentions must be None')
         if self.teacher is not None:
             raise ValueError('particles and teacher exclude each other')
-        M, G, dev = self.M, self.M // P, self.dev
-        self.particles, self.p_threshold, self.p_final, self.p_seeds = P, float(threshold), bool(final), seeds
-        self.p_lw = torch.zeros(M, dtype=torch.float32, device=dev)
-        self.p_wn = torch.full((M,), 1.0 / P, dtype=torch.float32, device=dev)
-        self.p_anc = torch.arange(M, dtype=torch.int32, device=dev)
-        self.p_evidence, self.p_pending = (torch.zeros(G, dtype=torch.float32, device=dev) for _ in range(2))
-        self.p_ess = torch.full((G,), float(P), dtype=torch.float32, device=dev)
-        self.p_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.p_hist_anc = torch.full((codes, M), -1, dtype=torch.int32, device=dev)
-        self.p_hist_wn = torch.full((codes, M), float('nan'), dtype=torch.float32, device=dev)
-        self.p_hist_ess = torch.full((codes, G), float('nan'), dtype=torch.float32, device=dev)
-
-    def _forget_particles(self):
-        if self.particles is None:
-            return
-        self.p_lw.zero_()
-        self.p_wn.fill_(1.0 / self.particles)
-        self.p_anc.copy_(torch.arange(self.M, dtype=torch.int32))
-        self.p_evidence.zero_()
-        self.p_pending.zero_()
-        self.p_ess.fill_(float(self.particles))
-        self.p_flag.zero_()
-        self.p_hist_anc.fill_(-1)
-        self.p_hist_wn.fill_(float('nan'))
-        self.p_hist_ess.fill_(float('nan'))
+        M, G, codes = self.M, self.M // P, self.frame.codes
+        self.particles, self.p_threshold, self.p_final, self.p_seeds = P, float(threshold), bool(final), self.frame.seeds
+        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
+        self.p_lw, self.p_wn, self.p_anc = torch.empty(M, **f32), torch.empty(M, **f32), torch.empty(M, **i32)
+        self.p_evidence, self.p_pending, self.p_ess = (torch.empty(G, **f32) for _ in range(3))
+        self.p_flag = torch.empty(1, **i32)
+        self.p_hist_anc, self.p_hist_wn = torch.empty(codes, M, **i32), torch.empty(codes, M, **f32)
+        self.p_hist_ess = torch.empty(codes, G, **f32)
 
     def _resample(self, last, move_cache, chorale=None):
         """After the U steps of a code: the weight update and the resampling decision (vqcpc_particle_resample), then the
@@ -250,12 +255,12 @@ class IncrementalDecoder(IncrementalStack):
         on the device flag when no row moved.  The launches are issued eagerly between the step replays of a graphed run: replaying
         them from a captured graph of their own measured slower (profiles/generate_particles_perf_log.md).  last: the code is the generation's last one -- a forced resampling
         (`final_resample`), or the weight update alone (threshold 0, nothing moves, no permute launch)."""
-        P, M, w = self.particles, self.M, self._cons_width
+        P, M, w = self.particles, self.M, self.frame.width
         force = bool(last and self.p_final)
         threshold = 0.0 if last and not self.p_final else self.p_threshold
         hip.call('vqcpc_particle_resample', self.p_lw, self.p_evidence, self.p_pending, self.p_seeds, self.constraint, w,
                  self.logp if self.constraint is not None else None, w, self.logmass if self.allowed is not None else None, w,
-                 self.pos, self._cons_win, self.U, threshold, int(force), self.p_anc, self.p_wn, self.p_ess, self.p_flag,
+                 self.pos, self.frame.win, self.U, threshold, int(force), self.p_anc, self.p_wn, self.p_ess, self.p_flag,
                  self.p_hist_anc, self.p_hist_wn, self.p_hist_ess, self.p_hist_anc.shape[0], M, P)
         if threshold == 0.0 and not force:
             return
@@ -280,24 +285,10 @@ class IncrementalDecoder(IncrementalStack):
         return {'weights': self.p_wn.view(G, P).clone(), 'log_evidence': evidence.clone(), 'ancestors': self.p_hist_anc,
                 'wn': self.p_hist_wn, 'ess': self.p_hist_ess}
 
-    def _constrain(self, constraint, want_logp, width, win):
-        """The constrained sampler's buffers, (M, width) each: width = T and win = None for the fixed window, width = nb * U and
-        win = the device window index in long mode (chorale coordinates)."""
-        if (constraint is not None or want_logp) and self.teacher is not None:
-            raise ValueError('constraint / want_logp and teacher exclude each other (an all-forced constraint is teacher forcing)')
-        if constraint is not None:
-            if tuple(constraint.shape) != (self.M, width) or constraint.dtype != torch.int64:
-                raise ValueError(f'constraint: ({self.M}, {width}) int64 expected, got {tuple(constraint.shape)} '
-                                 f'{constraint.dtype}')
-            constraint = constraint.to(self.dev).contiguous()
-        self.constraint = constraint
-        self.logp = torch.full((self.M, width), float('nan'), dtype=torch.float32, device=self.dev) if want_logp else None
-        self.constrained = constraint is not None or want_logp
-        self._cons_width, self._cons_win = width, win
-
-    def _mask(self, allowed, want_mass, width):
+    def _mask(self, allowed, want_mass):
         """The masked sampler's buffers, addressed like the constrained sampler's: the packed sets are COPIED into a buffer of
         this stack, (M, width, 8) int32, so a captured step or slide reads every window's sets through the window index."""
+        width = self.frame.width
         if (allowed is not None or want_mass) and self.teacher is not None:
             raise ValueError('allowed / want_allowed_mass and teacher exclude each other')
         self.allowed = None
@@ -307,13 +298,13 @@ class IncrementalDecoder(IncrementalStack):
                                  f'{allowed.dtype}')
             self.allowed = torch.empty(self.M, width, 8, dtype=torch.int32, device=self.dev)
             self.allowed.copy_(allowed)
-        self.logmass = torch.full((self.M, width), float('nan'), dtype=torch.float32, device=self.dev) if want_mass else None
+        self.logmass = torch.empty(self.M, width, dtype=torch.float32, device=self.dev) if want_mass else None
         self.masked = allowed is not None or bool(want_mass)
 
-    def _rule_sets(self, rules, width):
+    def _rule_sets(self, rules):
         """The rule kernel's buffers (after `_mask`): `kinds` and `max_leap` are uploaded once; the caller's sets stay in
         `rule_static` (None: none) and `allowed`, the buffer the sampler reads, becomes the kernel's output, which overwrites the
-        live column at every step; `rule_report` (M, width) int32 -- a dtype vqcpc_particle_permute_f32 moves -- starts at -1."""
+        live column at every step; `rule_report` (M, width) int32 -- a dtype vqcpc_particle_permute_f32 moves."""
         self.rules = self.rule_static = self.rule_report = None
         if rules is None:
             return
@@ -326,14 +317,13 @@ class IncrementalDecoder(IncrementalStack):
         self.rule_kinds = kinds.to(self.dev, torch.int32).contiguous()
         self.rule_leap = rules.max_leap.to(self.dev, torch.int32).contiguous()
         self.rule_static = self.allowed
-        self.allowed = torch.zeros(self.M, width, 8, dtype=torch.int32, device=self.dev)
-        self.rule_report = torch.full((self.M, width), -1, dtype=torch.int32, device=self.dev)
+        self.allowed = torch.zeros(self.M, self.frame.width, 8, dtype=torch.int32, device=self.dev)
+        self.rule_report = torch.empty(self.M, self.frame.width, dtype=torch.int32, device=self.dev)
         self.masked = True
 
-    def _record_attentions(self, layers, rows, win, stride):
-        """The attention-map buffers, allocated here once (before any warm-up step: a captured step holds their addresses):
-        rows = T and win = None for the fixed window, rows = nb * U, win = the device window index and stride = U in long mode
-        (chorale coordinates).  layers=None frees them and every launch is the plain one again."""
+    def _record_attentions(self, layers):
+        """The attention-map buffers, one row per column of the frame.  layers=None frees them and every launch is the plain one
+        again."""
         self.self_probs = self.cross_probs = None
         self._attn_slot, self.attn_layers = {}, None
         if layers is None:
@@ -342,31 +332,35 @@ class IncrementalDecoder(IncrementalStack):
         if not layers or list(layers) != sorted(set(layers)) or layers[0] < 0 or layers[-1] >= len(self.layers):
             raise ValueError(f'want_attentions: a sorted tuple of distinct layer indices in [0, {len(self.layers)}) expected, '
                              f'got {layers}')
-        nan = dict(fill_value=float('nan'), dtype=torch.float32, device=self.dev)
-        self.self_probs = torch.full((len(layers), self.M, self.H, rows, self.T), **nan)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.self_probs = torch.empty(len(layers), self.M, self.H, self.frame.width, self.T, **f32)
         if not self.diagonal:
-            self.cross_probs = torch.full((len(layers), self.M, self.H, rows, self.S), **nan)
+            self.cross_probs = torch.empty(len(layers), self.M, self.H, self.frame.width, self.S, **f32)
         self.attn_layers = layers
         self._attn_slot = {li: k for k, li in enumerate(layers)}
-        self._attn_rows, self._attn_win, self._attn_stride = int(rows), win, int(stride)
 
     def reset(self):
         self.pos.zero_()
         self.tokens.zero_()
         self.x.copy_(self.table[-1].expand(self.M, self.d))                            # start-of-sentence row
-        self._forget_logp()
+        self._clear_records()
 
-    def _forget_logp(self):
-        if self.logp is not None:
-            self.logp.fill_(float('nan'))                                               # what a warm-up step wrote
-        if self.logmass is not None:
-            self.logmass.fill_(float('nan'))
-        if self.rule_report is not None:
-            self.rule_report.fill_(-1)
-        for maps in (self.self_probs, self.cross_probs):
-            if maps is not None:
-                maps.fill_(float('nan'))
-        self._forget_particles()
+    def _clear_records(self):
+        """The initial values of everything a step records, in one place: NaN (report: -1) where no token was emitted yet, and
+        the filter before its first code.  A warm-up step of a capture writes into these buffers, so a run clears them again."""
+        nan = float('nan')
+        for rows, value in ((self.logp, nan), (self.logmass, nan), (self.rule_report, -1), (self.self_probs, nan),
+                            (self.cross_probs, nan)):
+            if rows is not None:
+                rows.fill_(value)
+        if self.particles is None:
+            return
+        P = self.particles
+        for rows, value in ((self.p_lw, 0.0), (self.p_wn, 1.0 / P), (self.p_evidence, 0.0), (self.p_pending, 0.0),
+                            (self.p_ess, float(P)), (self.p_flag, 0), (self.p_hist_anc, -1), (self.p_hist_wn, nan),
+                            (self.p_hist_ess, nan)):
+            rows.fill_(value)
+        self.p_anc.copy_(torch.arange(self.M, dtype=torch.int32))
 
     # ---- one step: the cross hooks and the sampler ----------------------------------------------------------------------
     def _cross_attention(self, li, lay):
@@ -380,7 +374,7 @@ class IncrementalDecoder(IncrementalStack):
         else:
             hip.call('vqcpc_decode_attn_probs', self.qc, d, kv, kv.data_ptr() + 4 * d, 2 * d, None, None, 0, ca.attn_bias.e1,
                      ca.attn_bias.e2, self.att, d, self.pos, self.M, self.S, self.T // self.S, self.H, self.hd, self.cross_mask,
-                     self.cross_probs[slot], self.S, self._attn_rows, self._attn_win, self._attn_stride)
+                     self.cross_probs[slot], self.S, self.frame.width, self.frame.win, self.frame.stride)
         self._linear(self.att, ca.out_proj.weight, ca.out_proj.bias, self.s, res=self.h1)
         self._ln(self.s, lay.norm2, self.h2)
         return self.h2
@@ -392,30 +386,27 @@ class IncrementalDecoder(IncrementalStack):
         return self.h2
 
     def _sample(self):
+        """One of the three sampler entry points: plain unless `constrained`, and masked wins over constrained.  They share
+        the operands before (`head`) and after (`tail`) what each one adds."""
         T, d = self.T, self.d
-        if self.masked:
-            w = self._cons_width
-            if self.rules is not None:                        # the live column's set, from the tokens emitted so far
-                windowed = self._cons_win is not None         # long mode: the history before the live window is the chorale's
-                hip.call('vqcpc_decode_rules', self.tokens, T, T, self.chorale if windowed else None, w if windowed else 0,
-                         self.constraint, w, self.rule_kinds, self.rule_kinds.shape[1], self._offsets_c, self.nc, self.rule_leap,
-                         self.rules.mask, self.exclude if self.excluding else None, self.rule_static, w, self.allowed, w,
-                         self.rule_report, w, self.pos, self._cons_win, self.U, self.M)
-            hip.call('vqcpc_decode_sample_masked', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M,
-                     self.temperature, self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds,
-                     self.constraint, w, self.logp, w, self._cons_win, self.allowed, w, self.logmass, w, self.tokens, T, T,
-                     self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
+        head = (self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.temperature, self.top_k, self.top_p,
+                self.exclude if self.excluding else None, self.seeds)
+        tail = (self.tokens, T, T, self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
+        if not (self.masked or self.constrained):
+            hip.call('vqcpc_decode_sample', *head, self.teacher, T, *tail)
             return
-        if self.constrained:
-            w = self._cons_width
-            hip.call('vqcpc_decode_sample_constrained', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M,
-                     self.temperature, self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds,
-                     self.constraint, w, self.logp, w, self._cons_win, self.tokens, T, T, self.table, self.table.shape[0], d,
-                     self.U, self.x, d, self.probs, self.vmax, self.pos)
+        w, win = self.frame.width, self.frame.win
+        forced = (self.constraint, w, self.logp, w, win)
+        if not self.masked:
+            hip.call('vqcpc_decode_sample_constrained', *head, *forced, *tail)
             return
-        hip.call('vqcpc_decode_sample', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.temperature,
-                 self.top_k, self.top_p, self.exclude if self.excluding else None, self.seeds, self.teacher, T, self.tokens, T, T,
-                 self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
+        if self.rules is not None:                            # the live column's set, from the tokens emitted so far
+            windowed = win is not None                        # long mode: the history before the live window is the chorale's
+            hip.call('vqcpc_decode_rules', self.tokens, T, T, self.chorale if windowed else None, w if windowed else 0,
+                     self.constraint, w, self.rule_kinds, self.rule_kinds.shape[1], self._offsets_c, self.nc, self.rule_leap,
+                     self.rules.mask, self.exclude if self.excluding else None, self.rule_static, w, self.allowed, w,
+                     self.rule_report, w, self.pos, win, self.U, self.M)
+        hip.call('vqcpc_decode_sample_masked', *head, *forced, self.allowed, w, self.logmass, w, *tail)
 
     # ---- a whole generation --------------------------------------------------------------------------------------------
     def run(self, use_graph=True):
@@ -478,12 +469,9 @@ class IncrementalDecoder(IncrementalStack):
             self.prefill(z_full[:, :S] if self.continuous else codes_full[:, :S])
         if self.continuous:
             self.z_full, self.z_nb = z_full, nb
-        self.start(seeds=seeds, **sampling)
-        self._particles(particles, resample_threshold, final_resample, nb, self.row_seeds, want_attentions)
-        self._constrain(constraint, want_logp or (particles is not None and constraint is not None), nb * U, self.win)
-        self._mask(allowed, want_allowed_mass or (particles is not None and (allowed is not None or rules is not None)), nb * U)
-        self._rule_sets(rules, nb * U)
-        self._record_attentions(want_attentions, nb * U, self.win, U)
+        self._sampling(seeds, **sampling)
+        self._configure(Frame(nb * U, self.win, U, nb, self.row_seeds), constraint, want_logp, allowed, want_allowed_mass,
+                        particles, resample_threshold, final_resample, rules, want_attentions)
         self.row_seeds.copy_(self.seeds)
 
     def _window(self, P, advance):
@@ -551,7 +539,7 @@ class IncrementalDecoder(IncrementalStack):
                 self.slide(tb0, tr_mid)
                 slide_graph = self.capture(lambda: self.slide(None, tr_mid, advance=1))
             self.chorale.copy_(chorale0)          # the warm-up launches drew and committed tokens: start again
-            self._forget_logp()
+            self._clear_records()
             self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
         live = None
         for k, (_, tb, _, tr) in enumerate(plan):

@@ -110,16 +110,7 @@ class IncrementalPrior(IncrementalStack):
         if seeds is not None:
             self.row_seeds.copy_(row_seeds(seeds, self.M))
         self.teacher = None if teacher is None else teacher.to(self.dev, torch.int64).reshape(self.M, self.N).contiguous()
-        if (constraint is not None or want_logp) and self.teacher is not None:
-            raise ValueError('constraint / want_logp and teacher exclude each other (an all-forced constraint is teacher forcing)')
-        if constraint is not None:
-            if tuple(constraint.shape) != (self.M, self.nt) or constraint.dtype != torch.int64:
-                raise ValueError(f'constraint: ({self.M}, {self.nt}) int64 expected, got {tuple(constraint.shape)} '
-                                 f'{constraint.dtype}')
-            constraint = constraint.to(self.dev).contiguous()
-        self.constraint = constraint
-        self.logp = torch.empty(self.M, self.nt, dtype=torch.float32, device=self.dev) if want_logp else None
-        self.constrained = constraint is not None or bool(want_logp)
+        self._constrain(constraint, want_logp, self.nt)
         self.probs = self._probs_buffer() if want_probs else None
         self.seq = torch.zeros(self.M, self.nt, dtype=torch.int64, device=self.dev)
         self.reset()

@@ -19,13 +19,25 @@ prior's N codes): position t's output depends on positions < t only (causal self
 
 Every kernel of the step reads `pos` from device memory, so ONE captured step (`capture`) is replayed for every position.
 Rows are independent and every kernel reduces in an order that does not depend on the number of rows, so a row's tokens do
-not depend on which other rows share the call (given the same inputs and seed)."""
+not depend on which other rows share the call (given the same inputs and seed).
+
+The stack also owns what both generators' constrained samplers need (`_constrain`: the constraint, `logp`, the `constrained`
+flag) and the coordinate frame of a generation's per-position buffers (`Frame`), which the recorded attention launch reads."""
+import collections
+
 import torch
 
 from .. import hip, ops
 from ..utils import STEP_LOCK
 
 MAX_ROWS = 64                # rows of one incremental stack (vqcpc_decode_*); larger batches run in chunks
+
+
+# The coordinates the per-position buffers of a generation are addressed in: `width` columns per row; `win` None (the column is
+# the window's position) or the device window index (the column is the position's place in the whole sequence); `stride`
+# positions per window step (the recorded attention rows'); `codes` rows of the per-code histories; `seeds` the per-row seeds
+# that never move.  Tensors and ints only: a bound method of the stack in it would be a reference cycle (`IncrementalStack`).
+Frame = collections.namedtuple('Frame', 'width win stride codes seeds')
 
 
 def _splitmix64(z):
@@ -100,7 +112,23 @@ class IncrementalStack:
         self.teacher = None
         self.probs = None
         self.self_probs, self._attn_slot = None, {}           # attention maps: off (a subclass's `start` may turn them on)
+        self.frame = None                                     # the `Frame` of the generation's option buffers
+        self.constraint, self.logp, self.constrained = None, None, False
         self._cross, self._prefix_cross = IncrementalStack._no_cross, IncrementalStack._no_prefix_cross
+
+    def _constrain(self, constraint, want_logp, width):
+        """The constrained sampler's set-up: `constraint` (M, width) int64 or None, `logp` (M, width) float32 -- allocated here,
+        filled by the subclass's `reset` -- or None, and `constrained`, which chooses the sampler."""
+        if (constraint is not None or want_logp) and self.teacher is not None:
+            raise ValueError('constraint / want_logp and teacher exclude each other (an all-forced constraint is teacher forcing)')
+        if constraint is not None:
+            if tuple(constraint.shape) != (self.M, width) or constraint.dtype != torch.int64:
+                raise ValueError(f'constraint: ({self.M}, {width}) int64 expected, got {tuple(constraint.shape)} '
+                                 f'{constraint.dtype}')
+            constraint = constraint.to(self.dev).contiguous()
+        self.constraint = constraint
+        self.logp = torch.empty(self.M, width, dtype=torch.float32, device=self.dev) if want_logp else None
+        self.constrained = constraint is not None or bool(want_logp)
 
     # ---- one step ----------------------------------------------------------------------------------------------------
     def _ln(self, s, norm, out):
@@ -132,7 +160,7 @@ class IncrementalStack:
             else:                                         # a recorded layer: the same kernel body, which also stores its row
                 hip.call('vqcpc_decode_attn_probs', self.qkv, 3 * d, self.kcache[li], self.vcache[li], d, q0 + 4 * d, q0 + 8 * d,
                          3 * d, sa.attn_bias.e1, sa.attn_bias.e2, self.att, d, self.pos, M, W, 1, H, hd, ops.MASK_CAUSAL,
-                         self.self_probs[slot], W, self._attn_rows, self._attn_win, self._attn_stride)
+                         self.self_probs[slot], W, self.frame.width, self.frame.win, self.frame.stride)
             self._linear(self.att, sa.out_proj.weight, sa.out_proj.bias, self.s, res=hin)
             self._ln(self.s, lay.norm1, self.h1)
             h = cross(self, li, lay)
