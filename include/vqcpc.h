@@ -1166,6 +1166,44 @@ int vqcpc_decode_rules(const int64_t* tokens, int64_t ldtok, int T, const int64_
 int vqcpc_rules_audit(const int64_t* x, int64_t ld, int64_t width, const int32_t* kinds, int ldk, const int32_t* voice_offsets, int nc,
                       const int32_t* max_leap, int rules, int32_t* report, int64_t ldreport, int64_t rows, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Beam search for decoder generation (csrc/beam.hip, decoders/generation.py `beam=W`; the rule is restated in numpy in
+ * tests/beam_reference.py).  The M <= 64 rows of an incremental stack are G = M / W groups of W consecutive rows ("slots"), the
+ * hypotheses of one user row, 1 <= W <= 64.
+ * vqcpc_decode_beam_select: ONE launch for all groups, in the sampler's place at the end of a step.  p = pos[0], voice c = p % nc
+ *   with V_c logits columns, column col = p (win == NULL) or win[1] * U + p, -1 when win[1] < 0 -- the samplers' rule.
+ *   p outside [0, T): flag[0] = 0 and nothing else happens.
+ *   Row log-probability: lp(b, v) = (logits[b][v] - m_b) - logf(s_b), m_b / s_b the row maximum and exp-sum over the voice's V_c
+ *   columns, formed exactly as vqcpc_decode_sample_constrained forms logp (lane l holds tokens 4l .. 4l + 3, the same wave
+ *   reductions): lp(b, v) has the bits that sampler writes for row b emitting v.
+ *   Candidates of row b: at a forced column (constraint[b][col] >= 0) the one token, clamped to [0, V_c), exclusion and set
+ *   ignored; at a free one the tokens of [0, V_c) in allowed[b][col] (no buffer, or no bit inside the vocabulary: all of them) that
+ *   are not in exclude[c].  cand(b, v) = score[b] + lp(b, v), one fp32 add; NaN counts as -inf; live means cand > -inf.
+ *   Per group the live candidates are ordered by cand descending, then row ascending, then token ascending.  Slot k < n (n = the
+ *   number of live candidates, at most W) gets the k-th: ancestors[k] = its row, its token, score[k] = cand.  Slots k >= n are dead:
+ *   slot 0's ancestor and token, score -inf.  n == 0: ancestors = the identity, every row emits its own lowest candidate token
+ *   (token 0 without one), score -inf.  The caller starts a group with score 0 for its first row and -inf for the others.
+ *   Written, all in slot order: tokens[k][p]; next_in row k = table row min(token * U + p % U, table_rows - 1); logp[k][col] =
+ *   lp(ancestor, token); logmass[k][col] = the ancestor's (m_a - m) + logf(s_a) - logf(s) over its set, as the masked sampler forms
+ *   it; rule_report[k][col] = the ancestor's value (every row is read before any is written); score (M); ancestors (M, int32 row
+ *   indices of the stack); flag[0] = 1 if any ancestor differs from its own row else 0; row col of hist_ancestors (hist_rows, M)
+ *   where given and col < hist_rows; bound[0] = p, bound[1] = col; then pos[0] = p + 1.  NULL buffers, col < 0 and a column at or
+ *   past a leading dimension are free / not written.  cand_out (optional, [M][256]): every row's cand as the selection used it,
+ *   -inf for a non-candidate.
+ *   The moves row k <- row ancestors[k] that follow are vqcpc_particle_permute_* with P = W (none for W = 1): the tokens' columns
+ *   [0, bound[0]), the record rows' columns [0, bound[1]) -- the live column is in slot order already -- and cache rows [0, pos[0]),
+ *   position p's K/V having been written for the ancestor.
+ *   Limits: 1 <= M <= 64, W dividing M, nc <= 16, V_c <= 256, d <= 4096.  One workgroup, no allocation or synchronisation.
+ * Adding it left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_decode_beam_select(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t M, int W,
+                             const uint32_t* exclude, const int64_t* constraint, int64_t ldcons, const uint32_t* allowed,
+                             int64_t ldallow, float* logp, int64_t ldlogp, float* logmass, int64_t ldmass, int32_t* rule_report,
+                             int64_t ldreport, const int32_t* win, int64_t* tokens, int64_t ldtok, int T, const float* table,
+                             int64_t table_rows, int d, int U, float* next_in, int64_t ldn, float* score, int32_t* ancestors,
+                             int32_t* flag, int32_t* bound, int32_t* hist_ancestors, int64_t hist_rows, float* cand_out,
+                             int32_t* pos, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

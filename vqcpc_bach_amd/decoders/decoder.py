@@ -460,7 +460,8 @@ class Decoder(FlatTraining, nn.Module):
     def generate_from_codes(self, codes, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, exclude_tokens=None, seed=None,
                             use_graph=True, constraint=None, return_logp=False, return_attentions=False,
                             max_attention_bytes=4 << 30, allowed=None, return_allowed_mass=False, particles=None,
-                            resample_threshold=0.5, return_particles=False, rules=None, return_rule_report=False):
+                            resample_threshold=0.5, return_particles=False, rules=None, return_rule_report=False, beam=None,
+                            return_beams=False):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
@@ -516,14 +517,27 @@ class Decoder(FlatTraining, nn.Module):
         rules and rows that paint themselves into a corner die out.  return_rule_report=True -> `rule_report` after
         allowed_mass and before attentions, int32 of the tokens' shape: at a drawn position the rules that had to be dropped
         (bit 0 crossing, 1 leap, 2 parallel), at a forced one the rules its token breaks << 4.  Results:
-        (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles]).  Without the keywords every launch, buffer
+        (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles][, beams]).  Without the keywords every launch,
+        buffer and result is what it was.
+        beam: None, or W in [1, 64]: a beam search in the sampler's place, the model's W most probable continuations instead of a
+        draw.  Every row becomes a group of W consecutive rows of the stack; at every position vqcpc_decode_beam_select expands each
+        row into its candidate tokens -- the forced token, or the tokens `allowed`, `rules` and `exclude_tokens` leave -- scores
+        them by the hypothesis's total log-probability under the model's own distribution (what `logp` scores), keeps the
+        group's W best (ties: the lower row, then the lower token) and the rows' tokens, scores and K/V caches follow their
+        ancestors (vqcpc_particle_permute_*).  The search is deterministic: `seed` is accepted and unused.  The result has the
+        shapes of a call without the keyword and holds each group's best hypothesis, for tokens[, logp][, allowed_mass]
+        [, rule_report].  return_beams=True returns all B * W rows in slot order, best first, followed by a dict: 'scores' (B, W)
+        float32, the hypotheses' total log-probabilities, non-increasing along W and -inf for a dead slot (fewer than W
+        sequences exist), and 'ancestors' (positions, B * W) int32, per generated position the row each slot descends from (-1
+        where nothing was generated).  ValueError with `particles`, `return_attentions`, num_decodings != 1, or a filter
+        (temperature other than 1, top_k, top_p): a filter has no meaning for a search.  Without `beam` every launch, buffer
         and result is what it was."""
         return self._result_tuple(self._window_results(
             codes, exclude_tokens, use_graph, temperature=temperature, top_k=top_k, top_p=top_p, num_decodings=num_decodings,
             seed=seed, constraint=constraint, return_logp=return_logp, return_attentions=return_attentions,
             max_attention_bytes=max_attention_bytes, allowed=allowed, return_allowed_mass=return_allowed_mass, particles=particles,
             resample_threshold=resample_threshold, return_particles=return_particles, rules=rules,
-            return_rule_report=return_rule_report))
+            return_rule_report=return_rule_report, beam=beam, return_beams=return_beams))
 
     def _window_results(self, codes, exclude_tokens, use_graph, **options):
         """`generate_from_codes` with its results by name (`_generate_rows`)."""
@@ -538,7 +552,7 @@ class Decoder(FlatTraining, nn.Module):
     def _generate_rows(self, source, name, length, form, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, seed=None,
                        constraint=None, return_logp=False, return_attentions=False, max_attention_bytes=4 << 30, allowed=None,
                        return_allowed_mass=False, particles=None, resample_threshold=0.5, return_particles=False, rules=None,
-                       return_rule_report=False):
+                       return_rule_report=False, beam=None, return_beams=False):
         """The body the public generators share: the option checks, then the source (`_source_on_device(source, name, length)`),
         then `form(codes)`, what the fixed window and the chorale differ in -- a dict of
           events, first, last   the events of a row, and the range [first, last) of them that is generated
@@ -546,15 +560,18 @@ class Decoder(FlatTraining, nn.Module):
           drive                 drive(stack, the chunk's codes, the keywords of its `start`) -> the chunk's (n, events * channels) tokens
           maps                  maps() -> the attention maps kept next to the decoder's: 'self_attns_encoder': [] (the stack's
                                 `enc_probs` of every chunk) or 'window_start': a tensor
-        -- then packing, repetition by num_decodings * particles, seeds, the chunks on their own stacks and their records.
-        -> a dict in the documented order of the results, every row (a group's first one with particles, unless they are returned)
-        as (rows, events, channels): 'tokens', 'logp', 'allowed_mass', 'rule_report', then 'attentions' and 'particles'; what was
-        not asked for is None."""
+        -- then packing, repetition by num_decodings * particles (or the beam width), seeds, the chunks on their own stacks and their records.
+        -> a dict in the documented order of the results, every row (a group's first one with particles or a beam, unless they are
+        returned) as (rows, events, channels): 'tokens', 'logp', 'allowed_mass', 'rule_report', then 'attentions', 'particles' and
+        'beams'; what was not asked for is None."""
         from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev, nc = self.sos.device, self.num_channels
         layers = self._attention_layers(return_attentions)
         P = self._particle_count(particles, resample_threshold, return_particles, layers)
+        W = self._beam_width(beam, return_beams, particles, layers, num_decodings, temperature, top_k, top_p)
+        if beam is not None:
+            P, temperature = W, 1.0                           # the group size of the chunks below, whichever kind the groups are
         self._check_rules(rules, return_rule_report)
         codes = self._source_on_device(source, name, length)
         form = form(codes)
@@ -573,7 +590,8 @@ class Decoder(FlatTraining, nn.Module):
         seeds = row_seeds(seed, B)
         settings = dict(temperature=temperature, top_k=top_k, top_p=top_p, exclude=exclude, want_logp=return_logp,
                         want_attentions=layers, want_allowed_mass=return_allowed_mass, particles=None if particles is None else P,
-                        resample_threshold=resample_threshold, final_resample=not return_particles, rules=rules)
+                        resample_threshold=resample_threshold, final_resample=not return_particles, rules=rules,
+                        beam=None if beam is None else W)
         kept = {'logp': ('logp', torch.float32, return_logp), 'allowed_mass': ('logmass', torch.float32, return_allowed_mass),
                 'rule_report': ('rule_report', torch.int32, return_rule_report)}          # result: the stack's buffer, ...
         records = {key: torch.empty(B, width, dtype=dtype, device=dev) for key, (_, dtype, wanted) in kept.items() if wanted}
@@ -581,7 +599,7 @@ class Decoder(FlatTraining, nn.Module):
         if layers is not None:
             maps = {'layers': layers, 'self_attns_decoder': [], 'attns_cross': [], **form['maps']()}
             self._check_attention_bytes(B, layers, width, 'self_attns_encoder' in maps, max_attention_bytes)
-        if particles is not None:
+        if particles is not None or beam is not None:
             filt = {}
 
         def chunk(n, rows):
@@ -597,20 +615,23 @@ class Decoder(FlatTraining, nn.Module):
                 if 'self_attns_encoder' in maps:
                     maps['self_attns_encoder'].append(torch.stack(inc.enc_probs, dim=1))
             if filt is not None:
-                self._keep_particle_results(filt, inc.particle_results(), rows.start)
+                self._keep_particle_results(filt, inc.particle_results() if beam is None else inc.beam_results(), rows.start)
             return tokens
         tokens = generate_in_chunks(self, B, width, chunk, MAX_ROWS // P * P)        # whole groups (P = 1: MAX_ROWS, as before)
-        keep = slice(None) if particles is None or return_particles else slice(0, B, P)      # a group's first row
+        whole = return_particles if beam is None else return_beams
+        keep = slice(None) if P == 1 or whole else slice(0, B, P)        # a group's first row: the survivor / the best hypothesis
         nk = len(range(B)[keep])
         res = {'tokens': tokens, **{key: records.get(key) for key in kept}}
         res = {key: None if t is None else t[keep].view(nk, events, nc) for key, t in res.items()}
         res['attentions'] = None if maps is None else self._join_attention_chunks(maps)
         res['particles'] = self._join_particle_results(filt) if return_particles and filt is not None else None
+        res['beams'] = self._join_particle_results(filt) if return_beams and filt is not None else None
         return res
 
     @staticmethod
     def _result_tuple(res, cut=lambda t: t):
-        """`_generate_rows`'s results -> the documented (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles]),
+        """`_generate_rows`'s results -> the documented (tokens[, logp][, allowed_mass][, rule_report][, attentions][, particles]
+        [, beams]),
         `tokens` alone when nothing else was asked for; cut: applied to the per-token tensors."""
         out = tuple(cut(v) if torch.is_tensor(v) else v for v in res.values() if v is not None)
         return out if len(out) > 1 else out[0]
@@ -671,6 +692,28 @@ class Decoder(FlatTraining, nn.Module):
         return int(particles)
 
     @staticmethod
+    def _beam_width(beam, return_beams, particles, attention_layers, num_decodings, temperature, top_k, top_p):
+        """The checks of the beam keywords, once per call -> the beam width (1 without a beam).  temperature None: the caller's
+        default."""
+        if beam is None:
+            if return_beams:
+                raise ValueError('return_beams=True needs beam=W')
+            return 1
+        if isinstance(beam, bool) or int(beam) != beam or not 1 <= int(beam) <= 64:
+            raise ValueError(f'beam: None or an integer in [1, 64] expected, got {beam!r}')
+        if particles is not None:
+            raise ValueError('beam with particles: a search and a particle filter both own the groups of rows; pass one of the two')
+        if attention_layers is not None:
+            raise ValueError('return_attentions with beam: the maps of a row are not moved when a hypothesis takes the row')
+        if num_decodings != 1:
+            raise ValueError(f'beam with num_decodings={num_decodings}: the search is deterministic, every decoding would be the '
+                             f'same; num_decodings must be 1 (return_beams=True returns the W best)')
+        if (temperature is not None and float(temperature) != 1.0) or top_k != 0 or 0.0 < float(top_p) < 1.0:
+            raise ValueError(f'beam with temperature={temperature}, top_k={top_k}, top_p={top_p}: the search scores the model\'s '
+                             f'own distribution, a filter has no meaning for it; temperature 1, top_k 0 and top_p 1 expected')
+        return int(beam)
+
+    @staticmethod
     def _keep_particle_results(filt, res, row0):
         """A chunk's filter results; its ancestors become row indices of the whole call (the chunk starts at row `row0`)."""
         anc = res['ancestors']
@@ -680,7 +723,7 @@ class Decoder(FlatTraining, nn.Module):
 
     @staticmethod
     def _join_particle_results(filt):
-        return {key: torch.cat(parts, dim=0 if key in ('weights', 'log_evidence') else 1).contiguous()
+        return {key: torch.cat(parts, dim=0 if key in ('weights', 'log_evidence', 'scores') else 1).contiguous()
                 for key, parts in filt.items()}
 
     @staticmethod
@@ -715,7 +758,8 @@ class Decoder(FlatTraining, nn.Module):
 
     def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
                  plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None, return_attentions=False,
-                 max_attention_bytes=4 << 30, particles=None, resample_threshold=0.5, rules=None, return_rule_report=False):
+                 max_attention_bytes=4 << 30, particles=None, resample_threshold=0.5, rules=None, return_rule_report=False,
+                 beam=None, return_beams=False):
         """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
@@ -731,7 +775,10 @@ class Decoder(FlatTraining, nn.Module):
         encoder's row (t // channels * channels) // tokens-per-code, the code of t's event (:650-659).
         particles, resample_threshold: `generate_from_codes`'s particle filter over the kept voices (each of the `batch_size`
         generations is the survivor of its own group of `particles` rows).
-        rules, return_rule_report: `generate_from_codes`'s voice-leading rules; the result gains 'rule_report'."""
+        rules, return_rule_report: `generate_from_codes`'s voice-leading rules; the result gains 'rule_report'.
+        beam, return_beams: `generate_from_codes`'s beam search (temperature must be 1): each of the `batch_size` generations is
+        the best hypothesis of its own group -- the same one, the search being deterministic --; with return_beams 'generation'
+        holds all batch_size * beam rows and the result gains 'beams'."""
         if plot_attentions:
             raise NotImplementedError('plot_attentions: no plots are drawn here (no matplotlib); return_attentions=True returns '
                                       'the attention maps of every emitted token and writes them as arrays')
@@ -766,7 +813,8 @@ class Decoder(FlatTraining, nn.Module):
             res = self._window_results(codes, exclude, True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                        constraint=constraint, return_attentions=layers or False,
                                        max_attention_bytes=max_attention_bytes, particles=particles,
-                                       resample_threshold=resample_threshold, rules=rules, return_rule_report=return_rule_report)
+                                       resample_threshold=resample_threshold, rules=rules, return_rule_report=return_rule_report,
+                                       beam=beam, return_beams=return_beams)
             x, rule_report, attentions = res['tokens'], res['rule_report'], res['attentions']
             recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
@@ -774,6 +822,8 @@ class Decoder(FlatTraining, nn.Module):
         extra = {} if attentions is None else {'attentions': attentions}
         if rule_report is not None:
             extra['rule_report'] = rule_report
+        if res['beams'] is not None:
+            extra['beams'] = res['beams']
         if recoding is None:
             return {'original': x_original, 'generation': x, 'codes': codes, 'recoding': None, **extra}
         timestamp = datetime.now().strftime('%Y-%m-%d_%H-%M-%S')
@@ -849,7 +899,7 @@ class Decoder(FlatTraining, nn.Module):
                                 use_graph=True, constraint=None, return_logp=False, return_attentions=False,
                                 max_attention_bytes=4 << 30, graph_slides=None, allowed=None, return_allowed_mass=False,
                                 particles=None, resample_threshold=0.5, return_particles=False, rules=None,
-                                return_rule_report=False):
+                                return_rule_report=False, beam=None, return_beams=False):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -882,7 +932,12 @@ class Decoder(FlatTraining, nn.Module):
         the moved tokens), and the histories of the returned dict have one row per code of the WHOLE sequence.
         rules, return_rule_report: as in `generate_from_codes`.  A held pitch is followed back through the chorale however far
         it reaches, also past the model window and before code_index_start (the PAD / START frame has no pitch).  rule_report
-        has the tokens' shape, after allowed_mass and before attentions."""
+        has the tokens' shape, after allowed_mass and before attentions.
+        beam, return_beams: as in `generate_from_codes`; temperature may stay None.  The hypotheses' chorale rows move with them, the
+        K/V caches too (a slide recomputes them from the moved tokens anyway), and 'ancestors' of the returned dict has one row
+        per position of the WHOLE sequence, in chorale coordinates."""
+        if temperature is None and beam is not None:
+            temperature = 1.0
         if encoding_indices is None or temperature is None:
             raise NotImplementedError('generate_from_code_long(encoding_indices, temperature, ...): generation without codes '
                                       'is not implemented')
@@ -910,14 +965,19 @@ class Decoder(FlatTraining, nn.Module):
             num_decodings=num_decodings, seed=seed, constraint=constraint, return_logp=return_logp,
             return_attentions=return_attentions, max_attention_bytes=max_attention_bytes, allowed=allowed,
             return_allowed_mass=return_allowed_mass, particles=particles, resample_threshold=resample_threshold,
-            return_particles=return_particles, rules=rules, return_rule_report=return_rule_report)
+            return_particles=return_particles, rules=rules, return_rule_report=return_rule_report, beam=beam,
+            return_beams=return_beams)
         return self._result_tuple(res, lambda t: t[:, code_index_start * epc:code_index_end * epc].contiguous())
 
-    def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, **kwargs):
+    def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, beam=None,
+                           return_beams=False, **kwargs):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent
         tensors, concatenated along time) decoded as one sequence, the body's events returned: int64 (num_decodings, events,
         channels).  kwargs go to `generate_from_code_long` -- `allowed` and `return_allowed_mass` among them, in the coordinates
-        of the whole start + body + end sequence, and `rules` / `return_rule_report`, which need no coordinates."""
+        of the whole start + body + end sequence, and `rules` / `return_rule_report`, which need no coordinates.
+        beam, return_beams: `generate_from_code_long`'s beam search; it needs num_decodings=1 and temperature may stay None."""
+        if temperature is None and beam is not None:
+            temperature = 1.0
         if start_codes is None or end_codes is None or body_codes is None or temperature is None:
             raise NotImplementedError('generate_alla_mano(start_codes, end_codes, body_codes, temperature): generation '
                                       'without codes is not implemented')
@@ -931,11 +991,12 @@ class Decoder(FlatTraining, nn.Module):
             codes = torch.tensor(start_codes + body_codes + end_codes, dtype=torch.int64).unsqueeze(0)
         return self.generate_from_code_long(codes, temperature=temperature, num_decodings=num_decodings,
                                             code_index_start=len(start_codes),
-                                            code_index_end=len(start_codes) + len(body_codes), **kwargs)
+                                            code_index_end=len(start_codes) + len(body_codes), beam=beam, return_beams=return_beams,
+                                            **kwargs)
 
     def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False,
                            keep_voices=None, return_logp=False, allowed=None, return_allowed_mass=False, rules=None,
-                           return_rule_report=False, **kwargs):
+                           return_rule_report=False, beam=None, return_beams=False, **kwargs):
         """The body of generate_reharmonisation (:871-941) on a (1, events, channels) token tensor: the chorale is cut into
         model-sized chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD),
         every chunk is encoded, the codes are glued and the chorale's own codes are decoded `num_reharmonisations` times.
@@ -951,7 +1012,9 @@ class Decoder(FlatTraining, nn.Module):
         every other event stays unrestricted.  return_allowed_mass=True: `tokens` above is the tuple of
         `generate_from_code_long`, (tokens[, logp], allowed_mass).
         rules, return_rule_report: `generate_from_code_long`'s; the rules compare the voices of a tick, so they need no
-        coordinates, and rule_report comes back with the tokens, in the same events."""
+        coordinates, and rule_report comes back with the tokens, in the same events.
+        beam, return_beams: `generate_from_code_long`'s beam search -- the most probable harmonisations of the kept voices --; it
+        needs num_reharmonisations=1 and temperature 1."""
         n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
         if n2i is None:
             raise ValueError('reharmonise_tokens needs dataset.note2index_dicts with the START / END / XX symbols')
@@ -1007,7 +1070,7 @@ class Decoder(FlatTraining, nn.Module):
         tokens = self.generate_from_code_long(codes, temperature=temperature, top_k=top_k, top_p=top_p,
                                               num_decodings=num_reharmonisations, code_index_start=code_index_start,
                                               code_index_end=code_index_end, return_logp=return_logp, rules=rules,
-                                              return_rule_report=return_rule_report, **kwargs)
+                                              return_rule_report=return_rule_report, beam=beam, return_beams=return_beams, **kwargs)
         return (tokens, code_index_start, code_index_end, codes.size(1)) if return_bounds else tokens
 
     def generate_reharmonisation(self, *a, **k):

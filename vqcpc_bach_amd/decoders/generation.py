@@ -55,12 +55,22 @@ rule kernel's output; vqcpc_decode_rules runs immediately before vqcpc_decode_sa
 overwrites the live column's set from the tokens emitted so far (the live window's, and the chorale's before it) and the
 column of `rule_report`.  The sampler, the mass and the particle weights read that set unchanged.
 
+Beam search (`start(beam=W)`, csrc/beam.hip): the rows are groups of W consecutive rows, the W best hypotheses of one user row.
+vqcpc_decode_beam_select takes the sampler's place (after vqcpc_decode_rules when rules are on): it expands every row into its
+candidate tokens, keeps each group's W best by total log-probability and writes the whole live column -- tokens, next input rows,
+logp, logmass, rule_report -- in SLOT order, with the ancestors and the two device words `b_bound` = {pos, col} before the
+increment.  The moves that follow (`_beam_moves`, vqcpc_particle_permute_* with P = W) bring the history behind the slots: the live
+tokens' columns [0, b_bound[0]), the record rows' columns [0, b_bound[1]) -- the new column must not move, it is in slot order
+already --, the chorale row, and the K/V cache rows [0, pos) of the incremented pos, because position pos's K/V were written by
+this step for the ancestor.  The moves read only device words, so they live INSIDE the captured step (`beam_moves_in_step`) or
+between the replays, where the cache move is skipped before a slide (profiles/generate_beam_perf_log.md compares the two).
+
 Where the options are set up: `start` and `start_long` take the sampling settings (`_sampling`) and then make ONE call of
 `_configure` with the generation's coordinate frame (`Frame`, transformer/incremental.py): (T, None, 1, S, seeds) for the fixed
 window, (nb * U, win, U, nb, row_seeds) for a chorale.  Every option buffer above has `frame.width` columns and is addressed
 through `frame.win`; the step, the cross hook, the sampler and the resampling read the frame and nothing else about the
 coordinates.  `_configure` sets every option at every call, so a second `start` leaves the earlier call's options off.  The
-record buffers (`logp`, `logmass`, `rule_report`, `self_probs`, `cross_probs`, the `p_*` state) are allocated there and get their
+record buffers (`logp`, `logmass`, `rule_report`, `self_probs`, `cross_probs`, the `p_*` and `b_*` state) are allocated there and get their
 initial values in one place, `_clear_records`, which `reset` and the post-warm-up path of `run_long` call."""
 import ctypes
 
@@ -80,6 +90,8 @@ class IncrementalDecoder(IncrementalStack):
 
     `start` + `step` expose the single steps (teacher forcing, the sampler's inputs `logits` and its optional
     probability output `probs`) for the tests."""
+
+    beam_moves_in_step = True         # the beam's moves are launches of the (captured) step; False: between the steps
 
     def __init__(self, decoder, batch):
         if not 1 <= batch <= MAX_ROWS:
@@ -111,6 +123,7 @@ class IncrementalDecoder(IncrementalStack):
         self.rules, self.rule_static, self.rule_report = None, None, None
         self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
         self.particles = None                                                     # group size P, or None: plain rows
+        self.beam = None                                                          # beam width W, or None: the rows are sampled
         self.continuous = bool(getattr(dec, 'continuous_source', False))
         if self.continuous:
             self.dz = dec.source_dim
@@ -161,7 +174,7 @@ class IncrementalDecoder(IncrementalStack):
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
               constraint=None, want_logp=False, want_attentions=None, allowed=None, want_allowed_mass=False, particles=None,
-              resample_threshold=0.5, final_resample=True, rules=None):
+              resample_threshold=0.5, final_resample=True, rules=None, beam=None):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
         probabilities of the last step in `probs` (M, max V_c).
@@ -181,10 +194,12 @@ class IncrementalDecoder(IncrementalStack):
         forced resampling makes the first row of every group an unweighted draw from the final weights.
         rules: None, or a `templates.VoiceLeadingRules`: vqcpc_decode_rules writes every position's set before the masked
         sampler reads it (`_rule_sets`); `rule_report` (M, T) int32 keeps what was relaxed or broken, -1 where no token was
-        emitted yet."""
+        emitted yet.
+        beam: None, or W in [1, 64] dividing M: the rows are M / W groups of W hypotheses and vqcpc_decode_beam_select replaces the
+        sampler (`_beam`); seeds, temperature, top_k and top_p are then unused."""
         self._sampling(seeds, temperature, top_k, top_p, exclude, teacher, want_probs)
         self._configure(Frame(self.T, None, 1, self.S, self.seeds), constraint, want_logp, allowed, want_allowed_mass, particles,
-                        resample_threshold, final_resample, rules, want_attentions)
+                        resample_threshold, final_resample, rules, want_attentions, beam)
 
     def _sampling(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False):
         """The sampling settings of `start`: what the sampler takes whatever options are on."""
@@ -206,13 +221,14 @@ class IncrementalDecoder(IncrementalStack):
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
 
     def _configure(self, frame, constraint, want_logp, allowed, want_allowed_mass, particles, resample_threshold, final_resample,
-                   rules, want_attentions):
+                   rules, want_attentions, beam=None):
         """The options of one generation, all of them at every call (what is not asked for is switched off), in the coordinates
         of `frame`: `Frame(T, None, 1, S, seeds)` for the fixed window, `Frame(nb * U, win, U, nb, row_seeds)` for a chorale,
         whose buffers are addressed through the device window index.  The record buffers are allocated here, once and before any
         warm-up step (a captured step or slide holds their addresses), and get their values from `reset`, which ends the call."""
         self.frame = frame
         self._particles(particles, resample_threshold, final_resample, want_attentions)
+        self._beam(beam, want_attentions)
         scored = particles is not None                        # the weights are the forced tokens' logp and the sets' mass
         self._constrain(constraint, want_logp or (scored and constraint is not None), frame.width)
         self._mask(allowed, want_allowed_mass or (scored and (allowed is not None or rules is not None)))
@@ -246,6 +262,52 @@ class IncrementalDecoder(IncrementalStack):
         self.p_flag = torch.empty(1, **i32)
         self.p_hist_anc, self.p_hist_wn = torch.empty(codes, M, **i32), torch.empty(codes, M, **f32)
         self.p_hist_ess = torch.empty(codes, G, **f32)
+
+    def _beam(self, W, want_attentions):
+        """The beam's state: per row the hypothesis's total log-probability `b_score` and its last ancestor `b_anc`; the device
+        flag `b_flag` (some row moved), the two words `b_bound` = {pos, col} of the last select before its increment, and per
+        column of the frame the ancestors `b_hist` (int32, -1 where nothing was generated)."""
+        self.beam = None
+        if W is None:
+            return
+        W = int(W)
+        if not 1 <= W <= MAX_ROWS or self.M % W:
+            raise ValueError(f'beam: 1 <= beam <= {MAX_ROWS} dividing the stack\'s {self.M} rows expected, got {W}')
+        if self.particles is not None:
+            raise ValueError('beam and particles exclude each other')
+        if want_attentions is not None:
+            raise ValueError('beam: attention maps are not moved with a hypothesis; want_attentions must be None')
+        if self.teacher is not None or self.probs is not None:
+            raise ValueError('beam and teacher / want_probs exclude each other')
+        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
+        self.beam = W
+        self.b_score, self.b_anc = torch.empty(self.M, **f32), torch.empty(self.M, **i32)
+        self.b_flag, self.b_bound = torch.empty(1, **i32), torch.empty(2, **i32)
+        self.b_hist = torch.empty(self.frame.width, self.M, **i32)
+
+    def _beam_moves(self, move_cache=True):
+        """After vqcpc_decode_beam_select: row k <- row b_anc[k] of everything behind the live column, which the select wrote in
+        slot order already.  The bounds are device words: the tokens move in [0, b_bound[0]), the record rows in [0, b_bound[1]),
+        the caches in [0, pos) of the incremented pos.  move_cache=False before a slide, which recomputes the caches from the
+        moved tokens.  W = 1 has nothing to move."""
+        W, M, w = self.beam, self.M, self.frame.width
+        if W == 1:
+            return
+        anc, flag, bound = self.b_anc, self.b_flag, self.b_bound
+        hip.call('vqcpc_particle_permute_i64', self.tokens, self.T, self.T, bound[0:1], anc, flag, M, W)
+        if self.frame.win is not None:                        # long mode: the history before the live window
+            hip.call('vqcpc_particle_permute_i64', self.chorale, w, w, None, anc, flag, M, W)
+        for rows in (self.logp, self.logmass, self.rule_report):
+            if rows is not None:
+                hip.call('vqcpc_particle_permute_f32', rows, w, w, bound[1:2], anc, flag, M, W)
+        if move_cache:
+            for cache in (self.kcache, self.vcache):
+                hip.call('vqcpc_particle_permute_cache', cache, len(self.layers), self.W, self.d, self.pos, anc, flag, M, W)
+
+    def beam_results(self):
+        """After a run: the hypotheses' total log-probabilities (G, W), non-increasing along W and -inf for a dead slot, and the
+        ancestors per column of the frame."""
+        return {'scores': self.b_score.view(self.M // self.beam, self.beam).clone(), 'ancestors': self.b_hist}
 
     def _resample(self, last, move_cache, chorale=None):
         """After the U steps of a code: the weight update and the resampling decision (vqcpc_particle_resample), then the
@@ -353,6 +415,12 @@ class IncrementalDecoder(IncrementalStack):
                             (self.cross_probs, nan)):
             if rows is not None:
                 rows.fill_(value)
+        if self.beam is not None:                             # the standard start: identical rows would fill the beam with copies
+            self.b_score.fill_(float('-inf'))
+            self.b_score[0::self.beam] = 0.0
+            self.b_anc.copy_(torch.arange(self.M, dtype=torch.int32))
+            for rows, value in ((self.b_flag, 0), (self.b_bound, 0), (self.b_hist, -1)):
+                rows.fill_(value)
         if self.particles is None:
             return
         P = self.particles
@@ -389,6 +457,17 @@ class IncrementalDecoder(IncrementalStack):
         """One of the three sampler entry points: plain unless `constrained`, and masked wins over constrained.  They share
         the operands before (`head`) and after (`tail`) what each one adds."""
         T, d = self.T, self.d
+        if self.beam is not None:
+            w, win = self.frame.width, self.frame.win
+            if self.rules is not None:
+                self._rules_launch()
+            hip.call('vqcpc_decode_beam_select', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.beam,
+                     self.exclude if self.excluding else None, self.constraint, w, self.allowed, w, self.logp, w, self.logmass, w,
+                     self.rule_report, w, win, self.tokens, T, T, self.table, self.table.shape[0], d, self.U, self.x, d,
+                     self.b_score, self.b_anc, self.b_flag, self.b_bound, self.b_hist, self.b_hist.shape[0], None, self.pos)
+            if self.beam_moves_in_step:
+                self._beam_moves()
+            return
         head = (self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.temperature, self.top_k, self.top_p,
                 self.exclude if self.excluding else None, self.seeds)
         tail = (self.tokens, T, T, self.table, self.table.shape[0], d, self.U, self.x, d, self.probs, self.vmax, self.pos)
@@ -400,13 +479,18 @@ class IncrementalDecoder(IncrementalStack):
         if not self.masked:
             hip.call('vqcpc_decode_sample_constrained', *head, *forced, *tail)
             return
-        if self.rules is not None:                            # the live column's set, from the tokens emitted so far
-            windowed = win is not None                        # long mode: the history before the live window is the chorale's
-            hip.call('vqcpc_decode_rules', self.tokens, T, T, self.chorale if windowed else None, w if windowed else 0,
-                     self.constraint, w, self.rule_kinds, self.rule_kinds.shape[1], self._offsets_c, self.nc, self.rule_leap,
-                     self.rules.mask, self.exclude if self.excluding else None, self.rule_static, w, self.allowed, w,
-                     self.rule_report, w, self.pos, win, self.U, self.M)
+        if self.rules is not None:
+            self._rules_launch()
         hip.call('vqcpc_decode_sample_masked', *head, *forced, self.allowed, w, self.logmass, w, *tail)
+
+    def _rules_launch(self):
+        """The live column's set, from the tokens emitted so far."""
+        T, w, win = self.T, self.frame.width, self.frame.win
+        windowed = win is not None                            # long mode: the history before the live window is the chorale's
+        hip.call('vqcpc_decode_rules', self.tokens, T, T, self.chorale if windowed else None, w if windowed else 0,
+                 self.constraint, w, self.rule_kinds, self.rule_kinds.shape[1], self._offsets_c, self.nc, self.rule_leap,
+                 self.rules.mask, self.exclude if self.excluding else None, self.rule_static, w, self.allowed, w,
+                 self.rule_report, w, self.pos, win, self.U, self.M)
 
     # ---- a whole generation --------------------------------------------------------------------------------------------
     def run(self, use_graph=True):
@@ -428,14 +512,18 @@ class IncrementalDecoder(IncrementalStack):
         return self.tokens
 
     def _code_done(self, steps):
-        """Fixed window, after `steps` steps: resamples when they complete a code (the caches always move, nothing slides)."""
+        """Fixed window, after `steps` steps: resamples when they complete a code (the caches always move, nothing slides); a
+        beam's moves follow every step where the step does not hold them."""
+        if self.beam is not None and not self.beam_moves_in_step:
+            self._beam_moves(move_cache=steps < self.T)
         if self.particles is not None and steps % self.U == 0:
             self._resample(steps == self.T, True)
 
     # ---- long mode: sliding window -----------------------------------------------------------------------------------
     @torch.no_grad()
     def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, allowed=None,
-                   want_allowed_mass=False, particles=None, resample_threshold=0.5, final_resample=True, rules=None, **sampling):
+                   want_allowed_mass=False, particles=None, resample_threshold=0.5, final_resample=True, rules=None, beam=None,
+                   **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
         tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
         want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
@@ -447,6 +535,7 @@ class IncrementalDecoder(IncrementalStack):
         particles, resample_threshold, final_resample: as in `start`; the histories have one row per code of the chorale.
         rules: as in `start`, with `rule_report` (M, nb * U) in chorale coordinates; the history of a position reaches back through
         the chorale, wherever the model window lies.
+        beam: as in `start`; `b_hist` has one row per chorale position.
         sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
@@ -471,7 +560,7 @@ class IncrementalDecoder(IncrementalStack):
             self.z_full, self.z_nb = z_full, nb
         self._sampling(seeds, **sampling)
         self._configure(Frame(nb * U, self.win, U, nb, self.row_seeds), constraint, want_logp, allowed, want_allowed_mass,
-                        particles, resample_threshold, final_resample, rules, want_attentions)
+                        particles, resample_threshold, final_resample, rules, want_attentions, beam)
         self.row_seeds.copy_(self.seeds)
 
     def _window(self, P, advance):
@@ -549,8 +638,12 @@ class IncrementalDecoder(IncrementalStack):
                 else:
                     self.slide(tb, tr)
                 live = tb
-            for _ in range(U):
+            between = self.beam is not None and not self.beam_moves_in_step
+            for j in range(U):
                 step_graph.replay() if step_graph is not None else self.step()
+                if between:                               # the caches move only where the next token is generated without a slide
+                    nxt = tb if j + 1 < U else plan[k + 1][1] if k + 1 < len(plan) else None
+                    self._beam_moves(move_cache=nxt == tb)
             if self.particles is not None:                # the caches move only where the next code is generated without a slide
                 last = k + 1 == len(plan)
                 self._resample(last, not last and plan[k + 1][1] == tb, self.chorale)
