@@ -1204,6 +1204,36 @@ int vqcpc_decode_beam_select(const float* logits, int64_t ldl, const int32_t* vo
                              int32_t* flag, int32_t* bound, int32_t* hist_ancestors, int64_t hist_rows, float* cand_out,
                              int32_t* pos, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Scoring given tokens under the decoder (csrc/score.hip, decoders/scoring.py `Decoder.score_tokens`; the outputs are restated in
+ * numpy float64 in tests/score_reference.py).
+ * vqcpc_decode_score: ONE launch scores R independent rows of logits (R, ldl) in the samplers' layout (all voices concatenated,
+ *   voice_offsets [nc + 1]); a wavefront per row, four rows per workgroup, no LDS.  Row r belongs to piece b = row_b[r] and chorale
+ *   column col = row_col[r] (device int32 [R]); its voice is c = col % nc with V_c logits columns, only those are read.  A row with
+ *   col outside [0, cols) or b outside [0, B) is skipped: nothing is read or written for it.  Target t = chorale[b][col] (int64,
+ *   [B][ldch]), clamped to [0, V_c) as the samplers clamp a forced token.  Every output is optional (NULL: not computed) and is
+ *   written at [b * ld + col] of its own [B][ld] array, nowhere else:
+ *     logp      float32  (x_t - m) - logf(s), m / s the row maximum and exp-sum over the V_c columns, formed exactly as
+ *               vqcpc_decode_sample_constrained forms logp (lane l holds tokens 4l .. 4l + 3, a lane-serial sum of four, the same
+ *               wave reductions): the bits that sampler writes for this row with t forced
+ *     logmass   float32  (m_a - m) + logf(s_a) - logf(s) over the set allowed[b][col][0..8) (uint32 words, [B][ldallow][8], bit
+ *               i & 31 of word i >> 5), formed exactly as vqcpc_decode_sample_masked forms it: its bits.  Only bits [0, V_c) count,
+ *               a set without any is no restriction, allowed == NULL is the full set; the full set gives exactly 0
+ *     entropy   float32  -sum_i p_i log p_i in nats over the V_c tokens, as logf(s) + (sum_i e_i (m - x_i)) / s with e_i = expf(x_i - m):
+ *               every term is >= 0; the sums in the order above
+ *     rank      int32    #{i < V_c : x_i > x_t or (x_i == x_t and i < t)}: 0 = the model's first choice.  Exact
+ *     best      int64    the arg-max over [0, V_c), the lowest index among equals.  Exact
+ *     best_logp float32  logp formed for `best`
+ *   A row's results depend on nothing but its own logits, set and target: a row alone gives the bits it gives among others.
+ *   The launch function refuses, before any HIP call: NULL required pointers, nc > 16, V_c outside [1, 256], R, B or cols < 1,
+ *   ldl smaller than the voices' widths, ldch, ld or (with allowed) ldallow smaller than cols.  No allocation or synchronisation.
+ * Adding it left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_decode_score(const float* logits, int64_t ldl, const int32_t* voice_offsets, int nc, int64_t R, const int32_t* row_b,
+                       const int32_t* row_col, const int64_t* chorale, int64_t ldch, const uint32_t* allowed, int64_t ldallow,
+                       int64_t B, int64_t cols, int64_t ld, float* logp, float* logmass, float* entropy, int32_t* rank, int64_t* best,
+                       float* best_logp, void* stream);
+
 #ifdef VQCPC_LAB
 /* ==================================================================================================================
  * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).

@@ -17,6 +17,9 @@ A decoder on continuous latents (a `NoQuantization` encoder without upscaler, de
 `check_duplicate` / `check_duplicate_all_corpus` (:983-1017) report the longest run of tokens a generation shares with another
 sequence or with the training corpus (csrc/duplicates.hip; dataloaders/corpus.py states the definition and where it departs from
 the reference's character-level difflib match).  Plots and the absolute-position variant are out of scope and raise.
+`score_tokens` / `score_chorale` / `score_window_plan` (ours) give the log-probability, entropy, rank and arg-max of GIVEN tokens
+under the long form's window rule, every window of a piece as one row of a teacher-forced forward (decoders/scoring.py,
+csrc/score.hip).
 `source_embedding='product'` (ours, `decoder_kwargs['source_embedding']`; default 'merged' = the reference's table of
 K**ncb rows): `source_embeddings` is a `ProductEmbedding` (ncb, K, d_model) and a code's source row the sum of the rows of its
 ncb digits (quantizer/product_embedding.py).  Merged codes stay the interface; only the lookup differs.
@@ -229,12 +232,13 @@ class Decoder(FlatTraining, nn.Module):
         tgt_table = ops.linear(x_table, self.linear_target.weight, self.linear_target.bias)  # (vmax * U, d)
         return torch.cat([tgt_table, self.sos.view(1, d)], dim=0)                            # + start-of-sentence row
 
-    def _target_rows(self, x):
-        """(B, events, channels) int64 on the device -> (B * T, d_model) shifted target rows (see module docstring)."""
+    def _target_rows(self, x, table=None):
+        """(B, events, channels) int64 on the device -> (B * T, d_model) shifted target rows (see module docstring).  table: a
+        `_target_table` the caller already has (one evaluation for many batches of the same weights)."""
         B = x.shape[0]
         U = self.total_upscaling
         dev = x.device
-        table = self._target_table(dev)
+        table = self._target_table(dev) if table is None else table
         vmax = (table.shape[0] - 1) // U
         tok = flatten(x)                                                                     # (B, T), t = event * nc + voice
         T = tok.shape[1]
@@ -994,6 +998,114 @@ class Decoder(FlatTraining, nn.Module):
                                             code_index_end=len(start_codes) + len(body_codes), beam=beam, return_beams=return_beams,
                                             **kwargs)
 
+    def _frame_and_encode(self, x, n2i):
+        """The framing of generate_reharmonisation (:871-941): x (1, events, channels) int64 on the host is cut into model-sized
+        chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD), every chunk is
+        encoded and the codes are glued.  -> (codes (1, chunks * S [, dz]), code_index_start, code_index_end -- the codes of x's own
+        chunks without the completion's --, the framed tokens (chunks, E, channels) on the device)."""
+        nc, E, dev = self.num_channels, self.data_processor.num_events, self.sos.device
+        PAD, START, END = ([int(n2i[c][sym]) for c in range(nc)] for sym in ('XX', 'START', 'END'))
+        row = lambda ids, n: torch.tensor(ids, dtype=torch.int64).view(1, 1, nc).repeat(1, n, 1)
+        x_chunks = list(x.split(E, 1))
+        last_chunk = x_chunks[-1]
+        start_chunk = torch.cat([row(PAD, E - 1), row(START, 1)], 1)
+        completion_length = E - last_chunk.size(1)
+        if completion_length >= 1:
+            x_chunks[-1] = torch.cat([last_chunk, row(END, 1), row(PAD, completion_length - 1)], 1)
+            end_chunk = row(PAD, E)
+        else:
+            end_chunk = torch.cat([row(END, 1), row(PAD, E - 1)], 1)
+        chunks = torch.cat([start_chunk] + x_chunks + [end_chunk], dim=0).to(dev)
+        was_training = self.training
+        self.eval()
+        try:
+            codes = self.encode(chunks)                                               # glued: (1, chunks * S [, dz])
+            codes = codes.reshape(1, -1, self.source_dim) if self.continuous_source else codes.reshape(1, -1)
+        finally:
+            self.train(was_training)
+        U = self.total_upscaling
+        code_index_start = start_chunk.size(1) * nc // U
+        code_index_end = codes.size(1) - (end_chunk.size(1) + completion_length) * nc // U
+        return codes, code_index_start, code_index_end, chunks
+
+    # ---- scoring given tokens: every window of a piece at once, decoders/scoring.py, csrc/score.hip ----------------------------
+    @staticmethod
+    def score_window_plan(num_blocks, num_blocks_model, code_index_start, code_index_end):
+        """Host only: the distinct model windows in which `generate_from_code_long` emits the codes of [code_index_start,
+        code_index_end) of a sequence of `num_blocks` codes, as a list of (first code of the window, first code scored in it, one
+        past the last code scored in it), windows ascending.  Code t's window is `compute_start_end_times(t, ...)`'s, the one
+        `attention_window_starts` reports for its positions: every code of the range lies in exactly one window, no window is
+        without a code, and num_blocks == num_blocks_model gives one window.  ValueError on num_blocks < num_blocks_model or a
+        bad code range."""
+        from .scoring import window_plan
+        return window_plan(num_blocks, num_blocks_model, code_index_start, code_index_end, Decoder.compute_start_end_times)
+
+    def score_tokens(self, x, codes, code_index_start=None, code_index_end=None, pad=None, start=None, allowed=None,
+                     return_details=False, window_rows=32):
+        """How probable the tokens x are under this decoder, given the codes: the log-probabilities a forced
+        `generate_from_code_long(codes, constraint=x, return_logp=True)` returns, computed without generating -- every model
+        window of every piece is one row of a batched, teacher-forced forward (decoders/scoring.py).
+        x: (B, nb * events_per_code, channels) int64 over the WHOLE code sequence, in chorale coordinates, like `constraint`;
+        codes: (B, nb) merged codes [continuous decoder: (B, nb, dz) latents], nb >= S.  The scored chorale is
+        `init_generation_chorale` (PAD, START at the event before code_index_start; pad / start as there) with x written over the
+        events of codes [code_index_start, code_index_end) (None: the whole sequence) -- the chorale a forced generation ends
+        with; x outside that range is ignored.
+        -> logp float32 (B, events of the range, channels), the shape `generate_from_code_long` returns.
+        return_details=True -> a dict of tensors of that shape: 'logp'; 'entropy' (float32, nats) of the model's distribution at
+        the position; 'rank' (int32) of the written token, 0 = the model's first choice, equal logits in index order; 'best'
+        (int64), what the model would have written (arg-max, the lowest index among equals); 'best_logp' (float32); and with
+        `allowed` 'allowed_mass' (float32), the log of the probability the position's set leaves open.
+        allowed: `generate_from_code_long`'s mask, bool (B, nb * events_per_code, channels, vmax) or shared by the rows, with its
+        validation and packing; a written token outside its set is scored all the same.
+        window_rows: (piece, window) rows per forward; 32 is the decoder's training batch, the shape the forward's launches are
+        tuned for.  The results of two values agree within the teacher-forced tolerance, not necessarily bit for bit.
+        Runs in eval mode without gradients under STEP_LOCK; the previous mode is restored.  ValueError on wrong shapes or dtypes,
+        nb < S, a bad code range, a source of the wrong kind, window_rows < 1, and a token of the range outside its voice's
+        vocabulary (the first (row, event, voice) is named)."""
+        from .scoring import score_tokens
+        return score_tokens(self, x, codes, code_index_start, code_index_end, pad, start, allowed, return_details, window_rows)
+
+    def score_chorale(self, x, allowed=None, **kwargs):
+        """`score_tokens` for a bare piece x (1, events, channels): x is framed and encoded as `reharmonise_tokens` frames it
+        (PAD...START chunk, END / PAD completion; needs the dataset's START / END / XX symbols), its own codes are scored, and
+        the results come back on x's own events -- the END / PAD completion is scored with the last chunk but not returned.
+        allowed: bool (events, channels, vmax) or (1, events, channels, vmax) in x's OWN event coordinates, as in
+        `reharmonise_tokens`; the other events are unrestricted.  kwargs: `return_details`, `window_rows`."""
+        n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
+        if n2i is None:
+            raise ValueError('score_chorale needs dataset.note2index_dicts with the START / END / XX symbols')
+        nc, E = self.num_channels, self.data_processor.num_events
+        x = torch.as_tensor(x).long().cpu()
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[2] != nc or x.shape[1] < 1:
+            raise ValueError(f'x: (1, events, {nc}) tokens expected, got {tuple(x.shape)}')
+        vocab = torch.tensor([int(v) for v in self.num_tokens_per_channel], dtype=torch.int64)
+        bad = ((x < 0) | (x >= vocab)).reshape(-1)                                        # checked before the encoder embeds x
+        if bool(bad.any()):
+            e, c = divmod(int(bad.to(torch.int32).argmax()), nc)
+            raise ValueError(f'x: (row 0, event {e}, voice {c}) holds token {int(x[0, e, c])}, outside its voice\'s vocabulary '
+                             f'[0, {int(vocab[c])})')
+        unknown = set(kwargs) - {'return_details', 'window_rows'}
+        if unknown:
+            raise TypeError(f'score_chorale: unexpected keyword arguments {sorted(unknown)}')
+        n = x.shape[1]
+        codes, code_index_start, code_index_end, chunks = self._frame_and_encode(x, n2i)
+        framed = chunks.reshape(1, -1, nc)
+        if allowed is not None:
+            allowed = torch.as_tensor(allowed)
+            if allowed.dtype != torch.bool or allowed.dim() not in (3, 4) or allowed.shape[-3:-1] != (n, nc) or \
+                    (allowed.dim() == 4 and allowed.shape[0] != 1):
+                raise ValueError(f'allowed: bool ({n}, {nc}, vmax) in x\'s event coordinates expected, got '
+                                 f'{tuple(allowed.shape)} {allowed.dtype}')
+            whole = torch.ones(framed.shape[1], nc, allowed.shape[-1], dtype=torch.bool, device=allowed.device)
+            whole[E:E + n] = allowed.reshape(n, nc, -1)
+            allowed = whole
+        n2 = [n2i[c] for c in range(nc)]
+        res = self.score_tokens(framed, codes, code_index_start=code_index_start, code_index_end=code_index_end,
+                                pad=[int(d['XX']) for d in n2], start=[int(d['START']) for d in n2], allowed=allowed, **kwargs)
+        first = E - code_index_start * self.num_events_per_code                           # x's event 0 in the returned range
+        take = lambda t: t[:, first:first + n].contiguous()
+        return {k: take(v) for k, v in res.items()} if isinstance(res, dict) else take(res)
+
     def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False,
                            keep_voices=None, return_logp=False, allowed=None, return_allowed_mass=False, rules=None,
                            return_rule_report=False, beam=None, return_beams=False, **kwargs):
@@ -1030,28 +1142,7 @@ class Decoder(FlatTraining, nn.Module):
             kept = torch.full_like(x, -1)
             kept[:, :, voices] = x[:, :, voices]
             self._constraint_rows(kept, 1, x.shape[1])
-        PAD, START, END = ([int(n2i[c][sym]) for c in range(nc)] for sym in ('XX', 'START', 'END'))
-        row = lambda ids, n: torch.tensor(ids, dtype=torch.int64).view(1, 1, nc).repeat(1, n, 1)
-        x_chunks = list(x.split(E, 1))
-        last_chunk = x_chunks[-1]
-        start_chunk = torch.cat([row(PAD, E - 1), row(START, 1)], 1)
-        completion_length = E - last_chunk.size(1)
-        if completion_length >= 1:
-            x_chunks[-1] = torch.cat([last_chunk, row(END, 1), row(PAD, completion_length - 1)], 1)
-            end_chunk = row(PAD, E)
-        else:
-            end_chunk = torch.cat([row(END, 1), row(PAD, E - 1)], 1)
-        chunks = torch.cat([start_chunk] + x_chunks + [end_chunk], dim=0).to(dev)
-        was_training = self.training
-        self.eval()
-        try:
-            codes = self.encode(chunks)                                               # glued: (1, chunks * S [, dz])
-            codes = codes.reshape(1, -1, self.source_dim) if self.continuous_source else codes.reshape(1, -1)
-        finally:
-            self.train(was_training)
-        U = self.total_upscaling
-        code_index_start = start_chunk.size(1) * nc // U
-        code_index_end = codes.size(1) - (end_chunk.size(1) + completion_length) * nc // U
+        codes, code_index_start, code_index_end, _ = self._frame_and_encode(x, n2i)
         if voices is not None:
             constraint = torch.full((1, codes.size(1) * self.num_events_per_code, nc), -1, dtype=torch.int64)
             constraint[:, E:E + x.shape[1]] = kept
