@@ -39,9 +39,8 @@ extern "C" {
  * enqueued and do not change them from a second thread while another one launches.
  *   vqcpc_gemm_set_mode        which GEMM ARITHMETIC vqcpc_gemm_* launch: 0 fp32 MFMA / 1 bf16x6 / 8 bf16 (read by vqcpc_gemm_nt,
  *                              _tn, _tn_grouped, _nt_splitk, _nt_relu_mask, _nt_gatebits and by the *_workspace / *_supported /
- *                              *_groupable queries, whose answers belong to the mode they were asked in).  The product library
- *                              has NO kernel-selection switch (round 5: the A/B bits +2 / +4 of this call and
- *                              vqcpc_gemm_bf16_set_variant exist in lab builds only)
+ *                              *_groupable queries, whose answers belong to the mode they were asked in).  The library has NO
+ *                              kernel-selection switch and reads no tuning variable: every other mode value is refused
  *   vqcpc_gemm_set_gradient_products / vqcpc_gemm_gradient_scope   the bf16-pair gradient arithmetic of round 3 (kept for
  *                              comparison): the scope is a counter, opened and closed by ONE thread around its backward pass.
  *                              The f16x3 gradient GEMMs that training uses (vqcpc_gemm_nt_grad / _tn_grad) are explicit entry
@@ -174,7 +173,8 @@ int vqcpc_product_gather_bwd(const float* g, int64_t ldg, const int64_t* sorted_
  * (v_mfma_f32_32x32x16_bf16) and fp32 accumulation -- fp32-class accuracy at 2.67x the fp32 MFMA rate.
  * mode 8 = plain bf16: operands rounded to bf16 (nearest even), ONE bf16 MFMA per product, fp32 accumulation and epilogue
  * (reduced precision; BASELINE configs[4] names it; 128 x 128 tile kernels).  vqcpc_gemm_get_mode returns 0 / 1 / 2.
- * Process-wide; the initial value comes from the environment variable VQCPC_GEMM_MODE (0, 1, or 8; default 0). */
+ * Process-wide; the initial value comes from the environment variable VQCPC_GEMM_MODE (0, 1, or 8; default 0).
+ * vqcpc_gemm_set_mode accepts 0, 1 and 8 and refuses every other value (VQCPC_EINVAL; the mode in force stays). */
 int vqcpc_gemm_set_mode(int mode);
 int vqcpc_gemm_get_mode(void);
 /* Gradient arithmetic of the bf16x6 mode -- OPT-IN, default 6 (= the forward's exact split everywhere).  With 3, the
@@ -693,8 +693,7 @@ int vqcpc_cast_bf16(const float* in, int64_t ld_in, void* out, int64_t rows, int
 int vqcpc_gemm_nt_bf16_supported(int64_t M, int N, int K);
 /* vqcpc_gemm_nt_bf16 / vqcpc_gemm_tn_bf16 deliver their operands global -> LDS by DMA in whole 128-byte lines -- NT: K tiles of
  * 64, one barrier per K tile (K % 128 == 0, otherwise the register-staged ping-pong kernel with K tiles of 32: bit-identical
- * results); TN: 64-row slots in their row-major form, fragments by ds_read_b64_tr_b16.  (The A/B switch between the DMA and
- * the register-staged kernels, vqcpc_gemm_bf16_set_variant, is a lab-build entry point.) */
+ * results); TN: 64-row slots in their row-major form, fragments by ds_read_b64_tr_b16. */
 int vqcpc_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, void* Cb, int64_t ldcb,
                        int64_t M, int N, int K, const float* bias, int act, float drop_p, uint64_t seed, const float* gate,
                        int64_t ldgate, const void* gate_bf16, int64_t ldgate_bf16, float gate_scale, const float* add,
@@ -1233,36 +1232,6 @@ int vqcpc_decode_score(const float* logits, int64_t ldl, const int32_t* voice_of
                        const int32_t* row_col, const int64_t* chorale, int64_t ldch, const uint32_t* allowed, int64_t ldallow,
                        int64_t B, int64_t cols, int64_t ld, float* logp, float* logmass, float* entropy, int32_t* rank, int64_t* best,
                        float* best_logp, void* stream);
-
-#ifdef VQCPC_LAB
-/* ==================================================================================================================
- * LAB BUILDS ONLY (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so; never loaded by the training steps).
- * Rejected kernel designs kept for A/B measurements by the tools under tools/; the lab library additionally honours the
- * tools' environment switches (VQCPC_PP_ABL, VQCPC_PP_GRID, VQCPC_TN_PQ, VQCPC_S64_MAX_TILES, VQCPC_SPLITK_MIN_K / _KS,
- * VQCPC_BF16_STAGGER, VQCPC_LN_BWD_BLOCKS, VQCPC_RELATTN16_LDS, VQCPC_GEMM_ABL) and the vqcpc_gemm_set_mode bits +16
- * (gemm_dma.hip) and +32 (gemm_sw.hip).  The product library reads none of them.
- * ================================================================================================================== */
-/* ------------------------------------------------------------------------------------------------------------------
- * bf16x6 GEMM on pre-split operands (csrc/gemm_planes.hip; no reference counterpart: the same F.linear products as
- * vqcpc_gemm_nt in mode 1, bit-identical results, with the exact 3-way bf16 split done once by the producer).
- *   "P3" format of an fp32 matrix X[rows][cols], cols % 16 == 0: three bf16 planes p = 0 (high), 1 (mid), 2 (low) with
- *   x == high + mid + low exactly, stored K-tile-major: element (p, r, k) at ((p * cols/16 + k/16) * rows + r) * 16 + k % 16
- *   (bf16 units); vqcpc_planes_bytes(rows, cols) = 6 * rows * cols bytes.
- *   vqcpc_split3_planes  X (row stride ld floats) -> P3;  vqcpc_join3_planes  P3 -> X (exact; tests)
- *   vqcpc_gemm_nt_planes C[M,N] = epi(A . B^T) with A = P3 of [M][K], B = P3 of [N][K]; epilogue arguments as vqcpc_gemm_nt.
- *                        M, N multiples of 256, K of 32, each operand's planes below 4 GB (vqcpc_gemm_nt_planes_supported).
- * ------------------------------------------------------------------------------------------------------------------ */
-/* A/B switch of vqcpc_gemm_nt_bf16 / _tn_bf16: 1 (default) = the LDS-DMA kernels, 0 = the register-staged ones. */
-int vqcpc_gemm_bf16_set_variant(int variant);
-int64_t vqcpc_planes_bytes(int64_t rows, int cols);
-int vqcpc_split3_planes(const float* x, int64_t ld, int64_t rows, int cols, void* planes, void* stream);
-int vqcpc_join3_planes(const void* planes, int64_t rows, int cols, float* x, int64_t ld, void* stream);
-int vqcpc_gemm_nt_planes_supported(int64_t M, int N, int K);
-int vqcpc_gemm_nt_planes(const void* a_planes, const void* b_planes, float* C, int64_t ldc, int64_t M, int N, int K,
-                         const float* bias, int act, float drop_p, uint64_t seed, const float* gate, int64_t ldgate,
-                         float gate_scale, const float* add, int64_t ldadd, void* stream);
-
-#endif /* VQCPC_LAB */
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // Host check of vqcpc_bach_amd/csrc/gemm_forms.h (no HIP, no GPU; built and run by tests/test_gemm_forms.py, with the address and
-// undefined-behaviour sanitizers): the table of gemm_nt_g3_kernel<EPI, 0, PL> instantiations is the 28 forms written out below, the
+// undefined-behaviour sanitizers): the table of gemm_nt_g3_kernel<EPI, PL> instantiations is the 28 forms written out below, the
 // operands -> form mapping sends every combination of operands the entry points document to an entry and every other combination to
 // none, and every entry is reached by some combination (no dead instantiation).
 #include <cstdio>

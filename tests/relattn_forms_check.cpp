@@ -29,12 +29,12 @@ static int failures = 0;
     } while (0)
 
 // The documented rule, written entry by entry without the table under test.  `al`: the aligned pointers.
-static AttKernel documented(int family, bool bwd, int L, int H, int hd, bool force, bool lds_only, unsigned al, bool tokens) {
+static AttKernel documented(int family, bool bwd, int L, int H, int hd, bool force, unsigned al, bool tokens) {
     const bool qkv = al & P_QKV, e1 = al & P_E1, e2 = al & P_E2, out = al & P_OUT, dctx = !bwd || (al & P_DCTX), ws = al & P_WS;
     const bool hd3 = hd == 16 || hd == 32 || hd == 64;
     // "L = 16 and L = 4 run the one-wavefront-per-block kernels": 4 (L = 16) or 16 (L = 4) problems per workgroup, whole heads
     const bool wave = !force && hd3 && ((L == 16 && (H == 1 || H == 2 || H % 4 == 0)) || (L == 4 && (16 % H == 0 || H % 16 == 0)));
-    const bool cores = L == 16 && !lds_only;                       // the matrix-core kernels, given aligned operands
+    const bool cores = L == 16;                                  // the matrix-core kernels, given aligned operands
     switch (family) {
         case ATT_F32:
             if (wave) return cores && qkv && e1 && e2 && out && dctx ? ATT_MFMA16 : ATT_LDS;
@@ -46,7 +46,7 @@ static AttKernel documented(int family, bool bwd, int L, int H, int hd, bool for
             return cores && e1 && e2 ? ATT_MFMA16 : ATT_LDS;
         case ATT16_B16:
         case ATT16_B16IO:                                          // L = 16 matrix-core attention only, any head count
-            return !force && !lds_only && hd3 && H >= 1 && qkv && e1 && e2 && out && dctx ? ATT_MFMA16 : ATT_REFUSED;
+            return !force && hd3 && H >= 1 && qkv && e1 && e2 && out && dctx ? ATT_MFMA16 : ATT_REFUSED;
         default:                                                   // ATT_TAB: "L in {16, 4} only", rows through the tokens
             if (!tokens || !wave) return ATT_REFUSED;
             return cores && qkv && e1 && e2 && out && dctx ? ATT_MFMA16 : ATT_LDS;
@@ -79,15 +79,15 @@ int main() {
         for (int L : Ls)
             for (int H : Hs)
                 for (int hd : hds)
-                    for (int flags = 0; flags < 8; ++flags)
+                    for (int flags = 0; flags < 4; ++flags)
                         for (unsigned al = 0; al < 64; ++al) {
                             const AttEntry& e = kAttEntries[i];
-                            const bool force = flags & 1, lds_only = flags & 2, tokens = flags & 4;
-                            const AttRoute r = att_route(e, L, H, hd, force, lds_only, al, tokens);
-                            const AttKernel want = documented(i / 2, e.bwd, e.has_L ? L : 16, H, hd, force, lds_only, al, tokens);
+                            const bool force = flags & 1, tokens = flags & 2;
+                            const AttRoute r = att_route(e, L, H, hd, force, al, tokens);
+                            const AttKernel want = documented(i / 2, e.bwd, e.has_L ? L : 16, H, hd, force, al, tokens);
                             ++calls, ++count[r.kernel];
-                            CHECK(r.kernel == want, "%s L=%d H=%d hd=%d force=%d lds_only=%d aligned=%#x tokens=%d: route %d, documented %d",
-                                  e.name, L, H, hd, force, lds_only, al, tokens, r.kernel, want);
+                            CHECK(r.kernel == want, "%s L=%d H=%d hd=%d force=%d aligned=%#x tokens=%d: route %d, documented %d",
+                                  e.name, L, H, hd, force, al, tokens, r.kernel, want);
                             CHECK((r.kernel == ATT_REFUSED) == (r.why != nullptr), "%s: a refusal and only a refusal says why", e.name);
                             if (r.kernel == ATT_LDS) {
                                 CHECK(dispatch(AttLdsForms{}, L, hd, [&](auto) {}) && !(e.io & IN16), "%s: no LDS kernel <%d, %d>", e.name, L, hd);

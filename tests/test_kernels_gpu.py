@@ -5,7 +5,6 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import lab_only  # noqa: F401
 from conftest import load_golden, rel_err, sub_state
 from oracle import vqcpc_oracle as O
 
@@ -257,55 +256,8 @@ def test_gemm_nt_bf16x6_epilogues(ops, bf16x6, M, N, K):
     assert float(dst[1::4].abs().max()) == 0.0
 
 
-@lab_only
-@pytest.mark.parametrize('M,N,K', [(512, 256, 64), (1024, 768, 256), (256 * 300, 256, 128), (2048, 1024, 1024), (256 * 130, 512, 64)])
-def test_gemm_nt_bf16x6_dma_kernel_is_bit_identical_to_the_register_staged_kernel(ops, M, N, K):
-    """gemm_nt_x6_dma_kernel (operands global -> LDS by DMA, fragments split per wave) against gemm_nt_x6_pp_kernel
-    (global -> registers -> split -> LDS): same exact split, same MFMA order per K tile -> bitwise-equal outputs, for every
-    epilogue of the 256-tile path, with several output tiles per persistent workgroup (300 / 260 tiles on 256 CUs) and
-    strided operand / output rows; and against the fp64 product."""
-    from vqcpc_bach_amd import hip
-    gen = torch.Generator().manual_seed(M + N + K)
-    a, b, bias = torch.randn(M, K, generator=gen), torch.randn(N, K, generator=gen), torch.randn(N, generator=gen)
-    gate, add = torch.randn(M, N, generator=gen), torch.randn(M, N, generator=gen)
-    ad, bd, biasd, gated, addd = dev(a), dev(b), dev(bias), dev(gate), dev(add)
-    big = dev(torch.randn(2 * M, K, generator=gen))
-    outs = {}
-    try:
-        for mode in (17, 1):                      # 17: LDS-DMA kernel, 1: register-staged ping-pong kernel
-            hip.set_gemm_mode(mode)
-            dst = torch.zeros(2 * M, N, device='cuda')
-            ops.gemm_nt(big[::2], bd, bias=biasd, out=dst[::2])
-            outs[mode] = [ops.gemm_nt(ad, bd), ops.gemm_nt(ad, bd, bias=biasd), ops.gemm_nt(ad, bd, bias=biasd, act=1),
-                          ops.gemm_nt(ad, bd, bias=biasd, act=1, drop_p=0.25, seed=5),
-                          ops.gemm_nt(ad, bd, gate=gated, gate_scale=1.5), ops.gemm_nt(ad, bd, add=addd), dst]
-    finally:
-        hip.set_gemm_mode(0)
-    for x, y in zip(outs[1], outs[17]):
-        assert torch.equal(x, y)
-    ref = a.double() @ b.double().t()
-    assert rel_err(outs[17][0].cpu(), ref) < 2e-6 * max(1, K ** 0.5)
-    assert rel_err(outs[17][5].cpu(), ref + add.double()) < 2e-6 * max(1, K ** 0.5)
-    assert float(outs[17][6][1::2].abs().max()) == 0.0
-
-
-@pytest.fixture(params=[1, 0], ids=['k64-dma', 'k32-pingpong'])
-def bf16_nt_variant(request):
-    """Both kernels behind vqcpc_gemm_nt_bf16: 1 = K tiles of 64 by LDS-DMA (default, K % 128 == 0), 0 = ping-pong, K tiles of 32."""
-    from vqcpc_bach_amd import hip
-    hip.load()
-    if not hip.is_lab():
-        if request.param == 0:
-            pytest.skip('the A/B switch between the bf16 kernels is a lab-build entry point (VQCPC_LAB=1)')
-        yield request.param                       # the product library always prefers the DMA kernels
-        return
-    hip.call('vqcpc_gemm_bf16_set_variant', request.param)
-    yield request.param
-    hip.call('vqcpc_gemm_bf16_set_variant', 1)
-
-
 @pytest.mark.parametrize('M,N,K', [(512, 256, 64), (1024, 768, 512), (256 * 260, 256, 128), (2048, 512, 2048), (256 * 300, 512, 256)])
-def test_gemm_nt_bf16_native_kernel(ops, bf16_nt_variant, M, N, K):
+def test_gemm_nt_bf16_native_kernel(ops, M, N, K):
     """vqcpc_gemm_nt_bf16 (bf16 operands in HBM, fp32 accumulation) against the fp64 product of the bf16-rounded operands:
     every epilogue / output combination the training step uses, several output tiles per persistent workgroup."""
     gen = torch.Generator().manual_seed(M + N + K)
@@ -341,34 +293,6 @@ def test_gemm_nt_bf16_native_kernel(ops, bf16_nt_variant, M, N, K):
     n = 512
     eye, bb2 = torch.eye(n), (torch.arange(n * n, dtype=torch.float32).reshape(n, n) % 251)
     assert torch.equal(ops.gemm_nt_bf16(dev(eye), dev(bb2)).cpu(), bb2.t().contiguous())
-
-
-@lab_only
-@pytest.mark.parametrize('M,N,K', [(512, 256, 128), (256 * 260, 256, 256), (2048, 512, 2048), (256 * 300, 512, 512)])
-def test_gemm_nt_bf16_kernels_are_bit_identical(ops, M, N, K):
-    """The LDS-DMA kernel (K tiles of 64) sums every output element over k in the order of the ping-pong kernel (K tiles of
-    32): both give the same bits for every epilogue / output form of the training step (persistent workgroups with several
-    output tiles each at the larger shapes: tile-boundary handling of the DMA ring)."""
-    from vqcpc_bach_amd import hip
-    gen = torch.Generator().manual_seed(M + K)
-    a, b = ops.cast_bf16(dev(torch.randn(M, K, generator=gen))), ops.cast_bf16(dev(torch.randn(N, K, generator=gen)))
-    bias, add = dev(torch.randn(N, generator=gen)), dev(torch.randn(M, N, generator=gen))
-    gate, gb = dev(torch.randn(M, N, generator=gen)), dev(torch.randn(M, N, generator=gen)).bfloat16()
-    forms = [dict(), dict(out_f32=False, out_bf16=True), dict(bias=bias), dict(bias=bias, out_f32=True, out_bf16=True),
-             dict(bias=bias, act=1, out_f32=False, out_bf16=True), dict(bias=bias, act=1, drop_p=0.25, seed=7, out_f32=False, out_bf16=True),
-             dict(bias=bias, act=1, drop_p=0.25, seed=7, out_f32=True, out_bf16=True), dict(gate=gate, gate_scale=1.5),
-             dict(gate_b=gb, gate_scale=1.5, out_f32=False, out_bf16=True), dict(gate_b=gb, gate_scale=1.5, out_f32=True, out_bf16=True),
-             dict(add=add), dict(bias=bias, add=add), dict(bias=bias, drop_p=0.1, seed=3, add=add), dict(bias=bias, out_f32=False, out_bf16=True)]
-    try:
-        for kw in forms:
-            outs = []
-            for v in (0, 1):
-                hip.call('vqcpc_gemm_bf16_set_variant', v)
-                r = ops.gemm_nt_bf16(a, b, **kw)
-                outs.append([x.clone() for x in (r if isinstance(r, tuple) else (r,))])
-            assert all(torch.equal(x, y) for x, y in zip(*outs)), sorted(kw)
-    finally:
-        hip.call('vqcpc_gemm_bf16_set_variant', 1)
 
 
 @pytest.mark.parametrize('M,N,K', [(512, 512, 256), (256 * 260, 512, 2048)])
@@ -487,21 +411,14 @@ def test_dma_gemm_kernels_under_memory_contention(ops, M, N, K):
     """Race screen of the two kernels that order their LDS-DMA deliveries with COUNTED `s_waitcnt vmcnt(n)` instead of barriers
     around every transfer (gemm_nt_bf16_k64_kernel, gemm_tn_bf16_tr_kernel; SURVEY.md section 5 "race detection"): 200 launches
     each while a second stream streams 1 GB copies through HBM / L2 (which stretches and reorders the latency of every DMA), bit
-    for bit against the result of a quiet launch -- and, on a lab build, against the register-staged kernels, which have no
-    counted waits.  A counted wait that is one transfer short shows up as a stale fragment under exactly this load."""
-    from vqcpc_bach_amd import hip
+    for bit against the result of a quiet launch.  A counted wait that is one transfer short shows up as a stale fragment under
+    exactly this load."""
     gen = torch.Generator().manual_seed(M + K)
     a, b = ops.cast_bf16(dev(torch.randn(M, K, generator=gen))), ops.cast_bf16(dev(torch.randn(N, K, generator=gen)))
     bias = dev(torch.randn(N, generator=gen))
     g, x = ops.cast_bf16(dev(torch.randn(M, N, generator=gen))), a
     quiet_nt = ops.gemm_nt_bf16(a, b, bias=bias).clone()
     quiet_tn = [t.clone() for t in ops.gemm_tn_bf16(g, x)]
-    if hip.is_lab():
-        hip.call('vqcpc_gemm_bf16_set_variant', 0)
-        try:
-            assert torch.equal(ops.gemm_nt_bf16(a, b, bias=bias), quiet_nt), 'DMA vs register-staged NT kernel'
-        finally:
-            hip.call('vqcpc_gemm_bf16_set_variant', 1)
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
     src, dst = torch.empty(1 << 28, dtype=torch.float32, device='cuda'), torch.empty(1 << 28, dtype=torch.float32, device='cuda')
@@ -523,10 +440,10 @@ def test_dma_gemm_kernels_under_memory_contention(ops, M, N, K):
 
 @pytest.mark.parametrize('M,N,K', [(512, 256, 256), (4096, 512, 256), (128 * 700, 256, 768), (33280, 1024, 512), (128, 256, 256),
                                    (128 * 3, 512, 512)])
-def test_gemm_tn_bf16_native_kernel(ops, bf16_nt_variant, M, N, K):
+def test_gemm_tn_bf16_native_kernel(ops, M, N, K):
     """vqcpc_gemm_tn_bf16: dW = A^T B and db = column sums of A on bf16 operands, against fp64 on the rounded operands;
-    plain, accumulating into existing buffers, and A = I-like transpose detection -- for both kernels (variant 1: operands by
-    LDS-DMA, fragments by ds_read_b64_tr_b16; variant 0: row pairs interleaved in registers, ds_read_b32 fragments)."""
+    plain, accumulating into existing buffers, and A = I-like transpose detection (operands by LDS-DMA, fragments by
+    ds_read_b64_tr_b16)."""
     gen = torch.Generator().manual_seed(M + N + K)
     a, b = torch.randn(M, N, generator=gen), torch.randn(M, K, generator=gen)
     ab, bb = ops.cast_bf16(dev(a)), ops.cast_bf16(dev(b))
@@ -1533,51 +1450,6 @@ def test_grouped_weight_gradient_argument_checks(ops, bf16x6):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# bf16x6 GEMM on pre-split (P3) operands: csrc/gemm_planes.hip (lab build only)
-# ----------------------------------------------------------------------------------------------------------------
-@lab_only
-def test_split3_planes_round_trip_is_exact(ops):
-    gen = torch.Generator().manual_seed(11)
-    for rows, cols in [(256, 64), (1000, 256), (37, 1024), (16, 16)]:
-        x = torch.randn(rows, cols, generator=gen) * torch.logspace(-20, 20, rows).reshape(-1, 1)
-        x[0, :4] = torch.tensor([0.0, -0.0, 1e-30, -3.4e38])               # (pieces below 2^-126 would be flushed by the VALU)
-        xd = dev(x)
-        pl = ops.split3_planes(xd)
-        assert bool((ops.join3_planes(pl, rows, cols) == xd).all()), 'high + mid + low must reproduce every fp32 value'
-        wide = dev(torch.randn(rows, cols + 32, generator=gen))              # strided source rows
-        assert torch.equal(ops.join3_planes(ops.split3_planes(wide[:, 16:16 + cols]), rows, cols), wide[:, 16:16 + cols])
-
-
-@lab_only
-@pytest.mark.parametrize('M,N,K,epi', [(512, 256, 64, 'bias'), (2048, 768, 256, 'bias'), (1536, 256, 1024, 'none'),
-                                       (4096, 1024, 256, 'relu_drop'), (2560, 1024, 256, 'gate'), (1280, 256, 1024, 'add'),
-                                       (65536 + 256, 512, 160, 'bias')])
-def test_gemm_nt_planes_is_the_x6_gemm(ops, M, N, K, epi):
-    """Same products as the fp32-in bf16x6 GEMM (mode 1); bit-identical where that one runs its 256-tile ping-pong kernel
-    (same MFMA order), within fp32 rounding of the accumulation order otherwise (small shapes take its 128-tile kernel).
-    The large-M case runs many persistent rounds (the run-ahead LDS-DMA crosses output tiles)."""
-    from vqcpc_bach_amd import hip
-    gen = torch.Generator().manual_seed(M + N + K)
-    a, b = dev(torch.randn(M, K, generator=gen)), dev(torch.randn(N, K, generator=gen))
-    bias = dev(torch.randn(N, generator=gen))
-    aux = dev(torch.randn(M, N, generator=gen))
-    kw = dict(none={}, bias=dict(bias=bias), relu_drop=dict(bias=bias, act=1, drop_p=0.1, seed=77),
-              gate=dict(gate=aux, gate_scale=1.25), add=dict(add=aux))[epi]
-    hip.set_gemm_mode(1)
-    try:
-        ref = ops.gemm_nt(a, b, **kw)
-    finally:
-        hip.set_gemm_mode(0)
-    out = ops.gemm_nt_planes(ops.split3_planes(a), ops.split3_planes(b), M, N, K, **kw)
-    if M >= 65536 and epi != 'gate':                      # whole rounds of 256 tiles: rows [0, 65536) at N = 512
-        assert torch.equal(out[:65536], ref[:65536])
-    assert rel_err(out.cpu(), ref.cpu()) < 2e-6
-    exact = a.double() @ b.double().t()
-    if epi in ('none',):
-        assert rel_err(out.cpu(), exact.cpu()) < 2e-6 * max(1, K ** 0.5)
-
-
-# ----------------------------------------------------------------------------------------------------------------
 # relu / dropout gate as a bit mask (vqcpc_gemm_nt_relu_mask / vqcpc_gemm_nt_gatebits)
 # ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('M,N,K,p', [(512, 256, 64, 0.0), (4096, 1024, 256, 0.1), (2560, 512, 160, 0.3),
@@ -1642,27 +1514,6 @@ def test_ffn_uses_the_bit_gate_in_bf16x6_mode_and_matches_the_fp32_gate(ops):
         hip.set_gemm_mode(0)
     for a, b in zip(res[True], res[False]):
         assert rel_err(a, b) < 5e-6
-
-
-@lab_only
-@pytest.mark.parametrize('M,N,K,with_bias', [(512, 256, 64, True), (65536, 768, 256, True), (66048, 256, 1024, False),
-                                             (131072, 512, 96, True)])
-def test_gemm_nt_one_wave_per_simd_kernel_is_bitwise_the_ping_pong_kernel(ops, M, N, K, with_bias):
-    """gemm_sw.hip (mode +32): same LDS image, same fragments, same MFMA order as gemm_nt_x6_pp_kernel."""
-    from vqcpc_bach_amd import hip
-    gen = torch.Generator().manual_seed(M + N + K)
-    a, b = dev(torch.randn(M, K, generator=gen)), dev(torch.randn(N, K, generator=gen))
-    bias = dev(torch.randn(N, generator=gen)) if with_bias else None
-    try:
-        hip.set_gemm_mode(1)
-        ref = ops.gemm_nt(a, b, bias=bias)
-        hip.set_gemm_mode(33)
-        out = ops.gemm_nt(a, b, bias=bias)
-    finally:
-        hip.set_gemm_mode(0)
-    assert torch.equal(out, ref)
-    exact = a.double() @ b.double().t() + (bias.double() if with_bias else 0)
-    assert rel_err(out.cpu(), exact.cpu()) < 2e-6 * max(1, K ** 0.5)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -2404,44 +2255,6 @@ def test_gru_fused_steps_equal_the_gemm_plus_gate_launches(ops):
         ops.GRU_FUSED_STEPS = True
     for a, b in zip(res[True], res[False]):
         assert rel_err(a.cpu(), b.cpu()) < 2e-6
-
-
-@lab_only
-@pytest.mark.parametrize('M,N,K', [(65536, 256, 256), (131072, 1024, 256), (557056, 256, 512)])
-def test_gemm_tn_quad_row_lds_image_is_bit_identical_to_the_row_pair_image(ops, bf16x6, M, N, K):
-    """gemm_tn_x6_pq_kernel (four consecutive rows per staging thread, fragments by two ds_read_b64) against
-    gemm_tn_x6_pp_kernel (row pairs, two ds_read2_b32): the same products in the same order, so the weight gradient is
-    bit-identical (the bias sums are accumulated four rows at a time instead of two: fp32-rounding apart); also in the
-    opt-in three-product gradient arithmetic."""
-    import os
-    from vqcpc_bach_amd import hip
-    gen = torch.Generator(device='cuda').manual_seed(M // 1000 + N + K)
-    a, b = torch.randn(M, N, device='cuda', generator=gen), torch.randn(M, K, device='cuda', generator=gen)
-    saved = os.environ.get('VQCPC_TN_PQ')
-    res = {}
-    try:
-        for pq in ('0', '1'):
-            os.environ['VQCPC_TN_PQ'] = pq
-            dw, db = ops.gemm_tn(a, b)
-            hip.set_gradient_products(3)
-            hip.gradient_scope(True)
-            try:
-                dw3, _ = ops.gemm_tn(a, b)
-            finally:
-                hip.gradient_scope(False)
-                hip.set_gradient_products(6)
-            res[pq] = (dw, db, dw3)
-    finally:
-        if saved is None:
-            os.environ.pop('VQCPC_TN_PQ', None)
-        else:
-            os.environ['VQCPC_TN_PQ'] = saved
-    assert torch.equal(res['0'][0], res['1'][0]), 'weight gradient: same products, same order'
-    assert torch.equal(res['0'][2], res['1'][2])
-    assert rel_err(res['1'][1].cpu(), res['0'][1].cpu()) < 1e-6
-    ref = a.double().t() @ b.double()
-    assert rel_err(res['1'][0].cpu(), ref.cpu()) < 3e-6
-    assert rel_err(res['1'][1].cpu(), a.double().sum(0).cpu()) < 3e-6
 
 
 @pytest.mark.parametrize('mode', [1, 8])

@@ -1,7 +1,6 @@
 """Micro-benchmark of the GEMM kernels on the shapes of the C1 training step (HIP-event timed, GPU only).
     python tools/bench_gemm.py [reps] [modeA,modeB,...]
-Modes are vqcpc_gemm_set_mode() values (1 = bf16x6 with the register-staged ping-pong 256-tile NT kernel, 17 = bf16x6 with
-the LDS-DMA kernel, 0 = fp32 MFMA ...); variants are timed interleaved in ONE process (rounds of all modes),
+Modes are vqcpc_gemm_set_mode() values (1 = bf16x6, 0 = fp32 MFMA, 8 = bf16); they are timed interleaved in ONE process (rounds of all modes),
 median over rounds, random operands.  Prints algorithmic TFLOP/s per shape / epilogue and mode."""
 import os
 import statistics
@@ -25,7 +24,7 @@ def time_it(fn, reps):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    modes = [int(m) for m in sys.argv[2].split(',')] if len(sys.argv) > 2 else [1, 17]
+    modes = [int(m) for m in sys.argv[2].split(',')] if len(sys.argv) > 2 else [1, 0]
     rounds = 5
     hip.load()
     dev = 'cuda'

@@ -1,7 +1,6 @@
-"""L = 16 attention forward at the C1 size (34 816 blocks x 8 heads of 32): the fp32-MFMA kernel against the bf16x6 variant of its
-q . k / q . Erel contractions (lab build: VQCPC_RELATTN16_X6=1).     python tools/bench_relattn16.py"""
-import os, sys, statistics, subprocess
-import os as _os; _os.environ.setdefault('VQCPC_LAB', '1')
+"""L = 16 attention forward at the C1 size (34 816 blocks x 8 heads of 32): time per launch and the error of the
+probabilities against fp64, in the bf16x6 GEMM mode (six-product q . k / q . Erel contractions).     python tools/bench_relattn16.py"""
+import os, sys, statistics
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
 
@@ -9,6 +8,7 @@ def one():
     import torch
     from vqcpc_bach_amd import hip
     hip.load()
+    hip.set_gemm_mode(1)
     torch.manual_seed(0)
     nblk, L, H, hd = 34816, 16, 8, 32
     d = H * hd
@@ -37,12 +37,8 @@ def one():
     sc = sc + torch.gather(qe, 3, idx.view(1, 1, L, L).expand(n0, H, L, L))
     pr = torch.softmax(sc, -1)
     err = float((probs[:n0].double() - pr).abs().max())
-    print(f'X6={os.environ.get("VQCPC_RELATTN16_X6", "0")}  {statistics.median(ts):8.1f} us   max |probs - fp64| on 64 blocks: {err:.2e}', flush=True)
+    print(f'{statistics.median(ts):8.1f} us   max |probs - fp64| on 64 blocks: {err:.2e}', flush=True)
 
 
 if __name__ == '__main__':
-    if len(sys.argv) > 1:
-        one()
-    else:
-        for x6 in ('0', '1', '0', '1'):
-            subprocess.run([sys.executable, os.path.abspath(__file__), 'child'], env=dict(os.environ, VQCPC_RELATTN16_X6=x6))
+    one()

@@ -1,8 +1,6 @@
-"""L = 16 attention backward, all-bf16 form, at the configs[4] size (69 632 blocks x 8 heads of 64): the fp32-MFMA contractions
-(relattn16_bwd_kernel) against every contraction on the bf16 matrix pipe (relattn16_bwd_mm16_kernel); lab build:
-VQCPC_RELATTN16_MM16=0 / 1.     python tools/bench_relattn16_bwd.py [hd]"""
-import os, sys, statistics, subprocess
-os.environ.setdefault('VQCPC_LAB', '1')
+"""L = 16 attention backward, all-bf16 form, at the configs[4] size (69 632 blocks x 8 heads of 64): every contraction on the
+bf16 matrix pipe (relattn16_bwd_mm16_kernel).     python tools/bench_relattn16_bwd.py [hd]"""
+import os, sys, statistics
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
 
@@ -37,14 +35,9 @@ def one(hd):
         ts.append(a.elapsed_time(b) / 5 * 1e3)
     gb = nblk * H * (4 * 16 * hd * 2 + 1024 + 3 * 16 * hd * 2) / 1e9
     t = statistics.median(ts)
-    print(f'hd={hd} MM16={os.environ.get("VQCPC_RELATTN16_MM16", "1")}  {t:8.1f} us  {gb / t * 1e3:.2f} TB/s  checksum {float(dqkv.float().abs().mean()):.6e} '
+    print(f'hd={hd}  {t:8.1f} us  {gb / t * 1e3:.2f} TB/s  checksum {float(dqkv.float().abs().mean()):.6e} '
           f'{float(de1.abs().mean()):.6e}', flush=True)
 
 
 if __name__ == '__main__':
-    if len(sys.argv) > 2:
-        one(int(sys.argv[2]))
-    else:
-        hd = sys.argv[1] if len(sys.argv) > 1 else '64'
-        for v in ('0', '1', '0', '1'):
-            subprocess.run([sys.executable, os.path.abspath(__file__), 'child', hd], env=dict(os.environ, VQCPC_RELATTN16_MM16=v))
+    one(int(sys.argv[1]) if len(sys.argv) > 1 else 64)

@@ -87,11 +87,9 @@ def main():
     out.write('counters collected: ' + ' '.join(COUNTERS) + '\n\n')
     for N, K in ((768, 256), (256, 256), (1024, 256), (256, 768), (256, 1024)):
         run('one_gemm.py', [N, K], {'VQCPC_ONE_GEMM_MODE': '1'}, ['gemm_nt_x6_'], 2048, N, K, f'NT gemm_nt_x6_pp_kernel {M} x {N} x {K} (bias epilogue)', out)
-    run('one_gemm.py', [256, 1024], {'VQCPC_ONE_GEMM_MODE': '1', 'VQCPC_PP_ABL': '3'}, ['gemm_nt_x6_'], 2048, 256, 1024,
-        f'NT schedule-only ablation (ABL 3) {M} x 256 x 1024', out)
     for N, K in ((1024, 256), (256, 256), (768, 256)):
-        run('one_gemm_tn.py', [N, K], {'VQCPC_TN_MODE': '1'}, ['gemm_tn_x6_p', 'gemm_tn_x6_256'], 2048, N, K,
-            f'TN gemm_tn_x6_pp_kernel (weight gradient) {M} x {N} x {K}', out)
+        run('one_gemm_tn.py', [N, K], {'VQCPC_TN_MODE': '1'}, ['gemm_tn_x6_p'], 2048, N, K,
+            f'TN gemm_tn_x6_pq_kernel (weight gradient) {M} x {N} x {K}', out)
     if out is not sys.stdout: out.close()
 
 

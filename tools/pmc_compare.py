@@ -1,4 +1,4 @@
-"""SQ counter groups of the bf16x6 NT (K = 1024) and TN (557056 x 1024 x 256, both LDS images) GEMM kernels side by side, per
+"""SQ counter groups of the bf16x6 NT (K = 1024) and TN (557056 x 1024 x 256) GEMM kernels side by side, per
 launch and per wave and K step (16 rows / columns of the contraction), to see what the TN memory phase does more of:
     python tools/pmc_compare.py [out.txt]   (needs a GPU; rocprofv3 --kernel-trace --pmc <8 counters> per pass)."""
 import collections, csv, glob, os, shutil, subprocess, sys
@@ -34,12 +34,10 @@ def run(script, args, env_extra, match, counters):
 def main():
     out = open(sys.argv[1], 'w') if len(sys.argv) > 1 else sys.stdout
     cases = [('NT 557056 x 256 x 1024', 'one_gemm.py', [256, 1024], {'VQCPC_ONE_GEMM_MODE': '1'}, ['gemm_nt_x6_'], 1024 // 16 * (M // 256) * 1 / 256.0),
-             ('TN row-pair image (pp)', 'one_gemm_tn.py', [1024, 256], {'VQCPC_TN_MODE': '1', 'VQCPC_TN_PQ': '0'}, ['gemm_tn_x6_p'], M / 16.0 * 4 / 256.0),
-             ('TN quad-row image (pq)', 'one_gemm_tn.py', [1024, 256], {'VQCPC_TN_MODE': '1', 'VQCPC_TN_PQ': '1'}, ['gemm_tn_x6_p'], M / 16.0 * 4 / 256.0)]
+             ('TN quad-row image (pq)', 'one_gemm_tn.py', [1024, 256], {'VQCPC_TN_MODE': '1'}, ['gemm_tn_x6_p'], M / 16.0 * 4 / 256.0)]
     if os.environ.get('PMC_COMPARE') == 'nt':       # the output-tile epilogue: K = 256 (16 steps per tile) against K = 1024 (64)
         cases = [('NT 557056 x 256 x 1024', 'one_gemm.py', [256, 1024], {'VQCPC_ONE_GEMM_MODE': '1'}, ['gemm_nt_x6_'], 544.0),
-                 ('NT 557056 x 1024 x 256', 'one_gemm.py', [1024, 256], {'VQCPC_ONE_GEMM_MODE': '1'}, ['gemm_nt_x6_'], 544.0),
-                 ('NT 1024 x 256, no stores (ABL 32)', 'one_gemm.py', [1024, 256], {'VQCPC_ONE_GEMM_MODE': '1', 'VQCPC_PP_ABL': '32'}, ['gemm_nt_x6_'], 544.0)]
+                 ('NT 557056 x 1024 x 256', 'one_gemm.py', [1024, 256], {'VQCPC_ONE_GEMM_MODE': '1'}, ['gemm_nt_x6_'], 544.0)]
     if os.environ.get('PMC_COMPARE') == 'grad':     # six-product against three-product (gradient arithmetic) kernels, round 5
         g3 = {'VQCPC_ONE_GEMM_MODE': '1', 'VQCPC_ONE_GEMM_GRAD': '3'}
         g6 = {'VQCPC_ONE_GEMM_MODE': '1', 'VQCPC_ONE_GEMM_NOBIAS': '1'}

@@ -10,11 +10,11 @@ import csv, glob, collections
 tot = collections.defaultdict(float); n = collections.Counter(); dur = []
 for f in glob.glob('/tmp/pgt/**/*counter_collection.csv', recursive=True):
     for r in csv.DictReader(open(f)):
-        if 'gemm_tn_x6_p' in r['Kernel_Name'] or 'gemm_tn_x6_256' in r['Kernel_Name']:
+        if 'gemm_tn_x6_p' in r['Kernel_Name']:
             tot[r['Counter_Name']] += float(r['Counter_Value']); n[r['Counter_Name']] += 1
 for f in glob.glob('/tmp/pgt/**/*kernel_trace.csv', recursive=True):
     for r in csv.DictReader(open(f)):
-        if 'gemm_tn_x6_p' in r['Kernel_Name'] or 'gemm_tn_x6_256' in r['Kernel_Name']:
+        if 'gemm_tn_x6_p' in r['Kernel_Name']:
             dur.append(float(r['End_Timestamp']) - float(r['Start_Timestamp']))
 M, N, K = 557056, $N, $K
 waves = 256 * 8

@@ -1,10 +1,10 @@
 #!/bin/bash
-# HBM fetch bytes of one weight-gradient (TN) launch, ping-pong kernel (XCD-aware tile/split mapping) vs lockstep kernel
-# (dispatch-order mapping):   bash tools/pmc_tn_traffic.sh N K
+# HBM fetch bytes of one weight-gradient (TN) launch of the ping-pong kernel (XCD-aware tile/split mapping):
+#   bash tools/pmc_tn_traffic.sh N K
 cd /tmp; export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 N=$1; K=$2
-for mode in 1 5; do
+for mode in 1; do
 rm -rf /tmp/ptt
 VQCPC_TN_MODE=$mode timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d /tmp/ptt -- python $REPO/tools/one_gemm_tn.py $N $K > /tmp/ptt.log 2>&1
 python - <<PY

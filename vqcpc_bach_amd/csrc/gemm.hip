@@ -553,34 +553,13 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_256_kernel(const flo
 // phase that follows its last MFMA phase, so it also runs under the other group's MFMAs.
 //   LDS hazards: tile s+1 is written (by both groups) one full phase pair before anyone reads it; the buffer it
 //   replaces (tile s-1) was last read two barriers earlier by either group.
-// ABL (tools/ablate_pp_gemm.py, env VQCPC_PP_ABL, bias epilogue only) = measurement variants, never used by the library:
-//   1: planes written without the split arithmetic (garbage values)          -> +10-12 % (187 -> 211 TFLOP/s, 557056x768x256)
-//   2: no global loads after the first K tile                                -> +14-19 %
-//   3: both                                                                  -> +25-28 % (234 / 223 / 273 / 241)
-//   4: only the B (weight) operand without the split                          -> +5 %
-//      CAUTION: variants 1, 3, 4 feed the MFMAs planes made of raw fp32 bit patterns; part of their gain is the higher
-//      clock of lower-toggle data (MI355X clocks to its power budget), not removed work.  The REAL thing for variant 4 --
-//      weights pre-split once per step into K-tile-major bf16 planes, staged by three 16-byte loads + three ds_write_b128,
-//      bit-identical results -- measured 204 vs 204, 190 vs 191, 220 vs 221 TFLOP/s: no gain (row-major bf16 planes:
-//      3-5 % SLOWER, 768 cache lines of 32 used bytes per K tile thrash the L1); not kept.
-//   8: L2 prefetch touches of the next A cache line two K tiles ahead         -> -3 %
-//  16: mid / high A planes read under the MFMAs (56 instead of 72 live fragment registers) and a SECOND raw register
-//      set, i.e. every K tile requested two phase pairs before it is split   -> +-0 % (196 vs 197): the latency of the
-//      global loads is NOT what the memory phase waits for
-//  32: the epilogue without its stores                                        -> +15-17 % at K = 256, +5 % at K = 1024
-//      (an LDS-transposed epilogue with 4x fewer, 16-byte stores -- tried on this kernel -- changes nothing, 197 vs 198:
-//      it is the M x N x 4 bytes leaving the CU, not the store instructions; de-synchronising the workgroups' tile
-//      boundaries with start-up sleeps (across or within XCDs) changes nothing either).  In cycles (tools/pmc_gemm.sh,
-//      557056 x 768 x 256): 1.743 M per wave shipped, 1.731 M with the transposed epilogue, 1.524 M without stores -- the
-//      output leaves a CU at ~30 bytes per clock whatever the instruction width (tools/micro/store_rate.hip: 36 / 70 B/clk
-//      for dword / dwordx4 stores alone), and hiding it would take a second accumulator set
-//  64 / 128 / 256: output stores with the nt / sc1 / sc0 cache-policy bits     -> +0.7 % / -1 % / +-0 % (202.0 -> 203.5,
-//      190.6 -> 192.0, 205.7 -> 207.3 TFLOP/s with nt): within noise, not adopted (the consumer kernel wants the lines)
+// (The measurement variants of this kernel -- no split, no loads, no stores, cache-policy bits, a second raw register set, paired
+// loads -- are retired; what they showed is in profiles/r02_perf_log.md, r03_perf_log.md, r05_perf_log.md; profiles/lab_retirement_log.md.)
 // NP = bf16 planes per operand.  3: the exact 3-way truncation split, six products (hh, hm + mh, hl + lh + mm): fp32-class.
 //      2: GRADIENT arithmetic (vqcpc_gemm_set_gradient_products(3), opt-in, never the default): each operand is
 //         h = rn_bf16(x), m = rn_bf16(x - h) (|x - h - m| <= 2^-18 |x|), products hh + (hm + mh), the mm term (2^-18) dropped:
 //         ~2^-17 per product, unbiased -- 4 LDS planes per K tile, 12 fragment reads and 24 MFMAs per phase.
-template <int EPI, int ABL = 0, int NP = 3>
+template <int EPI, int NP = 3>
 __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const float* __restrict__ A, int64_t lda,
                                                                      const float* __restrict__ B, int64_t ldb,
                                                                      float* __restrict__ C, int64_t ldc, int64_t M, int N,
@@ -617,23 +596,11 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
     }
     PP_SET_SRC()
     float4 xa0, xa1, xb0, xb1;
-    float4 ya0, ya1, yb0, yb1;                          // V2: second raw set (prefetch distance 2)
-    constexpr bool V3 = (ABL & 1024) != 0 && NP == 3;    // paired loads (below); uses V2's fragment schedule for its registers
-    constexpr bool V2 = ((ABL & 16) != 0 || V3) && NP == 3;
-#define PP_OPAQUE(V) asm volatile("" : "+v"(V.x), "+v"(V.y), "+v"(V.z), "+v"(V.w));
-#define PP_LOAD(S_, PF0, PF1)                                                                    \
-    if (!(ABL & 2) || s < 1) {                                                            \
-    S_##a0 = *reinterpret_cast<const float4*>(a_src + ld_k);                              \
-    S_##a1 = *reinterpret_cast<const float4*>(a_src + (int64_t)64 * lda + ld_k);          \
-    S_##b0 = *reinterpret_cast<const float4*>(b_src + ld_k);                              \
-    S_##b1 = *reinterpret_cast<const float4*>(b_src + (int64_t)64 * ldb + ld_k);          \
-    } else { PP_OPAQUE(S_##a0) PP_OPAQUE(S_##a1) PP_OPAQUE(S_##b0) PP_OPAQUE(S_##b1) }    \
-    if (ABL & 8) {                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                \
-        const int pk_ = min(ld_k + 2 * kT2BK, K - kT2BK) - ld_c4;                         \
-        PF0 = a_src[pk_];                                                                 \
-        PF1 = a_src[(int64_t)64 * lda + pk_];                                             \
-    }                                                                                     \
+#define PP_LOAD()                                                                         \
+    xa0 = *reinterpret_cast<const float4*>(a_src + ld_k);                                 \
+    xa1 = *reinterpret_cast<const float4*>(a_src + (int64_t)64 * lda + ld_k);             \
+    xb0 = *reinterpret_cast<const float4*>(b_src + ld_k);                                 \
+    xb1 = *reinterpret_cast<const float4*>(b_src + (int64_t)64 * ldb + ld_k);             \
     ld_k += kT2BK;                                                                        \
     if (ld_k == K) {                                                                      \
         ld_k = 0;                                                                         \
@@ -644,9 +611,7 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
     {                                                                                \
         uint2 h_, m_, l_;                                                            \
         if (NP == 2) { split2x4(R, h_, m_); l_ = h_; }                               \
-        else if (ABL & 1) { h_ = make_uint2(__float_as_uint(R.x), __float_as_uint(R.y)); m_ = make_uint2(__float_as_uint(R.z), __float_as_uint(R.w)); l_ = h_; } \
-        else if (ABL & 4) { if (PLANE0 == 0) { split3x4(R, h_, m_, l_); } else { h_ = make_uint2(__float_as_uint(R.x), __float_as_uint(R.y)); m_ = make_uint2(__float_as_uint(R.z), __float_as_uint(R.w)); l_ = h_; } } \
-        else split3x4(R, h_, m_, l_);                                                     \
+        else split3x4(R, h_, m_, l_);                                                \
         /* unpadded 32-byte rows, the two 16-byte chunks of a row XOR-swizzled by bit 3 of the row: fragment reads     \
            (16 consecutive rows, one chunk each) and these stores (4 lanes = one row, rows consecutive) are conflict free */ \
         const int o_ = (ROW) * 32 + ((((ld_c4 >> 3) ^ ((ROW) >> 3)) & 1) << 4) + (ld_c4 & 7) * 2; \
@@ -654,8 +619,8 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
         *reinterpret_cast<uint2*>((BUFP) + ((PLANE0) + 1) * kPPPlane + o_) = m_;     \
         if (NP == 3) *reinterpret_cast<uint2*>((BUFP) + ((PLANE0) + 2) * kPPPlane + o_) = l_; \
     }
-#define PP_STORE(S_, BUFP) \
-    PP_ST1(S_##a0, 0, ld_row, BUFP) PP_ST1(S_##a1, 0, ld_row + 64, BUFP) PP_ST1(S_##b0, NP, ld_row, BUFP) PP_ST1(S_##b1, NP, ld_row + 64, BUFP)
+#define PP_STORE(BUFP) \
+    PP_ST1(xa0, 0, ld_row, BUFP) PP_ST1(xa1, 0, ld_row + 64, BUFP) PP_ST1(xb0, NP, ld_row, BUFP) PP_ST1(xb1, NP, ld_row + 64, BUFP)
 
     constexpr int kPPPlane = kT2 * 32, kPPBuf = 2 * NP * kPPPlane;  // 8 KB planes, 48 KB (NP = 2: 32 KB) per buffer
     const int swz = ((kh ^ (li >> 3)) & 1) << 4;                   // every fragment row is base + li with base % 16 == 0
@@ -664,37 +629,19 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
     unsigned char* const buf0 = smem2;
     unsigned char* const buf1 = smem2 + kPPBuf;
     bf16x8 fb[NP][2], fa[4][NP];                        // all fragments of a K tile: 18 (12) x ds_read_b128 in the memory phase
-#define PP_READ_A(BUFP, PC)                                                                                          \
-    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                                 \
-        fa[mt][PC] = *reinterpret_cast<const bf16x8*>((BUFP) + a_off + (PC) * kPPPlane + mt * 32 * 32);
 #define PP_READ_FRAGS(BUFP)                                                                                          \
     _Pragma("unroll") for (int pc = 0; pc < NP; ++pc) {                                                              \
         _Pragma("unroll") for (int tl = 0; tl < 2; ++tl)                                                             \
             fb[pc][tl] = *reinterpret_cast<const bf16x8*>((BUFP) + b_off + pc * kPPPlane + tl * 32 * 32);           \
-        if (!V2 || pc == 2) {                                                                                        \
-            PP_READ_A(BUFP, pc)                                                                                      \
-        }                                                                                                            \
+        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                             \
+            fa[mt][pc] = *reinterpret_cast<const bf16x8*>((BUFP) + a_off + pc * kPPPlane + mt * 32 * 32);           \
     }
 #define PP_TERM(PA, PB)                                                                                              \
     _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                                               \
         acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mt][PA], fb[PB][0], acc[mt][0], 0, 0, 0);            \
         acc[mt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mt][PA], fb[PB][1], acc[mt][1], 0, 0, 0);            \
     }
-#define PP_MFMA_V1() PP_TERM(NP - 1, 0) PP_TERM(0, NP - 1) PP_TERM(1, 1) PP_TERM(1, 0) PP_TERM(0, 1) PP_TERM(0, 0)
-    // V2: only the B fragments and the LOW A plane are read in the memory phase; the mid / high A planes of this wave's own
-    // rows (group-local staging: nobody writes them meanwhile) are read under the MFMAs that precede their first use, the
-    // high plane into the registers of the low one: 56 instead of 72 live fragment registers
-#define PP_MFMA_V2(BUFP)                                                          \
-    PP_READ_A(BUFP, 1)                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    PP_TERM(2, 0)                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    PP_READ_A(BUFP, 0)                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    PP_TERM(1, 1) PP_TERM(1, 0)                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    PP_TERM(0, 2) PP_TERM(0, 1) PP_TERM(0, 0)
-#define PP_MFMA(BUFP) if constexpr (NP == 2 || (ABL & 512) != 0) { PP_TERM(1, 0) PP_TERM(0, 1) PP_TERM(0, 0) } else if constexpr (V2) { PP_MFMA_V2(BUFP) } else { PP_MFMA_V1() }
+#define PP_MFMA() if constexpr (NP == 2) { PP_TERM(1, 0) PP_TERM(0, 1) PP_TERM(0, 0) } else { PP_TERM(NP - 1, 0) PP_TERM(0, NP - 1) PP_TERM(1, 1) PP_TERM(1, 0) PP_TERM(0, 1) PP_TERM(0, 0) }
 #define PP_BARRIER()                          \
     __builtin_amdgcn_sched_barrier(0);        \
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
@@ -797,10 +744,8 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
                     asm volatile("s_nop 4\n\tv_writelane_b32 %0, %1, %2\n\tv_writelane_b32 %0, %3, %4"                 \
                                  : "+v"(mword) : "s"((uint32_t)bal), "n"(r), "s"((uint32_t)(bal >> 32)), "n"(16 + r));   \
                 }                                                                                                      \
-                if (ABL & 32) { asm volatile("" :: "v"(v)); } else                                                      \
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rc, voff_c,                     \
-                                                      ((mt * 32 + (r & 3) + 8 * (r >> 2)) * ldci + nt * 32) * 4,       \
-                                                      (ABL & 64 ? 2 : 0) | (ABL & 128 ? 16 : 0) | (ABL & 256 ? 1 : 0)); \
+                                                      ((mt * 32 + (r & 3) + 8 * (r >> 2)) * ldci + nt * 32) * 4, 0);   \
                 acc[mt][nt][r] = 0.0f;                                                                                 \
             }                                                                                                          \
             if ((EPI & E_MASKOUT) && lane < 32) {    /* lane = r + 16 kh holds the word of row (r & 3) + 8 (r >> 2) + 4 kh */ \
@@ -818,36 +763,16 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
     // one phase pair for stream position s (RB_ = LDS buffer with K tile s, WB_ = buffer for tile s+1).  ONE raw-operand
     // register set: tile s+1 (requested in the previous memory phase) is split and stored, then the same registers are
     // reused for the request of tile s+2 -- a full MFMA phase + two barriers of latency cover.
-#define PP_PHASES(RB_, WB_, PF0_, PF1_, S_)                                               \
+#define PP_PHASES(RB_, WB_)                                                       \
     {                                                                             \
         if (kt == 0 && s > 0) PP_EPILOGUE()                                       \
         PP_READ_FRAGS(RB_)                                                        \
-        PP_STORE(S_, WB_)                                                         \
-        if (ABL & 8) asm volatile("" :: "v"(PF0_), "v"(PF1_));                    \
-        PP_LOAD(S_, PF0_, PF1_)                                                   \
+        PP_STORE(WB_)                                                             \
+        PP_LOAD()                                                                 \
         PP_BARRIER()                                                              \
-        if (!(ABL & 6144)) __builtin_amdgcn_s_setprio(1);                         \
-        PP_MFMA(RB_)                                                              \
-        if (!(ABL & 6144)) __builtin_amdgcn_s_setprio(0);                         \
-        PP_BARRIER()                                                              \
-        ++s;                                                                      \
-        kt = (kt + 1 == T) ? 0 : kt + 1;                                          \
-    }
-
-    // V3 (ABL 1024): K tiles 2j and 2j+1 are the two 64-byte halves of the SAME 128-byte lines of both operands.  Requested
-    // one K step apart (as above) the second half has left the L1 by the time it is asked for and every line crosses the
-    // L2 -> L1 path twice; here both halves are requested back to back (sets x and y) in the even phases, none in the odd
-    // ones: x (tile 2j) is split in the next phase, y (tile 2j+1) in the one after.
-#define PP_PHASES3(RB_, WB_, S_, LOADPAIR_)                                       \
-    {                                                                             \
-        if (kt == 0 && s > 0) PP_EPILOGUE()                                       \
-        PP_READ_FRAGS(RB_)                                                        \
-        PP_STORE(S_, WB_)                                                         \
-        if (LOADPAIR_) { PP_LOAD(x, pf0, pf1) PP_LOAD(y, pf2, pf3) }              \
-        PP_BARRIER()                                                              \
-        if (!(ABL & 6144)) __builtin_amdgcn_s_setprio(1);                         \
-        PP_MFMA(RB_)                                                              \
-        if (!(ABL & 6144)) __builtin_amdgcn_s_setprio(0);                         \
+        __builtin_amdgcn_s_setprio(1);                                            \
+        PP_MFMA()                                                                 \
+        __builtin_amdgcn_s_setprio(0);                                            \
         PP_BARRIER()                                                              \
         ++s;                                                                      \
         kt = (kt + 1 == T) ? 0 : kt + 1;                                          \
@@ -855,42 +780,24 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_nt_x6_pp_kernel(const floa
 
     // prologue: K tile 0 split into buffer 0, tile 1 requested
     int s = 0, kt = 0;
-    float pf0 = 0.f, pf1 = 0.f, pf2 = 0.f, pf3 = 0.f;
     PP_BIAS_REQUEST()
-    PP_LOAD(x, pf0, pf1)
-    if (V3) { PP_LOAD(y, pf2, pf3) }                     // V3: tiles 0 (x) and 1 (y) requested together
-    PP_STORE(x, buf0)
-    if (!V3) { PP_LOAD(x, pf2, pf3) }
-    if (V2 && !V3) { PP_LOAD(y, pf2, pf3) }              // V2: tiles 1 (x) and 2 (y) requested
+    PP_LOAD()
+    PP_STORE(buf0)
+    PP_LOAD()
     PP_BARRIER()
     if (wm == 1) { PP_BARRIER() }                        // group 1 falls one phase behind
-    // ABL 2048: no priority flips at all; ABL 4096: static priority 1 for the younger wave group only (MI355X_MICROARCH.md,
-    // "Two waves per SIMD", items 2 and 4)
-    if ((ABL & 4096) && __builtin_amdgcn_readfirstlane(wm) == 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll 1
     while (s < S) {
-        if (V3) {
-            PP_PHASES3(buf0, buf1, y, true)              // even phase: tile s+1 (y) stored, tiles s+2 (x), s+3 (y) requested
-            PP_PHASES3(buf1, buf0, x, false)             // odd phase:  tile s+1 (x) stored
-        } else if (V2) {
-            PP_PHASES(buf0, buf1, pf0, pf1, x)
-            PP_PHASES(buf1, buf0, pf2, pf3, y)
-        } else {
-            PP_PHASES(buf0, buf1, pf0, pf1, x)
-            PP_PHASES(buf1, buf0, pf2, pf3, x)
-        }
+        PP_PHASES(buf0, buf1)
+        PP_PHASES(buf1, buf0)
     }
     if (wm == 0) { PP_BARRIER() }                        // pairs with group 1's last barrier
     PP_EPILOGUE()
 #undef PP_PHASES
-#undef PP_PHASES3
 #undef PP_EPILOGUE
 #undef PP_BIAS_REQUEST
 #undef PP_BARRIER
 #undef PP_MFMA
-#undef PP_MFMA_V1
-#undef PP_MFMA_V2
-#undef PP_READ_A
 #undef PP_TERM
 #undef PP_READ_FRAGS
 #undef PP_STORE
@@ -1264,365 +1171,21 @@ __global__ __launch_bounds__(256) void reduce_splits_grouped_kernel(const RedGro
 
 // ---------------------------------------------------------------------------------------------------------------------
 // bf16x6 weight-gradient GEMM, 256 x 256 output tile, 16 rows of M per step, 8 waves (2 x 4, wave tile 128 x 64), two LDS
-// buffers, prefetch distance 2, branch-free steady-state loop (same structure as gemm_nt_x6_256_kernel; staging as
-// gemm_tn_x6_kernel: 2(m) x 4(n) register blocks, rows interleaved into dwords -> fragments are 4 ds_read_b32).
-constexpr int kW2TM = 16;                                  // contraction rows per step
-constexpr int kW2RS = kT2 * 4 + 16;                        // bytes per row pair (256 dwords + pad)
-constexpr int kW2Plane = (kW2TM / 2) * kW2RS;              // 8 320 B
-constexpr int kW2Buf = 6 * kW2Plane;                       // 49 920 B; two buffers = 99 840 B
-constexpr int kTPRS = (64 + 4) * 4;                        // ping-pong kernel: bytes per row pair of a 64-column block
-constexpr int kTPBlk = (kW2TM / 2) * kTPRS;                // 2 176 B per column block
-constexpr int kTPPlane = 4 * kTPBlk;                       // 8 704 B
-constexpr int kTPBuf = 6 * kTPPlane;                       // 52 224 B; two buffers = 104 448 B
-
-__global__ __launch_bounds__(kT2Threads, 2) void gemm_tn_x6_256_kernel(const float* __restrict__ A, int64_t lda,
-                                                                      const float* __restrict__ B, int64_t ldb, int64_t M,
-                                                                      int N, int K, int tiles_k, int64_t rows_per_split,
-                                                                      float* __restrict__ ws, float* __restrict__ ws_bias) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smemw[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const int li = lane & 31, kh = lane >> 5;
-    const int tn = blockIdx.x / tiles_k, tk = blockIdx.x % tiles_k;
-    const int n0 = tn * kT2, k0 = tk * kT2;
-    const int64_t m_begin = (int64_t)blockIdx.y * rows_per_split;
-    const int64_t m_end = min(m_begin + rows_per_split, M);          // (m_end - m_begin) % 32 == 0 (host)
-    const bool want_bias = (ws_bias != nullptr) && tk == 0;
-
-    floatx16 acc[4][2];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-
-    // staging: thread = (column quad c4 of 64, row pair rp of 8): rows 2rp, 2rp+1 of the 16-row step
-    const int c4 = (tid & 63) * 4, rp = tid >> 6;
-    const float* a_src = A + (m_begin + 2 * rp) * lda + n0 + c4;
-    const float* b_src = B + (m_begin + 2 * rp) * ldb + k0 + c4;
-    float4 xa0, xa1, xb0, xb1, ya0, ya1, yb0, yb1;
-#define W2_LOAD(S, MM)                                                                   \
-    S##a0 = *reinterpret_cast<const float4*>(a_src + (int64_t)(MM) * lda);               \
-    S##a1 = *reinterpret_cast<const float4*>(a_src + (int64_t)((MM) + 1) * lda);         \
-    S##b0 = *reinterpret_cast<const float4*>(b_src + (int64_t)(MM) * ldb);               \
-    S##b1 = *reinterpret_cast<const float4*>(b_src + (int64_t)((MM) + 1) * ldb);
-#define W2_STORE(S, BUFP)                                                                \
-    {                                                                                    \
-        uint4 h_, m_, l_;                                                                \
-        const int o_ = rp * kW2RS + c4 * 4;                                              \
-        split3_pair4(S##a0, S##a1, h_, m_, l_);                                          \
-        *reinterpret_cast<uint4*>((BUFP) + 0 * kW2Plane + o_) = h_;                      \
-        *reinterpret_cast<uint4*>((BUFP) + 1 * kW2Plane + o_) = m_;                      \
-        *reinterpret_cast<uint4*>((BUFP) + 2 * kW2Plane + o_) = l_;                      \
-        split3_pair4(S##b0, S##b1, h_, m_, l_);                                          \
-        *reinterpret_cast<uint4*>((BUFP) + 3 * kW2Plane + o_) = h_;                      \
-        *reinterpret_cast<uint4*>((BUFP) + 4 * kW2Plane + o_) = m_;                      \
-        *reinterpret_cast<uint4*>((BUFP) + 5 * kW2Plane + o_) = l_;                      \
-        if (want_bias) {                                                                 \
-            bsum.x += S##a0.x + S##a1.x;                                                 \
-            bsum.y += S##a0.y + S##a1.y;                                                 \
-            bsum.z += S##a0.z + S##a1.z;                                                 \
-            bsum.w += S##a0.w + S##a1.w;                                                 \
-        }                                                                                \
-    }
-#define W2_FRAG(DST, BASE)                                                               \
-    {                                                                                    \
-        uint4 u_;                                                                        \
-        u_.x = *reinterpret_cast<const uint32_t*>(BASE);                                 \
-        u_.y = *reinterpret_cast<const uint32_t*>((BASE) + kW2RS);                       \
-        u_.z = *reinterpret_cast<const uint32_t*>((BASE) + 2 * kW2RS);                   \
-        u_.w = *reinterpret_cast<const uint32_t*>((BASE) + 3 * kW2RS);                   \
-        DST = __builtin_bit_cast(bf16x8, u_);                                            \
-    }
-#define W2_TERM(PA, PB)                                                                                                   \
-    acc[hf * 2 + 0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA][0], b[PB][0], acc[hf * 2 + 0][0], 0, 0, 0);          \
-    acc[hf * 2 + 0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA][0], b[PB][1], acc[hf * 2 + 0][1], 0, 0, 0);          \
-    acc[hf * 2 + 1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA][1], b[PB][0], acc[hf * 2 + 1][0], 0, 0, 0);          \
-    acc[hf * 2 + 1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA][1], b[PB][1], acc[hf * 2 + 1][1], 0, 0, 0);
-#define W2_COMPUTE(BUFP)                                                                                                  \
-    {                                                                                                                     \
-        const unsigned char* ab_ = (BUFP) + (kh * 4) * kW2RS + (wm * 128 + li) * 4;                                       \
-        const unsigned char* bb_ = (BUFP) + 3 * kW2Plane + (kh * 4) * kW2RS + (wn * 64 + li) * 4;                         \
-        bf16x8 b[3][2];                                                                                                   \
-        _Pragma("unroll") for (int pc = 0; pc < 3; ++pc)                                                                  \
-            _Pragma("unroll") for (int tl = 0; tl < 2; ++tl) W2_FRAG(b[pc][tl], bb_ + pc * kW2Plane + tl * 128)           \
-        _Pragma("unroll") for (int hf = 0; hf < 2; ++hf) {                                                                \
-            bf16x8 a[3][2];                                                                                               \
-            _Pragma("unroll") for (int pc = 0; pc < 3; ++pc)                                                              \
-                _Pragma("unroll") for (int tl = 0; tl < 2; ++tl) W2_FRAG(a[pc][tl], ab_ + pc * kW2Plane + (hf * 2 + tl) * 128) \
-            W2_TERM(2, 0) W2_TERM(0, 2) W2_TERM(1, 1) W2_TERM(1, 0) W2_TERM(0, 1) W2_TERM(0, 0)                            \
-        }                                                                                                                 \
-    }
-
-    unsigned char* const buf0 = smemw;
-    unsigned char* const buf1 = smemw + kW2Buf;
-    const int64_t rows = m_end - m_begin;                     // multiple of 32, >= 32 when non-empty
-    if (rows > 0) {
-        W2_LOAD(x, 0)
-        W2_LOAD(y, kW2TM)
-        W2_STORE(x, buf0)
-        __syncthreads();
-        for (int64_t mm = 0; mm < rows - 2 * kW2TM; mm += 2 * kW2TM) {
-            W2_LOAD(x, mm + 2 * kW2TM)
-            __builtin_amdgcn_sched_barrier(0);
-            W2_COMPUTE(buf0)
-            __builtin_amdgcn_sched_barrier(0);
-            W2_STORE(y, buf1)
-            __syncthreads();
-            W2_LOAD(y, mm + 3 * kW2TM)
-            __builtin_amdgcn_sched_barrier(0);
-            W2_COMPUTE(buf1)
-            __builtin_amdgcn_sched_barrier(0);
-            W2_STORE(x, buf0)
-            __syncthreads();
-        }
-        W2_COMPUTE(buf0)
-        __builtin_amdgcn_sched_barrier(0);
-        W2_STORE(y, buf1)
-        __syncthreads();
-        W2_COMPUTE(buf1)
-    }
-#undef W2_LOAD
-#undef W2_STORE
-#undef W2_FRAG
-#undef W2_TERM
-#undef W2_COMPUTE
-
-    float* out = ws + (int64_t)blockIdx.y * N * K;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int col = k0 + wn * 64 + nt * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = n0 + wm * 128 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                out[(int64_t)row * K + col] = acc[mt][nt][r];
-            }
-        }
-    }
-    if (want_bias) {
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(smemw);          // [8][256]
-        *reinterpret_cast<float4*>(red + rp * kT2 + c4) = bsum;
-        __syncthreads();
-        if (tid < kT2) {
-            float tot = 0.0f;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) tot += red[g * kT2 + tid];
-            ws_bias[(int64_t)blockIdx.y * N + n0 + tid] = tot;
-        }
-    }
-}
-
-// Ping-pong variant of gemm_tn_x6_256_kernel (same tile, staging, LDS image and MFMA order => the same partial sums): the
-// 16-row steps of the workgroup are cut into a memory phase (read the 18 fragments of step s, split + store step s+1,
-// request step s+2) and an MFMA phase (48 MFMAs), each closed by a barrier; wave group 1 (the lower 128 output rows) runs one
-// phase behind group 0, so that on every SIMD one wave issues MFMAs while the other one does its memory phase (the lockstep
-// kernel kept the matrix pipes busy 64 % of the cycles: tools/pmc_gemm_tn.sh).
-template <int NP>
-__global__ __launch_bounds__(kT2Threads, 2) void gemm_tn_x6_pp_kernel(const float* __restrict__ A, int64_t lda,
-                                                                      const float* __restrict__ B, int64_t ldb, int64_t M,
-                                                                      int N, int K, int tiles_k, int64_t rows_per_split,
-                                                                      float* __restrict__ ws, float* __restrict__ ws_bias) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smemw[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const int li = lane & 31, kh = lane >> 5;
-    // (tile, split) of this workgroup.  The output tiles of ONE split read the same rows of A and B (they differ in the
-    // column tile of one operand only); in dispatch order (x fastest) they would land on different XCDs, i.e. behind
-    // different L2s, and every shared row would be fetched once per tile: 1.6 x the algorithmic HBM bytes.  Remapped so that
-    // the tiles of a split are neighbours on one XCD (workgroup L of the linearised grid runs on XCD L % 8).
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (gridDim.x > 1 && gridDim.y % 8 == 0) {
-        const int L = by * (int)gridDim.x + bx;
-        const int j = L >> 3;
-        bx = j % (int)gridDim.x;
-        by = (j / (int)gridDim.x) * 8 + (L & 7);
-    }
-    const int tn = bx / tiles_k, tk = bx % tiles_k;
-    const int n0 = tn * kT2, k0 = tk * kT2;
-    const int64_t m_begin = (int64_t)by * rows_per_split;
-    const int64_t m_end = min(m_begin + rows_per_split, M);          // (m_end - m_begin) % 32 == 0 (host)
-    const bool want_bias = (ws_bias != nullptr) && tk == 0;
-
-    floatx16 acc[4][2];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
-
-    // staging: thread = (column quad c4 of 64, row pair rp of 8): rows 2rp, 2rp+1 of the 16-row step
-    const int c4 = (tid & 63) * 4, rp = tid >> 6;
-    const float* a_src = A + (m_begin + 2 * rp) * lda + n0 + c4;
-    const float* b_src = B + (m_begin + 2 * rp) * ldb + k0 + c4;
-    float4 xa0, xa1, xb0, xb1, ya0, ya1, yb0, yb1;
-#define W2_LOAD(S, MM)                                                                   \
-    S##a0 = *reinterpret_cast<const float4*>(a_src + (int64_t)(MM) * lda);               \
-    S##a1 = *reinterpret_cast<const float4*>(a_src + (int64_t)((MM) + 1) * lda);         \
-    S##b0 = *reinterpret_cast<const float4*>(b_src + (int64_t)(MM) * ldb);               \
-    S##b1 = *reinterpret_cast<const float4*>(b_src + (int64_t)((MM) + 1) * ldb);
-#define W2_STORE(S, BUFP)                                                                \
-    {                                                                                    \
-        uint4 h_, m_, l_;                                                                \
-        const int o_ = (c4 >> 6) * kTPBlk + rp * kTPRS + (c4 & 63) * 4;                  \
-        if constexpr (NP == 2) { split2_pair4(S##a0, S##a1, h_, m_); } else { split3_pair4(S##a0, S##a1, h_, m_, l_); } \
-        *reinterpret_cast<uint4*>((BUFP) + 0 * kTPPlane + o_) = h_;                      \
-        *reinterpret_cast<uint4*>((BUFP) + 1 * kTPPlane + o_) = m_;                      \
-        if constexpr (NP == 3) *reinterpret_cast<uint4*>((BUFP) + 2 * kTPPlane + o_) = l_; \
-        if constexpr (NP == 2) { split2_pair4(S##b0, S##b1, h_, m_); } else { split3_pair4(S##b0, S##b1, h_, m_, l_); } \
-        *reinterpret_cast<uint4*>((BUFP) + (NP + 0) * kTPPlane + o_) = h_;               \
-        *reinterpret_cast<uint4*>((BUFP) + (NP + 1) * kTPPlane + o_) = m_;               \
-        if constexpr (NP == 3) *reinterpret_cast<uint4*>((BUFP) + (NP + 2) * kTPPlane + o_) = l_; \
-        if (want_bias && store_counts) {                                                 \
-            bsum.x += S##a0.x + S##a1.x;                                                 \
-            bsum.y += S##a0.y + S##a1.y;                                                 \
-            bsum.z += S##a0.z + S##a1.z;                                                 \
-            bsum.w += S##a0.w + S##a1.w;                                                 \
-        }                                                                                \
-    }
-#define W2_FRAG(DST, BASE)                                                               \
-    {                                                                                    \
-        uint4 u_;                                                                        \
-        u_.x = *reinterpret_cast<const uint32_t*>(BASE);                                 \
-        u_.y = *reinterpret_cast<const uint32_t*>((BASE) + kW2RS);                       \
-        u_.z = *reinterpret_cast<const uint32_t*>((BASE) + 2 * kW2RS);                   \
-        u_.w = *reinterpret_cast<const uint32_t*>((BASE) + 3 * kW2RS);                   \
-        DST = __builtin_bit_cast(bf16x8, u_);                                            \
-    }
-    // all 18 fragments of a 16-row step: 72 x ds_read_b32 in the memory phase (a[tile 0..3][plane], b[plane][tile 0..1])
-    bf16x8 fa[4][NP], fb[NP][2];
-    // LDS image of this kernel: plane = 4 column blocks of 64 columns, each [8 row pairs][64 + 4 dwords]: the four dwords of
-    // a fragment (row pairs 4 kh .. 4 kh + 3 of one column) are 68 dwords apart, so TWO ds_read2_b32 fetch a fragment
-    // straight into its four consecutive registers (36 reads per phase).  With the 256-column rows of the lockstep kernel
-    // the dwords are 260 apart, out of ds_read2's reach: hipcc paired other dwords and needed 54 v_mov + 28 v_add per
-    // phase to re-assemble the operands.  Inline asm (one base register per operand and plane, 8-bit dword offsets).
-#define TP_FRAG_ASM(DST, ADDR, OFF)                                                                                       \
-    {                                                                                                                     \
-        unsigned long long p0_, p1_;                                                                                      \
-        asm volatile("ds_read2_b32 %0, %2 offset0:%3 offset1:%4\n\tds_read2_b32 %1, %2 offset0:%5 offset1:%6"            \
-                     : "=&v"(p0_), "=&v"(p1_)                                                                             \
-                     : "v"(ADDR), "n"((OFF) / 4), "n"((OFF) / 4 + kTPRS / 4), "n"((OFF) / 4 + 2 * (kTPRS / 4)),           \
-                       "n"((OFF) / 4 + 3 * (kTPRS / 4)));                                                                 \
-        const u32x4 u_ = {(unsigned)p0_, (unsigned)(p0_ >> 32), (unsigned)p1_, (unsigned)(p1_ >> 32)};                    \
-        DST = __builtin_bit_cast(bf16x8, u_);                                                                             \
-    }
-#define TP_READ_FRAGS(BUFP)                                                                                               \
-    {                                                                                                                     \
-        const unsigned base_ = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(BUFP);             \
-        _Pragma("unroll") for (int pc = 0; pc < NP; ++pc) {                                                               \
-            const unsigned bb_ = base_ + (NP + pc) * kTPPlane + wn * kTPBlk + (kh * 4) * kTPRS + li * 4;                   \
-            TP_FRAG_ASM(fb[pc][0], bb_, 0)                                                                                \
-            TP_FRAG_ASM(fb[pc][1], bb_, 128)                                                                              \
-            const unsigned ab0_ = base_ + pc * kTPPlane + (wm * 2) * kTPBlk + (kh * 4) * kTPRS + li * 4;                  \
-            const unsigned ab1_ = ab0_ + kTPBlk;                                                                          \
-            TP_FRAG_ASM(fa[0][pc], ab0_, 0)                                                                               \
-            TP_FRAG_ASM(fa[1][pc], ab0_, 128)                                                                             \
-            TP_FRAG_ASM(fa[2][pc], ab1_, 0)                                                                               \
-            TP_FRAG_ASM(fa[3][pc], ab1_, 128)                                                                             \
-        }                                                                                                                 \
-    }
-#define TP_TERM(PA, PB)                                                                                                   \
-    _Pragma("unroll") for (int t4 = 0; t4 < 4; ++t4) {                                                                    \
-        acc[t4][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t4][PA], fb[PB][0], acc[t4][0], 0, 0, 0);                 \
-        acc[t4][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t4][PA], fb[PB][1], acc[t4][1], 0, 0, 0);                 \
-    }
-#define TP_MFMA() if constexpr (NP == 2) { TP_TERM(1, 0) TP_TERM(0, 1) TP_TERM(0, 0) } else { TP_TERM(NP - 1, 0) TP_TERM(0, NP - 1) TP_TERM(1, 1) TP_TERM(1, 0) TP_TERM(0, 1) TP_TERM(0, 0) }
-#define TP_BARRIER()                          \
-    __builtin_amdgcn_sched_barrier(0);        \
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0);
-    // one phase pair for step s: RB_ holds step s, WB_ receives step s+1 (held by the raw set, requested one phase pair
-    // ago), then the raw set is refilled with step s+2 (past the end: the last step again, never used)
-#define TP_PHASES(RB_, WB_)                                                       \
-    {                                                                             \
-        TP_READ_FRAGS(RB_)                                                        \
-        store_counts = st + 1 < nsteps;                                           \
-        W2_STORE(x, WB_)                                                          \
-        {                                                                         \
-            const int64_t nx_ = min((int64_t)(st + 2), nsteps - 1) * kW2TM;       \
-            W2_LOAD(x, nx_)                                                       \
-        }                                                                         \
-        TP_BARRIER()                                                              \
-        __builtin_amdgcn_s_setprio(1);                                            \
-        TP_MFMA()                                                                 \
-        __builtin_amdgcn_s_setprio(0);                                            \
-        TP_BARRIER()                                                              \
-        ++st;                                                                     \
-    }
-
-    unsigned char* const buf0 = smemw;
-    unsigned char* const buf1 = smemw + 2 * NP * kTPPlane;
-    const int64_t rows = m_end - m_begin;                     // multiple of 32: an even number of 16-row steps
-    const int64_t nsteps = rows / kW2TM;
-    if (rows > 0) {
-        // the bias sums must count every row exactly once: steps 0 .. nsteps-1 are stored once each (the store of the
-        // clamped "step nsteps" in the last phase is skipped for the sums)
-        int64_t st = 0;
-        bool store_counts = true;
-        W2_LOAD(x, 0)
-        W2_STORE(x, buf0)
-        W2_LOAD(x, min((int64_t)1, nsteps - 1) * kW2TM)
-        TP_BARRIER()
-        if (wm == 1) { TP_BARRIER() }                        // group 1 falls one phase behind
-#pragma unroll 1
-        while (st < nsteps) {
-            TP_PHASES(buf0, buf1)
-            TP_PHASES(buf1, buf0)
-        }
-        if (wm == 0) { TP_BARRIER() }                        // pairs with group 1's last barrier
-    }
-#undef TP_PHASES
-#undef TP_BARRIER
-#undef TP_MFMA
-#undef TP_TERM
-#undef TP_READ_FRAGS
-#undef TP_FRAG_ASM
-#undef W2_LOAD
-#undef W2_STORE
-#undef W2_FRAG
-
-    float* out = ws + (int64_t)by * N * K;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int col = k0 + wn * 64 + nt * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = n0 + wm * 128 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                out[(int64_t)row * K + col] = acc[mt][nt][r];
-            }
-        }
-    }
-    if (want_bias) {
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(smemw);          // [8][256]
-        *reinterpret_cast<float4*>(red + rp * kT2 + c4) = bsum;
-        __syncthreads();
-        if (tid < kT2) {
-            float tot = 0.0f;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) tot += red[g * kT2 + tid];
-            ws_bias[(int64_t)by * N + n0 + tid] = tot;
-        }
-    }
-}
-
-// gemm_tn_x6_pp_kernel with a different LDS image (same products in the same order => bit-identical partial sums).
-// Counters (tools/pmc_compare.py, profiles/r03_gemm_tn_lds.txt): per wave and 16-row step the kernel above spends 192 LDS-array
-// cycles (36 ds_read2_b32 at 4 cycles + 6 ds_write_b128) against 113 in the NT kernel (18 ds_read_b128 + 12 ds_write_b64), and
-// 400 instead of 250 cycles stalled on LDS issue -- the row-pair image makes every fragment four separate dwords.  Here a
-// thread stages FOUR consecutive rows of four columns of ONE operand (waves 0-3: A, waves 4-7: B; 16-byte row loads as
-// before), so the four m-values of a column are 8 contiguous bytes, and the image is [plane][col & 3][m >> 3][(m >> 2) & 1]
+// buffers.  Ping-pong: the 16-row steps of the workgroup are cut into a memory phase (read the 18 fragments of step s, split +
+// store step s+1, request step s+2) and an MFMA phase (48 MFMAs), each closed by a barrier; wave group 1 (the lower 128 output
+// rows) runs one phase behind group 0, so that on every SIMD one wave issues MFMAs while the other one does its memory phase
+// (a lockstep kernel kept the matrix pipes busy 64 % of the cycles: tools/pmc_gemm_tn.sh).
+// LDS image.  With the row-pair image of gemm_tn_x6_kernel every fragment is four separate dwords: counters (tools/pmc_compare.py,
+// profiles/r03_gemm_tn_lds.txt) showed 192 LDS-array cycles per wave and 16-row step (36 ds_read2_b32 at 4 cycles + 6
+// ds_write_b128) against 113 in the NT kernel (18 ds_read_b128 + 12 ds_write_b64), and 400 instead of 250 cycles stalled on LDS
+// issue.  Here a thread stages FOUR consecutive rows of four columns of ONE operand (waves 0-3: A, waves 4-7: B; 16-byte row
+// loads), so the four m-values of a column are 8 contiguous bytes, and the image is [plane][col & 3][m >> 3][(m >> 2) & 1]
 // [col >> 2] x 8 bytes (+64 B per col & 3 block): a fragment is two ds_read_b64 (2 LDS cycles each, conflict-free: the 32
 // lanes of a group read 4 x 64 contiguous bytes in 4 distinct bank windows), the 12 ds_write_b64 of a thread are 512
-// contiguous bytes per wave instruction.
+// contiguous bytes per wave instruction.  (The lockstep and the row-pair ping-pong kernels this one replaced, same partial sums
+// bit for bit, are retired: profiles/lab_retirement_log.md.)
+constexpr int kW2TM = 16;                                  // contraction rows per step
+
 template <int NP>
 __global__ __launch_bounds__(kT2Threads, 2) void gemm_tn_x6_pq_kernel(const float* __restrict__ A, int64_t lda,
                                                                       const float* __restrict__ B, int64_t ldb, int64_t M,
@@ -1701,22 +1264,9 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_tn_x6_pq_kernel(const floa
             bsum.w += ((S##0).w + (S##1).w) + ((S##2).w + (S##3).w);                             \
         }                                                                                \
     }
-#define W2_FRAG(DST, BASE)                                                               \
-    {                                                                                    \
-        uint4 u_;                                                                        \
-        u_.x = *reinterpret_cast<const uint32_t*>(BASE);                                 \
-        u_.y = *reinterpret_cast<const uint32_t*>((BASE) + kW2RS);                       \
-        u_.z = *reinterpret_cast<const uint32_t*>((BASE) + 2 * kW2RS);                   \
-        u_.w = *reinterpret_cast<const uint32_t*>((BASE) + 3 * kW2RS);                   \
-        DST = __builtin_bit_cast(bf16x8, u_);                                            \
-    }
-    // all 18 fragments of a 16-row step: 72 x ds_read_b32 in the memory phase (a[tile 0..3][plane], b[plane][tile 0..1])
+    // all 18 fragments of a 16-row step, read in the memory phase (a[tile 0..3][plane], b[plane][tile 0..1]): two ds_read_b64
+    // each, inline asm (one base register per operand and plane, immediate offsets)
     bf16x8 fa[4][NP], fb[NP][2];
-    // LDS image of this kernel: plane = 4 column blocks of 64 columns, each [8 row pairs][64 + 4 dwords]: the four dwords of
-    // a fragment (row pairs 4 kh .. 4 kh + 3 of one column) are 68 dwords apart, so TWO ds_read2_b32 fetch a fragment
-    // straight into its four consecutive registers (36 reads per phase).  With the 256-column rows of the lockstep kernel
-    // the dwords are 260 apart, out of ds_read2's reach: hipcc paired other dwords and needed 54 v_mov + 28 v_add per
-    // phase to re-assemble the operands.  Inline asm (one base register per operand and plane, 8-bit dword offsets).
 #define TP_FRAG_ASM(DST, ADDR, OFF)                                                                                       \
     {                                                                                                                     \
         unsigned long long p0_, p1_;                                                                                      \
@@ -1800,7 +1350,6 @@ __global__ __launch_bounds__(kT2Threads, 2) void gemm_tn_x6_pq_kernel(const floa
 #undef W2_LOAD
 #undef W2_STORE
 #undef PQ_COL
-#undef W2_FRAG
 
     float* out = ws + (int64_t)by * N * K;
 #pragma unroll
@@ -1841,19 +1390,7 @@ static std::atomic<int> g_grad_scope{0};
 static int gradient_products_now() {
     return g_grad_scope.load(std::memory_order_relaxed) > 0 ? g_grad_products.load(std::memory_order_relaxed) : 6;
 }
-// A/B switches of the kernel selection exist in LAB builds only (round 5: the product library keeps no such process-wide value;
-// what is left there is the arithmetic mode and the bf16-pair gradient scope, include/vqcpc.h "PROCESS-WIDE STATE")
-#if VQCPC_LAB
-static std::atomic<int> g_use_pp{1};   // bf16x6 NT 256-tile: ping-pong wave groups
-static std::atomic<int> g_use_sw{0};   // bf16x6 NT 256-tile: software-pipelined one-wave-per-SIMD kernel (gemm_sw.hip)
-static std::atomic<int> g_use_dma{0};  // bf16x6 NT 256-tile: LDS-DMA operand delivery (gemm_dma.hip) instead of register staging
-static std::atomic<int> g_use_t2{1};   // bf16x6 NT: use the 256x256 tile kernel where shapes allow
-static inline bool pp_enabled() { return g_use_pp.load(std::memory_order_relaxed) != 0; }
-static inline bool t2_enabled() { return g_use_t2.load(std::memory_order_relaxed) != 0; }
-#else
-static constexpr bool pp_enabled() { return true; }
-static constexpr bool t2_enabled() { return true; }
-#endif
+// (the library keeps no other process-wide value: include/vqcpc.h "PROCESS-WIDE STATE")
 static int gemm_mode() {
     int m = g_gemm_mode.load(std::memory_order_relaxed);
     if (m < 0) {
@@ -1969,7 +1506,7 @@ static bool skinny_ok(int64_t M, int N, int K, int flags, int* nw) {
     const bool narrow = N <= 64 && K >= 128 && M <= (1 << 21);          // gridDim.y = M / 32
     if (!narrow && (M > 1024 || ceil_div(M, BM) * ceil_div(N, BN) >= 128)) return false;     // enough big tiles: use them
     // bf16x6 mode, >= 96 tiles of 64 x 64: the LDS-staged 64-tile kernel reads full lines and beats the fragment-shaped global
-    // loads of this kernel from there on (768 x 1536 x 512: 37.7 -> 18.5 us, 768 x 512 x 512: 16.1 -> 14.7; tools/bench_s64.py)
+    // loads of this kernel from there on (768 x 1536 x 512: 37.7 -> 18.5 us, 768 x 512 x 512: 16.1 -> 14.7; profiles/r03_perf_log.md)
     if (!narrow && gemm_mode() == 1 && M % 64 == 0 && N % 64 == 0 && K % BK == 0 && (M / 64) * (N / 64) >= 96) return false;
     *nw = K >= 1024 ? 8 : 4;
     return K % (8 * *nw) == 0;
@@ -2008,8 +1545,8 @@ static int gemm_nt_launch(const float* A, int64_t lda, const float* B, int64_t l
         return VQCPC_OK;
     }
     // under-filled bf16x6 launches (at most one 128-tile per CU): 64 x 64 tiles, four times the workgroups
-    static const int s64_max_tiles = lab_env_int("VQCPC_S64_MAX_TILES", 256);
-    if (mode == 1 && tiles <= s64_max_tiles && (M % kS64 == 0) && (N % kS64 == 0) && (K % BK == 0) && M >= kS64) {
+    constexpr int kS64MaxTiles = 256;
+    if (mode == 1 && tiles <= kS64MaxTiles && (M % kS64 == 0) && (N % kS64 == 0) && (K % BK == 0) && M >= kS64) {
         const int tn64 = N / kS64;
         const dim3 g64((unsigned)((M / kS64) * tn64));
         if (dispatch(NtForms64{}, flags, 0, [&](auto f) {
@@ -2022,8 +1559,8 @@ static int gemm_nt_launch(const float* A, int64_t lda, const float* B, int64_t l
     // bf16x6, full 256 x 256 tiles: the high-arithmetic-intensity kernel (one workgroup of 8 waves per CU)
     // the 256-tile kernel runs ONE workgroup per CU: pick it only when its last (partial) round of tiles does not waste
     // more than the ~8 % it gains per tile over the 128-tile kernel (2 workgroups per CU, 4x more tiles)
-    bool t2_ok = mode == 1 && t2_enabled() && (M % kT2 == 0) && (N % kT2 == 0) &&
-                 (K % (2 * kT2BK) == 0) && (!add2 || (flags == (E_ADD | E_ADD2) && pp_enabled()));
+    bool t2_ok = mode == 1 && (M % kT2 == 0) && (N % kT2 == 0) &&
+                 (K % (2 * kT2BK) == 0) && (!add2 || flags == (E_ADD | E_ADD2));
     if (t2_ok && may_split) {
         // cost model in units of one round of 256-tiles (256 workgroups): a round of the 128-tile kernel (512 workgroups)
         // does half the work ~8 % less efficiently.  A partial last round wastes whole CUs, so a GEMM of 2.1 rounds is cut by
@@ -2054,52 +1591,27 @@ static int gemm_nt_launch(const float* A, int64_t lda, const float* B, int64_t l
         const double eff256 = r256 / ceil(r256), eff128 = r128 / ceil(r128);
         t2_ok = eff256 * 1.08 >= eff128;
     }
-#if VQCPC_LAB      // rejected designs kept for A/B measurements (gemm_sw.hip, gemm_dma.hip): lab builds only
-    if (t2_ok && g_use_sw.load(std::memory_order_relaxed) && gemm_nt_sw_ok(M, N, K, flags))
-        return gemm_nt_sw_launch(A, lda, B, ldb, C, ldc, M, N, K, flags, ep, st);
-    if (t2_ok && g_use_dma.load(std::memory_order_relaxed) && gemm_nt_dma_ok(M, N, K, flags))
-        return gemm_nt_dma_launch(A, lda, B, ldb, C, ldc, M, N, K, flags, ep, st);
-#endif
     if (t2_ok) {
         const int tn2 = N / kT2;
         const int tiles2 = (int)((M / kT2) * tn2);
-        // VQCPC_PP_GRID (measurement only): fewer persistent workgroups than CUs, to tell a per-CU store limit from a chip-wide burst
-        static const int grid_cap = lab_env_int("VQCPC_PP_GRID", kNumCU);
-        const dim3 grid2((unsigned)std::min(tiles2, grid_cap)), block2(kT2Threads);
+        const dim3 grid2((unsigned)std::min(tiles2, kNumCU)), block2(kT2Threads);
         // the gate epilogue (relu / dropout backward: reads an M x N operand, N = 4 K) is HBM-bound; all eight waves storing
-        // together (lockstep kernel) keep more bytes in flight than one wave group at a time: 0.92 vs 1.21 ms at C1
-        const bool use_pp = pp_enabled() && flags != E_GATE;
+        // together (lockstep kernel) keep more bytes in flight than one wave group at a time: 0.92 vs 1.21 ms at C1.  Every
+        // other form takes the ping-pong kernel; each kernel is instantiated for the forms it runs only.
         const size_t lds2 = 2 * kT2Buf;
         const size_t lds_pp = 2 * 6 * kT2 * 32;          // ping-pong kernel: unpadded swizzled planes (96 KB)
         const size_t lds_pp2 = 2 * 4 * kT2 * 32;         // its two-plane gradient variant (64 KB)
         // one of the nine forms (gemm_forms.h) on the 256-tile kernels; any other combination goes on to the 128-tile kernel
         const char* launched = nullptr;
-#if VQCPC_LAB
-        static const int pp_abl = lab_env_int("VQCPC_PP_ABL", 0);
-#endif
-        if (use_pp && gradient_products_now() == 3 && dispatch(NtGradForms{}, flags, 0, [&](auto f) {
+        if (gradient_products_now() == 3 && dispatch(NtGradForms{}, flags, 0, [&](auto f) {
                 // opt-in gradient arithmetic (input-gradient GEMMs inside a gradient scope): two planes, three products
-                launch_lds<gemm_nt_x6_pp_kernel<decltype(f)::a, 0, 2>>(grid2, block2, lds_pp2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2,
+                launch_lds<gemm_nt_x6_pp_kernel<decltype(f)::a, 2>>(grid2, block2, lds_pp2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2,
                                                                        tiles2, ep);
             }))
             launched = "gemm_nt_x6_pp (gradient arithmetic)";
-#if VQCPC_LAB
-        // ablation variants of the ping-pong kernel (tools/ablate_pp_gemm.py, VQCPC_PP_ABL; bias epilogue only): lab builds only
-        else if (use_pp && pp_abl && flags == E_BIAS) {
-            using PpAblForms = Forms<Form<E_BIAS, 1>, Form<E_BIAS, 2>, Form<E_BIAS, 3>, Form<E_BIAS, 4>, Form<E_BIAS, 8>, Form<E_BIAS, 16>,
-                                     Form<E_BIAS, 32>, Form<E_BIAS, 64>, Form<E_BIAS, 128>, Form<E_BIAS, 192>, Form<E_BIAS, 256>,
-                                     Form<E_BIAS, 512>, Form<E_BIAS, 1024>, Form<E_BIAS, 2048>, Form<E_BIAS, 4096>>;
-            VQ_REQUIRE(dispatch(PpAblForms{}, flags, pp_abl, [&](auto f) {
-                           launch_lds<gemm_nt_x6_pp_kernel<E_BIAS, decltype(f)::b>>(grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N,
-                                                                                    K, tn2, tiles2, ep);
-                       }),
-                       "gemm_nt: VQCPC_PP_ABL=%d is not an instantiated ablation", pp_abl);
-            launched = "gemm_nt_x6_pp (ablation)";
-        }
-#endif
         else if (dispatch(NtForms{}, flags, 0, [&](auto f) {
                      constexpr int EPI = decltype(f)::a;
-                     if (use_pp)
+                     if constexpr (EPI != E_GATE)
                          launch_lds<gemm_nt_x6_pp_kernel<EPI>>(grid2, block2, lds_pp, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep);
                      else
                          launch_lds<gemm_nt_x6_256_kernel<EPI>>(grid2, block2, lds2, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2, ep);
@@ -2147,33 +1659,11 @@ int vqcpc_gemm_gradient_scope(int open) {
 }
 
 int vqcpc_gemm_set_mode(int mode) {
-    // bit 0: arithmetic (0 fp32 MFMA, 1 bf16x6); bit 1 set: bf16x6 WITHOUT the 256x256-tile kernels (A/B testing);
-    // 8 = plain bf16 operands (one bf16 MFMA per product, fp32 accumulation)
-    // +16: 256-tile NT kernel with LDS-DMA operand delivery (gemm_dma.hip) instead of register staging (A/B switch; the
-    // register-staged ping-pong kernel is 3-5 % faster: an LDS-DMA instruction costs ~90 issue cycles on its SIMD)
-    // +32: software-pipelined one-wave-per-SIMD 256-tile NT kernel (gemm_sw.hip; A/B switch)
-#if VQCPC_LAB
-    const int use_sw = (mode >= 32 && mode < 48) ? 1 : 0;
-    if (use_sw) mode -= 32;
-    g_use_sw.store(use_sw, std::memory_order_relaxed);
-    const int use_dma = (mode >= 16 && mode < 32) ? 1 : 0;
-    if (use_dma) mode -= 16;
-    g_use_dma.store(use_dma, std::memory_order_relaxed);
-#endif
-    VQ_REQUIRE((mode >= 0 && mode <= 7) || mode == 8,
-               "gemm_set_mode: mode must be 0 (fp32 MFMA), 1 (bf16x6) [+2: 128-tile only, +4: no ping-pong; lab builds: +16 LDS-DMA "
-               "kernel, +32 one-wave-per-SIMD kernel] or 8 (bf16)");
+    VQ_REQUIRE(mode == 0 || mode == 1 || mode == 8, "gemm_set_mode: mode must be 0 (fp32 MFMA), 1 (bf16x6) or 8 (bf16), got %d", mode);
     if (mode == 8) {
         g_gemm_mode.store(2, std::memory_order_relaxed);
         return VQCPC_OK;
     }
-#if VQCPC_LAB
-    g_use_t2.store((mode & 2) ? 0 : 1, std::memory_order_relaxed);
-    g_use_pp.store((mode & 4) ? 0 : 1, std::memory_order_relaxed);
-#else
-    VQ_REQUIRE((mode & 6) == 0, "gemm_set_mode: the kernel-selection switches (+2, +4, +16, +32) exist in lab builds only");
-#endif
-    mode &= 1;
     g_gemm_mode.store(mode, std::memory_order_relaxed);
     return VQCPC_OK;
 }
@@ -2207,17 +1697,15 @@ int vqcpc_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, floa
 namespace vq {
 
 static int splitk_choose(int64_t M, int N, int K) {
-    static const int min_k = lab_env_int("VQCPC_SPLITK_MIN_K", 768);
-    if (gemm_mode() != 1 || M % BM || N % BN || K % BK || K < min_k) return 0;
+    if (gemm_mode() != 1 || M % BM || N % BN || K % BK || K < 768) return 0;
     const int64_t tiles = (M / BM) * (N / BN);
     if (tiles > 160) return 0;
     const int kt = K / BK;
     int best = 0;
     // at most 16 tiles (the GRU recurrence: 256 x 512 x 1536, one launch per time step on the critical path): planes of
     // 64 k keep the lone workgroup of a CU to a handful of K tiles (21 -> 15.5 us)
-    static const int min_ks = lab_env_int("VQCPC_SPLITK_MIN_KS", 64);
     for (int s = 2; s <= 16; ++s)
-        if (kt % s == 0 && K / s >= (tiles <= 16 ? min_ks : 256) && tiles * s <= 512) best = s;
+        if (kt % s == 0 && K / s >= (tiles <= 16 ? 64 : 256) && tiles * s <= 512) best = s;
     return best;
 }
 
@@ -2263,7 +1751,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __res
 // rows (M when it does not cut): a caller with a workspace can run the remaining rows through vqcpc_gemm_nt_splitk instead
 // of the single under-filled 128-tile launch (bias / residual epilogues, K >= 1024).
 int64_t vqcpc_gemm_nt_main_rows(int64_t M, int N, int K) {
-    if (gemm_mode() != 1 || !t2_enabled() || M % kT2 || N % kT2 || K % (2 * kT2BK)) return M;
+    if (gemm_mode() != 1 || M % kT2 || N % kT2 || K % (2 * kT2BK)) return M;
     const int64_t mt = M / kT2, tn = N / kT2, t256 = mt * tn;
     const int64_t tiles = ceil_div(M, BM) * ceil_div(N, BN);
     const double c256 = ceil((double)t256 / kNumCU);
@@ -2326,7 +1814,7 @@ int vqcpc_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, floa
         set_error("gemm_tn: workspace too small");
         return VQCPC_EWORKSPACE;
     }
-    const bool use256 = gemm_mode() == 1 && t2_enabled() && tn_can_use_256(M, N, K);
+    const bool use256 = gemm_mode() == 1 && tn_can_use_256(M, N, K);
     const int splits = use256 ? tn_splits_256(M, N, K) : tn_splits(M, N, K);
     const int64_t rows_per_split = round_up(ceil_div(M, splits), TM);
     const int tiles_k = (int)ceil_div(K, BN);
@@ -2338,25 +1826,11 @@ int vqcpc_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, floa
     if (use256) {
         const int tk2 = K / kT2;
         const dim3 g_((N / kT2) * tk2, splits), b_(kT2Threads);
-        if (pp_enabled()) {
-            constexpr int kPQBuf3 = 2 * 6 * 4 * (2048 + 64), kPQBuf2 = 2 * 4 * 4 * (2048 + 64);       // gemm_tn_x6_pq_kernel images
-#if VQCPC_LAB
-            // A/B switch of lab builds: VQCPC_TN_PQ=0 keeps the row-pair LDS image of gemm_tn_x6_pp_kernel (read per launch:
-            // the lab test flips it inside one process)
-            const char* pq_env = getenv("VQCPC_TN_PQ");
-            const bool use_pq = !(pq_env && pq_env[0] == '0');
-#else
-            constexpr bool use_pq = true;                       // the quad-row LDS image (gemm_tn_x6_pq_kernel)
-#endif
-            if (gradient_products_now() == 3) {        // opt-in gradient arithmetic, inside a gradient scope only
-                if (use_pq) launch_lds<gemm_tn_x6_pq_kernel<2>>(g_, b_, kPQBuf2, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
-                else launch_lds<gemm_tn_x6_pp_kernel<2>>(g_, b_, 2 * 4 * kTPPlane, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
-            } else if (use_pq)
-                launch_lds<gemm_tn_x6_pq_kernel<3>>(g_, b_, kPQBuf3, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
-            else
-                launch_lds<gemm_tn_x6_pp_kernel<3>>(g_, b_, 2 * kTPBuf, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
-        } else
-            launch_lds<gemm_tn_x6_256_kernel>(g_, b_, 2 * kW2Buf, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
+        constexpr int kPQBuf3 = 2 * 6 * 4 * (2048 + 64), kPQBuf2 = 2 * 4 * 4 * (2048 + 64);       // gemm_tn_x6_pq_kernel images
+        if (gradient_products_now() == 3)          // opt-in gradient arithmetic, inside a gradient scope only
+            launch_lds<gemm_tn_x6_pq_kernel<2>>(g_, b_, kPQBuf2, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
+        else
+            launch_lds<gemm_tn_x6_pq_kernel<3>>(g_, b_, kPQBuf3, s, A, lda, B, ldb, M, N, K, tk2, rows_per_split, ws, ws_bias);
     } else if (gemm_mode() == 1) {
         if (full_tn)
             hipLaunchKernelGGL((gemm_tn_x6_kernel<true, 1>), dim3(tiles, splits), dim3(kGemmThreads), 0, s, A, lda, B, ldb, M, N,
@@ -2388,7 +1862,7 @@ int vqcpc_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, floa
 // (small products): only then is the deferred result bit-identical to the immediate one.
 int vqcpc_gemm_tn_deferred_splits(int64_t M, int N, int K) {
     if (M < 1 || N < 4 || K < 4 || (N % 4) || (K % 4)) return 0;
-    const bool use256 = gemm_mode() == 1 && t2_enabled() && tn_can_use_256(M, N, K);
+    const bool use256 = gemm_mode() == 1 && tn_can_use_256(M, N, K);
     const int splits = use256 ? tn_splits_256(M, N, K) : tn_splits(M, N, K);
     return ((int64_t)N * K >= (1 << 16) && splits <= 64) ? splits : 0;
 }
@@ -2401,7 +1875,7 @@ int vqcpc_gemm_tn_groupable(int64_t M, int N, int K) {
     const int mode = gemm_mode();
     if (mode != 1 && mode != 2) return 0;
     if (M < 1 || N < 4 || K < 4 || (N % 4) || (K % 4)) return 0;
-    if (mode == 1 && t2_enabled() && tn_can_use_256(M, N, K)) return 0;
+    if (mode == 1 && tn_can_use_256(M, N, K)) return 0;
     // deferred problems keep both operands alive until the gradient scope closes and run on ~64 workgroups each: only the
     // genuinely small ones (student / decoder steps, narrow projections) are worth grouping -- at most 64 MB of operands
     return (M <= (1 << 20) && M * ((int64_t)N + K) * 4 <= (64ll << 20)) ? 1 : 0;
@@ -2529,7 +2003,7 @@ int vqcpc_gemm_tn_grouped(int n, const void* const* A, const int64_t* lda, const
 // element "output > 0"; the backward's epilogue d_h = (d_y . W2) * [h > 0] / (1 - p) reads the bits instead of the
 // M x 4d fp32 activation (2.3 GB per layer at C1).  256-tile ping-pong kernel only: M, N multiples of 256, K of 32, bf16x6.
 int vqcpc_gemm_gatebits_supported(int64_t M, int N, int K) {
-    return (gemm_mode() == 1 && t2_enabled() && pp_enabled() &&
+    return (gemm_mode() == 1 &&
             M >= kT2 && M % kT2 == 0 && N % kT2 == 0 && K % 32 == 0 && K >= 32)
                ? 1 : 0;
 }
@@ -2543,7 +2017,7 @@ static int gatebits_launch(const float* A, int64_t lda, const float* B, int64_t 
     const dim3 grid2((unsigned)std::min(tiles2, kNumCU)), block2(kT2Threads);
     const size_t lds_pp = 2 * 6 * kT2 * 32;
     if (flags == E_GATEBITS && gradient_products_now() == 3) {      // opt-in gradient arithmetic (see gemm_nt_launch)
-        launch_lds<gemm_nt_x6_pp_kernel<E_GATEBITS, 0, 2>>(grid2, block2, 2 * 4 * kT2 * 32, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2,
+        launch_lds<gemm_nt_x6_pp_kernel<E_GATEBITS, 2>>(grid2, block2, 2 * 4 * kT2 * 32, st, A, lda, B, ldb, C, ldc, M, N, K, tn2, tiles2,
                                                            ep);
         VQ_CHECK_LAUNCH("gemm_nt_x6_pp (mask, gradient arithmetic)");
         return VQCPC_OK;

@@ -13,7 +13,7 @@
 //                        LDS image of a K tile: A rows 0..255 then B rows 0..255, 64 bytes each, 16-byte chunk c of row r
 //                        at chunk position c ^ ((r >> 2) & 3): fragment reads (ds_read_b128, 16 rows per lane group) and
 //                        staging writes (ds_write_b128, 2 rows per 8-lane group) are conflict free.
-//                        Epilogue through a 4 KB LDS scratch per wave (see gemm_dma.hip): dwordx4 stores of fp32 and / or
+//                        Epilogue through a 4 KB LDS scratch per wave (B_EPI_* below): dwordx4 stores of fp32 and / or
 //                        dwordx2 stores of bf16.
 #include <stdlib.h>
 
@@ -51,10 +51,6 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
 
 // extra epilogue features of the bf16 kernel (on top of gemm_common.h's E_*)
 enum { B_OUT_F32 = 1, B_OUT_BF16 = 2, B_GATE_BF16 = 4, B_ADD_BF16 = 8 };   // B_ADD_BF16: the residual operand (E_ADD) is bf16, in `gate_b`
-// cache policy of the output stores (" nt", " sc1", ..: measurement builds, tools/build_lab_variants.sh)
-#ifndef VQ_BF16_STORE_POL
-#define VQ_BF16_STORE_POL ""
-#endif
 
 struct Bf16Out {
     float* c;            // fp32 output (B_OUT_F32)
@@ -63,8 +59,8 @@ struct Bf16Out {
     int64_t ldcb;
     const bf16_t* gate_b;   // bf16 gate operand (B_GATE_BF16): only its sign is used; or the bf16 residual operand (B_ADD_BF16)
     int64_t ldgate_b;
-    int stagger;            // start delay of workgroup b: ((b >> 3) & 3) * stagger * 64 clocks (see the kernel); -1 = measurement
-                            // variant without the epilogue's global stores (VQCPC_BF16_STAGGER=-1, tools/bench_gemm_bf16.py)
+    int stagger;            // always 0 / measurement variant retired (a start delay per workgroup, and -1 = no output stores: the
+                            // kernels still test the field, profiles/lab_retirement_log.md)
 };
 
 // =====================================================================================================================
@@ -77,7 +73,7 @@ struct Bf16Out {
 // finished (bias / activation / dropout / gate / residual, stores) the scratch round trip of tile t + 1 and the operand
 // loads of tile t + 3 are in flight.  A bf16 gate operand (24 VGPRs for three tiles) is requested one whole phase pair
 // earlier (B_AUX_PREFETCH in the last memory phase of the tile); fp32 operands (48 VGPRs) only in the epilogue itself.
-// LDS accesses and stores are inline asm (see gemm_dma.hip: no compiler-inserted vmcnt(0), explicit wait states).
+// LDS accesses and stores are inline asm (no compiler-inserted vmcnt(0), explicit wait states).
 // SCR_OFF = byte offset of the 8 x 4 KB scratch area inside the kernel's dynamic LDS.
 #define B_EPI_DECLS(SCR_OFF)                                                                                           \
     int ep_tile = blockIdx.x;                                                                                          \
@@ -142,13 +138,13 @@ struct Bf16Out {
                 ov[c] = v;                                                                                             \
             }                                                                                                          \
             if ((OUT & B_OUT_F32) && o.stagger != -1)                                                                  \
-                asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen" VQ_BF16_STORE_POL "\n\ts_nop 1" ::"v"(ov), "v"(voff_c), \
+                asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(ov), "v"(voff_c), \
                              "s"(rc), "s"(((MT * 32 + 8 * j) * ldci + NT * 32) * 4) : "memory");                       \
             if ((OUT & B_OUT_BF16) && o.stagger != -1) {                                                               \
                 u32x2 pk;                                                                                              \
                 pk[0] = cvt_pk_bf16(ov[0], ov[1]);                                                                     \
                 pk[1] = cvt_pk_bf16(ov[2], ov[3]);                                                                     \
-                asm volatile("s_nop 4\n\tbuffer_store_dwordx2 %0, %1, %2, %3 offen" VQ_BF16_STORE_POL "\n\ts_nop 1" ::"v"(pk), "v"(voff_cb), \
+                asm volatile("s_nop 4\n\tbuffer_store_dwordx2 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(pk), "v"(voff_cb), \
                              "s"(rcb), "s"(((MT * 32 + 8 * j) * ldcbi + NT * 32) * 2) : "memory");                     \
             }                                                                                                          \
         }                                                                                                              \
@@ -223,6 +219,7 @@ __global__ __launch_bounds__(kBThreads, 2) void gemm_nt_bf16_kernel(const bf16_t
     // round) at the same time, and at configs[4]'s row count those bytes go to HBM, not to the 256 MB MALL -- the chip
     // alternates between a phase that only computes and a phase that only writes.  Starting the four workgroups that share
     // an XCD slot group a quarter of a tile apart keeps the write stream continuous under the other workgroups' K loops.
+    // (o.stagger: always 0 / measurement variant retired -- it measured equal; the branch stays so that the kernel's code does.)
     if (o.stagger > 0) {
         const int n = (((int)blockIdx.x >> 3) & 3) * o.stagger;
         for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);
@@ -1001,21 +998,8 @@ int vqcpc_cast_bf16(const float* in, int64_t ld_in, void* out, int64_t rows, int
     return VQCPC_OK;
 }
 
-// 1: K tiles of 64 by LDS-DMA (gemm_nt_bf16_k64_kernel, K % 128 == 0; the transposed-read weight-gradient kernel); 0: the
-// ping-pong kernels, K tiles of 32 (what shapes the DMA kernels do not take still run on).  The A/B SWITCH between them is a
-// lab-build facility (round 5): the product library always prefers variant 1.
-#if VQCPC_LAB
-static std::atomic<int> g_bf16_nt_variant{1};
-static inline int bf16_variant() { return g_bf16_nt_variant.load(std::memory_order_relaxed); }
-int vqcpc_gemm_bf16_set_variant(int variant) {
-    VQ_REQUIRE(variant == 0 || variant == 1, "gemm_bf16_set_variant: 0 (ping-pong kernel, K tiles of 32) or 1 (K tiles of 64 by LDS-DMA)");
-    g_bf16_nt_variant.store(variant, std::memory_order_relaxed);
-    return VQCPC_OK;
-}
-#else
-static constexpr int bf16_variant() { return 1; }
-#endif
-
+// K tiles of 64 by LDS-DMA (gemm_nt_bf16_k64_kernel, K % 128 == 0; the transposed-read weight-gradient kernel) wherever the shape
+// allows; what they do not take runs on the ping-pong kernels, K tiles of 32.
 int vqcpc_gemm_nt_bf16_supported(int64_t M, int N, int K) { return (M % kB == 0 && N % kB == 0 && K % (2 * kBBK) == 0) ? 1 : 0; }
 
 int vqcpc_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, void* Cb, int64_t ldcb,
@@ -1037,10 +1021,7 @@ int vqcpc_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, f
     VQ_REQUIRE(act == 0 || act == 1, "gemm_nt_bf16: act must be 0 or 1");
     VQ_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gemm_nt_bf16: bad dropout probability");
     EpiParams ep{bias, act, drop_threshold(drop_p), 1.0f / (1.0f - drop_p), seed, gate, ldgate, gate_scale, add, ldadd, nullptr, 0, 0};
-    static const int stagger_per_ktile = lab_env_int("VQCPC_BF16_STAGGER", 0);
-    const int tiles_total = (int)((M / kB) * (N / kB));
-    Bf16Out o{C, ldc, (bf16_t*)Cb, ldcb, (const bf16_t*)(add_bf16 ? add_bf16 : gate_bf16), add_bf16 ? ldadd_bf16 : ldgate_bf16,
-              stagger_per_ktile < 0 ? stagger_per_ktile : (tiles_total >= 4 * kNumCU ? stagger_per_ktile * (K / kBBK) : 0)};
+    Bf16Out o{C, ldc, (bf16_t*)Cb, ldcb, (const bf16_t*)(add_bf16 ? add_bf16 : gate_bf16), add_bf16 ? ldadd_bf16 : ldgate_bf16, 0};
     const bool has_gate = gate || gate_bf16;
     const int flags = (bias ? E_BIAS : 0) | (act == 1 ? E_RELU : 0) | (ep.thr ? E_DROP : 0) | (has_gate ? E_GATE : 0) |
                       ((add || add_bf16) ? E_ADD : 0);
@@ -1049,7 +1030,7 @@ int vqcpc_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, f
     const int tiles = (int)((M / kB) * tn);
     const dim3 grid((unsigned)std::min(tiles, kNumCU)), block(kBThreads);
     hipStream_t st = (hipStream_t)stream;
-    const bool k64 = bf16_variant() == 1 && K % (2 * kKBK) == 0;
+    const bool k64 = K % (2 * kKBK) == 0;
     // the instantiated (epilogue, output) forms: the combinations the training step uses
     using Bf16Forms = Forms<
         Form<0, B_OUT_F32>, Form<E_BIAS, B_OUT_F32>, Form<E_BIAS, B_OUT_F32 | B_OUT_BF16>, Form<E_BIAS | E_RELU, B_OUT_BF16>,
@@ -1113,7 +1094,7 @@ int vqcpc_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, f
     // transposed-read kernel: splits of whole 128-row pairs of slots.  Its DMA offsets (row within the split) * ld * 2 are
     // 32-bit against a 2 GB buffer resource based at the split's first row: taken only when a split's rows fit that range
     const int64_t rps = round_up(ceil_div(M, splits), 2 * kTRRows);
-    if (bf16_variant() == 1 && lda < (1 << 20) && ldb < (1 << 20) &&
+    if (lda < (1 << 20) && ldb < (1 << 20) &&
         (rps + 2 * kTRRows) * std::max(lda, ldb) * 2 < ((int64_t)1 << 31)) {
         const int tkr = K / kB;
         launch_lds<gemm_tn_bf16_tr_kernel>(dim3((N / kB) * tkr, splits), dim3(kBThreads), kTRLds, s, (const bf16_t*)A, lda, (const bf16_t*)B,

@@ -55,7 +55,7 @@ using NtGradForms = Forms<Form<0>, Form<E_ADD>, Form<E_ADD | E_ADD2>>;
 // ... and its bit-mask forms (vqcpc_gemm_nt_relu_mask, vqcpc_gemm_nt_gatebits)
 using NtMaskForms = Forms<Form<E_BIAS | E_RELU | E_MASKOUT>, Form<E_BIAS | E_RELU | E_DROP | E_MASKOUT>, Form<E_GATEBITS>>;
 
-// ---- f16x3 256-tile kernel (gemm_grad.hip): gemm_nt_g3_kernel<EPI, 0, PL> ------------------------------------------------------
+// ---- f16x3 256-tile kernel (gemm_grad.hip): gemm_nt_g3_kernel<EPI, PL> ------------------------------------------------------
 // PL bit 0 / bit 1: operand A / B arrives pre-split ("P4").  Every epilogue takes an fp32 A, with B fp32 (PL 0) or P4 (PL 2) ...
 using G3Epilogues = Forms<Form<0>, Form<E_ADD>, Form<E_ADD | E_ADD2>, Form<G_ACCUM>, Form<E_ADD | G_ACCUM>, Form<E_GATEBITS>,
                           Form<E_BIAS>, Form<E_BIAS | E_ADD>, Form<E_BIAS | E_DROP | E_ADD>, Form<E_BIAS | E_RELU | E_MASKOUT>,

@@ -119,8 +119,6 @@ __device__ __forceinline__ void g3_amax_publish_wg(float amax_a, float amax_b, f
 // E_ADD all eight waves stall on those loads together at every tile boundary: the slowest epilogue of this kernel).
 // The instantiated (EPI, PL) forms and how a call's operands select one: gemm_forms.h.
 // =====================================================================================================================
-// ABL (lab builds, VQCPC_G3_ABL; results are wrong by construction): 1 = no operand requests after the prologue, 2 = no split /
-// LDS stores after the prologue, 4 = no MFMAs, 8 = no output stores, 16 = no fragment reads after the prologue
 // PL (round 6): bit 0 / bit 1 = operand A / B arrives PRE-SPLIT in the "P4" format -- same shape, leading dimension and bytes as the
 // fp32 matrix, every aligned group of four consecutive contraction elements (16 bytes) holding {h0 h1 | h2 h3 | m0 m1 | m2 m3} (fp16
 // pairs, element 0 in the low half) under the power-of-two scale of ep.pl_amax_a / _b.  The staging thread that would split its
@@ -128,7 +126,7 @@ __device__ __forceinline__ void g3_amax_publish_wg(float amax_a, float amax_b, f
 // the same order (bit-identical to the fp32-operand kernel under the same scale), no split, no amax in the K loop.  Weights are split
 // ONCE per step (vqcpc_weight_planes_many) instead of once per output tile; an activation whose only readers are GEMMs can be
 // written in P4 by its producer's epilogue.
-template <int EPI, int ABL = 0, int PL = 0>
+template <int EPI, int PL = 0>
 __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* __restrict__ A, int64_t lda,
                                                                   const float* __restrict__ B, int64_t ldb,
                                                                   float* __restrict__ C, int64_t ldc, int64_t M, int N, int K,
@@ -143,14 +141,6 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
     A += (int64_t)blockIdx.y * K;
     B += (int64_t)blockIdx.y * K;
     C += (int64_t)blockIdx.y * ep.split_plane;
-#if VQCPC_LAB
-    // measurement (VQCPC_G3_STAGGER = n, lab build): workgroup b starts (b & 7) * n * 512 clocks late, so that the output tiles of the 256
-    // persistent workgroups -- equal work, lockstep -- are not all stored at the same moment
-    if (ep.act > 0) {
-        const int n_ = ((int)blockIdx.x & 7) * ep.act;
-        for (int i = 0; i < n_; ++i) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
     const int T = K / kGBK;                              // steps per output tile (even: K % 32 == 0)
     const int my_tiles = (tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int S = my_tiles * T;                          // this workgroup's stream of steps (even)
@@ -177,23 +167,14 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
         const int t_ = xcd_swizzle(min(ld_tile, tiles - 1), tiles);         \
         a_src = A + ((int64_t)(t_ / tiles_n) * kG + ld_row) * lda + ld_c4;  \
         b_src = B + ((int64_t)(t_ % tiles_n) * kG + ld_row) * ldb + ld_c4;  \
-        if (ABL & 32) {     /* timing only: whole 128-byte lines per request (8 lanes per row), same bytes per two steps */ \
-            a_src = A + ((int64_t)(t_ / tiles_n) * kG + (tid >> 3)) * lda + (tid & 7) * 4;  \
-            b_src = B + ((int64_t)(t_ % tiles_n) * kG + (tid >> 3)) * ldb + (tid & 7) * 4;  \
-        }                                                                   \
     }
     G_SET_SRC()
     // the four pieces of a step are re-requested one by one (each right after it has been split), the cursor moves after the last
-#define G_LDK ((ABL & 32) ? (ld_k & ~16) : ld_k)
-#define G_OPAQUE(V) asm volatile("" : "+v"(V.x), "+v"(V.y), "+v"(V.z), "+v"(V.w));
-#define G_LD_A0(S_) if (!(ABL & 1) || !in_loop) { S_##a0 = *reinterpret_cast<const float4*>(a_src + G_LDK); } else { G_OPAQUE(S_##a0) }
-#define G_LD_A1(S_) if (!(ABL & 1) || !in_loop) { S_##a1 = *reinterpret_cast<const float4*>(a_src + (int64_t)64 * lda + G_LDK); } else { G_OPAQUE(S_##a1) }
-#define G_LD_B0(S_) if (!(ABL & 1) || !in_loop) { S_##b0 = *reinterpret_cast<const float4*>(b_src + G_LDK); } else { G_OPAQUE(S_##b0) }
-#define G_LD_B1(S_) if (!(ABL & 1) || !in_loop) { S_##b1 = *reinterpret_cast<const float4*>(b_src + (int64_t)64 * ldb + G_LDK); } else { G_OPAQUE(S_##b1) }
+#define G_LD_A0(S_) S_##a0 = *reinterpret_cast<const float4*>(a_src + ld_k);
+#define G_LD_A1(S_) S_##a1 = *reinterpret_cast<const float4*>(a_src + (int64_t)64 * lda + ld_k);
+#define G_LD_B0(S_) S_##b0 = *reinterpret_cast<const float4*>(b_src + ld_k);
+#define G_LD_B1(S_) S_##b1 = *reinterpret_cast<const float4*>(b_src + (int64_t)64 * ldb + ld_k);
 #define G_ADVANCE()                                                         \
-    if (ABL & 32) {                                                         \
-        if (ld_k & 16) { a_src -= 128 * lda; b_src -= 128 * ldb; } else { a_src += 128 * lda; b_src += 128 * ldb; } \
-    }                                                                       \
     ld_k += kGBK;                                                           \
     if (ld_k == K) {                                                        \
         ld_k = 0;                                                           \
@@ -205,7 +186,7 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
     // LDS image of a plane: unpadded 32-byte rows, the two 16-byte chunks of a row XOR-swizzled by bit 3 of the row (the image of
     // gemm_nt_x6_pp_kernel: fragment reads and the staging stores are conflict free)
 #define G_ST(R, PLANE0, ROW, SC, AM, WB)                                                                     \
-    if (!(ABL & 2) || !in_loop) {                                                                            \
+    {                                                                                                        \
         uint2 h_, m_;                                                                                        \
         if (PL & ((PLANE0) ? 2 : 1)) {           /* P4 operand: the 16 bytes ARE {h pair, h pair, m pair, m pair} */ \
             h_ = make_uint2(__float_as_uint(R.x), __float_as_uint(R.y));                                     \
@@ -224,8 +205,7 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
     half8 fa[2][2];                                      // [buffer][h | m]: row tile g of the step lives in buffer g & 1
     half8 fb[2][2];                                      // [h | m][column tile]
 #define G_MFMA1(MT, NT, PA, PB) \
-    if (!(ABL & 4)) acc[MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[(MT) & 1][PA], fb[PB][NT], acc[MT][NT], 0, 0, 0); \
-    else { asm volatile("" : "+v"(fa[(MT) & 1][PA]), "+v"(fb[PB][NT])); }
+    acc[MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[(MT) & 1][PA], fb[PB][NT], acc[MT][NT], 0, 0, 0);
 #define G_FENCE() __builtin_amdgcn_sched_barrier(0);
 #define G_BARRIER()                                                   \
     __builtin_amdgcn_sched_barrier(0);                                \
@@ -323,7 +303,7 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
                     asm volatile("s_nop 4\n\tv_writelane_b32 %0, %1, %2\n\tv_writelane_b32 %0, %3, %4"                 \
                                  : "+v"(mword) : "s"((uint32_t)bal), "n"(r), "s"((uint32_t)(bal >> 32)), "n"(16 + r));   \
                 }                                                                                                      \
-                if (ABL & 8) { asm volatile("" :: "v"(v)); } else if (EPI & G_ACCUM)                                   \
+                if (EPI & G_ACCUM)                                                                                     \
                 (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rc, voff_c,                                   \
                                                       ((mt * 32 + (r & 3) + 8 * (r >> 2)) * ldci + nt * 32) * 4, 0);   \
                 else                                                                                                   \
@@ -361,29 +341,29 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
 #define G_P_XY(R, SC, AM, PLF)                                                                               \
     if (PLF) {                                                                                               \
         ph = make_uint2(__float_as_uint(R.x), __float_as_uint(R.y));                                         \
-    } else if (!(ABL & 2) || !in_loop) {                                                                     \
+    } else {                                                                                                 \
         asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(AM) : "v"(R.x), "v"(R.y));                                \
         g3_split_pair(R.x, R.y, SC, ph.x, pm.x);                                                             \
     }
 #define G_P_ZW(R, SC, AM, PLF)                                                                               \
     if (PLF) {                                                                                               \
         pm = make_uint2(__float_as_uint(R.z), __float_as_uint(R.w));                                         \
-    } else if (!(ABL & 2) || !in_loop) {                                                                     \
+    } else {                                                                                                 \
         asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(AM) : "v"(R.z), "v"(R.w));                                \
         g3_split_pair(R.z, R.w, SC, ph.y, pm.y);                                                             \
     }
 #define G_P_WR(PLANE0, ROW, WB)                                                                              \
-    if (!(ABL & 2) || !in_loop) {                                                                            \
+    {                                                                                                        \
         const int o_ = (ROW) * 32 + ((((ld_c4 >> 3) ^ ((ROW) >> 3)) & 1) << 4) + (ld_c4 & 7) * 2;            \
         *reinterpret_cast<uint2*>((WB) + ((PLANE0) + 0) * kGPlane + o_) = ph;                                \
         *reinterpret_cast<uint2*>((WB) + ((PLANE0) + 1) * kGPlane + o_) = pm;                                \
     }
     // A fragment (plane PC) of row tile MT -> buffer MT & 1
 #define G_RA(MT, PC, RB)                                                                                     \
-    if (!(ABL & 16) || !in_loop) fa[(MT) & 1][PC] = *reinterpret_cast<const half8*>((RB) + a_off + (PC) * kGPlane + (MT) * 32 * 32);
+    fa[(MT) & 1][PC] = *reinterpret_cast<const half8*>((RB) + a_off + (PC) * kGPlane + (MT) * 32 * 32);
     // both planes of the B fragment of column tile NT
 #define G_RB(NT, RB)                                                                                         \
-    if (!(ABL & 16) || !in_loop) {                                                                           \
+    {                                                                                                        \
         fb[0][NT] = *reinterpret_cast<const half8*>((RB) + b_off + (NT) * 32 * 32);                          \
         fb[1][NT] = *reinterpret_cast<const half8*>((RB) + b_off + kGPlane + (NT) * 32 * 32);                \
     }
@@ -430,7 +410,6 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
 
     // prologue: steps 0 and 1 split into slots 0 and 1, steps 2 and 3 requested, first fragments of step 0 read
     int kt = 0, sc = 0, sr = 1, sw = 2;
-    bool in_loop = false;
     G_LD_A0(x) G_LD_A1(x) G_LD_B0(x) G_LD_B1(x) G_ADVANCE()
     G_LD_A0(y) G_LD_A1(y) G_LD_B0(y) G_LD_B1(y) G_ADVANCE()
     {
@@ -445,7 +424,6 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
         G_BARRIER()
         G_RA(0, 0, w0) G_RA(0, 1, w0) G_RB(0, w0) G_RB(1, w0)
     }
-    in_loop = true;
 #pragma unroll 1
     for (int s = 0; s < S; s += 2) {
         G_STEP(x)
@@ -471,8 +449,6 @@ __global__ __launch_bounds__(kGThreads, 2) void gemm_nt_g3_kernel(const float* _
 #undef G_LD_B0
 #undef G_LD_A1
 #undef G_LD_A0
-#undef G_OPAQUE
-#undef G_LDK
 #undef G_SET_SRC
 }
 
@@ -1032,19 +1008,13 @@ static int tn_g3_splits(int64_t M, int N, int K) {
 
 using namespace vq;
 
-#if VQCPC_LAB
-// ablation variants gemm_nt_g3_kernel<0, ABL> (VQCPC_G3_ABL; results are wrong by construction)
-using G3AblForms = Forms<Form<0, 1>, Form<0, 2>, Form<0, 4>, Form<0, 8>, Form<0, 16>, Form<0, 19>, Form<0, 32>>;
-#endif
-
 // Every launch of gemm_nt_g3_kernel: the shape and operand checks the entry points share, the operands -> (EPI, PL) mapping
 // (g3_form) and the table of instantiated forms (G3Forms), both in gemm_forms.h.  Absent operands are NULL; a form that is not in the
 // table is refused before anything is launched.  `splits` > 1 (vqcpc_gemm_nt_grad_splitk): K is the slice length, C the partial planes.
-// `lab_hooks`: the measurement switches of vqcpc_gemm_nt_grad (lab builds).
 static int g3_launch(const char* who, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N,
                      int K, const float* bias, int act, float drop_p, uint64_t seed, const float* add, int64_t ldadd, const float* add2,
                      int64_t ldadd2, const void* gate_mask, float gate_scale, void* mask_out, float* scale_state,
-                     const float* pl_amax_a, const float* pl_amax_b, void* stream, int splits = 1, bool lab_hooks = false) {
+                     const float* pl_amax_a, const float* pl_amax_b, void* stream, int splits = 1) {
     VQ_REQUIRE(vqcpc_gemm_nt_grad_supported(M, N, K), "%s: M, N multiples of 256 and K of 32, got M=%lld N=%d K=%d", who, (long long)M, N,
                K);
     VQ_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && lda >= K && ldb >= K && ldc >= N && aligned16(A) && aligned16(B),
@@ -1074,25 +1044,10 @@ static int g3_launch(const char* who, const float* A, int64_t lda, const float* 
     const dim3 grid((unsigned)std::min(tiles, kNumCU), (unsigned)splits), block(kGThreads);
     const size_t lds = (size_t)kGSlots * kGSlot;
     hipStream_t st = (hipStream_t)stream;
-    bool launched = false;
-#if VQCPC_LAB
-    if (lab_hooks) {
-        static const int stagger = lab_env_int("VQCPC_G3_STAGGER", 0), abl = lab_env_int("VQCPC_G3_ABL", 0);
-        ep.act = stagger;
-        if (abl && f.epi == 0 && f.pl == 0) {
-            launched = dispatch(G3AblForms{}, 0, abl, [&](auto v) {
-                launch_lds<gemm_nt_g3_kernel<0, decltype(v)::b>>(grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles, ep,
-                                                                 scale_state);
-            });
-            VQ_REQUIRE(launched, "%s: VQCPC_G3_ABL=%d is not an instantiated ablation", who, abl);
-        }
-    }
-#endif
-    if (!launched)
-        launched = dispatch(G3Forms{}, f.epi, f.pl, [&](auto v) {
-            launch_lds<gemm_nt_g3_kernel<decltype(v)::a, 0, decltype(v)::b>>(grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn,
-                                                                            tiles, ep, scale_state);
-        });
+    const bool launched = dispatch(G3Forms{}, f.epi, f.pl, [&](auto v) {
+        launch_lds<gemm_nt_g3_kernel<decltype(v)::a, decltype(v)::b>>(grid, block, lds, st, A, lda, B, ldb, C, ldc, M, N, K, tn, tiles, ep,
+                                                                      scale_state);
+    });
     VQ_REQUIRE(launched,
                "%s: no kernel for epilogue flags %d with operand format %d (bit 0 / 1: A / B pre-split).  Dropout goes with a residual or "
                "relu; a pre-split A with none / add / add == C / bias / bias + add / bias + dropout + add",
@@ -1152,7 +1107,7 @@ int vqcpc_gemm_nt_grad(const float* A, int64_t lda, const float* B, int64_t ldb,
     VQ_REQUIRE(A && B && C && scale_state, "gemm_nt_grad: null pointer");
     VQ_REQUIRE(!(add2 && !add) && !(gate_mask && add), "gemm_nt_grad: epilogue is one of none / add / add + add2 / gate mask");
     return g3_launch("gemm_nt_grad", A, lda, B, ldb, C, ldc, M, N, K, nullptr, 0, 0.0f, 0, add, ldadd, add2, ldadd2, gate_mask,
-                     gate_scale, nullptr, scale_state, nullptr, nullptr, stream, 1, true);
+                     gate_scale, nullptr, scale_state, nullptr, nullptr, stream);
 }
 
 // Few output tiles, long K: the remainder rows of a launch whose 256-tiles do not fill whole rounds (139 264 x 256: 2 rounds + 32

@@ -464,12 +464,8 @@ static int launch_bwd(const float* d_ctx, int64_t ldo, const float* qkv, int64_t
 }
 
 static int g_force_general = 0;   // tests: route L = 16 / 4 through the general-L kernels too
-// L = 16 runs on the matrix cores (relattn16.hip); VQCPC_RELATTN16_LDS=1 keeps the LDS-tiled VALU kernels (A/B, tests)
-static bool lds_only() {
-    static const bool on = lab_env_int("VQCPC_RELATTN16_LDS", 0) != 0;
-    return on;
-}
-static bool use_mfma16(int L, int H, int hd) { return att_mfma16_ok(L, H, hd, lds_only()); }
+// L = 16 runs on the matrix cores (relattn16.hip)
+static bool use_mfma16(int L, int H, int hd) { return att_mfma16_ok(L, H, hd); }
 static bool att_supported(int L, int H, int hd) { return !g_force_general && att_lds_ok(L, H, hd); }
 
 static int finish_de16(float* ws, int nsplit, int H, int hd, float* d_e1, float* d_e2, hipStream_t s) {
@@ -486,7 +482,7 @@ static AttRoute route_of(const AttEntry& e, int L, int H, int hd, const int64_t*
                          const void* e2, const void* out, const void* d_ctx = nullptr, const void* ws = nullptr) {
     const unsigned aligned = (aligned16(qkv) ? P_QKV : 0) | (aligned16(e1) ? P_E1 : 0) | (aligned16(e2) ? P_E2 : 0) |
                              (aligned16(out) ? P_OUT : 0) | (aligned16(d_ctx) ? P_DCTX : 0) | (aligned16(ws) ? P_WS : 0);
-    return att_route(e, L, H, hd, g_force_general != 0, lds_only(), aligned, tokens != nullptr);
+    return att_route(e, L, H, hd, g_force_general != 0, aligned, tokens != nullptr);
 }
 
 // The forward of every self-attention entry point (`family`: ATT_F32 .. ATT_TAB of relattn_forms.h): each check once, the kernel

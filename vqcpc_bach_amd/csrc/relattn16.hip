@@ -712,10 +712,9 @@ template <int HD, bool B16, bool IN16>
 static int a16_fwd_t(const float* qkv, int64_t ldq, const int64_t* tokens, const float* e1, const float* e2, float* ctx,
                      int64_t ldo, float* probs, int64_t n_blocks, int H, float drop_p, uint64_t seed, hipStream_t s) {
     const int64_t total = n_blocks * H;
-    static const int x6 = lab_env_int("VQCPC_RELATTN16_X6", 1);      // lab builds: =0 keeps the fp32-MFMA contractions (A/B)
     // GEMM mode 0 is documented as the exact fp32-MFMA arithmetic (include/vqcpc.h): there the contractions over head_dim
     // stay on v_mfma_f32_16x16x4_f32 too; the six-product bf16 form belongs to the bf16x6 / bf16 modes
-    const bool six = (HD == 32 || HD == 64) && x6 && vqcpc_gemm_get_mode() != 0;
+    const bool six = (HD == 32 || HD == 64) && vqcpc_gemm_get_mode() != 0;
     const auto kern = six ? relattn16_fwd_kernel<HD, B16, IN16, (HD == 32 || HD == 64)> : relattn16_fwd_kernel<HD, B16, IN16>;
     hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(total, kA16Waves)), dim3(kA16Waves * 64), 0, s, qkv, ldq, tokens, e1, e2, ctx, ldo,
                        probs, total, H, 1.0f / sqrtf((float)HD), drop_threshold(drop_p), 1.0f / (1.0f - drop_p), seed);
@@ -731,8 +730,7 @@ static int a16_bwd_t(const float* d_ctx, int64_t ldo, const float* qkv, int64_t 
     const int chunks = (int)ceil_div(n_blocks, bpc);
     if constexpr (B16 && IN16 && (HD == 32 || HD == 64)) {
         // all-bf16 form outside the exact GEMM mode 0: every contraction on the bf16 matrix pipe (relattn16_bwd_mm16_kernel)
-        static const int mm16 = lab_env_int("VQCPC_RELATTN16_MM16", 1);      // lab builds: =0 keeps the fp32-MFMA contractions (A/B)
-        if (mm16 && tokens == nullptr && vqcpc_gemm_get_mode() != 0) {
+        if (tokens == nullptr && vqcpc_gemm_get_mode() != 0) {
             hipLaunchKernelGGL((relattn16_bwd_mm16_kernel<HD>), dim3(chunks, H), dim3(kA16Waves * 64), 0, s,
                                reinterpret_cast<const unsigned short*>(d_ctx), ldo, reinterpret_cast<const unsigned short*>(qkv), ldq,
                                probs, e1, e2, reinterpret_cast<unsigned short*>(d_qkv), ldg, ws, n_blocks, H, bpc,

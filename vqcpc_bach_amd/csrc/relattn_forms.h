@@ -59,7 +59,7 @@ inline bool att_lds_ok(int L, int H, int hd) {
     const int slots = 4 * (64 / (4 * L));
     return slots % H == 0 || H % slots == 0;
 }
-inline bool att_mfma16_ok(int L, int H, int hd, bool lds_only) { return L == 16 && !lds_only && H >= 1 && att_hd_ok(hd); }
+inline bool att_mfma16_ok(int L, int H, int hd) { return L == 16 && H >= 1 && att_hd_ok(hd); }
 inline bool att_strip_ok(int L, int H, int hd) { return L >= 1 && L <= 1024 && H >= 1 && (att_hd_ok(hd) || hd == 128); }
 
 enum AttKernel { ATT_REFUSED, ATT_STRIP, ATT_MFMA16, ATT_LDS };
@@ -68,14 +68,14 @@ struct AttRoute {
     const char* why;      // ATT_REFUSED: what is wrong, to stand in front of "L=.. H=.. hd=.."
 };
 
-// force_general: vqcpc_relattn_force_general(1); lds_only: the lab switch VQCPC_RELATTN16_LDS; aligned: P_ bits of the 16-byte
+// force_general: vqcpc_relattn_force_general(1); aligned: P_ bits of the 16-byte
 // aligned pointers.  L is ignored (16) by an entry that does not take it.
-inline AttRoute att_route(const AttEntry& e, int L, int H, int hd, bool force_general, bool lds_only, unsigned aligned,
+inline AttRoute att_route(const AttEntry& e, int L, int H, int hd, bool force_general, unsigned aligned,
                           bool tokens_given) {
     const auto all = [&](unsigned set) { return (aligned & set) == set; };
     if (e.tokens == TOK_REQUIRED && !tokens_given) return {ATT_REFUSED, "no tokens for"};
     if (!e.has_L) {
-        if (force_general || !att_mfma16_ok(16, H, hd, lds_only)) return {ATT_REFUSED, "unsupported"};
+        if (force_general || !att_mfma16_ok(16, H, hd)) return {ATT_REFUSED, "unsupported"};
         return all(e.must) ? AttRoute{ATT_MFMA16, nullptr} : AttRoute{ATT_REFUSED, "a buffer is not 16-byte aligned for"};
     }
     if (force_general || !att_lds_ok(L, H, hd)) {
@@ -83,7 +83,7 @@ inline AttRoute att_route(const AttEntry& e, int L, int H, int hd, bool force_ge
         return all(e.strips) ? AttRoute{ATT_STRIP, nullptr} : AttRoute{ATT_REFUSED, "a buffer is not 16-byte aligned for"};
     }
     if (!all(e.must)) return {ATT_REFUSED, "a buffer is not 16-byte aligned for"};
-    return {att_mfma16_ok(L, H, hd, lds_only) && all(e.mfma) ? ATT_MFMA16 : ATT_LDS, nullptr};
+    return {att_mfma16_ok(L, H, hd) && all(e.mfma) ? ATT_MFMA16 : ATT_LDS, nullptr};
 }
 
 // relattn_fwd_kernel / relattn_bwd_kernel<L, HD> (relattn.hip) ...

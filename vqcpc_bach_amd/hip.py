@@ -9,8 +9,6 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libvqcpc_hip.so')
-LAB_LIB_PATH = os.path.join(_HERE, 'libvqcpc_hip_lab.so')
-_is_lab = False
 ABI_VERSION = 2       # 2 (round 6): vqcpc_gemm_nt_bf16 gained two arguments in round 5, the dropout mixer of csrc/common.h changed (masks of a given
                       # (seed, index) differ from ABI-1 builds), vqcpc_grad_scale_roll_logged and the plane-operand GEMM entry points were added
 
@@ -265,43 +263,24 @@ SIGNATURES = {
                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
-# Entry points of LAB builds only (`VQCPC_LAB=1 python -m vqcpc_bach_amd.build` -> libvqcpc_hip_lab.so, the `#ifdef VQCPC_LAB`
-# section of include/vqcpc.h): rejected kernel designs kept for A/B measurements by the tools under tools/
-LAB_SIGNATURES = {
-    'vqcpc_gemm_bf16_set_variant': (c_int, [c_int]),
-    'vqcpc_planes_bytes': (c_i64, [c_i64, c_int]),
-    'vqcpc_split3_planes': (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr]),
-    'vqcpc_join3_planes': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    'vqcpc_gemm_nt_planes_supported': (c_int, [c_i64, c_int, c_int]),
-    'vqcpc_gemm_nt_planes': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_int, c_f32, c_u64, c_ptr, c_i64,
-                                     c_f32, c_ptr, c_i64, c_ptr]),
-}
-
 
 class VqcpcHipError(RuntimeError):
     pass
 
 
 def load(path=None):
-    """dlopen the library (after torch, so that its libamdhip64.so.7 is the one HIP runtime in the process).  The product
-    library unless VQCPC_LAB=1 asks for the lab build (measurement tools; see build.py)."""
-    global _lib, _is_lab
+    """dlopen the library (after torch, so that its libamdhip64.so.7 is the one HIP runtime in the process)."""
+    global _lib
     if _lib is not None:
         return _lib
-    want_lab = os.environ.get('VQCPC_LAB', '0') == '1'
-    path = path or os.environ.get('VQCPC_HIP_LIB', LAB_LIB_PATH if want_lab else LIB_PATH)
+    path = path or os.environ.get('VQCPC_HIP_LIB', LIB_PATH)
     if not os.path.exists(path):
-        raise VqcpcHipError(f'{path} not found: build it with `{"VQCPC_LAB=1 " if want_lab else ""}python -m vqcpc_bach_amd.build` '
+        raise VqcpcHipError(f'{path} not found: build it with `python -m vqcpc_bach_amd.build` '
                             f'(hipcc --offload-arch=gfx950). There is no CPU fallback.')
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    _is_lab = hasattr(lib, 'vqcpc_gemm_nt_planes')
-    if _is_lab:
-        for name, (res, args) in LAB_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
     if lib.vqcpc_abi_version() != ABI_VERSION:
         raise VqcpcHipError(f'ABI version mismatch: library {lib.vqcpc_abi_version()} != binding {ABI_VERSION}')
     _lib = lib
@@ -311,12 +290,6 @@ def load(path=None):
 def clear_runtime_error():
     """Returns and clears the HIP runtime's pending (non-sticky) error of this thread (include/vqcpc.h)."""
     return int(load().vqcpc_clear_runtime_error())
-
-
-def is_lab():
-    """True when the loaded library is a lab build (LAB_SIGNATURES are bound, the tools' environment switches are live)."""
-    load()
-    return _is_lab
 
 
 def is_loaded():
@@ -363,8 +336,7 @@ def query(name, *args):
 
 
 def set_gemm_mode(mode):
-    """0 = fp32 MFMA (exact), 1 = bf16x6 split MFMA (fp32-class accuracy, faster); +2: 128-tile kernels only,
-    +4: 256-tile NT kernel without the ping-pong wave groups, +16: LDS-DMA 256-tile NT kernel, +32: one-wave-per-SIMD software-pipelined 256-tile NT kernel (A/B switches); 8 = plain bf16 operands (one bf16 MFMA per
+    """0 = fp32 MFMA (exact), 1 = bf16x6 split MFMA (fp32-class accuracy, faster); 8 = plain bf16 operands (one bf16 MFMA per
     product, fp32 accumulation: reduced precision, for BASELINE configs[4] only).  get_gemm_mode() returns 0 / 1 / 2."""
     global _gemm_mode, _gemm_mode_explicit
     rc = load().vqcpc_gemm_set_mode(int(mode))
@@ -385,7 +357,7 @@ def use_training_default_gemm_mode():
 
 def gemm_mode_state():
     """(arithmetic in force: 0 fp32 MFMA / 1 bf16x6 / 2 bf16, whether a caller chose it): what restore_gemm_mode_state() puts
-    back (the A/B sub-switches of set_gemm_mode are not part of it)."""
+    back."""
     return (get_gemm_mode(), _gemm_mode_explicit)
 
 

@@ -493,7 +493,7 @@ def gemm_nt_residual(a, b, res, res_may_alias=None):
 
 
 _rowcut = {}                   # (M, N, K) -> (rows of the whole 256-tile rounds, split-K workspace bytes of the rest)
-SPLIT_K = True                 # A/B switch (tools/bench_splitk.py)
+SPLIT_K = True                 # A/B switch (measured in profiles/r02_perf_log.md)
 _SPLITK_MAX_ROWS = 1 << 14     # 160 tiles of 128 x 128 at most: no shape above this many rows qualifies
 _splitk_ws = {}                # (M, N, K) -> workspace bytes in bf16x6 mode (0: not a split-K shape)
 
@@ -510,7 +510,7 @@ GATEBITS_MIN_TILES = 160
 def gatebits_worthwhile(M, N, K):
     """The bit-mask forms exist in the 256-tile ping-pong kernel only (one workgroup per CU): below ~160 tiles the
     fp32-gate forms on 128-tiles fill more of the chip and win (3072 x 2048 x 512: 47 vs 63 us, 768 rows: 33 vs 60 us; at
-    192 tiles the bit forms are ahead -- tools/bench_splitk.py)."""
+    192 tiles the bit forms are ahead)."""
     return (M // 256) * (N // 256) >= GATEBITS_MIN_TILES and gatebits_supported(M, N, K)
 
 
@@ -696,42 +696,6 @@ def flush_wgrads():
 # ------------------------------------------------------------------------------------------------------------------
 # bf16 path (BASELINE configs[4]: hip.set_gemm_mode(8)): operands are bf16 IN HBM (vqcpc_gemm_nt_bf16), fp32 accumulate
 # ------------------------------------------------------------------------------------------------------------------
-def _require_lab(what):
-    if not hip.is_lab():
-        raise hip.VqcpcHipError(f'{what} exists in the lab build only: VQCPC_LAB=1 python -m vqcpc_bach_amd.build, then run with VQCPC_LAB=1')
-
-
-def split3_planes(x):
-    """fp32 (rows, cols) -> the P3 format of csrc/gemm_planes.hip: three K-tile-major bf16 planes with
-    x == high + mid + low exactly.  Returns a uint8 buffer of 6 * rows * cols bytes tagged with its logical shape."""
-    _require_lab('split3_planes')
-    x = _f32(x)
-    assert x.dim() == 2 and x.stride(1) == 1 and x.shape[1] % 16 == 0
-    rows, cols = x.shape
-    out = torch.empty(6 * rows * cols, dtype=torch.uint8, device=x.device)
-    hip.call('vqcpc_split3_planes', x, x.stride(0), rows, cols, out)
-    out.p3_shape = (rows, cols)
-    return out
-
-
-def join3_planes(planes, rows, cols):
-    _require_lab('join3_planes')
-    x = torch.empty(rows, cols, dtype=torch.float32, device=planes.device)
-    hip.call('vqcpc_join3_planes', planes, rows, cols, x, cols)
-    return x
-
-
-def gemm_nt_planes(a_planes, b_planes, M, N, K, bias=None, act=0, drop_p=0.0, seed=0, gate=None, gate_scale=1.0, add=None,
-                   out=None):
-    """C[M, N] = epi(A . B^T) on pre-split (P3) operands: the same products, in the same order, as ops.gemm_nt in mode 1."""
-    _require_lab('gemm_nt_planes')
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.float32, device=a_planes.device)
-    hip.call('vqcpc_gemm_nt_planes', a_planes, b_planes, out, out.stride(0), M, N, K, bias, int(act), float(drop_p), int(seed),
-             gate, gate.stride(0) if gate is not None else 0, float(gate_scale), add, add.stride(0) if add is not None else 0)
-    return out
-
-
 def cast_bf16(x):
     """fp32 (rows, cols), rows possibly strided -> dense torch.bfloat16 (round to nearest even, like .bfloat16())."""
     if x.dtype == torch.bfloat16:
