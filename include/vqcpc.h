@@ -1233,6 +1233,38 @@ int vqcpc_decode_score(const float* logits, int64_t ldl, const int32_t* voice_of
                        int64_t B, int64_t cols, int64_t ld, float* logp, float* logmass, float* entropy, int32_t* rank, int64_t* best,
                        float* best_logp, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Scoring given codes under the prior (csrc/prior_score.hip, priors/scoring.py `PriorRelative.score_codes(method='windows')`; the
+ * outputs are restated in numpy float64 in tests/prior_score_reference.py).
+ * vqcpc_prior_score: ONE launch scores R >= 1 independent rows of logits (R, ldl) with 1 <= V <= 4096 columns; R is not bounded by the
+ *   samplers' 64.  Row r belongs to piece b = row_b[r] and sequence column col = row_col[r] (device int32 [R]).  A row with col
+ *   outside [0, cols) or b outside [0, B) is skipped: nothing is read or written for it.  The target t is the code seq[b][col]
+ *   (int64, [B][ldseq]) clamped to [0, V^ncb) as vqcpc_prior_sample_constrained clamps a forced code; with ncb > 1 the row is
+ *   stage `stage` of a product code (V = K) and t is digit `stage` of the clamped code, (code / K^stage) % K, the digit rule of
+ *   vqcpc_prior_sample_product.  Every output is optional (NULL: not computed):
+ *     logp      float32  [b * ldlogp + col]             (x_t - m) - logf(s), m / s the row maximum and exp-sum over the V columns,
+ *               formed exactly as vqcpc_prior_sample_constrained forms logp (thread t owns codes 16t .. 16t + 15 and sums them in
+ *               ascending order, then the wave butterfly and (w0 + w1) + (w2 + w3); a -inf logit contributes 0, a -inf target
+ *               gives -inf): the bits that sampler writes for this row with t forced.  Stage 0 stores; stage j >= 1 writes
+ *               old + own (one fp32 add), so that ncb launches in ascending stage order on one stream leave the bits of
+ *               vqcpc_prior_sample_product's logp_acc chain
+ *     entropy   float32  [b * ld + col * ncb + stage]   -sum_i p_i log p_i in nats over the V codes, as logf(s) + (sum_i e_i (m - x_i)) / s
+ *               with e_i = expf(x_i - m); every term is >= 0, a -inf logit contributes 0; the sums in the order above
+ *     rank      int32    [b * ld + col * ncb + stage]   #{i < V : x_i > x_t or (x_i == x_t and i < t)}: 0 = the model's first choice.  Exact
+ *     best      int64    [b * ld + col * ncb + stage]   the arg-max over [0, V), the lowest index among equals.  Exact
+ *     best_logp float32  [b * ld + col * ncb + stage]   logp's formula at `best`
+ *   A row's results depend on nothing but its own logits and target: a row alone gives the bits it gives among others.  Rows of
+ *   V <= 1024 codes are scored by a wavefront each (the other three wavefronts of the sampler's tree hold zeros and -inf there:
+ *   the same bits), larger rows by a workgroup of 256 threads each; the row is read once.
+ *   The launch function refuses, before any HIP call: NULL logits, row_b, row_col or seq, V outside [1, 4096], ncb outside [1, 4],
+ *   stage outside [0, ncb), V^ncb >= 2^31, R, B or cols < 1, ldl < V, ldseq < cols, (with logp) ldlogp < cols, (with any other
+ *   output) ld < cols * ncb.  No allocation, no synchronisation, no atomics.
+ * Adding it left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_prior_score(const float* logits, int64_t ldl, int V, int ncb, int stage, int64_t R, const int32_t* row_b,
+                      const int32_t* row_col, const int64_t* seq, int64_t ldseq, int64_t B, int64_t cols, float* logp,
+                      int64_t ldlogp, int64_t ld, float* entropy, int32_t* rank, int64_t* best, float* best_logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -261,6 +261,8 @@ SIGNATURES = {
                                          c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     'vqcpc_decode_score': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64,
                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_score': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64,
+                                  c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 

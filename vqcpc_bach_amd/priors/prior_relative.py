@@ -30,7 +30,9 @@ one, draws the others as it would without the constraint given the same prefix (
 returns every emitted code's log-probability -- under the model's UNMODIFIED row: temperature 1 and no filter, whatever
 `temperature`, `top_k` and `top_p` are (vqcpc_prior_sample_constrained; the default path launches vqcpc_prior_sample as
 before).  `score_codes` is the everything-forced call; `continue_tokens` encodes the opening of a piece, lets the prior go on
-from its codes and has the decoder write tokens around the given ones.
+from its codes and has the decoder write tokens around the given ones.  `score_codes(method='windows')` computes the same scores
+without generating -- every window of every piece is a row of one batched teacher-forced forward (priors/scoring.py,
+vqcpc_prior_score) -- and `score_chorale` adds the decoder's token scores to them: the nats the pipeline spends on a piece.
 
 PRODUCT CODES: `code_model='product'` (ours, `prior_kwargs['code_model']`; default 'merged' = the reference's model, one symbol
 of a vocabulary of V = K**ncb, which `generate_codes` samples up to V = 4096).  A merged code is ncb digits c_j = (code // K**j)
@@ -309,17 +311,61 @@ class PriorRelative(FlatTraining, nn.Module):
         codes = generate_in_chunks(self, B, num_tokens, chunk)
         return (codes, logp) if return_logp else codes
 
-    def score_codes(self, codes, use_graph=True, window_stride=1, method='auto'):
+    @staticmethod
+    def score_window_plan(num_tokens, N, window_stride=1):
+        """Host only: the distinct model windows in which `generate_codes` emits the `num_tokens` >= N codes of a sequence at
+        `window_stride` = k, as a list of (first code of the window, first scored column, one past the last scored column) in
+        sequence coordinates, windows ascending -- the columns `IncrementalPrior.run` scores in each window.  Window 0 scores
+        columns [0, N); window i * k its last k columns; when (num_tokens - N) % k != 0 a last window at num_tokens - N scores the
+        last (num_tokens - N) % k columns.  Every column lies in exactly one window; num_tokens == N gives one window.
+        ValueError on num_tokens < N or a stride outside [1, max(N, 2))."""
+        from .scoring import window_plan
+        return window_plan(num_tokens, N, window_stride)
+
+    def score_codes(self, codes, use_graph=True, window_stride=1, method='auto', return_details=False, window_rows=None):
         """log-probability of every code of `codes` (B, L) int64, L >= N, given the codes before it: float32 (B, L).  Column
         e < N is scored in the first window, column e >= N in the window that ends at e (the reference's window rule, at
-        `window_stride` = 1).  It is `generate_codes` with every code forced, so it is the model's distribution at temperature
-        1 without a filter; use_graph / window_stride / method as there."""
+        `window_stride` = 1).  With method 'auto' / 'cached' / 'forward' it is `generate_codes` with every code forced, so it is
+        the model's distribution at temperature 1 without a filter; use_graph / window_stride / method as there.
+        method='windows' computes the same scores without generating (priors/scoring.py): the windows `score_window_plan` names
+        are rows of one batched, teacher-forced forward, `window_rows` (piece, window) rows at a time (None: the measured
+        default), and vqcpc_prior_score (csrc/prior_score.hip) scores the rows.  The scores agree with the forced call's within
+        the teacher-forced tolerance, not bit for bit; `use_graph` is ignored.  'auto' never routes here.
+        return_details=True (method='windows' only) -> a dict of (B, L) tensors: 'logp'; 'entropy' (float32, nats) of the model's
+        distribution at the column; 'rank' (int32) of the given code, 0 = the model's first choice, equal logits in index order;
+        'best' (int64), the arg-max, the lowest index among equals; 'best_logp' (float32).  code_model 'product': the stages are
+        teacher-forced with the piece's own digits, 'logp' is the sum of the ncb stages in ascending order, and the other arrays
+        are (B, L, ncb) and describe each digit's conditional distribution ('best': the greedy digit given the piece's own
+        earlier digits); any K**ncb < 2**31 is scored, a merged prior up to 4096 codes.
+        Runs in eval mode without gradients under STEP_LOCK; the previous mode is restored.  ValueError on L < N, negative codes
+        or codes >= V, a bad stride, window_rows that is not an integer >= 1, and return_details / window_rows with another
+        method."""
         codes = self._checked_codes(codes)
         if bool((codes < 0).any()):
             raise ValueError('score_codes: negative codes')
+        if method == 'windows':
+            from .scoring import score_codes_windows
+            return score_codes_windows(self, codes, window_stride, return_details, window_rows)
+        if return_details or window_rows is not None:
+            raise ValueError(f"score_codes: return_details / window_rows belong to method='windows' (got method={method!r})")
         B, L = codes.shape
         return self.generate_codes(L, num_generated_codes=B, seed=0, use_graph=use_graph, window_stride=window_stride,
                                    method=method, constraint=codes, return_logp=True)[1]
+
+    def score_chorale(self, x, decoder, return_details=False, window_rows=None, decoder_window_rows=32):
+        """The bits the pipeline spends on an existing piece x (1, events, channels): -log p(codes) - log p(tokens | codes), a
+        bound on -log p(piece).  x is framed and encoded as `Decoder.score_chorale` frames it (one PAD ... START chunk, the END /
+        PAD completion; needs the dataset's START / END / XX symbols; the compatibility checks of `continue_tokens`); the prior
+        scores the framed code sequence with `score_codes(method='windows')`, `decoder.score_tokens` the tokens.  The framed
+        chunks go through this prior's frozen encoder for the prior's codes and through the decoder's for the decoder's: in a
+        trained pipeline one and the same encoder.
+        -> dict: 'code_logp' float32 (1, codes of x's own chunks), each code conditioned on everything before it, the framing
+        chunk's codes included; 'token_logp' float32 (1, events, channels) on x's own events (`Decoder.score_chorale`'s);
+        'total_logp', the float64 sum of both; 'nats_per_token' = -total_logp / (events * channels).  return_details=True adds
+        'code_details' and 'token_details', the two halves' detail dicts on the same ranges.  window_rows / decoder_window_rows:
+        the two halves' rows per forward.  A decoder on continuous latents raises NotImplementedError."""
+        from .scoring import score_chorale
+        return score_chorale(self, x, decoder, return_details, window_rows, decoder_window_rows)
 
     def generate(self, num_tokens, decoder, temperature=1.0, num_generated_codes=1, num_decodings_per_generating_code=1,
                  decoder_temperature=None, seed=None, code_constraint=None, return_logp=False, **decoder_sampling):
