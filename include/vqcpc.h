@@ -925,6 +925,22 @@ int vqcpc_decode_source_rows(const float* z_full, int64_t nb, int dz, const int3
  *       (not written): the window index is not known to the host, which checks ldcons, ldlogp >= N only.
  *   codes[b * ldc + pos], next_in, probs (the filtered distribution whatever is forced), the ticket that advances pos[0], the
  *   no-op once pos >= N and the limits are unchanged.
+ * vqcpc_prior_sample_masked: vqcpc_prior_sample_constrained (the same kernel body, one more compile-time flag) with two more
+ *   things at the same column col (col = pos, or win[1] + pos; win[1] < 0: no live window):
+ *     allowed[(b * ldallow + col) * words + w] (device uint32, [M][ldallow][words], words = ceil(V / 32) <= 128; NULL = no
+ *       restriction): bit i & 31 of word i >> 5 set means code i may be drawn at (row b, column col).  A code outside the set
+ *       becomes -inf right after logits * temperature, before top-k and top-p, so the filters and probs act on the allowed codes;
+ *       the draw is still keyed by (seeds[b], pos).  Thread t reads the one word that holds its 16 codes.  Only bits [0, V) count;
+ *       a set with none of them restricts nothing (the caller is expected to refuse such a set).  A forced code (constraint >= 0)
+ *       wins over the set.  col outside [0, ldallow) or no live window: no restriction.
+ *     logmass[b * ldmass + col] (may be NULL; column rule of logp) = (m_a - m) + log(s_a) - log(s): m, s the maximum and the
+ *       exp-sum of the unmodified row exactly as logp forms them (a thread's 16 codes ascending, then the block sum), m_a, s_a the
+ *       same over the allowed codes in the same order -- the log of the probability the model itself gives to the set
+ *       (temperature 1, no filter).  Exactly 0.0f for the full set and for a row that is not restricted, -inf when every allowed
+ *       logit is -inf; written at forced columns too; a row's value does not depend on M.  logp is unchanged: the emitted code
+ *       under the unmodified row.
+ *   ldallow >= N with allowed, ldmass >= N with logmass.  With allowed == NULL and logmass == NULL every output has the bits of
+ *   vqcpc_prior_sample_constrained.
  * vqcpc_prior_window: ONE workgroup; win (device int32 [2]) = {next window's first code, live window's first code or -1}.
  *   First the live window's codes [0, pos) go back into seq[M][ldseq] (code j of window w is column w + j).  Then, unless
  *   win[0] < 0 or win[0] + N > num_tokens (commit only): codes_win[M][N] = seq columns win[0].., prefix_rows[b * P + j] =
@@ -941,6 +957,11 @@ int vqcpc_prior_sample_constrained(const float* logits, int64_t ldl, int V, int6
                                    const int32_t* win, int64_t* codes, int64_t ldc, int N, const float* table,
                                    int64_t table_rows, int d, float* next_in, int64_t ldn, float* probs, int64_t ldp,
                                    int32_t* pos, int32_t* ticket, void* stream);
+int vqcpc_prior_sample_masked(const float* logits, int64_t ldl, int V, int64_t M, float temperature, int top_k, float top_p,
+                              const int64_t* seeds, const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp,
+                              const int32_t* win, const uint32_t* allowed, int64_t ldallow, float* logmass, int64_t ldmass,
+                              int64_t* codes, int64_t ldc, int N, const float* table, int64_t table_rows, int d, float* next_in,
+                              int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket, void* stream);
 int vqcpc_prior_window(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t* win, int advance, int64_t* codes_win, int N,
                        int P, int64_t* prefix_rows, const float* table, int64_t table_rows, int d, float* x, int64_t ldx,
                        const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M, void* stream);
@@ -972,6 +993,17 @@ int vqcpc_prior_window(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t*
  *   ncb - 1) and its own digit, writes codes[b * ldc + pos], next_in row b = tables[0][c_0] + tables[1][c_1] + ... (tables
  *   [ncb][K][d]: the chain of vqcpc_product_gather without res, same order, same bits), logp[b * ldlogp + col] = the accumulated
  *   sum, and advances pos[0] through the ticket as vqcpc_prior_sample does.
+ * vqcpc_prior_sample_product_masked: vqcpc_prior_sample_product with what vqcpc_prior_sample_masked adds, per stage.  The set of
+ *   stage j at (row b, column col) is the words = ceil(K / 32) words at allowed[((b * ldallow + col) * ncb + j) * words] (device
+ *   uint32, [M][ldallow][ncb][words]): a product code's allowed set is the Cartesian product of its digit sets, the one form that
+ *   needs no array of K^ncb entries.  A digit outside its set becomes -inf before the stage's filters; only bits [0, K) count, a
+ *   digit set with none of them restricts nothing; a forced digit (teacher excludes the mask; constraint >= 0) wins.
+ *   Stage log-mass (computed when logmass != NULL and col is in [0, ldmass) with a live window): (m_a - m) + log(s_a) - log(s) of
+ *   the stage's row and set as in vqcpc_prior_sample_masked; stage 0 STORES it in mass_acc[b] (device float scratch [M]), stage
+ *   j >= 1 ADDS it (one fp32 add, ascending j), the last stage writes the sum to logmass[b * ldmass + col].  That number is the sum
+ *   of the per-digit conditional masses ALONG THE EMITTED DIGITS -- the incremental importance weight of the digit-by-digit
+ *   proposal --, NOT the marginal mass of the product set under the model.  logp is unchanged.  With ncb = 1 the kernel is
+ *   vqcpc_prior_sample_masked bit for bit; with allowed == NULL and logmass == NULL, vqcpc_prior_sample_product.
  * vqcpc_prior_window_product: vqcpc_prior_window (commit, load, seeds rule, pos = P, win update) with the product row rule:
  *   prefix_rows[b * P + j] = the merged code of input j clamped to [0, V), or V for the start-of-sentence input (j = 0); x row b
  *   = the vqcpc_product_gather chain over tables [ncb][K][d] of the input of position P, or sos [d] when P = 0.
@@ -982,6 +1014,14 @@ int vqcpc_prior_sample_product(const float* logits, int64_t ldl, int K, int ncb,
                                int32_t* digits, float* logp_acc, const float* h, int64_t ldh, const float* dtab, float* h_next,
                                int64_t ldhn, int64_t* codes, int64_t ldc, int N, const float* tables, int d, float* next_in,
                                int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket, void* stream);
+int vqcpc_prior_sample_product_masked(const float* logits, int64_t ldl, int K, int ncb, int stage, int64_t M, float temperature,
+                                      int top_k, float top_p, const int64_t* seeds, const int64_t* teacher, int64_t ldteach,
+                                      const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
+                                      const uint32_t* allowed, int64_t ldallow, float* logmass, int64_t ldmass, int32_t* digits,
+                                      float* logp_acc, float* mass_acc, const float* h, int64_t ldh, const float* dtab,
+                                      float* h_next, int64_t ldhn, int64_t* codes, int64_t ldc, int N, const float* tables, int d,
+                                      float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket,
+                                      void* stream);
 int vqcpc_prior_window_product(int64_t* seq, int64_t ldseq, int64_t num_tokens, int32_t* win, int advance, int64_t* codes_win,
                                int N, int P, int64_t* prefix_rows, const float* tables, int ncb, int K, const float* sos, int d,
                                float* x, int64_t ldx, const int64_t* seeds_in, int64_t* seeds_out, int32_t* pos, int64_t M,

@@ -11,6 +11,8 @@
 //     workgroup to finish (a ticket in device memory) advances it.
 //   * vqcpc_prior_sample_constrained: the same kernel body under a compile-time flag.  Per (row, sequence column) a code to
 //     emit or < 0 for the draw, and the emitted code's log-probability under the row as the model gave it.
+//   * vqcpc_prior_sample_masked: one more compile-time flag on top of that.  Per (row, sequence column) a set of the codes that
+//     may be drawn, and the log of the probability the unmodified row gives to the set.
 //   * vqcpc_prior_window: ONE workgroup.  Commits the live window's codes into the sequence, loads the next window, the
 //     prefix's table-row indices, the input row of position P, the window's seeds and `pos`.
 // The kernels themselves are in prior_kernels.h, which csrc/product_codes.hip instantiates for product codes.
@@ -59,6 +61,30 @@ int vqcpc_prior_sample_constrained(const float* logits, int64_t ldl, int V, int6
                        logits, ldl, V, temperature, top_k, top_p, seeds, constraint, ldcons, codes, ldc, N, table, d, next_in,
                        ldn, probs, ldp, pos, ticket, logp, ldlogp, win, prior::NoStage{});
     VQ_CHECK_LAUNCH("prior_sample_constrained");
+    return VQCPC_OK;
+}
+
+int vqcpc_prior_sample_masked(const float* logits, int64_t ldl, int V, int64_t M, float temperature, int top_k, float top_p,
+                              const int64_t* seeds, const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp,
+                              const int32_t* win, const uint32_t* allowed, int64_t ldallow, float* logmass, int64_t ldmass,
+                              int64_t* codes, int64_t ldc, int N, const float* table, int64_t table_rows, int d, float* next_in,
+                              int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket, void* stream) {
+    VQ_REQUIRE(V >= 1 && V <= prior::kMaxVocab, "prior_sample_masked: %d codes (1 <= V <= 4096)", V);
+    VQ_REQUIRE(M >= 1 && M <= prior::kMaxRows, "prior_sample_masked: %lld rows (1 <= M <= 64)", (long long)M);
+    VQ_REQUIRE(logits && codes && table && next_in && pos && ticket, "prior_sample_masked: null pointer");
+    VQ_REQUIRE(seeds, "prior_sample_masked: seeds are needed (a position the constraint leaves free is drawn)");
+    VQ_REQUIRE(N >= 1 && N <= prior::kMaxWindow && d >= 1 && d <= prior::kMaxDim,
+               "prior_sample_masked: bad arguments (1 <= N <= 1024, 1 <= d <= 4096)");
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "prior_sample_masked: temperature > 0, top_k >= 0");
+    VQ_REQUIRE(ldl >= V && ldc >= N && ldn >= d && (!constraint || ldcons >= N) && (!logp || ldlogp >= N) &&
+               (!probs || ldp >= V) && table_rows >= V,
+               "prior_sample_masked: bad leading dimensions (ldcons, ldlogp >= N), or a table of fewer than V rows");
+    VQ_REQUIRE((!allowed || ldallow >= N) && (!logmass || ldmass >= N), "prior_sample_masked: bad leading dimensions (ldallow, ldmass >= N)");
+    const prior::MaskedNoStage ps{{}, {allowed, ldallow, logmass, ldmass, nullptr}};
+    hipLaunchKernelGGL((prior::prior_sample_kernel<true, false, true>), dim3((unsigned)M), dim3(prior::kThreads), 0,
+                       (hipStream_t)stream, logits, ldl, V, temperature, top_k, top_p, seeds, constraint, ldcons, codes, ldc, N,
+                       table, d, next_in, ldn, probs, ldp, pos, ticket, logp, ldlogp, win, ps);
+    VQ_CHECK_LAUNCH("prior_sample_masked");
     return VQCPC_OK;
 }
 

@@ -2,7 +2,8 @@
 // vqcpc_prior_sample_constrained, vqcpc_prior_window -- that file's header describes them) and csrc/product_codes.hip (the merged
 // code digit by digit: vqcpc_prior_sample_product, vqcpc_prior_window_product).  ONE kernel body each; the product forms are
 // compile-time flags (PROD), so that a product code of ONE codebook is the merged code's kernel instruction for instruction, and
-// without PROD the kernels are what they were before the flag: none of the added code is instantiated.
+// without PROD the kernels are what they were before the flag: none of the added code is instantiated.  The masked forms
+// (vqcpc_prior_sample_masked, vqcpc_prior_sample_product_masked) are one more flag of the sampler, MASK, under the same rule.
 #pragma once
 
 #include <type_traits>
@@ -115,6 +116,25 @@ struct ProductStage {
 };
 struct NoStage {};
 
+// MASK: what vqcpc_prior_sample_masked / vqcpc_prior_sample_product_masked add (include/vqcpc.h).  The arguments ride behind the
+// stage's in the kernel's LAST parameter, so the three instantiations without MASK keep their argument layout.
+struct MaskArgs {
+    const uint32_t* allowed;       // [M][ldallow][words] (PROD: [M][ldallow][ncb][words]), words = ceil(V / 32), or NULL
+    int64_t ldallow;
+    float* logmass;                // (M, ldmass), or NULL
+    int64_t ldmass;
+    float* mass_acc;               // PROD: [M] scratch, the sum of the earlier stages' log-masses
+};
+struct MaskedNoStage : NoStage {
+    MaskArgs mk;
+};
+struct MaskedProductStage : ProductStage {
+    MaskArgs mk;
+};
+template <bool PROD, bool MASK>
+using SampleExtra = std::conditional_t<MASK, std::conditional_t<PROD, MaskedProductStage, MaskedNoStage>,
+                                       std::conditional_t<PROD, ProductStage, NoStage>>;
+
 // the draw key of stage j: stage 0 draws with the row's seed, as the merged sampler; a later stage with a seed derived from it
 // and j alone (the constant differs from the window rule's, so no (window, stage) pair shares a key with another)
 __device__ __forceinline__ uint64_t stage_seed(uint64_t sd, int stage) {
@@ -134,15 +154,23 @@ __device__ __forceinline__ uint64_t stage_seed(uint64_t sd, int stage) {
 // forms the merged code from the stored digits and its own, writes next_in as the left-to-right sum of the digits' input-table
 // rows (the chain of vqcpc_product_gather), logp from the accumulator, and advances pos.  With ncb = 1 every added statement
 // reduces to the CONS kernel's: the same instructions on the same values.
-template <bool CONS, bool PROD = false>
+// MASK (with CONS; vqcpc_prior_sample_masked, and with PROD vqcpc_prior_sample_product_masked): at the column `col` the row has a
+// set of the codes (PROD: of the stage's digits) that may be drawn.  A thread's 16 codes are half a word of the set, so the set
+// costs one global word per thread and no LDS: a code outside it becomes -inf as the thread takes its codes from LDS, before top-k
+// and top-p.  Only bits [0, V) count and a set without any is no restriction (one block-wide count, uniform); a forced code
+// ignores it.  logmass gets, at logp's column rule, (m_a - m) + log(s_a) - log(s): maximum and exp-sum of the row (the logp
+// code's) and of its allowed codes, summed in the same order -- the full set gives exactly 0.  PROD: stage 0 stores the stage's
+// log-mass in mk.mass_acc, later stages add theirs, the last writes the sum.  Without MASK none of this is instantiated.
+template <bool CONS, bool PROD = false, bool MASK = false>
 __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
     const float* __restrict__ logits, int64_t ldl, int V, float temperature, int top_k, float top_p,
     const int64_t* __restrict__ seeds, const int64_t* __restrict__ teacher, int64_t ldteach, int64_t* __restrict__ codes,
     int64_t ldc, int N, const float* __restrict__ table, int d, float* __restrict__ next_in, int64_t ldn,
     float* __restrict__ probs, int64_t ldp, int32_t* __restrict__ posp, int32_t* __restrict__ ticket,
     float* __restrict__ logp, int64_t ldlogp, const int32_t* __restrict__ win,
-    std::conditional_t<PROD, ProductStage, NoStage> ps) {
+    SampleExtra<PROD, MASK> ps) {
     static_assert(CONS || !PROD, "the product stage builds on the constrained kernel");
+    static_assert(CONS || !MASK, "the mask is addressed at the constraint's column");
     __shared__ float sl[kMaxVocab];                           // the row's (filtered) logits
     __shared__ uint64_t keys[kMaxVocab];                      // top-p: (descending logit, index) sort keys
     __shared__ float redf[kWaves];
@@ -164,6 +192,24 @@ __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
     float l[kPer];
 #pragma unroll
     for (int t = 0; t < kPer; ++t) l[t] = sl[i0 + t];
+    uint32_t ok = 0xFFFFu;                                    // MASK: bit t = code i0 + t may be drawn
+    if constexpr (MASK) {
+        if (ps.mk.allowed && col >= 0 && col < ps.mk.ldallow) {       // uniform: the count below has barriers
+            const int words = (V + 31) >> 5;
+            int64_t set = b * ps.mk.ldallow + col;
+            if constexpr (PROD) set = set * ps.ncb + ps.stage;
+            const int w = tid >> 1;
+            const uint32_t word = w < words ? ps.mk.allowed[set * words + w] : 0u;
+            const int nv = min(max(V - i0, 0), kPer);                 // the thread's codes inside the vocabulary
+            const uint32_t mine = (word >> ((tid & 1) * kPer)) & ((1u << nv) - 1u);
+            if (block_sum_int(mine != 0u, redi) > 0) {                // a set without a code of the vocabulary restricts nothing
+                ok = mine;
+#pragma unroll
+                for (int t = 0; t < kPer; ++t)
+                    if (!((ok >> t) & 1u)) l[t] = ninf;
+            }
+        }
+    }
     // top-k (utils.py:111-114): drop logits < the k-th largest.  Its key is the largest T with #{key >= T} >= k, found bit
     // by bit from the top (integer counts: no order dependence)
     if (top_k > 0 && top_k < V) {
@@ -324,7 +370,10 @@ __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
         for (int k = tid; k < d; k += kThreads) next_in[b * ldn + k] = table[(int64_t)tok * d + k];   // input of position pos + 1
     }
     if constexpr (CONS) {
-        if (logp && col >= 0 && col < ldlogp) {              // uniform: every thread reaches the barriers below or none does
+        const bool wl = logp && col >= 0 && col < ldlogp;
+        bool wm = false;
+        if constexpr (MASK) wm = ps.mk.logmass && col >= 0 && col < ps.mk.ldmass;
+        if (wl || wm) {                                      // uniform: every thread reaches the barriers below or none does
             float raw[kPer], rmx = ninf;
 #pragma unroll
             for (int t = 0; t < kPer; ++t) {
@@ -336,14 +385,40 @@ __global__ __launch_bounds__(kThreads) void prior_sample_kernel(
 #pragma unroll
             for (int t = 0; t < kPer; ++t) rs += raw[t] > ninf ? expf(raw[t] - rmx) : 0.0f;
             rs = block_sum(rs, redf);
-            if constexpr (PROD) {                            // stage 0 stores, later stages add in ascending stage order
-                if (tid == 0) {
-                    const float lp = (logits[b * ldl + tok] - rmx) - logf(rs);
-                    const float acc = ps.stage == 0 ? lp : ps.logp_acc[b] + lp;
-                    if (last) logp[b * ldlogp + col] = acc; else ps.logp_acc[b] = acc;
+            if (wl) {
+                if constexpr (PROD) {                        // stage 0 stores, later stages add in ascending stage order
+                    if (tid == 0) {
+                        const float lp = (logits[b * ldl + tok] - rmx) - logf(rs);
+                        const float acc = ps.stage == 0 ? lp : ps.logp_acc[b] + lp;
+                        if (last) logp[b * ldlogp + col] = acc; else ps.logp_acc[b] = acc;
+                    }
+                } else {
+                    if (tid == 0) logp[b * ldlogp + col] = (logits[b * ldl + tok] - rmx) - logf(rs);
                 }
-            } else {
-                if (tid == 0) logp[b * ldlogp + col] = (logits[b * ldl + tok] - rmx) - logf(rs);
+            }
+            if constexpr (MASK) {
+                if (wm) {                                    // uniform: the same over the allowed codes, in the same order
+                    float amx = ninf;
+#pragma unroll
+                    for (int t = 0; t < kPer; ++t) {
+                        if (!((ok >> t) & 1u)) raw[t] = ninf;
+                        amx = fmaxf(amx, raw[t]);
+                    }
+                    amx = block_max(amx, redf);
+                    float as = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < kPer; ++t) as += raw[t] > ninf ? expf(raw[t] - amx) : 0.0f;
+                    as = block_sum(as, redf);
+                    if (tid == 0) {
+                        const float lm = amx > ninf ? (amx - rmx) + logf(as) - logf(rs) : ninf;
+                        if constexpr (PROD) {
+                            const float acc = ps.stage == 0 ? lm : ps.mk.mass_acc[b] + lm;
+                            if (last) ps.mk.logmass[b * ps.mk.ldmass + col] = acc; else ps.mk.mass_acc[b] = acc;
+                        } else {
+                            ps.mk.logmass[b * ps.mk.ldmass + col] = lm;
+                        }
+                    }
+                }
             }
         }
     }

@@ -130,32 +130,71 @@ int vqcpc_product_gather_bwd(const float* g, int64_t ldg, const int64_t* sorted_
     return VQCPC_OK;
 }
 
+// the checks the two product samplers share; `name` is the entry point's
+static int product_stage_check(const char* name, const float* logits, int64_t ldl, int K, int ncb, int stage, int64_t M,
+                               float temperature, int top_k, float top_p, const int64_t* seeds, const int64_t* teacher,
+                               int64_t ldteach, const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp,
+                               int32_t* digits, float* logp_acc, const float* h, int64_t ldh, const float* dtab, float* h_next,
+                               int64_t ldhn, int64_t* codes, int64_t ldc, int N, const float* tables, int d, float* next_in,
+                               int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket) {
+    VQ_REQUIRE(product_shape_ok(ncb, K, 1), "%s: need 1 <= ncb <= 4, 1 <= K <= 4096, K^ncb + 1 < 2^31", name);
+    VQ_REQUIRE(stage >= 0 && stage < ncb, "%s: stage %d of %d", name, stage, ncb);
+    VQ_REQUIRE(M >= 1 && M <= prior::kMaxRows, "%s: %lld rows (1 <= M <= 64)", name, (long long)M);
+    VQ_REQUIRE(logits && seeds && pos && ticket, "%s: null pointer", name);
+    VQ_REQUIRE(N >= 1 && N <= prior::kMaxWindow && d >= 1 && d <= prior::kMaxDim,
+               "%s: bad arguments (1 <= N <= 1024, 1 <= d <= 4096)", name);
+    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "%s: temperature > 0, top_k >= 0", name);
+    VQ_REQUIRE(!(teacher && (constraint || logp)), "%s: teacher excludes constraint and logp", name);
+    VQ_REQUIRE(ldl >= K && (!teacher || ldteach >= N) && (!constraint || ldcons >= N) && (!logp || ldlogp >= N) && (!probs || ldp >= K),
+               "%s: bad leading dimensions (ldl, ldp >= K; ldteach, ldcons, ldlogp >= N)", name);
+    VQ_REQUIRE(ncb == 1 || (digits && (!logp || logp_acc)), "%s: the digit and log-probability scratch is needed", name);
+    if (stage < ncb - 1)
+        VQ_REQUIRE(h && dtab && h_next && ldh >= d && ldhn >= d, "%s: an earlier stage needs h, dtab, h_next", name);
+    else
+        VQ_REQUIRE(codes && tables && next_in && ldc >= N && ldn >= d, "%s: the last stage needs codes, tables, next_in", name);
+    return VQCPC_OK;
+}
+
 int vqcpc_prior_sample_product(const float* logits, int64_t ldl, int K, int ncb, int stage, int64_t M, float temperature, int top_k,
                                float top_p, const int64_t* seeds, const int64_t* teacher, int64_t ldteach,
                                const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
                                int32_t* digits, float* logp_acc, const float* h, int64_t ldh, const float* dtab, float* h_next,
                                int64_t ldhn, int64_t* codes, int64_t ldc, int N, const float* tables, int d, float* next_in,
                                int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket, void* stream) {
-    VQ_REQUIRE(product_shape_ok(ncb, K, 1), "prior_sample_product: need 1 <= ncb <= 4, 1 <= K <= 4096, K^ncb + 1 < 2^31");
-    VQ_REQUIRE(stage >= 0 && stage < ncb, "prior_sample_product: stage %d of %d", stage, ncb);
-    VQ_REQUIRE(M >= 1 && M <= prior::kMaxRows, "prior_sample_product: %lld rows (1 <= M <= 64)", (long long)M);
-    VQ_REQUIRE(logits && seeds && pos && ticket, "prior_sample_product: null pointer");
-    VQ_REQUIRE(N >= 1 && N <= prior::kMaxWindow && d >= 1 && d <= prior::kMaxDim,
-               "prior_sample_product: bad arguments (1 <= N <= 1024, 1 <= d <= 4096)");
-    VQ_REQUIRE(temperature > 0.0f && top_k >= 0 && top_p == top_p, "prior_sample_product: temperature > 0, top_k >= 0");
-    VQ_REQUIRE(!(teacher && (constraint || logp)), "prior_sample_product: teacher excludes constraint and logp");
-    VQ_REQUIRE(ldl >= K && (!teacher || ldteach >= N) && (!constraint || ldcons >= N) && (!logp || ldlogp >= N) && (!probs || ldp >= K),
-               "prior_sample_product: bad leading dimensions (ldl, ldp >= K; ldteach, ldcons, ldlogp >= N)");
-    VQ_REQUIRE(ncb == 1 || (digits && (!logp || logp_acc)), "prior_sample_product: the digit and log-probability scratch is needed");
-    if (stage < ncb - 1)
-        VQ_REQUIRE(h && dtab && h_next && ldh >= d && ldhn >= d, "prior_sample_product: an earlier stage needs h, dtab, h_next");
-    else
-        VQ_REQUIRE(codes && tables && next_in && ldc >= N && ldn >= d, "prior_sample_product: the last stage needs codes, tables, next_in");
+    const int rc = product_stage_check("prior_sample_product", logits, ldl, K, ncb, stage, M, temperature, top_k, top_p, seeds, teacher,
+                                       ldteach, constraint, ldcons, logp, ldlogp, digits, logp_acc, h, ldh, dtab, h_next, ldhn, codes,
+                                       ldc, N, tables, d, next_in, ldn, probs, ldp, pos, ticket);
+    if (rc != VQCPC_OK) return rc;
     const prior::ProductStage ps{stage, ncb, teacher, ldteach, digits, logp_acc, h, ldh, dtab, h_next, ldhn};
     hipLaunchKernelGGL((prior::prior_sample_kernel<true, true>), dim3((unsigned)M), dim3(prior::kThreads), 0, (hipStream_t)stream,
                        logits, ldl, K, temperature, top_k, top_p, seeds, constraint, ldcons, codes, ldc, N, tables, d, next_in, ldn,
                        probs, ldp, pos, ticket, logp, ldlogp, win, ps);
     VQ_CHECK_LAUNCH("prior_sample_product");
+    return VQCPC_OK;
+}
+
+int vqcpc_prior_sample_product_masked(const float* logits, int64_t ldl, int K, int ncb, int stage, int64_t M, float temperature,
+                                      int top_k, float top_p, const int64_t* seeds, const int64_t* teacher, int64_t ldteach,
+                                      const int64_t* constraint, int64_t ldcons, float* logp, int64_t ldlogp, const int32_t* win,
+                                      const uint32_t* allowed, int64_t ldallow, float* logmass, int64_t ldmass, int32_t* digits,
+                                      float* logp_acc, float* mass_acc, const float* h, int64_t ldh, const float* dtab,
+                                      float* h_next, int64_t ldhn, int64_t* codes, int64_t ldc, int N, const float* tables, int d,
+                                      float* next_in, int64_t ldn, float* probs, int64_t ldp, int32_t* pos, int32_t* ticket,
+                                      void* stream) {
+    const int rc = product_stage_check("prior_sample_product_masked", logits, ldl, K, ncb, stage, M, temperature, top_k, top_p, seeds,
+                                       teacher, ldteach, constraint, ldcons, logp, ldlogp, digits, logp_acc, h, ldh, dtab, h_next,
+                                       ldhn, codes, ldc, N, tables, d, next_in, ldn, probs, ldp, pos, ticket);
+    if (rc != VQCPC_OK) return rc;
+    VQ_REQUIRE(!(teacher && (allowed || logmass)), "prior_sample_product_masked: teacher excludes allowed and logmass");
+    VQ_REQUIRE((!allowed || ldallow >= N) && (!logmass || ldmass >= N),
+               "prior_sample_product_masked: bad leading dimensions (ldallow, ldmass >= N)");
+    VQ_REQUIRE(ncb == 1 || !logmass || mass_acc, "prior_sample_product_masked: the log-mass scratch is needed");
+    const prior::MaskedProductStage ps{{stage, ncb, teacher, ldteach, digits, logp_acc, h, ldh, dtab, h_next, ldhn},
+                                       {allowed, ldallow, logmass, ldmass, mass_acc}};
+    hipLaunchKernelGGL((prior::prior_sample_kernel<true, true, true>), dim3((unsigned)M), dim3(prior::kThreads), 0,
+                       (hipStream_t)stream, logits, ldl, K, temperature, top_k, top_p, seeds, constraint, ldcons, codes, ldc, N,
+                       tables, d, next_in, ldn, probs, ldp, pos, ticket, logp, ldlogp, win, ps);
+    VQ_CHECK_LAUNCH("prior_sample_product_masked");
     return VQCPC_OK;
 }
 

@@ -236,33 +236,6 @@ class IncrementalDecoder(IncrementalStack):
         self._record_attentions(want_attentions)
         self.reset()
 
-    def _particles(self, P, threshold, final, want_attentions):
-        """The particle filter's state: per row the running log-weight `p_lw`, the last normalised weights `p_wn` and
-        ancestors `p_anc`; per group the log-evidence `p_evidence`, the last code's increment `p_pending` and effective sample
-        size `p_ess`; the device flag `p_flag`; and per code of the frame the histories `p_hist_anc` (int32, -1 where no code
-        was finished), `p_hist_wn`, `p_hist_ess` (NaN there).  `p_seeds`: the frame's seeds (the resampling uniform is keyed by
-        the group's first one and the code's chorale index)."""
-        self.particles = None
-        if P is None:
-            return
-        P = int(P)
-        if not 2 <= P <= MAX_ROWS or self.M % P:
-            raise ValueError(f'particles: 2 <= particles <= {MAX_ROWS} dividing the stack\'s {self.M} rows expected, got {P}')
-        if not 0.0 <= float(threshold) <= 1.0:
-            raise ValueError(f'resample_threshold: a share of the particles in [0, 1] expected, got {threshold}')
-        if want_attentions is not None:
-            raise ValueError('particles: attention maps are not moved with a resampled row; want_attentions must be None')
-        if self.teacher is not None:
-            raise ValueError('particles and teacher exclude each other')
-        M, G, codes = self.M, self.M // P, self.frame.codes
-        self.particles, self.p_threshold, self.p_final, self.p_seeds = P, float(threshold), bool(final), self.frame.seeds
-        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
-        self.p_lw, self.p_wn, self.p_anc = torch.empty(M, **f32), torch.empty(M, **f32), torch.empty(M, **i32)
-        self.p_evidence, self.p_pending, self.p_ess = (torch.empty(G, **f32) for _ in range(3))
-        self.p_flag = torch.empty(1, **i32)
-        self.p_hist_anc, self.p_hist_wn = torch.empty(codes, M, **i32), torch.empty(codes, M, **f32)
-        self.p_hist_ess = torch.empty(codes, G, **f32)
-
     def _beam(self, W, want_attentions):
         """The beam's state: per row the hypothesis's total log-probability `b_score` and its last ancestor `b_anc`; the device
         flag `b_flag` (some row moved), the two words `b_bound` = {pos, col} of the last select before its increment, and per
@@ -339,14 +312,6 @@ class IncrementalDecoder(IncrementalStack):
                 for cache in (self.kcache, self.vcache):
                     hip.call('vqcpc_particle_permute_cache', cache, len(self.layers), self.W, self.d, self.pos, anc, flag, M, P)
 
-    def particle_results(self):
-        """After a run: the final normalised weights (G, P), the log-evidence (G,) -- the resampled codes' increments plus the
-        last weights' mx + log(s / P), which a final forced resampling has added already --, and the per-code histories."""
-        G, P = self.M // self.particles, self.particles
-        evidence = self.p_evidence if self.p_final else self.p_evidence + self.p_pending
-        return {'weights': self.p_wn.view(G, P).clone(), 'log_evidence': evidence.clone(), 'ancestors': self.p_hist_anc,
-                'wn': self.p_hist_wn, 'ess': self.p_hist_ess}
-
     def _mask(self, allowed, want_mass):
         """The masked sampler's buffers, addressed like the constrained sampler's: the packed sets are COPIED into a buffer of
         this stack, (M, width, 8) int32, so a captured step or slide reads every window's sets through the window index."""
@@ -421,14 +386,7 @@ class IncrementalDecoder(IncrementalStack):
             self.b_anc.copy_(torch.arange(self.M, dtype=torch.int32))
             for rows, value in ((self.b_flag, 0), (self.b_bound, 0), (self.b_hist, -1)):
                 rows.fill_(value)
-        if self.particles is None:
-            return
-        P = self.particles
-        for rows, value in ((self.p_lw, 0.0), (self.p_wn, 1.0 / P), (self.p_evidence, 0.0), (self.p_pending, 0.0),
-                            (self.p_ess, float(P)), (self.p_flag, 0), (self.p_hist_anc, -1), (self.p_hist_wn, nan),
-                            (self.p_hist_ess, nan)):
-            rows.fill_(value)
-        self.p_anc.copy_(torch.arange(self.M, dtype=torch.int32))
+        self._clear_particles()
 
     # ---- one step: the cross hooks and the sampler ----------------------------------------------------------------------
     def _cross_attention(self, li, lay):

@@ -227,11 +227,18 @@ SIGNATURES = {
     'vqcpc_prior_sample_constrained': (c_int, [c_ptr, c_i64, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
                                                c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr,
                                                c_ptr, c_ptr]),
+    'vqcpc_prior_sample_masked': (c_int, [c_ptr, c_i64, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr,
+                                          c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr,
+                                          c_i64, c_ptr, c_ptr, c_ptr]),
     'vqcpc_prior_window': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr,
                                    c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'vqcpc_prior_sample_product': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64, c_ptr,
                                            c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
                                            c_int, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_sample_product_masked': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_f32, c_int, c_f32, c_ptr, c_ptr, c_i64,
+                                                  c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                                  c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_i64,
+                                                  c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     'vqcpc_prior_window_product': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr,
                                            c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'vqcpc_aligned_expand': (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),

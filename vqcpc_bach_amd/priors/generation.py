@@ -9,7 +9,17 @@ pos + 1 and advances the device counter `pos`.  With given codes or code scores 
 sampler is vqcpc_prior_sample_constrained: the same kernel body, which emits the given code where the constraint holds one
 and writes the emitted code's log-probability under the model's unmodified row (temperature 1, no filter); it addresses both
 at the sequence column win[1] + pos through the device's window index, so the captured step and the captured move below
-serve it unchanged.  The default path launches the plain sampler, exactly as before.
+serve it unchanged.  The default path launches the plain sampler, exactly as before.  With a set of allowed codes per column, its
+mass or particles (`start(allowed=..., want_allowed_mass=..., particles=...)`) the sampler is vqcpc_prior_sample_masked, one more
+compile-time flag on the same body: a code outside the column's set becomes -inf before the filters, and `logmass` receives the
+log of the probability the unmodified row gives to the set; sets and masses are addressed at the same sequence column.
+
+Particles (`start(particles=P)`, csrc/particles.hip with U = 1): the rows are groups of P consecutive rows with their own seeds.
+After every code vqcpc_particle_resample adds the code's forced logp / free logmass to every row's log-weight and, where a group's
+effective sample size fell below the threshold, draws its ancestors; vqcpc_particle_permute_* then moves the ancestors' state --
+the live window's codes, ALL of `seq` (older windows committed the history there, and the next window reloads from it), the logp /
+logmass rows, the next input row and, where a cached step follows, every layer's K/V cache rows [0, pos) -- onto the rows in
+place.  Before a slide or a forward-form step no cache moves: both recompute from the moved codes.
 
 Two regimes, as in the reference (:331-336):
 
@@ -48,7 +58,7 @@ a draw that sits within ~1e-6 of a cumulative-probability boundary can differ be
 import torch
 
 from .. import hip, ops
-from ..transformer.incremental import MAX_ROWS, IncrementalStack, row_seeds
+from ..transformer.incremental import MAX_ROWS, Frame, IncrementalStack, row_seeds
 
 # method='auto': rows from which the forward form replaces the cached step (profiles/generate_prior_perf_log.md: at the PRI
 # shape the head step costs 376 / 1 096 us cached against 735 / 995 us forward at 8 / 32 rows; a stride-1 move 651 / 910 / 1 916 us
@@ -61,8 +71,9 @@ class IncrementalPrior(IncrementalStack):
     """One generation of `batch` <= 64 rows of `prior` (a PriorRelative in eval mode; the caller holds utils.STEP_LOCK).
 
         inc = IncrementalPrior(prior, B)
-        inc.start(num_tokens, seeds, temperature, top_k, top_p)   # constraint=, want_logp=: given codes, code scores
-        codes = inc.run(use_graph, window_stride)                 # (B, num_tokens) int64; inc.logp (B, num_tokens) float32
+        inc.start(num_tokens, seeds, temperature, top_k, top_p)   # constraint=, want_logp=: given codes, code scores;
+                                                                  # allowed=, want_allowed_mass=, particles=: sets, their mass, a filter
+        codes = inc.run(use_graph, window_stride)                 # (B, num_tokens) int64; inc.logp, inc.logmass (B, num_tokens) float32
 
     `start` + `slide` + `step` expose the single launches (teacher forcing, the sampler's input `logits` and its optional
     probability output `probs`) for the tests."""
@@ -78,6 +89,7 @@ class IncrementalPrior(IncrementalStack):
         super().__init__(dev, M, layers, [lay.norm2 for lay in layers], N, pr.d_model)
         self.codes_win = torch.zeros(M, N, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.allowed, self.logmass, self.masked = None, None, False
         self._sos_col = torch.full((M, 1), self.V, dtype=torch.int64, device=dev)    # table row of the start-of-sentence input
         self._init_model()
 
@@ -94,13 +106,23 @@ class IncrementalPrior(IncrementalStack):
         return torch.zeros(self.M, self.V, dtype=torch.float32, device=self.dev)
 
     def start(self, num_tokens, seeds=None, temperature=1.0, top_k=0, top_p=1.0, teacher=None, want_probs=False,
-              constraint=None, want_logp=False):
+              constraint=None, want_logp=False, allowed=None, want_allowed_mass=False, particles=None, resample_threshold=0.5,
+              final_resample=True):
         """A new generation of `num_tokens` >= N codes per row.  teacher: (M, N) codes of the live window to force instead
         of drawing (single-step use); want_probs: keep the filtered probabilities of the last step in `probs` (M, V).
         constraint: (M, num_tokens) int64 in sequence coordinates, a code >= 0 is emitted at its column, < 0 leaves the draw
         free; want_logp: keep every emitted code's log-probability under the unfiltered row at temperature 1 in `logp`
         (M, num_tokens) float32 (NaN where no step has written yet).  Either one switches the sampler to
-        vqcpc_prior_sample_constrained, in both step forms."""
+        vqcpc_prior_sample_constrained, in both step forms.
+        allowed: packed sets (code_sets.pack_sets) int32 (M, num_tokens, words) -- a product prior: (M, num_tokens, ncb, words) --,
+        per (row, sequence column) the codes (digits) that may be drawn; the caller has checked that no set is empty and that
+        no forced code lies outside its set.  want_allowed_mass: keep in `logmass` (M, num_tokens) float32 the log of the
+        probability the unmodified row gives to the column's set (0 where nothing is restricted; a product prior: the sum of
+        the stages' conditional masses along the emitted digits).  particles: None, or P in [2, 64] dividing M: the rows are
+        M / P groups of P particles, resampled after every code (`_resample`); logp / logmass are then kept whenever a
+        constraint / sets are given.  resample_threshold, final_resample: as in `IncrementalDecoder.start`.  Any of the three
+        switches the sampler to vqcpc_prior_sample_masked (vqcpc_prior_sample_product_masked), in both step forms.  teacher
+        excludes all of them, want_probs excludes particles."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         if num_tokens < self.N:
@@ -110,17 +132,46 @@ class IncrementalPrior(IncrementalStack):
         if seeds is not None:
             self.row_seeds.copy_(row_seeds(seeds, self.M))
         self.teacher = None if teacher is None else teacher.to(self.dev, torch.int64).reshape(self.M, self.N).contiguous()
-        self._constrain(constraint, want_logp, self.nt)
+        if particles is not None and want_probs:
+            raise ValueError('particles and want_probs exclude each other (the probabilities are not moved with a resampled row)')
+        if particles is not None and self.d % 4:
+            raise ValueError(f'particles: d_model = {self.d}, a multiple of 4 is needed to move the K/V cache rows')
+        self.frame = Frame(self.nt, self.win, 1, self.nt, self.row_seeds)
+        self._particles(particles, resample_threshold, final_resample, None)
+        scored = particles is not None                        # the weights are the forced codes' logp and the sets' mass
+        self._constrain(constraint, want_logp or (scored and constraint is not None), self.nt)
+        self._mask(allowed, want_allowed_mass or (scored and allowed is not None))
         self.probs = self._probs_buffer() if want_probs else None
         self.seq = torch.zeros(self.M, self.nt, dtype=torch.int64, device=self.dev)
         self.reset()
 
+    def _set_shape(self):
+        """The shape of the packed sets of one generation."""
+        return (self.M, self.nt, (self.V + 31) // 32)
+
+    def _mask(self, allowed, want_mass):
+        """The masked sampler's buffers, addressed like the constrained sampler's: the packed sets are COPIED into a buffer of
+        this stack before any warm-up launch, so a captured step or move reads every window's sets through the window index."""
+        if (allowed is not None or want_mass) and self.teacher is not None:
+            raise ValueError('allowed / want_allowed_mass and teacher exclude each other')
+        self.allowed = None
+        if allowed is not None:
+            if tuple(allowed.shape) != self._set_shape() or allowed.dtype != torch.int32:
+                raise ValueError(f'allowed: packed sets {self._set_shape()} int32 expected, got {tuple(allowed.shape)} '
+                                 f'{allowed.dtype}')
+            self.allowed = torch.empty(self._set_shape(), dtype=torch.int32, device=self.dev)
+            self.allowed.copy_(allowed)
+        self.logmass = torch.empty(self.M, self.nt, dtype=torch.float32, device=self.dev) if want_mass else None
+        self.masked = allowed is not None or bool(want_mass) or self.particles is not None
+
     def reset(self):
-        """Back to the head regime's first position; the sequence is cleared, and so is every log-probability (NaN: a run
-        writes each column once, so none stays)."""
+        """Back to the head regime's first position; the sequence is cleared, and so is every log-probability and log-mass (NaN:
+        a run writes each column once, so none stays) and the particle filter's state."""
         self.seq.zero_()
-        if self.logp is not None:
-            self.logp.fill_(float('nan'))
+        for rows in (self.logp, self.logmass):
+            if rows is not None:
+                rows.fill_(float('nan'))
+        self._clear_particles()
         self.codes_win.zero_()
         self.ticket.zero_()
         self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
@@ -129,6 +180,12 @@ class IncrementalPrior(IncrementalStack):
     # ---- one step: the sampler, and the forward form ---------------------------------------------------------------------
     def _sample(self):
         N = self.N
+        if self.masked:
+            hip.call('vqcpc_prior_sample_masked', self.logits, self.V, self.V, self.M, self.temperature, self.top_k, self.top_p,
+                     self.seeds, self.constraint, self.nt, self.logp, self.nt, self.win, self.allowed, self.nt, self.logmass,
+                     self.nt, self.codes_win, N, N, self.table, self.table.shape[0], self.d, self.x, self.d, self.probs, self.V,
+                     self.pos, self.ticket)
+            return
         if self.constrained:
             hip.call('vqcpc_prior_sample_constrained', self.logits, self.V, self.V, self.M, self.temperature, self.top_k,
                      self.top_p, self.seeds, self.constraint, self.nt, self.logp, self.nt, self.win, self.codes_win, N, N,
@@ -185,6 +242,37 @@ class IncrementalPrior(IncrementalStack):
         self.win[0:1].fill_(-1)
         self._window(0, 0)
 
+    # ---- particles -----------------------------------------------------------------------------------------------------
+    def _resample(self, last, move_cache):
+        """After a code (one step: U = 1): the weight update and the resampling decision (vqcpc_particle_resample, the forced
+        code's logp or the set's logmass at the column win[1] + pos - 1), then the group's generation state follows the
+        ancestors in place (vqcpc_particle_permute_*): the live window's codes [0, pos), ALL of `seq` -- older windows committed
+        the history before the live window there, and the next vqcpc_prior_window reloads from it --, the logp / logmass rows,
+        the next input row and, with move_cache -- a cached step follows; a slide or a forward-form step recomputes from the
+        moved codes --, every layer's K and V cache rows [0, pos).  The seeds stay with their slots, so copies of one ancestor
+        diverge.  The launches are issued eagerly between the step replays of a graphed run, as the decoder's are.  last: the
+        code is the generation's last one -- a forced resampling (`final_resample`), or the weight update alone."""
+        P, M, nt, N = self.particles, self.M, self.nt, self.N
+        force = bool(last and self.p_final)
+        threshold = 0.0 if last and not self.p_final else self.p_threshold
+        hip.call('vqcpc_particle_resample', self.p_lw, self.p_evidence, self.p_pending, self.p_seeds, self.constraint, nt,
+                 self.logp if self.constraint is not None else None, nt, self.logmass if self.allowed is not None else None, nt,
+                 self.pos, self.win, 1, threshold, int(force), self.p_anc, self.p_wn, self.p_ess, self.p_flag,
+                 self.p_hist_anc, self.p_hist_wn, self.p_hist_ess, self.p_hist_anc.shape[0], M, P)
+        if threshold == 0.0 and not force:
+            return
+        anc, flag = self.p_anc, self.p_flag
+        hip.call('vqcpc_particle_permute_i64', self.codes_win, N, N, self.pos, anc, flag, M, P)
+        hip.call('vqcpc_particle_permute_i64', self.seq, nt, nt, None, anc, flag, M, P)
+        for rows in (self.logp, self.logmass):
+            if rows is not None:
+                hip.call('vqcpc_particle_permute_f32', rows, nt, nt, None, anc, flag, M, P)
+        if not last:
+            hip.call('vqcpc_particle_permute_f32', self.x, self.d, self.d, None, anc, flag, M, P)
+            if move_cache:
+                for cache in (self.kcache, self.vcache):
+                    hip.call('vqcpc_particle_permute_cache', cache, len(self.layers), self.W, self.d, self.pos, anc, flag, M, P)
+
     # ---- a whole generation --------------------------------------------------------------------------------------------
     def _forms(self, method, stride):
         if method not in ('auto', 'cached', 'forward'):
@@ -224,28 +312,38 @@ class IncrementalPrior(IncrementalStack):
         if warmed:
             self.reset()                          # the warm-up launches drew and committed codes: start again
         step = step_graph.replay if step_graph is not None else self.step
-        if head_form == 'forward':
-            for p in range(N):
+        done = 0                                  # codes emitted; with particles every code ends in `_resample`
+
+        def emitted(cached_step_follows):
+            nonlocal done
+            done += 1
+            if self.particles is not None:
+                self._resample(done == nt, cached_step_follows)
+        for p in range(N):
+            if head_form == 'forward':
                 self.step_forward(p)
-        else:
-            for _ in range(N):
+            else:
                 step()
+            emitted(head_form == 'cached' and p < N - 1)
         for i in range(n_full):
             if slide_form == 'forward':
                 if i == 0:
                     self.win[0:1].fill_(1)        # afterwards the window kernel advances the device's index by one per move
                 self._move_forward()
+                emitted(False)
             elif slide_graph is not None and i >= 1:
                 slide_graph.replay()              # the device's window index is (i + 1) * k already
             else:
                 self.slide((i + 1) * k, N - k, advance=k)
             if slide_form == 'cached':
-                for _ in range(k):
+                for j in range(k):
                     step()
+                    emitted(j < k - 1)
         if rem:
             self.slide(nt - N, N - rem, advance=0)
-            for _ in range(rem):
+            for j in range(rem):
                 step()
+                emitted(j < rem - 1)
         self.commit()
         torch.cuda.current_stream(self.dev).synchronize()
         del step_graph, slide_graph
@@ -284,6 +382,13 @@ class IncrementalProductPrior(IncrementalPrior):
     def _probs_buffer(self):
         return torch.zeros(self.ncb, self.M, self.K, dtype=torch.float32, device=self.dev)
 
+    def _set_shape(self):
+        return (self.M, self.nt, self.ncb, (self.K + 31) // 32)
+
+    def _mask(self, allowed, want_mass):
+        super()._mask(allowed, want_mass)
+        self.mass_acc = torch.zeros(self.M, dtype=torch.float32, device=self.dev) if self.masked else None
+
     def _input_rows(self, idx):
         return ops.ProductEmbeddingFn.apply(self.tables, self.sos, idx)
 
@@ -296,6 +401,13 @@ class IncrementalProductPrior(IncrementalPrior):
                 w, b = self.heads[j]
                 hip.call('vqcpc_decode_linear', h, d, None, w, b, None, 0, self.stage_logits[j], K, M, K, d, 0)
             last = j == ncb - 1
+            if self.masked:
+                hip.call('vqcpc_prior_sample_product_masked', self.stage_logits[j], K, K, ncb, j, M, self.temperature, self.top_k,
+                         self.top_p, self.seeds, self.teacher, N, self.constraint, self.nt, self.logp, self.nt, self.win,
+                         self.allowed, self.nt, self.logmass, self.nt, self.digits, self.logp_acc, self.mass_acc,
+                         None if last else h, ldh, None if last else self.dtab, None if last else self.hs[j], d, self.codes_win, N,
+                         N, self.tables, d, self.x, d, None if self.probs is None else self.probs[j], K, self.pos, self.ticket)
+                continue
             hip.call('vqcpc_prior_sample_product', self.stage_logits[j], K, K, ncb, j, M, self.temperature, self.top_k, self.top_p,
                      self.seeds, self.teacher, N, self.constraint, self.nt, self.logp, self.nt, self.win, self.digits,
                      self.logp_acc, None if last else h, ldh, None if last else self.dtab, None if last else self.hs[j], d,

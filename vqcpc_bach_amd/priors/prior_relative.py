@@ -33,6 +33,12 @@ before).  `score_codes` is the everything-forced call; `continue_tokens` encodes
 from its codes and has the decoder write tokens around the given ones.  `score_codes(method='windows')` computes the same scores
 without generating -- every window of every piece is a row of one batched teacher-forced forward (priors/scoring.py,
 vqcpc_prior_score) -- and `score_chorale` adds the decoder's token scores to them: the nats the pipeline spends on a piece.
+ALLOWED CODES AND PARTICLES: `generate_codes(allowed=..., return_allowed_mass=True)` restricts every column to a set of codes (a
+product prior: to a Cartesian product of digit sets; priors/code_sets.py builds them) and returns the log of the probability the
+model gives to each set; `particles=P` runs P rows per requested plan, weighs them by the forced codes' logp and the sets' mass and
+resamples after every code, so that codes forced AFTER free ones select the plans that lead to them (vqcpc_prior_sample_masked,
+vqcpc_prior_sample_product_masked; csrc/particles.hip).  `generate` and `continue_tokens` pass them through as `code_allowed`,
+`code_particles`, and `continue_tokens(code_constraint=...)` fixes codes after the opening, e.g. a close.
 
 PRODUCT CODES: `code_model='product'` (ours, `prior_kwargs['code_model']`; default 'merged' = the reference's model, one symbol
 of a vocabulary of V = K**ncb, which `generate_codes` samples up to V = 4096).  A merged code is ncb digits c_j = (code // K**j)
@@ -60,7 +66,7 @@ from ..training import FlatTraining
 from ..transformer.transformer_custom import TransformerEncoderCustom, TransformerEncoderLayerCustom
 from ..utils import STEP_LOCK
 
-MAX_SAMPLED_VOCAB = 4096         # vqcpc_prior_sample / vqcpc_prior_sample_constrained: codes per step of `generate_codes`
+MAX_SAMPLED_VOCAB = 4096         # vqcpc_prior_sample / _constrained / _masked: codes per step of `generate_codes`
 
 
 class PriorRelative(FlatTraining, nn.Module):
@@ -259,7 +265,8 @@ class PriorRelative(FlatTraining, nn.Module):
         return constraint.to(self.sos.device).expand(rows, num_tokens).contiguous()
 
     def generate_codes(self, num_tokens, temperature=1.0, num_generated_codes=1, top_k=0, top_p=1.0, seed=None, use_graph=True,
-                       window_stride=1, method='auto', constraint=None, return_logp=False):
+                       window_stride=1, method='auto', constraint=None, return_logp=False, allowed=None,
+                       return_allowed_mass=False, particles=None, resample_threshold=0.5, return_particles=False):
         """Samples `num_generated_codes` sequences of `num_tokens` >= N merged codes (:315-353).  Code e < N comes from the
         first window (one cached step per code); code e >= N from the window that ends at e, as in the reference, when
         `window_stride` = 1.  window_stride = k > 1 (an opt-in of this package, NOT the reference's model context) moves the
@@ -277,8 +284,28 @@ class PriorRelative(FlatTraining, nn.Module):
         temperature 1, no filter, whatever `temperature` is.
         code_model 'product': a code is drawn digit by digit; temperature, top_k and top_p filter EACH DIGIT'S conditional
         distribution over its K values (not the joint distribution over the K**ncb codes), a forced code forces every digit,
-        and logp is the sum of the ncb digits' log-probabilities.  Any K**ncb < 2**31 is sampled."""
-        from ..transformer.incremental import generate_in_chunks, row_seeds
+        and logp is the sum of the ncb digits' log-probabilities.  Any K**ncb < 2**31 is sampled.
+        allowed: bool (num_generated_codes | 1, num_tokens, V) [code_model 'product': (num_generated_codes | 1, num_tokens, ncb, K),
+        a digit set per codebook: the column's allowed codes are their Cartesian product]; True = the code may be drawn at that
+        column (priors/code_sets.py builds such tensors from {column: codes}).  A code outside the set gets probability 0 BEFORE
+        top_k / top_p, which then choose among the allowed codes; a forced code must lie in its own set.  ValueError, from one
+        check per call, naming the first (row, column[, codebook]) whose set is empty or forbids its forced code.
+        return_allowed_mass=True -> `allowed_mass` after codes and logp, float32 of the codes' shape: the log of the probability
+        the model's unmodified distribution gives to the column's set (0 where nothing is restricted; 'product': the sum of the
+        per-digit conditional masses along the emitted digits, the importance weight of the digit-by-digit proposal, not the
+        marginal mass of the product set).
+        particles=P in [2, 64]: every requested row is a group of P rows of the stack with the seeds row_seeds(seed, rows * P),
+        group g at [g P, (g + 1) P).  After every code a row's weight grows by the logp of a forced code / the allowed_mass of a
+        restricted one, and a group whose effective sample size falls below resample_threshold * P is resampled (systematic;
+        csrc/particles.hip): forced codes that come AFTER free ones then select the prefixes that lead to them.  The result has
+        the shapes of a call without the keyword: each group's first row after a final forced resampling.  return_particles=True
+        skips that and returns all rows * P rows followed by a dict: 'weights' (rows, P) the final normalised weights,
+        'log_evidence' (rows,), and per code 'ancestors' (num_tokens, rows * P), 'wn', 'ess' -- `Decoder.generate_from_codes`'
+        contract.  Results come in the order (codes[, logp][, allowed_mass][, particles]).  Any of the keywords switches the
+        step's sampler to vqcpc_prior_sample_masked (vqcpc_prior_sample_product_masked); without them every launch is what it was.
+        Out of scope: sets for `score_codes`, beam search over codes, relational rules on codes, and sets over the K**ncb codes
+        of a product prior that are not a product of digit sets."""
+        from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalPrior, IncrementalProductPrior
         if self.code_model == 'product':
             IncrementalPrior = IncrementalProductPrior
@@ -297,19 +324,58 @@ class PriorRelative(FlatTraining, nn.Module):
             raise ValueError('temperature must be > 0')
         if constraint is not None:
             constraint = self._code_constraint(constraint, B, num_tokens)
-        seeds = row_seeds(seed, B)
-        logp = torch.empty(B, num_tokens, dtype=torch.float32, device=self.sos.device) if return_logp else None
+        # with `particles` every requested row is a group of P rows of the stack (P = 1 without)
+        from ..decoders.decoder import Decoder
+        P = Decoder._particle_count(particles, resample_threshold, return_particles, None)
+        packed = None if allowed is None else self._code_sets(allowed, B, num_tokens, constraint)       # (B | 1, ...)
+        rows_all = B * P
+        if P > 1 and constraint is not None:
+            constraint = constraint.repeat_interleave(P, dim=0)
+        seeds = row_seeds(seed, rows_all)
+        dev = self.sos.device
+        kept = {'logp': return_logp, 'logmass': return_allowed_mass}
+        records = {key: torch.empty(rows_all, num_tokens, dtype=torch.float32, device=dev) for key, on in kept.items() if on}
+        filt = {} if particles is not None else None
 
         def chunk(n, rows):
             inc = IncrementalPrior(self, n)
+            sets = None
+            if packed is not None:                            # row r of the stack belongs to requested row r // P
+                idx = torch.arange(rows.start, rows.stop, device=dev) // P if packed.shape[0] > 1 else \
+                    torch.zeros(n, dtype=torch.int64, device=dev)
+                sets = packed[idx]
             inc.start(num_tokens, seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p,
-                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp)
+                      constraint=None if constraint is None else constraint[rows], want_logp=return_logp, allowed=sets,
+                      want_allowed_mass=return_allowed_mass, particles=None if particles is None else P,
+                      resample_threshold=resample_threshold, final_resample=not return_particles)
             codes = inc.run(use_graph=use_graph, window_stride=stride, method=method)
-            if return_logp:
-                logp[rows] = inc.logp
+            for key, buf in records.items():
+                buf[rows] = getattr(inc, key)
+            if filt is not None:
+                Decoder._keep_particle_results(filt, inc.particle_results(), rows.start)
             return codes
-        codes = generate_in_chunks(self, B, num_tokens, chunk)
-        return (codes, logp) if return_logp else codes
+        codes = generate_in_chunks(self, rows_all, num_tokens, chunk, MAX_ROWS // P * P)             # whole groups
+        keep = slice(None) if P == 1 or return_particles else slice(0, rows_all, P)                 # a group's first row
+        out = [codes[keep]] + [records[key][keep] for key in ('logp', 'logmass') if key in records]
+        if return_particles:
+            out.append(Decoder._join_particle_results(filt))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def _code_sets(self, allowed, rows, num_tokens, constraint):
+        """A public `allowed` -> packed sets int32 (rows | 1, num_tokens, words) [code_model 'product': (rows | 1, num_tokens, ncb,
+        words)] on the device, after the one host check of the call (priors/code_sets.py)."""
+        from .code_sets import check_sets, pack_sets
+        allowed = torch.as_tensor(allowed)
+        V = self.num_tokens_per_channel[0]
+        tail = (self.num_codebooks, self.codebook_size) if self.code_model == 'product' else (V,)
+        shape = tuple(allowed.shape)
+        if allowed.dtype != torch.bool or len(shape) != 2 + len(tail) or shape[0] not in (1, rows) or \
+                shape[1:] != (num_tokens,) + tail:
+            raise ValueError(f'allowed: bool ({rows} | 1, {num_tokens}, {", ".join(map(str, tail))}) expected, got {shape} '
+                             f'{allowed.dtype}')
+        allowed = allowed.to(self.sos.device)
+        check_sets(allowed, constraint)
+        return pack_sets(allowed)
 
     @staticmethod
     def score_window_plan(num_tokens, N, window_stride=1):
@@ -368,16 +434,19 @@ class PriorRelative(FlatTraining, nn.Module):
         return score_chorale(self, x, decoder, return_details, window_rows, decoder_window_rows)
 
     def generate(self, num_tokens, decoder, temperature=1.0, num_generated_codes=1, num_decodings_per_generating_code=1,
-                 decoder_temperature=None, seed=None, code_constraint=None, return_logp=False, **decoder_sampling):
+                 decoder_temperature=None, seed=None, code_constraint=None, return_logp=False, code_allowed=None,
+                 code_particles=None, code_resample_threshold=0.5, **decoder_sampling):
         """:308-368: `generate_codes`, then `decoder.generate_from_code_long` on them.  `temperature` goes to BOTH, as in the
         reference (where it sharpens the prior and flattens the decoder as it grows, module docstring);
         decoder_temperature overrides the decoder's.  decoder_sampling: top_k, top_p, pad, start, ... of
         `generate_from_code_long`.  -> (codes (B, num_tokens), tokens (B * decodings, events, channels)) int64 tensors on the
         device; score objects and XML files need music21 and are out of scope.
         code_constraint / return_logp: `generate_codes`' constraint / return_logp; with return_logp=True the result is
-        (codes, tokens, code_logp (B, num_tokens) float32)."""
+        (codes, tokens, code_logp (B, num_tokens) float32).  code_allowed / code_particles / code_resample_threshold:
+        `generate_codes`' allowed / particles / resample_threshold (each group's surviving row goes to the decoder)."""
         out = self.generate_codes(num_tokens, temperature=temperature, num_generated_codes=num_generated_codes, seed=seed,
-                                  constraint=code_constraint, return_logp=return_logp)
+                                  constraint=code_constraint, return_logp=return_logp, allowed=code_allowed,
+                                  particles=code_particles, resample_threshold=code_resample_threshold)
         codes, code_logp = out if return_logp else (out, None)
         tokens = decoder.generate_from_code_long(encoding_indices=codes,
                                                  temperature=temperature if decoder_temperature is None else decoder_temperature,
@@ -385,7 +454,8 @@ class PriorRelative(FlatTraining, nn.Module):
         return (codes, tokens, code_logp) if return_logp else (codes, tokens)
 
     def continue_tokens(self, x, num_new_codes, decoder, temperature=1.0, decoder_temperature=None, num_continuations=1,
-                        seed=None, return_logp=False, **decoder_sampling):
+                        seed=None, return_logp=False, code_constraint=None, code_allowed=None, code_particles=None,
+                        code_resample_threshold=0.5, **decoder_sampling):
         """"Here are the first bars, go on": x (1, events, channels) tokens of a piece's opening, events a multiple of the
         events per code.  The opening is framed at the front as `Decoder.reharmonise_tokens` frames a chorale (one model-sized
         PAD ... START chunk, then x; no END completion), encoded by this prior's frozen encoder in model-sized chunks and the
@@ -396,6 +466,10 @@ class PriorRelative(FlatTraining, nn.Module):
         -> (codes (num_continuations, L + num_new_codes), tokens (num_continuations, x's events + num_new_codes * events per
         code, channels)): events [0, x.shape[1]) of every token row equal x.  return_logp=True -> (codes, tokens, code_logp,
         token_logp), the scores of `generate_codes` and of `generate_from_code_long` (each at temperature 1, unfiltered).
+        code_constraint: (1 | num_continuations, L + num_new_codes) int64, -1 = free, over ALL columns: the given opening is merged
+        into it, so "continue this opening and close on that cadence" is one call; a value >= 0 inside the opening that differs
+        from the encoded code is a ValueError.  code_allowed: `generate_codes`' allowed over the same columns; code_particles /
+        code_resample_threshold: its particles / resample_threshold, which make the free codes lead to the forced close.
         Needs the decoder's dataset's START / XX symbols."""
         if decoder.continuous_source:
             raise NotImplementedError('a prior over continuous (NoQuantization) codes does not exist')
@@ -428,10 +502,18 @@ class PriorRelative(FlatTraining, nn.Module):
         if total < max(self.num_tokens, decoder.num_tokens_source):
             raise ValueError(f'continue_tokens: {L} given + {num_new_codes} new codes, fewer than one model window '
                              f'({max(self.num_tokens, decoder.num_tokens_source)})')
-        constraint = torch.full((1, total), -1, dtype=torch.int64, device=prefix.device)
+        if code_constraint is None:
+            constraint = torch.full((1, total), -1, dtype=torch.int64, device=prefix.device)
+        else:
+            constraint = self._code_constraint(code_constraint, int(num_continuations), total).clone()
+            given = constraint[:, :L]
+            if bool(((given >= 0) & (given != prefix)).any()):
+                raise ValueError("continue_tokens: code_constraint forces a code inside the opening that differs from the opening's "
+                                 'own encoded code')
         constraint[:, :L] = prefix
         out = self.generate_codes(total, temperature=temperature, num_generated_codes=num_continuations, seed=seed,
-                                  constraint=constraint, return_logp=return_logp)
+                                  constraint=constraint, return_logp=return_logp, allowed=code_allowed, particles=code_particles,
+                                  resample_threshold=code_resample_threshold)
         codes, code_logp = out if return_logp else (out, None)
         token_constraint = torch.full((int(num_continuations), total * epc, nc), -1, dtype=torch.int64)
         token_constraint[:, E:E + x.shape[1]] = x

@@ -22,7 +22,8 @@ Rows are independent and every kernel reduces in an order that does not depend o
 not depend on which other rows share the call (given the same inputs and seed).
 
 The stack also owns what both generators' constrained samplers need (`_constrain`: the constraint, `logp`, the `constrained`
-flag) and the coordinate frame of a generation's per-position buffers (`Frame`), which the recorded attention launch reads."""
+flag), the particle filter's state (`_particles`, `_clear_particles`, `particle_results`; each generator has its own `_resample`,
+which knows what of its state follows a resampled row) and the coordinate frame of a generation's per-position buffers (`Frame`), which the recorded attention launch reads."""
 import collections
 
 import torch
@@ -114,6 +115,7 @@ class IncrementalStack:
         self.self_probs, self._attn_slot = None, {}           # attention maps: off (a subclass's `start` may turn them on)
         self.frame = None                                     # the `Frame` of the generation's option buffers
         self.constraint, self.logp, self.constrained = None, None, False
+        self.particles = None                                 # group size P, or None: plain rows (`_particles`)
         self._cross, self._prefix_cross = IncrementalStack._no_cross, IncrementalStack._no_prefix_cross
 
     def _constrain(self, constraint, want_logp, width):
@@ -129,6 +131,53 @@ class IncrementalStack:
         self.constraint = constraint
         self.logp = torch.empty(self.M, width, dtype=torch.float32, device=self.dev) if want_logp else None
         self.constrained = constraint is not None or bool(want_logp)
+
+    # ---- particles (csrc/particles.hip): the state both generators' filters keep -----------------------------------------
+    def _particles(self, P, threshold, final, want_attentions):
+        """The particle filter's state: per row the running log-weight `p_lw`, the last normalised weights `p_wn` and
+        ancestors `p_anc`; per group the log-evidence `p_evidence`, the last code's increment `p_pending` and effective sample
+        size `p_ess`; the device flag `p_flag`; and per code of the frame the histories `p_hist_anc` (int32, -1 where no code
+        was finished), `p_hist_wn`, `p_hist_ess` (NaN there).  `p_seeds`: the frame's seeds (the resampling uniform is keyed by
+        the group's first one and the code's chorale index)."""
+        self.particles = None
+        if P is None:
+            return
+        P = int(P)
+        if not 2 <= P <= MAX_ROWS or self.M % P:
+            raise ValueError(f'particles: 2 <= particles <= {MAX_ROWS} dividing the stack\'s {self.M} rows expected, got {P}')
+        if not 0.0 <= float(threshold) <= 1.0:
+            raise ValueError(f'resample_threshold: a share of the particles in [0, 1] expected, got {threshold}')
+        if want_attentions is not None:
+            raise ValueError('particles: attention maps are not moved with a resampled row; want_attentions must be None')
+        if self.teacher is not None:
+            raise ValueError('particles and teacher exclude each other')
+        M, G, codes = self.M, self.M // P, self.frame.codes
+        self.particles, self.p_threshold, self.p_final, self.p_seeds = P, float(threshold), bool(final), self.frame.seeds
+        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
+        self.p_lw, self.p_wn, self.p_anc = torch.empty(M, **f32), torch.empty(M, **f32), torch.empty(M, **i32)
+        self.p_evidence, self.p_pending, self.p_ess = (torch.empty(G, **f32) for _ in range(3))
+        self.p_flag = torch.empty(1, **i32)
+        self.p_hist_anc, self.p_hist_wn = torch.empty(codes, M, **i32), torch.empty(codes, M, **f32)
+        self.p_hist_ess = torch.empty(codes, G, **f32)
+
+    def _clear_particles(self):
+        """The filter before its first code (a warm-up step of a capture writes into these buffers, so a run clears them again)."""
+        if self.particles is None:
+            return
+        P, nan = self.particles, float('nan')
+        for rows, value in ((self.p_lw, 0.0), (self.p_wn, 1.0 / P), (self.p_evidence, 0.0), (self.p_pending, 0.0),
+                            (self.p_ess, float(P)), (self.p_flag, 0), (self.p_hist_anc, -1), (self.p_hist_wn, nan),
+                            (self.p_hist_ess, nan)):
+            rows.fill_(value)
+        self.p_anc.copy_(torch.arange(self.M, dtype=torch.int32))
+
+    def particle_results(self):
+        """After a run: the final normalised weights (G, P), the log-evidence (G,) -- the resampled codes' increments plus the
+        last weights' mx + log(s / P), which a final forced resampling has added already --, and the per-code histories."""
+        G, P = self.M // self.particles, self.particles
+        evidence = self.p_evidence if self.p_final else self.p_evidence + self.p_pending
+        return {'weights': self.p_wn.view(G, P).clone(), 'log_evidence': evidence.clone(), 'ancestors': self.p_hist_anc,
+                'wn': self.p_hist_wn, 'ess': self.p_hist_ess}
 
     # ---- one step ----------------------------------------------------------------------------------------------------
     def _ln(self, s, norm, out):
