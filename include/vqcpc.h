@@ -1244,6 +1244,87 @@ int vqcpc_decode_beam_select(const float* logits, int64_t ldl, const int32_t* vo
                              int32_t* pos, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Beam search over the prior's code plans (csrc/prior_beam.hip, priors/generation.py `beam=W`; the rule is restated in numpy in
+ * tests/prior_beam_reference.py).  Rows, groups and slots as for vqcpc_decode_beam_select, whose rule this is on a vocabulary of up
+ * to 4096 merged codes.  Two launches take the sampler's place at the end of a step:
+ * vqcpc_prior_beam_expand: one workgroup per row (256 threads, thread t owns codes 16t .. 16t + 15, vqcpc_prior_sample's layout).
+ *   p = pos[0], column col = p (win == NULL) or win[1] + p, -1 when win[1] < 0 -- the constrained sampler's rule.  p outside
+ *   [0, N): nothing is written.
+ *   Row log-probability: lp(b, v) = (logits[b][v] - m_b) - logf(s_b), m_b / s_b the row maximum and exp-sum over the V columns,
+ *   formed exactly as vqcpc_prior_sample_constrained forms logp (the raw row, thread-ascending sums, the same block reductions):
+ *   lp(b, v) has the bits that sampler writes for row b emitting v.  row_mass[b] = (m_a - m) + logf(s_a) - logf(s) over the row's
+ *   set allowed[b][col] ([M][ldallow][ceil(V / 32)] words), as vqcpc_prior_sample_masked forms logmass (0 without a set).
+ *   Candidates of row b: at a forced column (constraint[b][col] >= 0) the one code, clamped to [0, V), the set ignored; at a free
+ *   one the codes of [0, V) in the set (no buffer, or no bit inside the vocabulary: all of them).  cand(b, v) = score[b] + lp(b, v),
+ *   one fp32 add; NaN counts as -inf; live means cand > -inf.
+ *   Written: scratch_cand / scratch_code / scratch_lp (M, W): the row's min(W, live) best candidates in the order cand
+ *   descending, then code ascending, the rest -inf / 0 / 0; row_mass (M); row_low (M) the row's lowest candidate code (0 without
+ *   one) and row_lowlp (M) its lp.  cand_out (optional, [M][4096]): every row's cand as the selection used it, -inf for a
+ *   non-candidate.
+ * vqcpc_prior_beam_select: ONE workgroup for all groups, reading what the expansion wrote.  p and col as above; p outside [0, N):
+ *   flag[0] = 0 and nothing else happens.  Per group the live candidates are ordered by cand descending, then row ascending, then
+ *   code ascending.  Slot k < n (n = the number of live candidates, at most W) gets the k-th: ancestors[k] = its row, its code,
+ *   score[k] = cand.  Slots k >= n are dead: slot 0's ancestor and code, score -inf.  n == 0: ancestors = the identity, every row
+ *   emits its own lowest candidate code, score -inf.  The caller starts a group with score 0 for its first row and -inf for the
+ *   others.
+ *   Written, all in slot order: codes[k][p]; next_in row k = table row of the code; logp[k][col] = lp(ancestor, code);
+ *   logmass[k][col] = row_mass[ancestor]; score (M); ancestors (M, int32 row indices of the stack); flag[0] = 1 if any ancestor
+ *   differs from its own row else 0; row col of hist_ancestors (hist_rows, M) where given and col < hist_rows; bound[0] = p,
+ *   bound[1] = col; then pos[0] = p + 1.  NULL buffers, col < 0 and a column at or past a leading dimension are free / not written.
+ *   The moves row k <- row ancestors[k] that follow are vqcpc_particle_permute_* with P = W (none for W = 1): the codes' columns
+ *   [0, bound[0]), the whole sequence, the record rows' columns [0, bound[1]) -- the live column is in slot order already -- and
+ *   cache rows [0, pos[0]), position p's K/V having been written for the ancestor.
+ * Limits are vqcpc_prior_sample's: V <= 4096, 1 <= M <= 64, N <= 1024, d <= 4096; 1 <= W <= 64 dividing M.  The launch functions
+ * refuse NULL required pointers and leading dimensions smaller than the widths before any HIP call.  No allocation or
+ * synchronisation.
+ * vqcpc_prior_beam_expand_product / vqcpc_prior_beam_select_product: the same two kernel bodies for ONE DIGIT STAGE of a product
+ *   prior (1 <= ncb <= 4 codebooks of K <= 4096, K^ncb + 1 < 2^31; code = sum_j digit_j K^j), launched as a pair per stage j = 0 ..
+ *   ncb - 1 of a position: the search prunes to the group's W best (row, digit) pairs AFTER EVERY DIGIT -- a beam over the digit
+ *   sequence, not over the K^ncb merged codes.  With ncb = 1 every output equals the merged pair's bit for bit.
+ *   expand, stage j: logits are the stage's K logits, lp / row_mass as above with V = K; `base` is what the stage adds to: the
+ *   hypotheses' scores at stage 0, the previous stage's stage_score afterwards (cand = base[b] + lp).  From stage 1 on the rows
+ *   are in slot order, so the constraint and the digit sets of row b are those of the stack row it descends from, anc_in[b] (the
+ *   previous select's anc_total; ignored at stage 0).  A forced code (clamped to the K^ncb codes) gives its digit j as the one
+ *   candidate; otherwise the candidates are the digits of allowed[row][col][j] ([M][ldallow][ncb][ceil(K / 32)] words), all K where
+ *   the set has no digit inside.
+ *   select, a stage before the last: the slot rule above on (row, digit) pairs; written per slot k, every value of an ancestor
+ *   read before any is written: digits[k][0..j] (M, ncb) = the ancestor's digits with digit j appended; logp_acc[k] and mass_acc[k]
+ *   -- stage 0 stores lp / the ancestor's row_mass, later stages add theirs with one fp32 add in ascending stage order, the chain
+ *   of vqcpc_prior_sample_product(_masked) --; stage_score[k] = cand (-inf for a dead slot); anc_total[k] = the stack row the
+ *   slot descends from, composed over the stages (stage 0: the ancestor itself); h_next[k] = h[ancestor] + dtab[j][digit] (h and
+ *   h_next are different buffers).  codes, next_in, logp, logmass, score, ancestors, flag, bound, hist_ancestors and pos are
+ *   left alone.
+ *   select, the last stage: what vqcpc_prior_beam_select writes, with codes[k][p] = the merged code of the slot's digits, next_in
+ *   the left-to-right sum of the digits' rows of tables [ncb][K][d] (the chain of vqcpc_product_gather), logp / logmass from the
+ *   accumulators plus this stage's, and ancestors / hist_ancestors / flag from the composition over all stages; then pos + 1.
+ *   p outside [0, N): the last stage sets flag[0] = 0, nothing else happens.
+ * Adding them left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_prior_beam_expand(const float* logits, int64_t ldl, int V, int64_t M, int W, const int64_t* constraint, int64_t ldcons,
+                            const uint32_t* allowed, int64_t ldallow, const int32_t* win, const float* score, int N,
+                            const int32_t* pos, float* scratch_cand, int32_t* scratch_code, float* scratch_lp, float* row_mass,
+                            int32_t* row_low, float* row_lowlp, float* cand_out, void* stream);
+int vqcpc_prior_beam_select(const float* scratch_cand, const int32_t* scratch_code, const float* scratch_lp, const float* row_mass,
+                            const int32_t* row_low, const float* row_lowlp, int V, int64_t M, int W, float* logp, int64_t ldlogp,
+                            float* logmass, int64_t ldmass, const int32_t* win, int64_t* codes, int64_t ldc, int N,
+                            const float* table, int64_t table_rows, int d, float* next_in, int64_t ldn, float* score,
+                            int32_t* ancestors, int32_t* flag, int32_t* bound, int32_t* hist_ancestors, int64_t hist_rows,
+                            int32_t* pos, void* stream);
+int vqcpc_prior_beam_expand_product(const float* logits, int64_t ldl, int K, int ncb, int stage, int64_t M, int W,
+                                    const int64_t* constraint, int64_t ldcons, const uint32_t* allowed, int64_t ldallow,
+                                    const int32_t* win, const float* base, const int32_t* anc_in, int N, const int32_t* pos,
+                                    float* scratch_cand, int32_t* scratch_code, float* scratch_lp, float* row_mass,
+                                    int32_t* row_low, float* row_lowlp, float* cand_out, void* stream);
+int vqcpc_prior_beam_select_product(const float* scratch_cand, const int32_t* scratch_code, const float* scratch_lp,
+                                    const float* row_mass, const int32_t* row_low, const float* row_lowlp, int K, int ncb, int stage,
+                                    int64_t M, int W, int32_t* digits, float* logp_acc, float* mass_acc, float* stage_score,
+                                    int32_t* anc_total, const float* h, int64_t ldh, const float* dtab, float* h_next, int64_t ldhn,
+                                    float* logp, int64_t ldlogp, float* logmass, int64_t ldmass, const int32_t* win, int64_t* codes,
+                                    int64_t ldc, int N, const float* tables, int d, float* next_in, int64_t ldn, float* score,
+                                    int32_t* ancestors, int32_t* flag, int32_t* bound, int32_t* hist_ancestors, int64_t hist_rows,
+                                    int32_t* pos, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Scoring given tokens under the decoder (csrc/score.hip, decoders/scoring.py `Decoder.score_tokens`; the outputs are restated in
  * numpy float64 in tests/score_reference.py).
  * vqcpc_decode_score: ONE launch scores R independent rows of logits (R, ldl) in the samplers' layout (all voices concatenated,

@@ -266,6 +266,17 @@ SIGNATURES = {
     'vqcpc_decode_beam_select': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64,
                                          c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr,
                                          c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_beam_expand': (c_int, [c_ptr, c_i64, c_int, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr,
+                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_beam_select': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64,
+                                        c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                        c_ptr, c_i64, c_ptr, c_ptr]),
+    'vqcpc_prior_beam_expand_product': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr,
+                                                c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'vqcpc_prior_beam_select_product': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_i64, c_int, c_ptr,
+                                                c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr,
+                                                c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                                c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     'vqcpc_decode_score': (c_int, [c_ptr, c_i64, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64,
                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'vqcpc_prior_score': (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64,

@@ -10,8 +10,9 @@ no array of K**ncb entries.  True = the code (digit) may be drawn.  Sets combine
   check_sets   the one check of a call: the first empty set, or the first forced code its own set forbids -> ValueError
   pack_sets    bool (..., V) -> int32 (..., ceil(V / 32)): bit i & 31 of word i >> 5 is code i (the samplers' layout)
 
-Out of scope: sets for `score_codes` / vqcpc_prior_score, relational (voice-leading-style) rules on codes, beam search over codes,
-and arbitrary (non-product) sets over the K**ncb codes of a product prior."""
+The same tensors restrict the candidates of `generate_codes(beam=W)`: a search through sets.
+Out of scope: sets for `score_codes` / vqcpc_prior_score, relational (voice-leading-style) rules on codes, and arbitrary
+(non-product) sets over the K**ncb codes of a product prior."""
 import torch
 
 

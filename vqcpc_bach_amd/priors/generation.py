@@ -21,6 +21,21 @@ the live window's codes, ALL of `seq` (older windows committed the history there
 logmass rows, the next input row and, where a cached step follows, every layer's K/V cache rows [0, pos) -- onto the rows in
 place.  Before a slide or a forward-form step no cache moves: both recompute from the moved codes.
 
+Beam search (`start(beam=W)`, csrc/prior_beam.hip): the rows are groups of W consecutive rows, the W best plans of one user row so
+far.  vqcpc_prior_beam_expand + vqcpc_prior_beam_select take the sampler's place, in both step forms: every row is expanded into
+its candidate codes (a forced column's one code, else the column's set, else the vocabulary), scored by the row's total
+log-probability plus the code's, and the group's W best (row, code) pairs become the new rows, best first.  The select writes the
+live column -- code, next input row, logp, logmass -- in SLOT order, with the ancestors and the two device words `b_bound` =
+{pos, col} before the increment.  The moves that follow (`_beam_moves`, vqcpc_particle_permute_* with P = W) bring the history
+behind the slots: the live window's codes [0, b_bound[0]), ALL of `seq` (as `_resample` does and for its reason), the logp /
+logmass rows' columns [0, b_bound[1]) -- the new column must not move, it is in slot order already -- and, in the cached step only,
+the K/V cache rows [0, pos): position p's K/V were written for the ancestor; the forward form and a slide recompute from the moved
+codes.  The moves read only device words, so they are launches of the step and a captured step holds them.  Seeds, temperature,
+top_k and top_p are unused: the search is deterministic.  A product prior (`IncrementalProductPrior`) launches one
+vqcpc_prior_beam_expand_product + vqcpc_prior_beam_select_product pair PER DIGIT STAGE: its search prunes to the W best after
+every digit -- a beam over the digit sequence, not over the merged codes -- and only the last stage moves the stack's state, by
+the ancestors composed over the stages.
+
 Two regimes, as in the reference (:331-336):
 
   head (e < N): the first window.  One step per code; ONE captured step replayed N times.
@@ -73,6 +88,7 @@ class IncrementalPrior(IncrementalStack):
         inc = IncrementalPrior(prior, B)
         inc.start(num_tokens, seeds, temperature, top_k, top_p)   # constraint=, want_logp=: given codes, code scores;
                                                                   # allowed=, want_allowed_mass=, particles=: sets, their mass, a filter
+                                                                  # beam=W: the W best plans per group of W rows (`beam_results`)
         codes = inc.run(use_graph, window_stride)                 # (B, num_tokens) int64; inc.logp, inc.logmass (B, num_tokens) float32
 
     `start` + `slide` + `step` expose the single launches (teacher forcing, the sampler's input `logits` and its optional
@@ -90,6 +106,7 @@ class IncrementalPrior(IncrementalStack):
         self.codes_win = torch.zeros(M, N, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.allowed, self.logmass, self.masked = None, None, False
+        self.beam, self._beam_cache = None, True              # beam width W, or None: the rows are sampled
         self._sos_col = torch.full((M, 1), self.V, dtype=torch.int64, device=dev)    # table row of the start-of-sentence input
         self._init_model()
 
@@ -107,7 +124,7 @@ class IncrementalPrior(IncrementalStack):
 
     def start(self, num_tokens, seeds=None, temperature=1.0, top_k=0, top_p=1.0, teacher=None, want_probs=False,
               constraint=None, want_logp=False, allowed=None, want_allowed_mass=False, particles=None, resample_threshold=0.5,
-              final_resample=True):
+              final_resample=True, beam=None):
         """A new generation of `num_tokens` >= N codes per row.  teacher: (M, N) codes of the live window to force instead
         of drawing (single-step use); want_probs: keep the filtered probabilities of the last step in `probs` (M, V).
         constraint: (M, num_tokens) int64 in sequence coordinates, a code >= 0 is emitted at its column, < 0 leaves the draw
@@ -122,7 +139,10 @@ class IncrementalPrior(IncrementalStack):
         M / P groups of P particles, resampled after every code (`_resample`); logp / logmass are then kept whenever a
         constraint / sets are given.  resample_threshold, final_resample: as in `IncrementalDecoder.start`.  Any of the three
         switches the sampler to vqcpc_prior_sample_masked (vqcpc_prior_sample_product_masked), in both step forms.  teacher
-        excludes all of them, want_probs excludes particles."""
+        excludes all of them, want_probs excludes particles.
+        beam: None, or W in [1, 64] dividing M: the rows are M / W groups of W hypotheses and vqcpc_prior_beam_expand +
+        vqcpc_prior_beam_select (a product prior: their _product forms, a pair per digit stage) replace the sampler (`_beam`);
+        seeds, temperature, top_k and top_p are then unused.  It excludes particles, teacher and want_probs."""
         if not temperature > 0:
             raise ValueError('temperature must be > 0')
         if num_tokens < self.N:
@@ -142,6 +162,7 @@ class IncrementalPrior(IncrementalStack):
         self._constrain(constraint, want_logp or (scored and constraint is not None), self.nt)
         self._mask(allowed, want_allowed_mass or (scored and allowed is not None))
         self.probs = self._probs_buffer() if want_probs else None
+        self._beam(beam)
         self.seq = torch.zeros(self.M, self.nt, dtype=torch.int64, device=self.dev)
         self.reset()
 
@@ -164,6 +185,81 @@ class IncrementalPrior(IncrementalStack):
         self.logmass = torch.empty(self.M, self.nt, dtype=torch.float32, device=self.dev) if want_mass else None
         self.masked = allowed is not None or bool(want_mass) or self.particles is not None
 
+    # ---- beam search (csrc/prior_beam.hip) -------------------------------------------------------------------------------
+    def _beam(self, W):
+        """The beam's state: per row the plan's total log-probability `b_score` and its last ancestor `b_anc`; the device flag
+        `b_flag` (some row moved), the two words `b_bound` = {pos, col} of the last select before its increment, per column of the
+        sequence the ancestors `b_hist` (int32, -1 where nothing was generated), and the scratch the expansion hands to the
+        select: per row its W best (cand, code, lp), its set's log-mass and its lowest candidate code with that code's lp."""
+        self.beam = None
+        if W is None:
+            return
+        if isinstance(W, bool) or int(W) != W or not 1 <= int(W) <= MAX_ROWS or self.M % int(W):
+            raise ValueError(f'beam: 1 <= beam <= {MAX_ROWS} dividing the stack\'s {self.M} rows expected, got {W}')
+        W = int(W)
+        if self.particles is not None:
+            raise ValueError('beam and particles exclude each other')
+        if self.teacher is not None or self.probs is not None:
+            raise ValueError('beam and teacher / want_probs exclude each other')
+        if W > 1 and self.d % 4:
+            raise ValueError(f'beam: d_model = {self.d}, a multiple of 4 is needed to move the K/V cache rows')
+        self._beam_buffers(W)
+        self.beam = W
+
+    def _beam_buffers(self, W):
+        M = self.M
+        f32, i32 = dict(dtype=torch.float32, device=self.dev), dict(dtype=torch.int32, device=self.dev)
+        self.b_score, self.b_anc = torch.empty(M, **f32), torch.empty(M, **i32)
+        self.b_flag, self.b_bound = torch.empty(1, **i32), torch.empty(2, **i32)
+        self.b_hist = torch.empty(self.nt, M, **i32)
+        self.b_cand, self.b_code, self.b_lp = torch.empty(M, W, **f32), torch.zeros(M, W, **i32), torch.empty(M, W, **f32)
+        self.b_mass, self.b_low, self.b_lowlp = torch.empty(M, **f32), torch.zeros(M, **i32), torch.empty(M, **f32)
+
+    def _clear_beam(self):
+        """The standard start: score 0 for a group's first row, -inf for the others -- identical rows would fill the beam with
+        copies of one plan."""
+        if self.beam is None:
+            return
+        self.b_score.fill_(float('-inf'))
+        self.b_score[0::self.beam] = 0.0
+        self.b_anc.copy_(torch.arange(self.M, dtype=torch.int32))
+        for rows, value in ((self.b_flag, 0), (self.b_bound, 0), (self.b_hist, -1)):
+            rows.fill_(value)
+
+    def _beam_moves(self, move_cache):
+        """After vqcpc_prior_beam_select: row k <- row b_anc[k] of everything behind the live column, which the select wrote in
+        slot order already.  The bounds are device words: the window's codes move in [0, b_bound[0]), the record rows in
+        [0, b_bound[1]), the caches in [0, pos) of the incremented pos; `seq` moves whole (`_resample`).  move_cache=False in the
+        forward form, which recomputes from the moved codes.  W = 1 has nothing to move."""
+        W, M, nt, N = self.beam, self.M, self.nt, self.N
+        if W == 1:
+            return
+        anc, flag, bound = self.b_anc, self.b_flag, self.b_bound
+        hip.call('vqcpc_particle_permute_i64', self.codes_win, N, N, bound[0:1], anc, flag, M, W)
+        hip.call('vqcpc_particle_permute_i64', self.seq, nt, nt, None, anc, flag, M, W)
+        for rows in (self.logp, self.logmass):
+            if rows is not None:
+                hip.call('vqcpc_particle_permute_f32', rows, nt, nt, bound[1:2], anc, flag, M, W)
+        if move_cache:
+            for cache in (self.kcache, self.vcache):
+                hip.call('vqcpc_particle_permute_cache', cache, len(self.layers), self.W, self.d, self.pos, anc, flag, M, W)
+
+    def _beam_step(self):
+        """The two launches in the sampler's place, and the moves."""
+        N, nt, M = self.N, self.nt, self.M
+        hip.call('vqcpc_prior_beam_expand', self.logits, self.V, self.V, M, self.beam, self.constraint, nt, self.allowed, nt,
+                 self.win, self.b_score, N, self.pos, self.b_cand, self.b_code, self.b_lp, self.b_mass, self.b_low, self.b_lowlp,
+                 None)
+        hip.call('vqcpc_prior_beam_select', self.b_cand, self.b_code, self.b_lp, self.b_mass, self.b_low, self.b_lowlp, self.V, M,
+                 self.beam, self.logp, nt, self.logmass, nt, self.win, self.codes_win, N, N, self.table, self.table.shape[0], self.d,
+                 self.x, self.d, self.b_score, self.b_anc, self.b_flag, self.b_bound, self.b_hist, nt, self.pos)
+        self._beam_moves(self._beam_cache)
+
+    def beam_results(self):
+        """After a run: the plans' total log-probabilities (G, W), non-increasing along W and -inf for a dead slot, and the
+        ancestors per column of the sequence."""
+        return {'scores': self.b_score.view(self.M // self.beam, self.beam).clone(), 'ancestors': self.b_hist}
+
     def reset(self):
         """Back to the head regime's first position; the sequence is cleared, and so is every log-probability and log-mass (NaN:
         a run writes each column once, so none stays) and the particle filter's state."""
@@ -172,6 +268,7 @@ class IncrementalPrior(IncrementalStack):
             if rows is not None:
                 rows.fill_(float('nan'))
         self._clear_particles()
+        self._clear_beam()
         self.codes_win.zero_()
         self.ticket.zero_()
         self.win.copy_(torch.tensor([0, -1], dtype=torch.int32))
@@ -180,6 +277,9 @@ class IncrementalPrior(IncrementalStack):
     # ---- one step: the sampler, and the forward form ---------------------------------------------------------------------
     def _sample(self):
         N = self.N
+        if self.beam is not None:
+            self._beam_step()
+            return
         if self.masked:
             hip.call('vqcpc_prior_sample_masked', self.logits, self.V, self.V, self.M, self.temperature, self.top_k, self.top_p,
                      self.seeds, self.constraint, self.nt, self.logp, self.nt, self.win, self.allowed, self.nt, self.logmass,
@@ -211,7 +311,11 @@ class IncrementalPrior(IncrementalStack):
         M, N, d, V = self.M, self.N, self.d, self.V
         hip.call('vqcpc_decode_linear', out.data_ptr() + 4 * p * d, N * d, None, self.head_w, self.head_b, None, 0, self.logits,
                  V, M, V, d, 0)
-        self._sample()
+        self._beam_cache = False                              # the forward form keeps no cache: a beam moves codes and records only
+        try:
+            self._sample()
+        finally:
+            self._beam_cache = True
 
     def _move_forward(self):
         """One stride-1 move in the forward form: commit / load the next window at position N - 1, then its one code."""
@@ -382,6 +486,35 @@ class IncrementalProductPrior(IncrementalPrior):
     def _probs_buffer(self):
         return torch.zeros(self.ncb, self.M, self.K, dtype=torch.float32, device=self.dev)
 
+    def _beam_buffers(self, W):
+        """On top of the merged beam's: the stage's scores (the next stage's base), the ancestors composed over the stages of a
+        position, and the log-mass accumulator (the masked sampler's exists only with sets)."""
+        super()._beam_buffers(W)
+        self.b_stage = torch.empty(self.M, dtype=torch.float32, device=self.dev)
+        self.b_anc_total = torch.zeros(self.M, dtype=torch.int32, device=self.dev)
+        self.b_mass_acc = torch.zeros(self.M, dtype=torch.float32, device=self.dev)
+
+    def _beam_stages(self, h0, ldh0):
+        """`_stages` under a beam: per stage the head (stage 0's logits are there), the expansion of the stage's K digits on the
+        base the stage adds to, and the select, which prunes to the group's W best (row, digit) pairs and hands the next stage
+        its rows in slot order; the last stage emits the merged codes with the composed ancestors, and the moves follow."""
+        M, N, K, ncb, d, nt, W = self.M, self.N, self.K, self.ncb, self.d, self.nt, self.beam
+        scratch = (self.b_cand, self.b_code, self.b_lp, self.b_mass, self.b_low, self.b_lowlp)
+        for j in range(ncb):
+            h, ldh = (h0, ldh0) if j == 0 else (self.hs[j - 1], d)
+            if j > 0:
+                w, b = self.heads[j]
+                hip.call('vqcpc_decode_linear', h, d, None, w, b, None, 0, self.stage_logits[j], K, M, K, d, 0)
+            last = j == ncb - 1
+            hip.call('vqcpc_prior_beam_expand_product', self.stage_logits[j], K, K, ncb, j, M, W, self.constraint, nt, self.allowed,
+                     nt, self.win, self.b_score if j == 0 else self.b_stage, None if j == 0 else self.b_anc_total, N, self.pos,
+                     *scratch, None)
+            hip.call('vqcpc_prior_beam_select_product', *scratch, K, ncb, j, M, W, self.digits, self.logp_acc, self.b_mass_acc,
+                     self.b_stage, self.b_anc_total, None if last else h, ldh, None if last else self.dtab,
+                     None if last else self.hs[j], d, self.logp, nt, self.logmass, nt, self.win, self.codes_win, N, N, self.tables, d,
+                     self.x, d, self.b_score, self.b_anc, self.b_flag, self.b_bound, self.b_hist, nt, self.pos)
+        self._beam_moves(self._beam_cache)
+
     def _set_shape(self):
         return (self.M, self.nt, self.ncb, (self.K + 31) // 32)
 
@@ -395,6 +528,9 @@ class IncrementalProductPrior(IncrementalPrior):
     def _stages(self, h0, ldh0):
         """The ncb stages on h_0 = the stack's output rows (a pointer and its leading dimension); stage 0's logits are there."""
         M, N, K, ncb, d = self.M, self.N, self.K, self.ncb, self.d
+        if self.beam is not None:
+            self._beam_stages(h0, ldh0)
+            return
         for j in range(ncb):
             h, ldh = (h0, ldh0) if j == 0 else (self.hs[j - 1], d)
             if j > 0:
@@ -421,7 +557,11 @@ class IncrementalProductPrior(IncrementalPrior):
         M, N, d, K = self.M, self.N, self.d, self.K
         h0 = out.data_ptr() + 4 * p * d                                     # row p of every sequence
         hip.call('vqcpc_decode_linear', h0, N * d, None, self.head_w, self.head_b, None, 0, self.logits, K, M, K, d, 0)
-        self._stages(h0, N * d)
+        self._beam_cache = False                              # as the merged tail: no cache moves in the forward form
+        try:
+            self._stages(h0, N * d)
+        finally:
+            self._beam_cache = True
 
     def _window(self, P, advance):
         hip.call('vqcpc_prior_window_product', self.seq, self.nt, self.nt, self.win, int(advance), self.codes_win, self.N, int(P),

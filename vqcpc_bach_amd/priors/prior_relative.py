@@ -266,7 +266,8 @@ class PriorRelative(FlatTraining, nn.Module):
 
     def generate_codes(self, num_tokens, temperature=1.0, num_generated_codes=1, top_k=0, top_p=1.0, seed=None, use_graph=True,
                        window_stride=1, method='auto', constraint=None, return_logp=False, allowed=None,
-                       return_allowed_mass=False, particles=None, resample_threshold=0.5, return_particles=False):
+                       return_allowed_mass=False, particles=None, resample_threshold=0.5, return_particles=False, beam=None,
+                       return_beams=False):
         """Samples `num_generated_codes` sequences of `num_tokens` >= N merged codes (:315-353).  Code e < N comes from the
         first window (one cached step per code); code e >= N from the window that ends at e, as in the reference, when
         `window_stride` = 1.  window_stride = k > 1 (an opt-in of this package, NOT the reference's model context) moves the
@@ -303,8 +304,26 @@ class PriorRelative(FlatTraining, nn.Module):
         'log_evidence' (rows,), and per code 'ancestors' (num_tokens, rows * P), 'wn', 'ess' -- `Decoder.generate_from_codes`'
         contract.  Results come in the order (codes[, logp][, allowed_mass][, particles]).  Any of the keywords switches the
         step's sampler to vqcpc_prior_sample_masked (vqcpc_prior_sample_product_masked); without them every launch is what it was.
-        Out of scope: sets for `score_codes`, beam search over codes, relational rules on codes, and sets over the K**ncb codes
-        of a product prior that are not a product of digit sets."""
+        beam=W in [1, 64] (csrc/prior_beam.hip): a deterministic search in the sampler's place.  Every
+        requested row is a group of W rows of the stack, the W most probable plans so far: at each column every row is expanded
+        into its candidate codes -- the forced code, else the codes of the column's set, else all V --, and the group's W best
+        (row, code) pairs by total log-probability become the new rows, best first (equal totals: the lower row, then the lower
+        code).  The result has the shapes of a call without the keyword: each group's slot 0, the best plan found.
+        return_beams=True returns all rows * W rows in slot order followed by a dict: 'scores' (rows, W) float32, the plans' total
+        log-probabilities -- the ordered fp32 sum of their logp --, non-increasing along W and -inf for a dead slot (fewer than W
+        plans exist), and 'ancestors' (num_tokens, rows * W) int32, per column the row each slot descends from.  W at least the
+        number of admitted plans makes the search exhaustive; beam=1 is greedy decoding.  `seed` is accepted and unused.
+        code_model 'product': the search PRUNES AFTER EVERY DIGIT.  A code is ncb digit stages; at each stage the rows are expanded
+        into the stage's candidate digits (the forced code's digit, else the stage's digit set, else all K) and the group's W best
+        (row, digit) pairs go on to the next stage: it is a beam over the digit sequence, not over the K**ncb merged codes, so
+        a code whose first digit is not among the W best prefixes is never scored, and W >= the admitted plans is exhaustive only
+        if it also covers every stage's partial codes.  logp and scores are the sums of the digits' log-probabilities, with
+        vqcpc_prior_sample_product's bits.
+        ValueError with `particles`, a filter (temperature other than 1, top_k, top_p) or return_beams without beam.  Results come
+        in the order (codes[, logp][, allowed_mass][, particles | beams]).  Chunks are whole groups.  Without the keywords every
+        launch, buffer and result is what it was.
+        Out of scope: sets for `score_codes`, relational rules on codes, and sets over the K**ncb codes of a product prior that
+        are not a product of digit sets."""
         from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalPrior, IncrementalProductPrior
         if self.code_model == 'product':
@@ -327,6 +346,9 @@ class PriorRelative(FlatTraining, nn.Module):
         # with `particles` every requested row is a group of P rows of the stack (P = 1 without)
         from ..decoders.decoder import Decoder
         P = Decoder._particle_count(particles, resample_threshold, return_particles, None)
+        W = Decoder._beam_width(beam, return_beams, particles, None, 1, temperature, top_k, top_p)
+        if beam is not None:
+            P = W                                             # the group size of the chunks below, whichever kind the groups are
         packed = None if allowed is None else self._code_sets(allowed, B, num_tokens, constraint)       # (B | 1, ...)
         rows_all = B * P
         if P > 1 and constraint is not None:
@@ -335,7 +357,7 @@ class PriorRelative(FlatTraining, nn.Module):
         dev = self.sos.device
         kept = {'logp': return_logp, 'logmass': return_allowed_mass}
         records = {key: torch.empty(rows_all, num_tokens, dtype=torch.float32, device=dev) for key, on in kept.items() if on}
-        filt = {} if particles is not None else None
+        filt = {} if particles is not None or beam is not None else None
 
         def chunk(n, rows):
             inc = IncrementalPrior(self, n)
@@ -347,17 +369,19 @@ class PriorRelative(FlatTraining, nn.Module):
             inc.start(num_tokens, seeds=seeds[rows], temperature=temperature, top_k=top_k, top_p=top_p,
                       constraint=None if constraint is None else constraint[rows], want_logp=return_logp, allowed=sets,
                       want_allowed_mass=return_allowed_mass, particles=None if particles is None else P,
-                      resample_threshold=resample_threshold, final_resample=not return_particles)
+                      resample_threshold=resample_threshold, final_resample=not return_particles,
+                      beam=None if beam is None else W)
             codes = inc.run(use_graph=use_graph, window_stride=stride, method=method)
             for key, buf in records.items():
                 buf[rows] = getattr(inc, key)
             if filt is not None:
-                Decoder._keep_particle_results(filt, inc.particle_results(), rows.start)
+                Decoder._keep_particle_results(filt, inc.particle_results() if beam is None else inc.beam_results(), rows.start)
             return codes
         codes = generate_in_chunks(self, rows_all, num_tokens, chunk, MAX_ROWS // P * P)             # whole groups
-        keep = slice(None) if P == 1 or return_particles else slice(0, rows_all, P)                 # a group's first row
+        whole = return_particles if beam is None else return_beams
+        keep = slice(None) if P == 1 or whole else slice(0, rows_all, P)        # a group's first row: the survivor / the best plan
         out = [codes[keep]] + [records[key][keep] for key in ('logp', 'logmass') if key in records]
-        if return_particles:
+        if return_particles or return_beams:
             out.append(Decoder._join_particle_results(filt))
         return out[0] if len(out) == 1 else tuple(out)
 
@@ -435,7 +459,7 @@ class PriorRelative(FlatTraining, nn.Module):
 
     def generate(self, num_tokens, decoder, temperature=1.0, num_generated_codes=1, num_decodings_per_generating_code=1,
                  decoder_temperature=None, seed=None, code_constraint=None, return_logp=False, code_allowed=None,
-                 code_particles=None, code_resample_threshold=0.5, **decoder_sampling):
+                 code_particles=None, code_resample_threshold=0.5, code_beam=None, **decoder_sampling):
         """:308-368: `generate_codes`, then `decoder.generate_from_code_long` on them.  `temperature` goes to BOTH, as in the
         reference (where it sharpens the prior and flattens the decoder as it grows, module docstring);
         decoder_temperature overrides the decoder's.  decoder_sampling: top_k, top_p, pad, start, ... of
@@ -443,10 +467,14 @@ class PriorRelative(FlatTraining, nn.Module):
         device; score objects and XML files need music21 and are out of scope.
         code_constraint / return_logp: `generate_codes`' constraint / return_logp; with return_logp=True the result is
         (codes, tokens, code_logp (B, num_tokens) float32).  code_allowed / code_particles / code_resample_threshold:
-        `generate_codes`' allowed / particles / resample_threshold (each group's surviving row goes to the decoder)."""
-        out = self.generate_codes(num_tokens, temperature=temperature, num_generated_codes=num_generated_codes, seed=seed,
+        `generate_codes`' allowed / particles / resample_threshold (each group's surviving row goes to the decoder).
+        code_beam: `generate_codes`' beam (the prior then takes temperature 1, whatever `temperature` is): the decoder receives each
+        group's best plan; with the decoder's own `beam=` in decoder_sampling the whole chain prior -> codes -> tokens is
+        deterministic and most-probable-first."""
+        out = self.generate_codes(num_tokens, temperature=1.0 if code_beam is not None else temperature,
+                                  num_generated_codes=num_generated_codes, seed=seed,
                                   constraint=code_constraint, return_logp=return_logp, allowed=code_allowed,
-                                  particles=code_particles, resample_threshold=code_resample_threshold)
+                                  particles=code_particles, resample_threshold=code_resample_threshold, beam=code_beam)
         codes, code_logp = out if return_logp else (out, None)
         tokens = decoder.generate_from_code_long(encoding_indices=codes,
                                                  temperature=temperature if decoder_temperature is None else decoder_temperature,
@@ -455,7 +483,7 @@ class PriorRelative(FlatTraining, nn.Module):
 
     def continue_tokens(self, x, num_new_codes, decoder, temperature=1.0, decoder_temperature=None, num_continuations=1,
                         seed=None, return_logp=False, code_constraint=None, code_allowed=None, code_particles=None,
-                        code_resample_threshold=0.5, **decoder_sampling):
+                        code_resample_threshold=0.5, code_beam=None, **decoder_sampling):
         """"Here are the first bars, go on": x (1, events, channels) tokens of a piece's opening, events a multiple of the
         events per code.  The opening is framed at the front as `Decoder.reharmonise_tokens` frames a chorale (one model-sized
         PAD ... START chunk, then x; no END completion), encoded by this prior's frozen encoder in model-sized chunks and the
@@ -470,6 +498,8 @@ class PriorRelative(FlatTraining, nn.Module):
         into it, so "continue this opening and close on that cadence" is one call; a value >= 0 inside the opening that differs
         from the encoded code is a ValueError.  code_allowed: `generate_codes`' allowed over the same columns; code_particles /
         code_resample_threshold: its particles / resample_threshold, which make the free codes lead to the forced close.
+        code_beam: its beam (the prior then takes temperature 1): every continuation is the most probable plan the search finds
+        from the opening, through the constraint and the sets.
         Needs the decoder's dataset's START / XX symbols."""
         if decoder.continuous_source:
             raise NotImplementedError('a prior over continuous (NoQuantization) codes does not exist')
@@ -511,9 +541,10 @@ class PriorRelative(FlatTraining, nn.Module):
                 raise ValueError("continue_tokens: code_constraint forces a code inside the opening that differs from the opening's "
                                  'own encoded code')
         constraint[:, :L] = prefix
-        out = self.generate_codes(total, temperature=temperature, num_generated_codes=num_continuations, seed=seed,
+        out = self.generate_codes(total, temperature=1.0 if code_beam is not None else temperature,
+                                  num_generated_codes=num_continuations, seed=seed,
                                   constraint=constraint, return_logp=return_logp, allowed=code_allowed, particles=code_particles,
-                                  resample_threshold=code_resample_threshold)
+                                  resample_threshold=code_resample_threshold, beam=code_beam)
         codes, code_logp = out if return_logp else (out, None)
         token_constraint = torch.full((int(num_continuations), total * epc, nc), -1, dtype=torch.int64)
         token_constraint[:, E:E + x.shape[1]] = x

@@ -25,6 +25,7 @@ The stack also owns what both generators' constrained samplers need (`_constrain
 flag), the particle filter's state (`_particles`, `_clear_particles`, `particle_results`; each generator has its own `_resample`,
 which knows what of its state follows a resampled row) and the coordinate frame of a generation's per-position buffers (`Frame`), which the recorded attention launch reads."""
 import collections
+import gc
 
 import torch
 
@@ -266,6 +267,15 @@ class IncrementalStack:
         loading, workspace and buffer allocation) stay outside the capture."""
         torch.cuda.synchronize(self.dev)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-            fn()
+        # no cyclic garbage collection while the stream captures: a collection that starts inside fn() runs the finalizers of
+        # whatever dead cycles earlier generations left (graphs, events, tensors), and a runtime call of theirs that is not
+        # allowed during a thread-local capture aborts the process.  The collector only waits: nothing is collected here.
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                fn()
+        finally:
+            if collecting:
+                gc.enable()
         return graph
