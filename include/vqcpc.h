@@ -1206,6 +1206,58 @@ int vqcpc_rules_audit(const int64_t* x, int64_t ld, int64_t width, const int32_t
                       const int32_t* max_leap, int rules, int32_t* report, int64_t ldreport, int64_t rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Copy guard: token sets that keep a generation from reciting the corpus (csrc/nocopy.hip, decoders/generation.py `no_copy=`,
+ * DeviceCorpus.copy_index; the rule is restated in numpy, without hashing, in tests/nocopy_reference.py).  Exact integer logic.
+ * DEFINITION.  Everything follows the duplicate check above: positions are flattened tick-major, voice-minor; a query position is
+ *   matched only with a corpus position of the same voice; a run never crosses a piece boundary; only stored corpus ticks take part
+ *   (the virtual PAD / START / END never match); there are 4 voices.  With max_copy = n, token k is BANNED at column c (voice
+ *   v = c % 4) of a row when c >= n and some corpus token position j satisfies all of: j has voice v; j - n .. j - 1 lie in j's own
+ *   piece; corpus[j - m] == history[c - m] for m = 1 .. n; corpus[j] == k.  history is every column before c, read as
+ *   vqcpc_decode_rules reads it: tokens[b][c' - win[1] * U] for c' >= win[1] * U, else chorale[b][c']; forced and free tokens are
+ *   treated alike; a column that holds no token (< 0, >= 0xFFFF, at or past a leading dimension) equals nothing.  Emitting a banned
+ *   token would complete a shared run of n + 1 tokens, so a row none of whose positions is flagged RELAXED or FORCED_COPY (below) has
+ *   longest_common_run <= n.
+ * THE INDEX.  `framed`: n_framed words of the duplicate check's framed corpus (a sub-array that starts and ends on a sentinel), read
+ *   as 4 n_framed 16-bit tokens; token position j = 4 framed tick + voice.  An ENTRY is a position j >= n whose token is < 256 and
+ *   whose n tokens before it hold no sentinel.  key = hash(voice, context) << 8 | token, a non-negative int64; `keys` sorted
+ *   ascending, `where` the entries' positions in the same order.  The hash is not part of the contract: equal (voice, context) give
+ *   equal hashes, and every candidate of a key range is compared token by token, so a collision costs a comparison and never a result.
+ * vqcpc_copy_index_keys: keys[j] for every token position j < 4 n_framed: the entry's key, or -1 where j is no entry.
+ * vqcpc_copy_index_unique: over SORTED keys / where (entries >= 1): keep[i] (bytes) = 0 where entry i - 1 has the same key and a
+ *   context that compares equal, else 1.  Dropping the zeros leaves every (voice, context, token) at least once, and a context's
+ *   range no longer than its distinct continuations plus whatever collisions interleave.
+ * vqcpc_decode_nocopy: ONE launch, a wavefront per row, M <= 64, inside the step immediately before the sampler or
+ *   vqcpc_decode_beam_select and after vqcpc_decode_rules.  col = pos[0] (win == NULL) or win[1] * U + pos[0]; pos[0] outside
+ *   [0, T) or win[1] < 0: nothing happens.  in_set = copy_static[b][col] (NULL: the whole vocabulary [0, V_v); copy_static may be
+ *   `sets` itself, in place, when the rule kernel wrote the column this step); an in_set without a token of the vocabulary is read
+ *   as the whole vocabulary, as the samplers read it.  ban = the banned tokens (none when col < n).
+ *   Free position: sets[b][col] = in_set & ~ban and copy_report[b][col] = |in_set & ban| (bits 0-8); if the ban removed something and
+ *   left no token of [0, V_v) outside exclude[v], sets = in_set and copy_report = RELAXED (bit 16): the sampler never meets an
+ *   empty set.  Forced position (constraint[b][col] >= 0): sets = in_set, copy_report = FORCED_COPY (bit 17) when the forced token is
+ *   banned, else 0.  Every write is a pure overwrite; a column at or past a leading dimension is neither read nor written.
+ * vqcpc_nocopy_audit: x [rows][ld], width columns (a multiple of 4): every token is taken as given and the history comes from x;
+ *   report[b][c] = FORCED_COPY where token c completes a shared run of n + 1 tokens, else 0.  Grid of (column range, row).
+ * vqcpc_nocopy_beam_column: after vqcpc_decode_beam_select (`flag`, `bound` = {pos, col} as it left them): where flag[0] != 0,
+ *   copy_report[k][bound[1]] <- copy_report[ancestors[k]][bound[1]] for every row, in place, loads before stores.
+ * The launch functions refuse, before any HIP call: NULL required pointers, M outside [1, 64], nc != 4, V_c > 256, max_copy outside
+ * [1, 512], n_framed outside [1, 2^30), leading dimensions smaller than the widths.  No allocation or synchronisation.  Adding them
+ * left the ABI version alone.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int vqcpc_copy_index_keys(const uint64_t* framed, int64_t n_framed, int max_copy, int64_t* keys, void* stream);
+int vqcpc_copy_index_unique(const uint64_t* framed, int64_t n_framed, int max_copy, const int64_t* keys, const int64_t* where,
+                            int64_t entries, uint8_t* keep, void* stream);
+int vqcpc_decode_nocopy(const int64_t* tokens, int64_t ldtok, int T, const int64_t* chorale, int64_t ldch, const int64_t* constraint,
+                        int64_t ldcons, const int64_t* keys, const int64_t* where, int64_t entries, const uint64_t* framed,
+                        int64_t n_framed, int max_copy, const int32_t* voice_offsets, int nc, const uint32_t* exclude,
+                        const uint32_t* copy_static, int64_t ldstatic, uint32_t* sets, int64_t ldsets, int32_t* copy_report,
+                        int64_t ldreport, const int32_t* pos, const int32_t* win, int U, int64_t M, void* stream);
+int vqcpc_nocopy_audit(const int64_t* x, int64_t ld, int64_t width, const int64_t* keys, const int64_t* where, int64_t entries,
+                       const uint64_t* framed, int64_t n_framed, int max_copy, int32_t* report, int64_t ldreport, int64_t rows,
+                       void* stream);
+int vqcpc_nocopy_beam_column(int32_t* copy_report, int64_t ldreport, const int32_t* ancestors, const int32_t* flag, const int32_t* bound,
+                             int64_t M, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Beam search for decoder generation (csrc/beam.hip, decoders/generation.py `beam=W`; the rule is restated in numpy in
  * tests/beam_reference.py).  The M <= 64 rows of an incremental stack are G = M / W groups of W consecutive rows ("slots"), the
  * hypotheses of one user row, 1 <= W <= 64.

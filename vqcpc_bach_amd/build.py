@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libvqcpc_hip.so')
-SOURCES = ['util.hip', 'vq.hip', 'nce.hip', 'embed_ln.hip', 'relattn.hip', 'relattn_sub.hip', 'relattn16.hip', 'relattn_x.hip', 'gemm.hip', 'gemm_bf16.hip', 'gemm_grad.hip', 'student.hip', 'gru.hip', 'decode.hip', 'prior.hip', 'aligned.hip', 'corpus.hip', 'duplicates.hip', 'clusters.hip', 'product_codes.hip', 'particles.hip', 'rules.hip', 'beam.hip', 'score.hip', 'prior_score.hip', 'prior_beam.hip']
+SOURCES = ['util.hip', 'vq.hip', 'nce.hip', 'embed_ln.hip', 'relattn.hip', 'relattn_sub.hip', 'relattn16.hip', 'relattn_x.hip', 'gemm.hip', 'gemm_bf16.hip', 'gemm_grad.hip', 'student.hip', 'gru.hip', 'decode.hip', 'prior.hip', 'aligned.hip', 'corpus.hip', 'duplicates.hip', 'clusters.hip', 'product_codes.hip', 'particles.hip', 'rules.hip', 'nocopy.hip', 'beam.hip', 'score.hip', 'prior_score.hip', 'prior_beam.hip']
 # the VQ argmin, the codeword neighbours and the particle weights must reproduce separately-rounded sub/mul/add: no FMA
 # contraction in those files (beam.hip, score.hip, prior_score.hip and prior_beam.hip must reproduce the samplers' logp bits instead: decode.hip's / prior.hip's flags, see their heads)
 EXTRA = {'vq.hip': ['-ffp-contract=off'], 'clusters.hip': ['-ffp-contract=off'], 'particles.hip': ['-ffp-contract=off']}

@@ -51,6 +51,11 @@ is the longest run; among equals the smallest i; among those the smallest j (the
 `difflib.SequenceMatcher(None, a, b, autojunk=False).find_longest_match` returns per piece on lists of (voice, token) pairs,
 combined by (longest, smallest a, earliest piece).  The reference matches the CHARACTERS of the dumped note names instead, so its
 count depends on the names' lengths and a match may end inside a name; lengths here are tokens.
+
+THE COPY GUARD (`DeviceCorpus.copy_index`, csrc/nocopy.hip; `Decoder.generate_from_codes(no_copy=...)`): the same run, prevented
+instead of measured.  The index holds every corpus token position whose `max_copy` tokens before it lie in its own piece, keyed by
+a hash of (voice, those tokens) with the position's token in the low 8 bits, sorted; the step looks the generation's last
+`max_copy` tokens up and bans the tokens found, so that no run of `max_copy + 1` shared tokens can be completed.
 """
 import numpy as np
 import torch
@@ -254,6 +259,43 @@ def unframe(j, piece_start, first=0):
     return piece, int(tick), int(voice)
 
 
+# ---- the copy guard's index (include/vqcpc.h, "Copy guard") ------------------------------------------------------------------------
+COPY_MAX_N = 512                       # max_copy: a lane of the guard kernel keeps 8 history tokens
+COPY_MAX_VOCAB = 256                   # the next token takes the low 8 bits of a key
+COPY_RELAXED, COPY_FORCED = 1 << 16, 1 << 17           # the flags of copy_report; bits 0-8 count the removed tokens
+
+
+class CopyIndex:
+    """What `DeviceCorpus.copy_index` built, device resident: sorted `keys` (int64), `where` (int64, the entries' token positions
+    inside the framed sub-array), `framed` (the sub-array itself, a view of the duplicate check's), `max_copy`, `pieces` = (lo, hi),
+    `vocab` (per voice) and `entries_before`, the number of entries before the duplicate removal."""
+
+    def __init__(self, keys, where, framed, max_copy, pieces, vocab, entries_before):
+        self.keys, self.where, self.framed = keys, where, framed
+        self.max_copy, self.pieces, self.vocab, self.entries_before = int(max_copy), tuple(pieces), tuple(vocab), int(entries_before)
+
+    @property
+    def device(self):
+        return self.framed.device
+
+    @property
+    def entries(self):
+        return int(self.keys.numel())
+
+    @property
+    def n_framed(self):
+        return int(self.framed.numel())
+
+    def nbytes(self):
+        """Bytes of keys + where (the framed corpus is the duplicate check's and is shared)."""
+        return self.keys.numel() * 8 + self.where.numel() * 8
+
+    def args(self):
+        """The index operands of vqcpc_decode_nocopy / vqcpc_nocopy_audit, in order."""
+        e = self.entries
+        return (self.keys if e else None, self.where if e else None, e, self.framed, self.n_framed, self.max_copy)
+
+
 # ---- the corpus on the device ---------------------------------------------------------------------------------------------
 def permute(ids, lo, n, key, q0):
     """ids[i] = lo + pi_key((q0 + i) mod n) for the whole int64 device tensor `ids`."""
@@ -336,6 +378,36 @@ class DeviceCorpus:
                 out['query_tick'][g], out['query_voice'][g] = divmod(i, NUM_VOICES)
                 out['piece'][g], out['piece_tick'][g], out['voice'][g] = unframe(j, ps, first)
         return {k: int(v[0]) for k, v in out.items()} if single else out
+
+    def copy_index(self, max_copy, pieces=None, deduplicate=True):
+        """The copy guard's index (module docstring of csrc/nocopy.hip; include/vqcpc.h, "Copy guard") over the pieces [lo, hi) =
+        `pieces` (default: all), built once on the device: every corpus token position whose `max_copy` tokens before it lie in
+        its own piece, keyed by hash(voice, those tokens) << 8 | its token, sorted (torch.sort), and -- deduplicate -- without the
+        entries that repeat their predecessor's (voice, context, token).  ValueError: max_copy outside [1, 512], a vocab above 256,
+        the duplicate check's framed limits."""
+        c = self.corpus
+        max_copy = int(max_copy)
+        if not 1 <= max_copy <= COPY_MAX_N:
+            raise ValueError(f'copy_index: 1 <= max_copy <= {COPY_MAX_N} expected, got {max_copy}')
+        if int(c.vocab.max()) > COPY_MAX_VOCAB:
+            raise ValueError(f'copy_index: a key keeps the next token in 8 bits; the vocab {c.vocab.tolist()} does not fit '
+                             f'{COPY_MAX_VOCAB}')
+        pieces = (0, c.num_pieces) if pieces is None else tuple(int(p) for p in pieces)
+        first, n_framed = framed_range(c.piece_start, *pieces)
+        if int(c.piece_start[-1]) + c.num_pieces + 1 >= 1 << 30:
+            raise ValueError('copy_index: the framed corpus must stay below 2^30 ticks')
+        framed = self.framed()[first:first + n_framed]
+        keys = torch.empty(NUM_VOICES * n_framed, dtype=torch.int64, device=self.device)
+        hip.call('vqcpc_copy_index_keys', framed, n_framed, max_copy, keys)
+        where = torch.nonzero(keys >= 0).reshape(-1)
+        keys, order = torch.sort(keys[where])
+        where = where[order]
+        entries = int(keys.numel())
+        if deduplicate and entries:
+            keep = torch.empty(entries, dtype=torch.bool, device=self.device)
+            hip.call('vqcpc_copy_index_unique', framed, n_framed, max_copy, keys, where, entries, keep)
+            keys, where = keys[keep].contiguous(), where[keep].contiguous()
+        return CopyIndex(keys, where, framed, max_copy, pieces, tuple(int(v) for v in c.vocab), entries)
 
     def table(self, num_beats):
         """(win_cum on the device, number of windows) of the window set of `num_beats` beats."""

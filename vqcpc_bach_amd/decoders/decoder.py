@@ -465,7 +465,7 @@ class Decoder(FlatTraining, nn.Module):
                             use_graph=True, constraint=None, return_logp=False, return_attentions=False,
                             max_attention_bytes=4 << 30, allowed=None, return_allowed_mass=False, particles=None,
                             resample_threshold=0.5, return_particles=False, rules=None, return_rule_report=False, beam=None,
-                            return_beams=False):
+                            return_beams=False, no_copy=None, return_copy_report=False):
         """Samples target sequences from MERGED codes (B, S) (what `forward` takes; a continuous decoder takes (B, S, dz)
         latents, ValueError on the other kind): each row repeated `num_decodings` times
         (repeat_interleave, as generate_from_code_long :747-752), then one token per position with the reference's
@@ -535,13 +535,26 @@ class Decoder(FlatTraining, nn.Module):
         sequences exist), and 'ancestors' (positions, B * W) int32, per generated position the row each slot descends from (-1
         where nothing was generated).  ValueError with `particles`, `return_attentions`, num_decodings != 1, or a filter
         (temperature other than 1, top_k, top_p): a filter has no meaning for a search.  Without `beam` every launch, buffer
-        and result is what it was."""
+        and result is what it was.
+        no_copy: None, or a `dataloaders.corpus.CopyIndex` (`copy_index(max_copy)`): a generation that cannot recite the corpus.
+        Before every draw vqcpc_decode_nocopy looks the row's last max_copy tokens up in the index and takes out of the
+        position's set -- `allowed`'s, the rules', or the whole vocabulary -- every token that would complete a run of
+        max_copy + 1 tokens shared with the corpus (same voice, inside one piece: `check_duplicate_all_corpus`'s run).  It
+        switches the step to the masked sampler and combines with `constraint`, `allowed`, `exclude_tokens`, `rules`,
+        `particles` and `beam`; `allowed_mass` is the mass of the narrowed set, so particles that can only go on by copying
+        lose weight.  return_copy_report=True -> `copy_report` after rule_report and before attentions, int32 of the tokens'
+        shape: bits 0-8 the number of tokens the guard took out of the set; bit 16 RELAXED, every token left was banned and
+        the set was used as it came; bit 17 FORCED_COPY, a token forced by `constraint` was banned.  A row without either
+        flag shares no run longer than max_copy with the index's pieces.  ValueError for a decoder whose voices or
+        vocabularies are not the index's, or an index on another device.  Without the keyword every launch, buffer and
+        result is what it was."""
         return self._result_tuple(self._window_results(
             codes, exclude_tokens, use_graph, temperature=temperature, top_k=top_k, top_p=top_p, num_decodings=num_decodings,
             seed=seed, constraint=constraint, return_logp=return_logp, return_attentions=return_attentions,
             max_attention_bytes=max_attention_bytes, allowed=allowed, return_allowed_mass=return_allowed_mass, particles=particles,
             resample_threshold=resample_threshold, return_particles=return_particles, rules=rules,
-            return_rule_report=return_rule_report, beam=beam, return_beams=return_beams))
+            return_rule_report=return_rule_report, beam=beam, return_beams=return_beams, no_copy=no_copy,
+            return_copy_report=return_copy_report))
 
     def _window_results(self, codes, exclude_tokens, use_graph, **options):
         """`generate_from_codes` with its results by name (`_generate_rows`)."""
@@ -556,7 +569,7 @@ class Decoder(FlatTraining, nn.Module):
     def _generate_rows(self, source, name, length, form, temperature=1.0, top_k=0, top_p=1.0, num_decodings=1, seed=None,
                        constraint=None, return_logp=False, return_attentions=False, max_attention_bytes=4 << 30, allowed=None,
                        return_allowed_mass=False, particles=None, resample_threshold=0.5, return_particles=False, rules=None,
-                       return_rule_report=False, beam=None, return_beams=False):
+                       return_rule_report=False, beam=None, return_beams=False, no_copy=None, return_copy_report=False):
         """The body the public generators share: the option checks, then the source (`_source_on_device(source, name, length)`),
         then `form(codes)`, what the fixed window and the chorale differ in -- a dict of
           events, first, last   the events of a row, and the range [first, last) of them that is generated
@@ -566,8 +579,8 @@ class Decoder(FlatTraining, nn.Module):
                                 `enc_probs` of every chunk) or 'window_start': a tensor
         -- then packing, repetition by num_decodings * particles (or the beam width), seeds, the chunks on their own stacks and their records.
         -> a dict in the documented order of the results, every row (a group's first one with particles or a beam, unless they are
-        returned) as (rows, events, channels): 'tokens', 'logp', 'allowed_mass', 'rule_report', then 'attentions', 'particles' and
-        'beams'; what was not asked for is None."""
+        returned) as (rows, events, channels): 'tokens', 'logp', 'allowed_mass', 'rule_report', 'copy_report', then 'attentions',
+        'particles' and 'beams'; what was not asked for is None."""
         from ..transformer.incremental import MAX_ROWS, generate_in_chunks, row_seeds
         from .generation import IncrementalDecoder
         dev, nc = self.sos.device, self.num_channels
@@ -577,6 +590,7 @@ class Decoder(FlatTraining, nn.Module):
         if beam is not None:
             P, temperature = W, 1.0                           # the group size of the chunks below, whichever kind the groups are
         self._check_rules(rules, return_rule_report)
+        self._check_no_copy(no_copy, return_copy_report)
         codes = self._source_on_device(source, name, length)
         form = form(codes)
         events, first, last, exclude = form['events'], form['first'], form['last'], form['exclude']
@@ -596,8 +610,11 @@ class Decoder(FlatTraining, nn.Module):
                         want_attentions=layers, want_allowed_mass=return_allowed_mass, particles=None if particles is None else P,
                         resample_threshold=resample_threshold, final_resample=not return_particles, rules=rules,
                         beam=None if beam is None else W)
+        if no_copy is not None:                               # only then: the stacks' `start` is called as before without it
+            settings['no_copy'] = no_copy
         kept = {'logp': ('logp', torch.float32, return_logp), 'allowed_mass': ('logmass', torch.float32, return_allowed_mass),
-                'rule_report': ('rule_report', torch.int32, return_rule_report)}          # result: the stack's buffer, ...
+                'rule_report': ('rule_report', torch.int32, return_rule_report),          # result: the stack's buffer, ...
+                'copy_report': ('copy_report', torch.int32, return_copy_report)}
         records = {key: torch.empty(B, width, dtype=dtype, device=dev) for key, (_, dtype, wanted) in kept.items() if wanted}
         maps = filt = None
         if layers is not None:
@@ -653,6 +670,57 @@ class Decoder(FlatTraining, nn.Module):
         if rules.kinds.shape[0] != self.num_channels or rules.kinds.shape[1] < max(sizes):
             raise ValueError(f'rules: a kinds table ({self.num_channels}, >= {max(sizes)}) expected for this decoder, got '
                              f'{tuple(rules.kinds.shape)}')
+
+    def _check_no_copy(self, no_copy, return_copy_report):
+        """The checks of the copy-guard keywords, once per call."""
+        from ..dataloaders.corpus import CopyIndex
+        if no_copy is None:
+            if return_copy_report:
+                raise ValueError('return_copy_report=True needs no_copy=copy_index(max_copy)')
+            return
+        if not isinstance(no_copy, CopyIndex):
+            raise ValueError(f'no_copy: None or a dataloaders.corpus.CopyIndex expected, got {type(no_copy).__name__}')
+        sizes = tuple(int(v) for v in self.num_tokens_per_channel)
+        if self.num_channels != 4 or sizes != tuple(no_copy.vocab):
+            raise ValueError(f'no_copy: the index is of a corpus with 4 voices and the vocab {tuple(no_copy.vocab)}, the decoder has '
+                             f'{self.num_channels} voices and {sizes}')
+        if no_copy.device != self.sos.device:
+            raise ValueError(f'no_copy: the index lives on {no_copy.device}, the decoder on {self.sos.device}')
+
+    def copy_index(self, max_copy, split='train'):
+        """The copy guard's index (`generate_from_codes(no_copy=...)`) over the pieces of `split`, resolved as
+        `check_duplicate_all_corpus` resolves it (None: every piece): `DeviceCorpus.copy_index`, built once and device resident.
+        Needs a corpus dataloader generator; the synthetic ones have no corpus and raise ValueError."""
+        dc = getattr(self.dataloader_generator, 'device_corpus', None)
+        if dc is None:
+            raise ValueError('copy_index needs a corpus dataloader generator (dataloaders/corpus.py); '
+                             f'{type(self.dataloader_generator).__name__} has no corpus')
+        pieces = None
+        if split is not None:
+            pieces = dc.split_pieces(split, self.dataloader_generator.sequences_size)
+            if pieces[0] == pieces[1]:
+                raise ValueError(f'copy_index: no piece begins in the {split} split')
+        return dc.copy_index(max_copy, pieces=pieces)
+
+    def audit_copies(self, x, index):
+        """x: (rows, events, 4) tokens, index: a `CopyIndex` -> int32 of x's shape: FORCED_COPY (bit 17) where the token completes a
+        run of max_copy + 1 tokens shared with the index's pieces, else 0 -- a copy map of an existing piece, without running the
+        model (vqcpc_nocopy_audit).  Every token is taken as given."""
+        from .. import hip
+        self._check_no_copy(index, False)
+        if index is None:
+            raise ValueError('audit_copies: index=copy_index(max_copy) is needed')
+        x = torch.as_tensor(x)
+        nc, dev = self.num_channels, self.sos.device
+        if x.dim() != 3 or x.shape[2] != nc or x.shape[0] < 1 or x.shape[1] < 1 or x.dtype != torch.int64:
+            raise ValueError(f'x: (rows, events, {nc}) int64 tokens expected, got {tuple(x.shape)} {x.dtype}')
+        rows, events = x.shape[0], x.shape[1]
+        flat = x.to(dev).reshape(rows, events * nc).contiguous()
+        report = torch.empty(rows, events * nc, dtype=torch.int32, device=dev)
+        for r0 in range(0, rows, 65535):
+            n = min(65535, rows - r0)
+            hip.call('vqcpc_nocopy_audit', flat[r0:r0 + n], events * nc, events * nc, *index.args(), report[r0:r0 + n], events * nc, n)
+        return report.view(rows, events, nc)
 
     def audit_voice_leading(self, x, rules):
         """x: (rows, events, channels) tokens, rules: a `templates.VoiceLeadingRules` -> int32 of x's shape: the enabled rules
@@ -763,7 +831,7 @@ class Decoder(FlatTraining, nn.Module):
     def generate(self, temperature, batch_size=1, top_k=0, top_p=1., seed_set=None, exclude_meta_symbols=False,
                  plot_attentions=False, code_juxtaposition=False, seed=None, keep_voices=None, return_attentions=False,
                  max_attention_bytes=4 << 30, particles=None, resample_threshold=0.5, rules=None, return_rule_report=False,
-                 beam=None, return_beams=False):
+                 beam=None, return_beams=False, no_copy=None, return_copy_report=False):
         """:552-721: a seed chorale from the train / val stream (or, code_juxtaposition, the first half of one and the
         second half of another), its merged codes, `batch_size` generations from them, the codes of original +
         generations written to {model_dir}/generations/<timestamp>.txt ({model_dir}/juxtapositions with
@@ -782,7 +850,8 @@ class Decoder(FlatTraining, nn.Module):
         rules, return_rule_report: `generate_from_codes`'s voice-leading rules; the result gains 'rule_report'.
         beam, return_beams: `generate_from_codes`'s beam search (temperature must be 1): each of the `batch_size` generations is
         the best hypothesis of its own group -- the same one, the search being deterministic --; with return_beams 'generation'
-        holds all batch_size * beam rows and the result gains 'beams'."""
+        holds all batch_size * beam rows and the result gains 'beams'.
+        no_copy, return_copy_report: `generate_from_codes`'s copy guard; the result gains 'copy_report'."""
         if plot_attentions:
             raise NotImplementedError('plot_attentions: no plots are drawn here (no matplotlib); return_attentions=True returns '
                                       'the attention maps of every emitted token and writes them as arrays')
@@ -818,7 +887,8 @@ class Decoder(FlatTraining, nn.Module):
                                        constraint=constraint, return_attentions=layers or False,
                                        max_attention_bytes=max_attention_bytes, particles=particles,
                                        resample_threshold=resample_threshold, rules=rules, return_rule_report=return_rule_report,
-                                       beam=beam, return_beams=return_beams)
+                                       beam=beam, return_beams=return_beams, no_copy=no_copy,
+                                       return_copy_report=return_copy_report)
             x, rule_report, attentions = res['tokens'], res['rule_report'], res['attentions']
             recoding = None if self.continuous_source else self.encode(torch.cat([x_original_single, x], dim=0))
         finally:
@@ -826,6 +896,8 @@ class Decoder(FlatTraining, nn.Module):
         extra = {} if attentions is None else {'attentions': attentions}
         if rule_report is not None:
             extra['rule_report'] = rule_report
+        if res['copy_report'] is not None:
+            extra['copy_report'] = res['copy_report']
         if res['beams'] is not None:
             extra['beams'] = res['beams']
         if recoding is None:
@@ -903,7 +975,7 @@ class Decoder(FlatTraining, nn.Module):
                                 use_graph=True, constraint=None, return_logp=False, return_attentions=False,
                                 max_attention_bytes=4 << 30, graph_slides=None, allowed=None, return_allowed_mass=False,
                                 particles=None, resample_threshold=0.5, return_particles=False, rules=None,
-                                return_rule_report=False, beam=None, return_beams=False):
+                                return_rule_report=False, beam=None, return_beams=False, no_copy=None, return_copy_report=False):
         """:729-829: decodes MERGED codes (B, nb) [continuous decoder: latents (B, nb, dz)] of any length nb >= S by sliding
         the model window one code at a time
         (`compute_start_end_times`), each row repeated `num_decodings` times (repeat_interleave).  The reference runs one
@@ -939,7 +1011,10 @@ class Decoder(FlatTraining, nn.Module):
         has the tokens' shape, after allowed_mass and before attentions.
         beam, return_beams: as in `generate_from_codes`; temperature may stay None.  The hypotheses' chorale rows move with them, the
         K/V caches too (a slide recomputes them from the moved tokens anyway), and 'ancestors' of the returned dict has one row
-        per position of the WHOLE sequence, in chorale coordinates."""
+        per position of the WHOLE sequence, in chorale coordinates.
+        no_copy, return_copy_report: as in `generate_from_codes`.  A context reaches back through the chorale however far
+        max_copy asks, also past the model window and before code_index_start (the PAD / START frame is compared like any
+        token; the corpus holds stored ticks only).  copy_report has the tokens' shape, after rule_report and before attentions."""
         if temperature is None and beam is not None:
             temperature = 1.0
         if encoding_indices is None or temperature is None:
@@ -970,7 +1045,7 @@ class Decoder(FlatTraining, nn.Module):
             return_attentions=return_attentions, max_attention_bytes=max_attention_bytes, allowed=allowed,
             return_allowed_mass=return_allowed_mass, particles=particles, resample_threshold=resample_threshold,
             return_particles=return_particles, rules=rules, return_rule_report=return_rule_report, beam=beam,
-            return_beams=return_beams)
+            return_beams=return_beams, no_copy=no_copy, return_copy_report=return_copy_report)
         return self._result_tuple(res, lambda t: t[:, code_index_start * epc:code_index_end * epc].contiguous())
 
     def generate_alla_mano(self, start_codes=None, end_codes=None, body_codes=None, temperature=None, num_decodings=3, beam=None,
@@ -978,7 +1053,8 @@ class Decoder(FlatTraining, nn.Module):
         """:960-981: start_codes + body_codes + end_codes (lists of merged codes; continuous decoder: (n_i, dz) latent
         tensors, concatenated along time) decoded as one sequence, the body's events returned: int64 (num_decodings, events,
         channels).  kwargs go to `generate_from_code_long` -- `allowed` and `return_allowed_mass` among them, in the coordinates
-        of the whole start + body + end sequence, and `rules` / `return_rule_report`, which need no coordinates.
+        of the whole start + body + end sequence, and `rules` / `return_rule_report` and `no_copy` / `return_copy_report`, which
+        need no coordinates.
         beam, return_beams: `generate_from_code_long`'s beam search; it needs num_decodings=1 and temperature may stay None."""
         if temperature is None and beam is not None:
             temperature = 1.0
@@ -1108,7 +1184,8 @@ class Decoder(FlatTraining, nn.Module):
 
     def reharmonise_tokens(self, x, num_reharmonisations, temperature, top_k=0, top_p=1., return_bounds=False,
                            keep_voices=None, return_logp=False, allowed=None, return_allowed_mass=False, rules=None,
-                           return_rule_report=False, beam=None, return_beams=False, **kwargs):
+                           return_rule_report=False, beam=None, return_beams=False, no_copy=None, return_copy_report=False,
+                           **kwargs):
         """The body of generate_reharmonisation (:871-941) on a (1, events, channels) token tensor: the chorale is cut into
         model-sized chunks, framed by a PAD...START chunk and an END / PAD chunk (the last chunk completed with END + PAD),
         every chunk is encoded, the codes are glued and the chorale's own codes are decoded `num_reharmonisations` times.
@@ -1126,7 +1203,9 @@ class Decoder(FlatTraining, nn.Module):
         rules, return_rule_report: `generate_from_code_long`'s; the rules compare the voices of a tick, so they need no
         coordinates, and rule_report comes back with the tokens, in the same events.
         beam, return_beams: `generate_from_code_long`'s beam search -- the most probable harmonisations of the kept voices --; it
-        needs num_reharmonisations=1 and temperature 1."""
+        needs num_reharmonisations=1 and temperature 1.
+        no_copy, return_copy_report: `generate_from_code_long`'s copy guard; the kept voices are forced, so where they are the
+        corpus's own the report says FORCED_COPY rather than hiding it.  copy_report comes back with the tokens."""
         n2i = getattr(getattr(self.dataloader_generator, 'dataset', None), 'note2index_dicts', None)
         if n2i is None:
             raise ValueError('reharmonise_tokens needs dataset.note2index_dicts with the START / END / XX symbols')
@@ -1161,7 +1240,8 @@ class Decoder(FlatTraining, nn.Module):
         tokens = self.generate_from_code_long(codes, temperature=temperature, top_k=top_k, top_p=top_p,
                                               num_decodings=num_reharmonisations, code_index_start=code_index_start,
                                               code_index_end=code_index_end, return_logp=return_logp, rules=rules,
-                                              return_rule_report=return_rule_report, beam=beam, return_beams=return_beams, **kwargs)
+                                              return_rule_report=return_rule_report, beam=beam, return_beams=return_beams,
+                                              no_copy=no_copy, return_copy_report=return_copy_report, **kwargs)
         return (tokens, code_index_start, code_index_end, codes.size(1)) if return_bounds else tokens
 
     def generate_reharmonisation(self, *a, **k):

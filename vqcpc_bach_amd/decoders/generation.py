@@ -55,6 +55,12 @@ rule kernel's output; vqcpc_decode_rules runs immediately before vqcpc_decode_sa
 overwrites the live column's set from the tokens emitted so far (the live window's, and the chorale's before it) and the
 column of `rule_report`.  The sampler, the mass and the particle weights read that set unchanged.
 
+Copy guard (`start(no_copy=CopyIndex)`, csrc/nocopy.hip): the same kind of thing with another question.  vqcpc_decode_nocopy runs
+after vqcpc_decode_rules and immediately before the sampler or the beam select, INSIDE the captured step: it looks the row's last
+max_copy tokens up in the corpus index and takes every token that would complete a shared run of max_copy + 1 out of the live
+column's set (`copy_static`'s, the rule kernel's in place, or the whole vocabulary), and writes the column of `copy_report`.  It is
+stateless per step, so whatever moves rows -- particles, the beam -- only has to move `copy_report` with them.
+
 Beam search (`start(beam=W)`, csrc/beam.hip): the rows are groups of W consecutive rows, the W best hypotheses of one user row.
 vqcpc_decode_beam_select takes the sampler's place (after vqcpc_decode_rules when rules are on): it expands every row into its
 candidate tokens, keeps each group's W best by total log-probability and writes the whole live column -- tokens, next input rows,
@@ -70,7 +76,7 @@ Where the options are set up: `start` and `start_long` take the sampling setting
 window, (nb * U, win, U, nb, row_seeds) for a chorale.  Every option buffer above has `frame.width` columns and is addressed
 through `frame.win`; the step, the cross hook, the sampler and the resampling read the frame and nothing else about the
 coordinates.  `_configure` sets every option at every call, so a second `start` leaves the earlier call's options off.  The
-record buffers (`logp`, `logmass`, `rule_report`, `self_probs`, `cross_probs`, the `p_*` and `b_*` state) are allocated there and get their
+record buffers (`logp`, `logmass`, `rule_report`, `copy_report`, `self_probs`, `cross_probs`, the `p_*` and `b_*` state) are allocated there and get their
 initial values in one place, `_clear_records`, which `reset` and the post-warm-up path of `run_long` call."""
 import ctypes
 
@@ -121,6 +127,7 @@ class IncrementalDecoder(IncrementalStack):
         self.memkv = None
         self.allowed, self.logmass, self.masked = None, None, False
         self.rules, self.rule_static, self.rule_report = None, None, None
+        self.no_copy, self.copy_static, self.copy_report = None, None, None
         self.cross_probs, self.enc_probs, self.attn_layers = None, None, None
         self.particles = None                                                     # group size P, or None: plain rows
         self.beam = None                                                          # beam width W, or None: the rows are sampled
@@ -174,7 +181,7 @@ class IncrementalDecoder(IncrementalStack):
 
     def start(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False,
               constraint=None, want_logp=False, want_attentions=None, allowed=None, want_allowed_mass=False, particles=None,
-              resample_threshold=0.5, final_resample=True, rules=None, beam=None):
+              resample_threshold=0.5, final_resample=True, rules=None, beam=None, no_copy=None):
         """Resets the generation to position 0 with the given sampling settings.  exclude: per voice, a list of token ids
         never drawn; teacher: (M, T) int64 tokens to force instead of drawing; want_probs: keep the filtered
         probabilities of the last step in `probs` (M, max V_c).
@@ -196,10 +203,13 @@ class IncrementalDecoder(IncrementalStack):
         sampler reads it (`_rule_sets`); `rule_report` (M, T) int32 keeps what was relaxed or broken, -1 where no token was
         emitted yet.
         beam: None, or W in [1, 64] dividing M: the rows are M / W groups of W hypotheses and vqcpc_decode_beam_select replaces the
-        sampler (`_beam`); seeds, temperature, top_k and top_p are then unused."""
+        sampler (`_beam`); seeds, temperature, top_k and top_p are then unused.
+        no_copy: None, or a `dataloaders.corpus.CopyIndex`: vqcpc_decode_nocopy takes the tokens that would complete a run of
+        max_copy + 1 tokens shared with the corpus out of every position's set (`_copy_guard`); `copy_report` (M, T) int32 keeps
+        how many it took and the RELAXED / FORCED_COPY flags, -1 where no token was emitted yet."""
         self._sampling(seeds, temperature, top_k, top_p, exclude, teacher, want_probs)
         self._configure(Frame(self.T, None, 1, self.S, self.seeds), constraint, want_logp, allowed, want_allowed_mass, particles,
-                        resample_threshold, final_resample, rules, want_attentions, beam)
+                        resample_threshold, final_resample, rules, want_attentions, beam, no_copy)
 
     def _sampling(self, seeds=None, temperature=1.0, top_k=0, top_p=1.0, exclude=None, teacher=None, want_probs=False):
         """The sampling settings of `start`: what the sampler takes whatever options are on."""
@@ -221,7 +231,7 @@ class IncrementalDecoder(IncrementalStack):
         self.probs = torch.zeros(self.M, self.vmax, dtype=torch.float32, device=self.dev) if want_probs else None
 
     def _configure(self, frame, constraint, want_logp, allowed, want_allowed_mass, particles, resample_threshold, final_resample,
-                   rules, want_attentions, beam=None):
+                   rules, want_attentions, beam=None, no_copy=None):
         """The options of one generation, all of them at every call (what is not asked for is switched off), in the coordinates
         of `frame`: `Frame(T, None, 1, S, seeds)` for the fixed window, `Frame(nb * U, win, U, nb, row_seeds)` for a chorale,
         whose buffers are addressed through the device window index.  The record buffers are allocated here, once and before any
@@ -231,8 +241,10 @@ class IncrementalDecoder(IncrementalStack):
         self._beam(beam, want_attentions)
         scored = particles is not None                        # the weights are the forced tokens' logp and the sets' mass
         self._constrain(constraint, want_logp or (scored and constraint is not None), frame.width)
-        self._mask(allowed, want_allowed_mass or (scored and (allowed is not None or rules is not None)))
+        narrowed = allowed is not None or rules is not None or no_copy is not None
+        self._mask(allowed, want_allowed_mass or (scored and narrowed))
         self._rule_sets(rules)
+        self._copy_guard(no_copy)
         self._record_attentions(want_attentions)
         self.reset()
 
@@ -270,7 +282,7 @@ class IncrementalDecoder(IncrementalStack):
         hip.call('vqcpc_particle_permute_i64', self.tokens, self.T, self.T, bound[0:1], anc, flag, M, W)
         if self.frame.win is not None:                        # long mode: the history before the live window
             hip.call('vqcpc_particle_permute_i64', self.chorale, w, w, None, anc, flag, M, W)
-        for rows in (self.logp, self.logmass, self.rule_report):
+        for rows in (self.logp, self.logmass, self.rule_report, self.copy_report):
             if rows is not None:
                 hip.call('vqcpc_particle_permute_f32', rows, w, w, bound[1:2], anc, flag, M, W)
         if move_cache:
@@ -303,7 +315,7 @@ class IncrementalDecoder(IncrementalStack):
         hip.call('vqcpc_particle_permute_i64', self.tokens, self.T, self.T, self.pos, anc, flag, M, P)
         if chorale is not None:
             hip.call('vqcpc_particle_permute_i64', chorale, chorale.shape[1], chorale.shape[1], None, anc, flag, M, P)
-        for rows in (self.logp, self.logmass, self.rule_report):     # the report's int32 rows move as 4-byte words
+        for rows in (self.logp, self.logmass, self.rule_report, self.copy_report):    # the reports' int32 rows move as 4-byte words
             if rows is not None:
                 hip.call('vqcpc_particle_permute_f32', rows, w, w, None, anc, flag, M, P)
         if not last:
@@ -348,6 +360,29 @@ class IncrementalDecoder(IncrementalStack):
         self.rule_report = torch.empty(self.M, self.frame.width, dtype=torch.int32, device=self.dev)
         self.masked = True
 
+    def _copy_guard(self, index):
+        """The copy guard's buffers (after `_rule_sets`).  `copy_static` is the set the guard kernel reads.  Without rules the
+        caller's sets move there (None: none) and `allowed`, the buffer the sampler reads, becomes the kernel's output; with rules
+        the rule kernel has written the live column of `allowed` this step, `copy_static` IS `allowed` and the guard narrows it in
+        place.  `copy_report` (M, width) int32 moves with its row like `rule_report`."""
+        self.no_copy = self.copy_static = self.copy_report = None
+        if index is None:
+            return
+        if self.teacher is not None:
+            raise ValueError('no_copy and teacher exclude each other')
+        sizes = tuple(b - a for a, b in zip(self.offsets[:-1], self.offsets[1:]))
+        if self.nc != 4 or sizes != tuple(index.vocab):
+            raise ValueError(f'no_copy: the index is of a corpus with 4 voices and the vocab {tuple(index.vocab)}, the decoder has '
+                             f'{self.nc} voices and {sizes}')
+        if index.device != self.dev:
+            raise ValueError(f'no_copy: the index lives on {index.device}, the decoder on {self.dev}')
+        self.no_copy = index
+        self.copy_static = self.allowed
+        if self.rules is None:
+            self.allowed = torch.zeros(self.M, self.frame.width, 8, dtype=torch.int32, device=self.dev)
+        self.copy_report = torch.empty(self.M, self.frame.width, dtype=torch.int32, device=self.dev)
+        self.masked = True
+
     def _record_attentions(self, layers):
         """The attention-map buffers, one row per column of the frame.  layers=None frees them and every launch is the plain one
         again."""
@@ -376,8 +411,8 @@ class IncrementalDecoder(IncrementalStack):
         """The initial values of everything a step records, in one place: NaN (report: -1) where no token was emitted yet, and
         the filter before its first code.  A warm-up step of a capture writes into these buffers, so a run clears them again."""
         nan = float('nan')
-        for rows, value in ((self.logp, nan), (self.logmass, nan), (self.rule_report, -1), (self.self_probs, nan),
-                            (self.cross_probs, nan)):
+        for rows, value in ((self.logp, nan), (self.logmass, nan), (self.rule_report, -1), (self.copy_report, -1),
+                            (self.self_probs, nan), (self.cross_probs, nan)):
             if rows is not None:
                 rows.fill_(value)
         if self.beam is not None:                             # the standard start: identical rows would fill the beam with copies
@@ -419,10 +454,14 @@ class IncrementalDecoder(IncrementalStack):
             w, win = self.frame.width, self.frame.win
             if self.rules is not None:
                 self._rules_launch()
+            if self.no_copy is not None:
+                self._nocopy_launch()
             hip.call('vqcpc_decode_beam_select', self.logits, self.logits.shape[1], self._offsets_c, self.nc, self.M, self.beam,
                      self.exclude if self.excluding else None, self.constraint, w, self.allowed, w, self.logp, w, self.logmass, w,
                      self.rule_report, w, win, self.tokens, T, T, self.table, self.table.shape[0], d, self.U, self.x, d,
                      self.b_score, self.b_anc, self.b_flag, self.b_bound, self.b_hist, self.b_hist.shape[0], None, self.pos)
+            if self.no_copy is not None and self.beam > 1:    # the select does not know this record: its live column follows
+                hip.call('vqcpc_nocopy_beam_column', self.copy_report, w, self.b_anc, self.b_flag, self.b_bound, self.M, self.beam)
             if self.beam_moves_in_step:
                 self._beam_moves()
             return
@@ -439,6 +478,8 @@ class IncrementalDecoder(IncrementalStack):
             return
         if self.rules is not None:
             self._rules_launch()
+        if self.no_copy is not None:
+            self._nocopy_launch()
         hip.call('vqcpc_decode_sample_masked', *head, *forced, self.allowed, w, self.logmass, w, *tail)
 
     def _rules_launch(self):
@@ -449,6 +490,14 @@ class IncrementalDecoder(IncrementalStack):
                  self.constraint, w, self.rule_kinds, self.rule_kinds.shape[1], self._offsets_c, self.nc, self.rule_leap,
                  self.rules.mask, self.exclude if self.excluding else None, self.rule_static, w, self.allowed, w,
                  self.rule_report, w, self.pos, win, self.U, self.M)
+
+    def _nocopy_launch(self):
+        """The live column's set without the tokens that would complete a copied run."""
+        T, w, win = self.T, self.frame.width, self.frame.win
+        windowed = win is not None                            # long mode: the history before the live window is the chorale's
+        hip.call('vqcpc_decode_nocopy', self.tokens, T, T, self.chorale if windowed else None, w if windowed else 0,
+                 self.constraint, w, *self.no_copy.args(), self._offsets_c, self.nc, self.exclude if self.excluding else None,
+                 self.copy_static, w, self.allowed, w, self.copy_report, w, self.pos, win, self.U, self.M)
 
     # ---- a whole generation --------------------------------------------------------------------------------------------
     def run(self, use_graph=True):
@@ -481,7 +530,7 @@ class IncrementalDecoder(IncrementalStack):
     @torch.no_grad()
     def start_long(self, codes_full, chorale, seeds=None, constraint=None, want_logp=False, want_attentions=None, allowed=None,
                    want_allowed_mass=False, particles=None, resample_threshold=0.5, final_resample=True, rules=None, beam=None,
-                   **sampling):
+                   no_copy=None, **sampling):
         """codes_full (M, nb) merged codes [continuous decoder: (M, nb, dz) latents], nb >= S; chorale (M, nb * U) int64
         tokens, position-major (the initial PAD / START sequence; generated tokens are written into it).  constraint,
         want_logp: as in `start`, but (M, nb * U), position-major like `chorale`: the sampler reads and writes them at the
@@ -494,6 +543,7 @@ class IncrementalDecoder(IncrementalStack):
         rules: as in `start`, with `rule_report` (M, nb * U) in chorale coordinates; the history of a position reaches back through
         the chorale, wherever the model window lies.
         beam: as in `start`; `b_hist` has one row per chorale position.
+        no_copy: as in `start`, with `copy_report` (M, nb * U) in chorale coordinates; a context reaches back through the chorale.
         sampling: the other keywords of `start`."""
         M, S, U = self.M, self.S, self.U
         z_full = None
@@ -518,7 +568,7 @@ class IncrementalDecoder(IncrementalStack):
             self.z_full, self.z_nb = z_full, nb
         self._sampling(seeds, **sampling)
         self._configure(Frame(nb * U, self.win, U, nb, self.row_seeds), constraint, want_logp, allowed, want_allowed_mass,
-                        particles, resample_threshold, final_resample, rules, want_attentions, beam)
+                        particles, resample_threshold, final_resample, rules, want_attentions, beam, no_copy)
         self.row_seeds.copy_(self.seeds)
 
     def _window(self, P, advance):
